@@ -127,7 +127,7 @@ def main():
     fl = bench.get("fit_launch", {})
     md = ["# rocprofv3 summary, %s" % a.tag, "",
           "Commands (on the MI355X box, see tools/run_measure.sh):", "",
-          "    python bench.py                                   -> %s_bench.json" % a.tag,
+          "    python bench.py --full                            -> %s_bench.json" % a.tag,
           "    L=\"--no-cpu-baseline --no-fixed-line --no-driver-line --no-extra-lines\"",
           "    rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 1 $L   -> %s_kernel_stats.csv" % a.tag,
           "    rocprofv3 --kernel-trace --pmc FETCH_SIZE -- python3 bench.py --steps 5 --warmup 0 $L",

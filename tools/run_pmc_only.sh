@@ -7,7 +7,7 @@ R=$PWD
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 python -c "from gapro_amd._lib import source_build_id; print(source_build_id())" > $O/build_id.txt
-( time timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time
+( time timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err ) 2> $O/bench.time; tail -3 $O/bench.time
 LIGHT="--no-cpu-baseline --no-fixed-line --no-driver-line --no-extra-lines"
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o bench --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 $LIGHT > $O/stats.log 2>&1
