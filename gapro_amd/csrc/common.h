@@ -62,6 +62,21 @@ struct gapro_fit_timing {
   unsigned* tickets = nullptr;  // the launch's counter set (gapro_ctx::d_tickets): [5..7] = cluster kernel diagnostics
 };
 
+// svgp_fit_large.hip: the generic kernel (one workgroup per fit, working set in global memory)
+void gapro_launch_fit_large(hipStream_t stream, int n_fits, int feat_dim, const float* d_feats_spp, const int* d_idx,
+                            const gapro_fit_desc* d_descs, const double* d_init_mean, const gapro_fit_options& opt,
+                            double* d_workspace, float* d_probs, float* d_probs_new, unsigned char* d_labels,
+                            float* d_mu, float* d_var, int* d_fit_status, double* d_fit_loss);
+
+// svgp_fit_small.hip: the strip kernel built with 256 threads per fit (M_p <= 64, two fits per CU)
+extern "C" int gapro_launch_fit_strip_small(void* stream, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim,
+                                            size_t lds_bytes, const float* d_feats_spp, const int32_t* d_idx,
+                                            const gapro_fit_desc* d_descs, const double* d_init_mean,
+                                            const gapro_fit_options* opt, double* d_workspace, float* d_probs,
+                                            float* d_probs_new, uint8_t* d_labels, float* d_mu, float* d_var,
+                                            int32_t* d_fit_status, double* d_fit_loss);
+extern "C" long long gapro_fit_strip_small_lds_bytes(int m, int feat_dim);
+
 // svgp_fit_cluster.hip
 int gapro_cluster_size(int Mp, bool all);
 size_t gapro_cluster_stage_bytes(int n_fits);

@@ -21,17 +21,13 @@ inline __host__ __device__ int round_up(int x, int a) { return (x + a - 1) / a *
 constexpr int kClMaxG = 32;                      // largest cluster (workgroups per fit)
 constexpr int kClThreads = 512;                  // threads per cluster workgroup
 constexpr int kClusterMinMp = 64;                // smallest padded M the cluster kernel takes (64-wide panels)
-constexpr int kClusterDefaultMinMp = 512;        // default routing threshold (gapro_cluster_min_mp)
+constexpr int kClusterDefaultMinMp = 512;        // default routing threshold (gapro_cluster_size)
 // workgroups a fit of padded size Mp is spread over: the work grows with Mp^3 while a launch's other fits finish in
 // a fraction of a second, so the largest fits get the most CUs (powers of two; one CU up to Mp = 384)
-inline __host__ __device__ int cluster_g(int Mp, double unit = 384.0, bool pow2 = true) {
+inline __host__ __device__ int cluster_g(int Mp, double unit = 384.0) {
   const double work = (double)Mp * Mp * Mp / (unit * unit * unit);
   int g = 1;
-  if (pow2) {
-    while (g < kClMaxG && (double)g < work) g *= 2;
-  } else {
-    while (g < kClMaxG && (double)g < work) ++g;
-  }
+  while (g < kClMaxG && (double)g < work) g *= 2;
   return g;
 }
 // largest padded M the cluster kernel takes: its pairwise-merge inverse keeps one record per pair of 64-wide panels in
@@ -40,13 +36,13 @@ constexpr int kClusterMaxMp = 5120;
 inline __host__ __device__ bool cluster_capable(int Mp) {
   return Mp >= kClusterMinMp && Mp % 32 == 0 && Mp <= kClusterMaxMp;
 }
-// a plane of the ordered two-stage column sums: sized for the largest cluster ANY policy can give a fit of this size
-// (gapro_cluster_size: the work unit is tunable down to kClusterMinUnit), so that the layout does not depend on the
-// policy -- and not for 32 workgroups whatever the size: M_p = 64 .. 128 fits, thousands per batch and never on the
-// cluster kernel by default, carried 400 KB of scratch each
+// a plane of the ordered two-stage column sums: sized for the cluster a work unit of kClusterMinUnit would give a fit
+// of this size (the unit was once tunable down to it; the workspace layout is kept as it was) -- and not for 32
+// workgroups whatever the size: M_p = 64 .. 128 fits, thousands per batch and never on the cluster kernel by default,
+// carried 400 KB of scratch each
 constexpr double kClusterMinUnit = 64.0;
 inline __host__ __device__ long long cluster_plane_doubles(int Mp) {
-  const long long t = (long long)cluster_g(Mp, kClusterMinUnit, true) * kClThreads;
+  const long long t = (long long)cluster_g(Mp, kClusterMinUnit) * kClThreads;
   return Mp > t ? Mp : t;
 }
 inline __host__ __device__ long long cluster_part_doubles(int Mp) {

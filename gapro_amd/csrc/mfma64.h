@@ -50,22 +50,15 @@ __device__ inline AFrag make_afrag(double a) {
 
 // acc (rotated layout) += A B for one 16 x 16 x 4 step
 __device__ inline void mma16(const AFrag& a, double b, d4& acc) {
-#ifdef GAPRO_MFMA_16X16  // A/B experiments: the 16x16x4 form (standard layout; unrotate() is then the identity)
-  acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a.r[0], b, acc, 0, 0, 0);
-#else
   acc[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.r[0], b, acc[0], 0, 0, 0);
   acc[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.r[1], b, acc[1], 0, 0, 0);
   acc[2] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.r[2], b, acc[2], 0, 0, 0);
   acc[3] = __builtin_amdgcn_mfma_f64_4x4x4f64(a.r[3], b, acc[3], 0, 0, 0);
-#endif
 }
 __device__ inline void mma16(double a, double b, d4& acc) { mma16(make_afrag(a), b, acc); }
 
 // rotated layout -> the 16x16x4 form's layout: register r' of a lane = rotated register (r' - b) & 3, b = (lane >> 2) & 3
 __device__ inline d4 unrotate(const d4& acc) {
-#ifdef GAPRO_MFMA_16X16
-  return acc;
-#else
   const int b = (threadIdx.x >> 2) & 3;
   d4 t, o;
   // barrel shifter: by one register if b & 1, by two if b & 2
@@ -78,13 +71,9 @@ __device__ inline d4 unrotate(const d4& acc) {
   o[2] = (b & 2) ? t[0] : t[2];
   o[3] = (b & 2) ? t[1] : t[3];
   return o;
-#endif
 }
 // the inverse: a block in the standard layout (an accumulator to continue from) -> rotated layout
 __device__ inline d4 rotate_in(const d4& c) {
-#ifdef GAPRO_MFMA_16X16
-  return c;
-#else
   const int b = (threadIdx.x >> 2) & 3;
   d4 t, o;  // rotated register r = standard register (r + b) & 3
   t[0] = (b & 1) ? c[1] : c[0];
@@ -96,7 +85,6 @@ __device__ inline d4 rotate_in(const d4& c) {
   o[2] = (b & 2) ? t[0] : t[2];
   o[3] = (b & 2) ? t[1] : t[3];
   return o;
-#endif
 }
 
 }  // namespace gapro_mfma

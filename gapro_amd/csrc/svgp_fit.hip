@@ -51,11 +51,6 @@
 #include "mfma64.h"
 #endif
 
-void gapro_launch_fit_large(hipStream_t stream, int n_fits, int feat_dim, const float* d_feats_spp, const int* d_idx,
-                            const gapro_fit_desc* d_descs, const double* d_init_mean, const gapro_fit_options& opt,
-                            double* d_workspace, float* d_probs, float* d_probs_new, unsigned char* d_labels,
-                            float* d_mu, float* d_var, int* d_fit_status, double* d_fit_loss);
-
 namespace {
 using namespace gapro_fit;
 
@@ -67,21 +62,12 @@ constexpr int NW = NT / 64;   // waves per fit
 constexpr int kMaxMpLds = 512;          // largest padded M the LDS-staged kernel takes
 constexpr int kMaxDynLds = 150 * 1024;  // dynamic LDS budget (160 KiB per CU minus the static part)
 constexpr int kRedSlots = 8;            // values reduced across row groups per pass
-#ifndef GAPRO_WAVES_PER_SIMD
-#define GAPRO_WAVES_PER_SIMD 4           // 2 workgroups of 8 waves per CU -> 128 VGPRs per lane
-#endif
-constexpr int kWavesPerSimd = GAPRO_WAVES_PER_SIMD;
-#ifndef GAPRO_TU4_MIN
-#define GAPRO_TU4_MIN 320
-#endif
+constexpr int kWavesPerSimd = 4;        // 2 workgroups of 8 waves per CU -> 128 VGPRs per lane
 // 64 x 64 wave tiles from this M_p on (one-per-CU build, D = 6; multiples of 32).  Round 3, 512 fits: M_p = 320 +2.4 %,
 // 288 -2.2 % against 32 x 32 tiles; with the copy-free forms, one per CU, M_p = 192 / 224: -15 % (and one per CU with
 // 32 x 32 tiles is 7 .. 10 % behind two per CU there).
-constexpr int kTu4MinMp = GAPRO_TU4_MIN;
+constexpr int kTu4MinMp = 320;
 constexpr int kKminMaxMp = 256;         // largest M_p with the copy-free product forms (fit_body's KMIN)
-#ifndef GAPRO_GEMM_RING
-#define GAPRO_GEMM_RING 2
-#endif
 
 using gapro_mfma::d4;
 // LDS pointers carry their address space explicitly: ds_read/ds_write instead of flat accesses, and no
@@ -210,9 +196,6 @@ __device__ inline double ndtr_ratio(double z) {
 // one symmetric pair of Gauss-Hermite nodes (t, weight w) of a point: sums for E (want_e only), dE/dmu, dE/dvar
 __device__ inline void gh_pair(double y, double mu, double sd, double t, double w, bool want_e, double* E, double* dmu,
                                double* dvar) {
-#ifdef GAPRO_LIK_ALWAYS_LOG  // A/B builds
-  want_e = true;
-#endif
   if (want_e) {  // workgroup-uniform
     double lp, r;
     log_ndtr_ratio(y * (mu - sd * t), &lp, &r);
@@ -335,11 +318,7 @@ typedef __attribute__((address_space(1))) d2 g_d2;
 // register allocator then carries the kernel's long-lived values through every k loop); inlining them into ONE
 // out-of-line function per Adam step (step_fn in fit_body, through gemm_tn_in) pays the callee-saved traffic once per
 // step: M = 160 -3.3 %, 200 -1.7 %, 256 +0.7 %, 320 / 384 +-0 in time, bit-identical.  The strip kernels' tail products keep
-// the out-of-line form (their caller holds 80 accumulator registers across them).  -DGAPRO_NO_STEP_FN restores the
-// per-product calls everywhere.
-#ifndef GAPRO_NO_STEP_FN
-#define GAPRO_STEP_FN
-#endif
+// the out-of-line form (their caller holds 80 accumulator registers across them).
 template <int TU, bool SCALE, int KS = 2, int ORD = ORD_ROWMAJOR, bool TRIM = false, int PK = 0, int QK = 0,
           typename KRange, typename Epi>
 __device__ __forceinline__ void gemm_tn_body(int mo_tiles, int no_tiles, bool lower_only, const gd* __restrict__ P,
@@ -520,11 +499,7 @@ template <int TU, bool SCALE, int KS = 2, int ORD = ORD_ROWMAJOR, bool TRIM = fa
 __device__ __forceinline__ void gemm_tn_in(int mo_tiles, int no_tiles, bool lower_only, const gd* __restrict__ P,
                                         const gd* __restrict__ Q, int ld, const gd* __restrict__ qscale, KRange kr,
                                         Epi epi) {
-#ifdef GAPRO_STEP_FN
   gemm_tn_body<TU, SCALE, KS, ORD, TRIM, PK, QK>(mo_tiles, no_tiles, lower_only, P, Q, ld, qscale, kr, epi);
-#else
-  gemm_tn<TU, SCALE, KS, ORD, TRIM, PK, QK>(mo_tiles, no_tiles, lower_only, P, Q, ld, qscale, kr, epi);
-#endif
 }
 
 // ---- TN-form MFMA product, workgroup-tiled through an LDS ring (round 3) ---------------------------------
@@ -651,13 +626,8 @@ __device__ __noinline__ void gemm_wg(int rows16, int cols16, bool lower_only, co
         auto gload = [&](int n, d2& p, d2& q, double& sc) {
           n = n < nch ? n : nch - 1;
           const size_t o = (size_t)(klo + kWgKC * n) * ld;
-#ifdef GAPRO_WG_NOLOAD  // timing experiment: no operand traffic (results are wrong)
-          p = (d2){1.0 + (double)o, 2.0};
-          q = (d2){0.5, 0.25};
-#else
           p = *(const g_d2*)(pg + o);
           q = *(const g_d2*)(qg + o);
-#endif
           if (SCALE) sc = qscale[klo + kWgKC * n + wave];
         };
         auto lstore = [&](int stage, const d2& p, const d2& q, double sc) {
@@ -686,11 +656,7 @@ __device__ __noinline__ void gemm_wg(int rows16, int cols16, bool lower_only, co
           for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int v = 0; v < 4; ++v)
-#ifdef GAPRO_WG_NOMFMA  // timing experiment: no matrix work (results are wrong)
-              acc[u][v][0] += a[u] * b[v];
-#else
               acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[v], acc[u][v], 0, 0, 0);
-#endif
         };
         // chunk c: CUR = its LDS stage, SLOT = the register stage holding chunk c + 1, refilled with chunk c + 1 + PF
         auto chunk = [&](auto cur_tag, auto slot_tag, int c) {
@@ -1516,11 +1482,6 @@ __device__ __noinline__ double quadrature(double c, double min_variance, double 
 //   zz: w  = sym(G)[i][j] s E_ij  ->  G_s += sym(G) E,  G_l += w d2,   G_Z[j] += 2 w (Z_j - Z_i)
 //   zx: wx = G_KX[j][n=i] KX_jn   ->  G_s += G_KX E,    G_l += wx d2,  G_Z[j] += wx (Z_j - X_i)
 // (sym(G) o K is symmetric, so the sum over i of column j equals the row sum of the oracle's formula.)
-#ifdef GAPRO_X_NOEXP
-#define KG_EXP(x) (1.0 + (x))
-#else
-#define KG_EXP(x) gapro_fit_math::rbf_exp(x)
-#endif
 template <int DMAX, bool ZX, int U, int DC>
 __device__ __noinline__ void kernel_grads_adam_z(ldsd* Zt, const ldsd* Xt, const gd* Gm, const gd* GTm,
                                                  const gd* GKXT, double s, double inv_l2, double step_size,
@@ -1556,13 +1517,13 @@ __device__ __noinline__ void kernel_grads_adam_z(ldsd* Zt, const ldsd* Xt, const
             d2x += bx * bx;
           }
         }
-        const double e = KG_EXP(-0.5 * inv_l2 * d2);
+        const double e = gapro_fit_math::rbf_exp(-0.5 * inv_l2 * d2);
         const double w = gsym * s * e;
         gs += gsym * e;
         gl += w * d2;
         double wx = 0.0;
         if (ZX) {
-          const double ex = KG_EXP(-0.5 * inv_l2 * d2x);
+          const double ex = gapro_fit_math::rbf_exp(-0.5 * inv_l2 * d2x);
           wx = g3 * s * ex;
           gs += g3 * ex;
           gl += wx * d2x;
@@ -1605,7 +1566,7 @@ __device__ __noinline__ void kernel_grads_adam_z(ldsd* Zt, const ldsd* Xt, const
             t[d] = (d < D) ? zj[d] - Zt[d * Mp + i] : 0.0;
             d2 += t[d] * t[d];
           }
-          const double e = KG_EXP(-0.5 * inv_l2 * d2);
+          const double e = gapro_fit_math::rbf_exp(-0.5 * inv_l2 * d2);
           const double gsym = 0.5 * (g1[u] + g2[u]);
           const double w = gsym * s * e;
           gs += gsym * e;
@@ -1619,7 +1580,7 @@ __device__ __noinline__ void kernel_grads_adam_z(ldsd* Zt, const ldsd* Xt, const
               t[d] = (d < D) ? zj[d] - Xt[d * Mp + i] : 0.0;
               d2x += t[d] * t[d];
             }
-            const double ex = KG_EXP(-0.5 * inv_l2 * d2x);
+            const double ex = gapro_fit_math::rbf_exp(-0.5 * inv_l2 * d2x);
             const double wx = g3[u] * s * ex;
             gs += g3[u] * ex;
             gl += wx * d2x;
@@ -1788,8 +1749,6 @@ __device__ void fit_body(const gapro_fit_options& opt, ldsd* Zt, ldsd* Pt, ldsd*
   // the per-product stamps (and with them the barriers: GAPRO_PROFILE_SPLIT) or charges the whole phase to slot 10
 #if defined(GAPRO_PROFILE) && defined(GAPRO_PROFILE_SPLIT)
 #define STAMP_MERGED(id) do { __syncthreads(); stamp(id); } while (0)
-#elif defined(GAPRO_NO_MERGED_BWD)  // A/B builds: the three products as three barrier-separated phases (round 3)
-#define STAMP_MERGED(id) do { __syncthreads(); } while (0)
 #else
   // merged only in the KMIN instantiations (M_p <= 256).  Beyond, G_A^T lives in the G_KX^T slot until G_KX^T is formed
   // (GAT below), so Pm -- which reads it -- must be complete before G_KX^T starts; and with one workgroup per CU and
@@ -1808,15 +1767,11 @@ __device__ void fit_body(const gapro_fit_options& opt, ldsd* Zt, ldsd* Pt, ldsd*
   };
   auto factorize = [&]() {
     stamp(19);
-#ifdef GAPRO_NO_CHOL_LOOKAHEAD
-    cholesky_psd_safe<DC, 0>(Zt, scratch, sh.s, sh.inv_l2, jitter, opt.psd_retries, opt.psd_jitter);
-#else
     // The register look-ahead (next column's tiles built while wave 0 factors the diagonal block) beyond M_p = 256:
     // one workgroup per CU there, nobody else fills the CU while seven waves wait for the diagonal block (512 fits:
     // M = 320 -1.9 %, 384 -1.6 %, 448 -1.0 % in time, bit-identical).  Up to 256 two workgroups share a CU and hide
     // each other's serial stretches: 160 +-0, 200 +1.3 %, 256 +1 % -- not used there.
     cholesky_psd_safe<DC, KMIN ? 0 : 3>(Zt, scratch, sh.s, sh.inv_l2, jitter, opt.psd_retries, opt.psd_jitter);
-#endif
     stamp(1);
     if (Mp <= 128)
       tri_inverse<8>(scratch);
@@ -1934,13 +1889,9 @@ __device__ void fit_body(const gapro_fit_options& opt, ldsd* Zt, ldsd* Pt, ldsd*
     __syncthreads();
   };
 
-#ifdef GAPRO_STEP_FN
   // one Adam step as ONE out-of-line function with the products inlined into it: the callee-saved registers are saved
   // once per step instead of once per product call (see gemm_tn_in)
   auto step_fn = [&](int step) __attribute__((noinline)) {
-#else
-  for (int step = 1; step <= opt.training_iter; ++step) {
-#endif
     refresh_hypers();
     const double s = sh.s, ell = sh.ell, inv_l2 = sh.inv_l2, c = sh.c;
     const bool last = step == opt.training_iter;
@@ -2188,13 +2139,9 @@ __device__ void fit_body(const gapro_fit_options& opt, ldsd* Zt, ldsd* Pt, ldsd*
     }
     __syncthreads();
     stamp(16);
-  #ifdef GAPRO_STEP_FN
   };
 #pragma nounroll
   for (int step = 1; step <= opt.training_iter; ++step) step_fn(step);
-#else
-  }
-#endif
 
   // ------------------------------- prediction ------------------------------
   refresh_hypers();
@@ -2350,22 +2297,21 @@ __global__ __launch_bounds__(NT, WPS) void k_svgp_fit(int n_fits, int D, const f
 #define GAPRO_FIT_KM(TUV, DM, DCV, WGV)                                                                       \
   fit_body<TUV, DM, DCV, WGV, KMIN, (WPS == 2 ? 4 : 1)>(opt, Zt, Pt, scratch, desc, o_probs, o_probs_new, o_labels, o_mu, \
                                                         o_var, loss_slot)
-#define GAPRO_FIT_BODY(DM, DCV)                                                                              \
-  do {                                                                                                       \
-    if (Mp > kFuseMaxMp && Mp % 32 == 0 && !(opt.reserved & 131072) &&                                       \
-        ((opt.reserved & 8192) ? !(WPS == 2 && (opt.reserved & 16384)) : Mp % 128 == 0))                      \
-      /* workgroup-tiled products (gemm_wg; bit-identical to the per-wave ones) where whole 128 x 128 tiles   \
-         cover the matrix: M_p = 256, 384 (+6 % / +4 % fits/s, a quarter less traffic; neutral to -7 % at     \
-         the other sizes: DESIGN 6.0).  Bit 13: every M_p > 128 that is a multiple of 32 (bit 14: not in the  \
-         one-per-CU build); bit 17: nowhere */                                                                \
-      GAPRO_FIT_KM(1, DM, DCV, (WPS == 2 ? 4 : 2));                                                            \
-    else if (WPS == 2 && DM == 6 && !KMIN && Mp >= kTu4MinMp && Mp % 32 == 0 && !(opt.reserved & 4096)) {   \
-      if constexpr (WPS == 2 && DM == 6 && !KMIN)                                                            \
+#define GAPRO_FIT_BODY(DM, DCV)                                                                                   \
+  do {                                                                                                            \
+    if (Mp > kFuseMaxMp && Mp % 32 == 0 && !(opt.reserved & GAPRO_FIT_DBG_WG_TILED_NONE) &&                       \
+        ((opt.reserved & GAPRO_FIT_DBG_WG_TILED_ALL) || Mp % 128 == 0))                                           \
+      /* workgroup-tiled products (gemm_wg; bit-identical to the per-wave ones) where whole 128 x 128 tiles       \
+         cover the matrix: M_p = 256, 384 (+6 % / +4 % fits/s, a quarter less traffic; neutral to -7 % at         \
+         the other sizes: DESIGN 6.0).  The debug bits: every M_p > 128 that is a multiple of 32, or nowhere */   \
+      GAPRO_FIT_KM(1, DM, DCV, (WPS == 2 ? 4 : 2));                                                               \
+    else if (WPS == 2 && DM == 6 && !KMIN && Mp >= kTu4MinMp && Mp % 32 == 0) {                                   \
+      if constexpr (WPS == 2 && DM == 6 && !KMIN)                                                                 \
         fit_body<4, DM, DCV>(opt, Zt, Pt, scratch, desc, o_probs, o_probs_new, o_labels, o_mu, o_var, loss_slot); \
-    } else if (Mp >= 128)                                                                                    \
-      GAPRO_FIT_KM(2, DM, DCV, 0);                                                                             \
-    else                                                                                                     \
-      GAPRO_FIT_KM(1, DM, DCV, 0);                                                                             \
+    } else if (Mp >= 128)                                                                                         \
+      GAPRO_FIT_KM(2, DM, DCV, 0);                                                                                \
+    else                                                                                                          \
+      GAPRO_FIT_KM(1, DM, DCV, 0);                                                                                \
   } while (0)
   if (D == 6) GAPRO_FIT_BODY(6, 6);
   else if (D == 32) GAPRO_FIT_BODY(32, 32);
@@ -2726,7 +2672,7 @@ __device__ __noinline__ void strip_kgrad_zx(const ldsd* Gs, const ldsd* Zt, cons
           t[d] = zk[d] - Xpts[d * Mp + n0 + n];
           d2 += t[d] * t[d];
         }
-        const double e = KG_EXP(-0.5 * inv_l2 * d2);
+        const double e = gapro_fit_math::rbf_exp(-0.5 * inv_l2 * d2);
         const double g = Gs[row * RS + n];
         const double wx = g * s * e;
         gs += g * e;
@@ -3423,14 +3369,6 @@ int gapro_debug_stream(gapro_ctx* ctx, void* stream_, int64_t n, const double* d
 
 }  // extern "C"
 #else
-extern "C" int gapro_launch_fit_strip_small(void* stream, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim,
-                                            size_t lds_bytes, const float* d_feats_spp, const int32_t* d_idx,
-                                            const gapro_fit_desc* d_descs, const double* d_init_mean,
-                                            const gapro_fit_options* opt, double* d_workspace, float* d_probs,
-                                            float* d_probs_new, uint8_t* d_labels, float* d_mu, float* d_var,
-                                            int32_t* d_fit_status, double* d_fit_loss);
-extern "C" long long gapro_fit_strip_small_lds_bytes(int m, int feat_dim);
-
 // Conditioning figure of every fit of a launch (round 6): every kernel leaves the inverses of the 16 x 16 diagonal blocks of
 // its LAST Cholesky factor in the fit's workspace (f.dinv: the triangular solves read them; the wave-per-fit kernel, which
 // keeps L^-1 on chip, stores the diagonal on its way out), and the diagonal of L^-1 is 1 / L_jj.  One wave per fit:
@@ -3464,23 +3402,54 @@ __global__ __launch_bounds__(256) void k_fit_cond(int n_fits, int D, const gapro
 // 0 = strip-streaming kernel, 1 = LDS-staged kernel, 2 = generic kernel, 3 = strip-streaming kernel of the small-fit
 // translation unit (M_p <= 64: 256 threads per fit, two fits per CU), 4 = cluster kernel (one fit over several
 // workgroups), 5 = the wave-per-fit kernel (svgp_fit_wave.hip: M_p <= 48 at feat_dim 6).  flags:
-// gapro_fit_options.reserved debug bits (bit 0: never the strip kernels, bit 2: no small-fit kernel, bit 3: no cluster
-// kernel, bit 4: the cluster kernel for every fit it can take, M_p >= 64 and M_p % 32 == 0, bit 20: no wave kernel).
+// gapro_fit_options.reserved (GAPRO_FIT_DBG_*).
 constexpr int kSmallFitMp = 64;
-constexpr int kNoWaveFlag = 1 << 20;
 static int fit_route(int m, int feat_dim, int flags) {
-  if (!(flags & kNoWaveFlag) && gapro_pad_m(m, feat_dim) <= gapro_fit_wave_max_mp(feat_dim)) return 5;
-  // large fits: spread over several CUs (svgp_fit_cluster.hip); debug bit 3 keeps them on one workgroup
-  if (!(flags & 8) && feat_dim <= 32 && gapro_cluster_size(gapro_pad_m(m, feat_dim), (flags & 16) != 0) > 0) return 4;
-  if (!(flags & 1) && strip_ok(m, feat_dim)) {
-    const bool small = gapro_pad_m(m, feat_dim) <= kSmallFitMp && 2 * gapro_fit_strip_small_lds_bytes(m, feat_dim) + 16384 <= 160 * 1024;
-    return (small && !(flags & 4)) ? 3 : 0;
+  const int Mp = gapro_pad_m(m, feat_dim);
+  if (!(flags & GAPRO_FIT_DBG_NO_WAVE) && Mp <= gapro_fit_wave_max_mp(feat_dim)) return 5;
+  // large fits: spread over several CUs (svgp_fit_cluster.hip)
+  const bool clus = !(flags & GAPRO_FIT_DBG_NO_CLUSTER) && feat_dim <= 32;
+  if (clus && gapro_cluster_size(Mp, (flags & GAPRO_FIT_DBG_CLUSTER_ALL) != 0) > 0) return 4;
+  if (!(flags & GAPRO_FIT_DBG_NO_STRIP) && strip_ok(m, feat_dim)) {
+    const bool small = Mp <= kSmallFitMp && 2 * gapro_fit_strip_small_lds_bytes(m, feat_dim) + 16384 <= 160 * 1024;
+    return (small && !(flags & GAPRO_FIT_DBG_NO_SMALL)) ? 3 : 0;
   }
   if (staged_ok(m, feat_dim)) return 1;
   // neither LDS-resident kernel takes it (deep features: Z and X of M_p > 192 points at D = 32 do not fit beside the
   // Cholesky block column): the cluster kernel keeps the points in global memory and runs such a fit on one workgroup
-  if (!(flags & 8) && feat_dim <= 32 && gapro_cluster_size(gapro_pad_m(m, feat_dim), true) > 0) return 4;
+  if (clus && gapro_cluster_size(Mp, true) > 0) return 4;
   return 2;
+}
+
+// The launch groups of gapro_svgp_fit_batch, in the order of the descriptor array it uploads.  Kernels are launched
+// in another order: cluster, large, staged, strip, small, wave 3 / 2 / 1 (LABNOTES R4.4).
+enum FitGroupId { G_LARGE, G_STAGED, G_STRIP, G_SMALL, G_CLUSTER, G_WAVE3, G_WAVE2, G_WAVE1, kFitGroups };
+struct FitGroup {
+  int stream;  // ctx->fit_stream index
+  int ticket;  // counter of the launch's ticket set (-1: none)
+  int timing;  // gapro_fit_timing kernel k: events ev[2 k] (start), ev[2 k + 1] (end)
+  int join;    // ctx->ev_join index that joins `stream` back into the caller's stream
+  std::vector<gapro_fit_desc> descs;  // longest first
+  size_t base = 0;                    // offset of descs in the uploaded array
+  long long max_lds = 0;              // largest dynamic LDS need of a fit
+};
+static int fit_group(int route, int m, int feat_dim) {
+  switch (route) {
+    case 0: return G_STRIP;
+    case 1: return G_STAGED;
+    case 3: return G_SMALL;
+    case 4: return G_CLUSTER;
+    case 5: return G_WAVE1 + 1 - gapro_pad_m(m, feat_dim) / 16;  // M_p = 16 nb
+    default: return G_LARGE;
+  }
+}
+static long long fit_lds_bytes(int group, int m, int feat_dim) {
+  switch (group) {
+    case G_STRIP: return strip_lds_bytes(m, feat_dim);
+    case G_SMALL: return gapro_fit_strip_small_lds_bytes(m, feat_dim);
+    case G_STAGED: return staged_lds_bytes(m, feat_dim);
+    default: return 0;
+  }
 }
 
 extern "C" {
@@ -3531,15 +3500,29 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
   if (opt->training_iter < 0 || !(opt->lr > 0.0) || !(opt->jitter >= 0.0) || opt->psd_retries < 0 ||
       opt->psd_retries > 8 || !(opt->psd_jitter >= 0.0))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch: bad options");
-  hipStream_t stream = (hipStream_t)stream_;
-  // Routing (gapro_fit_route): strip-streaming kernel, LDS-staged kernel, generic kernel (working set beyond
-  // LDS).  Every group is sorted longest processing time first (cost ~ M^3): workgroups are dispatched in
-  // block order, so the expensive fits start first and the tail of a launch stays short.
-  std::vector<gapro_fit_desc> strip, small, staged, large, clus, wave[3];  // wave[nb - 1]: M_p = 16 nb
-  strip.reserve(n_fits);
-  small.reserve(n_fits);
-  long long need = 0, max_lds = 0, max_lds_strip = 0, max_lds_small = 0;
   const int route_flags = opt->reserved;
+  if (route_flags & ~GAPRO_FIT_DBG_ALL)
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch: unknown or retired debug bits 0x%x in reserved",
+                      (unsigned)(route_flags & ~GAPRO_FIT_DBG_ALL));
+  hipStream_t stream = (hipStream_t)stream_;
+  FitGroup grp[kFitGroups] = {
+      // stream, ticket, timing, join
+      {0, -1, 0, 0},  // large: the generic kernel, ahead of the staged fits on their stream
+      {0, 0, 0, 0},   // staged: tickets 0 .. 2 for its three launches; the third may go to fit stream 4 (below)
+      {1, 3, 1, 1},   // strip
+      {2, 4, 2, 2},   // small
+      {3, 5, 3, 3},   // cluster: tickets 5 .. 7 are its diagnostics (gapro_fit_timing_cluster_info)
+      {5, 10, 4, 7},  // wave, M_p = 48
+      {6, 9, 4, 6},   // wave, M_p = 32
+      {7, 8, 4, 5},   // wave, M_p = 16
+  };
+  FitGroup &large = grp[G_LARGE], &staged = grp[G_STAGED], &strip = grp[G_STRIP], &small = grp[G_SMALL],
+           &clus = grp[G_CLUSTER];
+  strip.descs.reserve(n_fits);
+  small.descs.reserve(n_fits);
+  // Routing (gapro_fit_route).  Every group is sorted longest processing time first (cost ~ M^3): workgroups are
+  // dispatched in block order, so the expensive fits start first and the tail of a launch stays short.
+  long long need = 0;
   for (int i = 0; i < n_fits; ++i) {
     gapro_fit_desc d = h_descs[i];
     const int m = d.m1 + d.m2;
@@ -3547,32 +3530,18 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
       return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch: fit %d has an empty side", i);
     d.slot = i;
     need = std::max<long long>(need, (d.ws_offset + gapro_fit_workspace_doubles(m, d.t, feat_dim)) * 8LL);
-    const int route = fit_route(m, feat_dim, route_flags);
-    if (route == 0) {
-      strip.push_back(d);
-      max_lds_strip = std::max(max_lds_strip, strip_lds_bytes(m, feat_dim));
-    } else if (route == 3) {
-      small.push_back(d);
-      max_lds_small = std::max(max_lds_small, gapro_fit_strip_small_lds_bytes(m, feat_dim));
-    } else if (route == 1) {
-      staged.push_back(d);
-      max_lds = std::max(max_lds, staged_lds_bytes(m, feat_dim));
-    } else if (route == 4) {
-      clus.push_back(d);
-    } else if (route == 5) {
-      wave[gapro_pad_m(m, feat_dim) / 16 - 1].push_back(d);
-    } else {
-      large.push_back(d);
-      // beyond the cluster kernel's cap (kClusterMaxMp: its merge inverse keeps one LDS record per pair of panels) a
-      // fit runs on ONE workgroup of the generic kernel: correct, but minutes per fit -- never silently
-      if (feat_dim <= 32 && gapro_pad_m(m, feat_dim) > gapro_fit::kClusterMaxMp) {
-        static bool warned = false;
-        if (!warned) {
-          warned = true;
-          fprintf(stderr, "libgapro_hip: a GP fit with M = %d inducing points exceeds the multi-workgroup kernel's cap "
-                          "(M_p <= %d): it runs on one workgroup of the generic kernel (minutes per fit)\n", m,
-                  gapro_fit::kClusterMaxMp);
-        }
+    const int g = fit_group(fit_route(m, feat_dim, route_flags), m, feat_dim);
+    grp[g].descs.push_back(d);
+    grp[g].max_lds = std::max(grp[g].max_lds, fit_lds_bytes(g, m, feat_dim));
+    // beyond the cluster kernel's cap (kClusterMaxMp: its merge inverse keeps one LDS record per pair of panels) a
+    // fit runs on ONE workgroup of the generic kernel: correct, but minutes per fit -- never silently
+    if (g == G_LARGE && feat_dim <= 32 && gapro_pad_m(m, feat_dim) > gapro_fit::kClusterMaxMp) {
+      static bool warned = false;
+      if (!warned) {
+        warned = true;
+        fprintf(stderr, "libgapro_hip: a GP fit with M = %d inducing points exceeds the multi-workgroup kernel's cap "
+                        "(M_p <= %d): it runs on one workgroup of the generic kernel (minutes per fit)\n", m,
+                gapro_fit::kClusterMaxMp);
       }
     }
   }
@@ -3580,17 +3549,12 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
     return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_svgp_fit_batch: workspace too small (%lld > %zu)", need,
                       workspace_bytes);
   auto by_cost = [](const gapro_fit_desc& a, const gapro_fit_desc& b) { return a.m1 + a.m2 > b.m1 + b.m2; };
-  std::stable_sort(strip.begin(), strip.end(), by_cost);
-  std::stable_sort(small.begin(), small.end(), by_cost);
-  std::stable_sort(staged.begin(), staged.end(), by_cost);
-  std::stable_sort(large.begin(), large.end(), by_cost);
-  std::stable_sort(clus.begin(), clus.end(), by_cost);
-  for (auto& w : wave) std::stable_sort(w.begin(), w.end(), by_cost);
+  for (FitGroup& g : grp) std::stable_sort(g.descs.begin(), g.descs.end(), by_cost);
   // the staged fits whose LDS fits a CU twice and the larger ones are two launches (see below)
   const long long kTwice = 72 * 1024;
   size_t nbig = 0, nkmaj = 0;  // sorted by M, the LDS need grows with M: [0, nkmaj) M_p > kKminMaxMp, [0, nbig) "big"
   long long lds_big = 0, lds_rest = 0, lds_kmaj = 0;
-  for (const gapro_fit_desc& d : staged) {
+  for (const gapro_fit_desc& d : staged.descs) {
     const long long b = staged_lds_bytes(d.m1 + d.m2, feat_dim);
     // (the product forms of a fit are a function of its M_p, k_svgp_fit's KMIN: fits beyond kKminMaxMp are a launch of
     // their own -- with D = 6 exactly the fits that need more than kTwice)
@@ -3599,7 +3563,7 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
       ++nkmaj;
       lds_kmaj = std::max(lds_kmaj, b);
     }
-    if (kmaj || (b > kTwice && !(route_flags & 128))) {
+    if (kmaj || b > kTwice) {
       ++nbig;
       if (!kmaj) lds_big = std::max(lds_big, b);
     } else {
@@ -3614,27 +3578,22 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
     for (size_t g0 = lo + 8; g0 + 8 <= hi; g0 += 16) std::reverse(v.begin() + g0, v.begin() + g0 + 8);
   };
   // Default since round 4: ticket counters (claim_fit) -- the fits stay in plain longest-first order and are taken by
-  // the workgroups in the order in which they start; debug bit 18 restores the static mapping fit = blockIdx.x
-  const bool tickets = !(route_flags & 262144) && ctx->d_tickets;
-  if (!(route_flags & 512) && !tickets) {
-    serpentine(strip, 0, strip.size());
-    serpentine(small, 0, small.size());
-    serpentine(staged, 0, nbig);
-    serpentine(staged, nbig, staged.size());
+  // the workgroups in the order in which they start; GAPRO_FIT_DBG_STATIC_MAP restores the mapping fit = blockIdx.x
+  const bool tickets = !(route_flags & GAPRO_FIT_DBG_STATIC_MAP) && ctx->d_tickets;
+  if (!tickets) {
+    serpentine(strip.descs, 0, strip.descs.size());
+    serpentine(small.descs, 0, small.descs.size());
+    serpentine(staged.descs, 0, nbig);
+    serpentine(staged.descs, nbig, staged.descs.size());
   }
-  std::vector<gapro_fit_desc> all(large);
-  all.insert(all.end(), staged.begin(), staged.end());
-  all.insert(all.end(), strip.begin(), strip.end());
-  all.insert(all.end(), small.begin(), small.end());
-  const size_t clus_base = all.size();
-  all.insert(all.end(), clus.begin(), clus.end());
-  size_t wave_base[3];
-  for (int k = 2; k >= 0; --k) {  // the largest first
-    wave_base[k] = all.size();
-    all.insert(all.end(), wave[k].begin(), wave[k].end());
+  std::vector<gapro_fit_desc> all;
+  all.reserve(n_fits);
+  for (FitGroup& g : grp) {
+    g.base = all.size();
+    all.insert(all.end(), g.descs.begin(), g.descs.end());
   }
-  if (!clus.empty()) {  // staging of the cluster kernel: block table + one barrier counter line per fit
-    const size_t need_stage = gapro_cluster_stage_bytes((int)clus.size());
+  if (!clus.descs.empty()) {  // staging of the cluster kernel: block table + one barrier counter line per fit
+    const size_t need_stage = gapro_cluster_stage_bytes((int)clus.descs.size());
     if (2 * need_stage > ctx->cl_stage_bytes) {  // cl_stage_bytes counts BOTH halves; a launch uses one of them
       if (ctx->h_cl_stage) (void)hipHostFree(ctx->h_cl_stage);
       if (ctx->d_cl_stage) (void)hipFree(ctx->d_cl_stage);
@@ -3644,17 +3603,16 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
       GAPRO_HIP_CHECK(ctx, hipMalloc(&ctx->d_cl_stage, 2 * need_stage));
       ctx->cl_stage_bytes = 2 * need_stage;
     }
-    if (clus.size() > ctx->cl_ctl_fits) {
+    if (clus.descs.size() > ctx->cl_ctl_fits) {
       if (ctx->d_cl_ctl) (void)hipFree(ctx->d_cl_ctl);
       ctx->d_cl_ctl = nullptr;
       ctx->cl_ctl_fits = 0;
-      GAPRO_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_cl_ctl, 2 * 2 * clus.size() * 128));  // two halves
-      ctx->cl_ctl_fits = 2 * clus.size();
+      GAPRO_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_cl_ctl, 2 * 2 * clus.descs.size() * 128));  // two halves
+      ctx->cl_ctl_fits = 2 * clus.descs.size();
     }
   }
-  // ticket counters of this launch: [0] staged beyond kKminMaxMp, [1] staged "big", [2] the other staged fits, [3] strip,
-  // [4] small, [5..7] cluster kernel diagnostics, [8..10] wave kernels.  The sets rotate, so that a set is zeroed again
-  // only kTicketSets launches later
+  // ticket counters of this launch (FitGroup::ticket; kTicketsPerSet of them).  The sets rotate, so that a set is zeroed
+  // again only kTicketSets launches later
   unsigned* tk = nullptr;
   if (tickets) {
     tk = ctx->d_tickets + (size_t)(ctx->ticket_seq++ % gapro_ctx::kTicketSets) * gapro_ctx::kTicketsPerSet;
@@ -3665,18 +3623,20 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
   int cl_blocks = 0, cl_members = 0, cl_par = 0;
   char* cl_d_half = nullptr;
   unsigned* cl_ctl_half = nullptr;
-  if (!clus.empty()) {
-    std::vector<int> fi(clus.size()), fmp(clus.size()), fg(clus.size());
-    for (size_t k = 0; k < clus.size(); ++k) {
-      fi[k] = (int)(clus_base + k);
-      fmp[k] = gapro_pad_m(clus[k].m1 + clus[k].m2, feat_dim);
+  if (!clus.descs.empty()) {
+    const size_t n = clus.descs.size();
+    std::vector<int> fi(n), fmp(n), fg(n);
+    for (size_t k = 0; k < n; ++k) {
+      fi[k] = (int)(clus.base + k);
+      fmp[k] = gapro_pad_m(clus.descs[k].m1 + clus.descs[k].m2, feat_dim);
       fg[k] = gapro_cluster_size(fmp[k], true);
     }
     // the block table is built in one half of the context's pinned buffer, the halves alternating per launch: the
     // copy of launch i - 2 has long been consumed (callers collect a launch before they issue the one after next),
     // so the host never waits for the previous cluster kernel here
-    // (the device copies alternate the same way, so that two launches issued from different streams -- debug bit 1
-    // puts the kernels on the caller's stream -- never share a block table or a barrier counter)
+    // (the device copies alternate the same way, so that two launches issued from different streams --
+    // GAPRO_FIT_DBG_CALLER_STREAM puts the kernels on the caller's stream -- never share a block table or a barrier
+    // counter)
     const size_t par = ctx->cl_parity & 1;
     cl_par = (int)par;
     // this half's previous user may still be running on another stream (overlapping launches, several caller streams):
@@ -3686,94 +3646,85 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
     cl_d_half = (char*)ctx->d_cl_stage + par * (ctx->cl_stage_bytes / 2);
     cl_ctl_half = ctx->d_cl_ctl + par * ctx->cl_ctl_fits * 32;
     ctx->cl_parity++;
-    const int rc = gapro_prepare_fit_cluster(stream, (int)clus.size(), fi.data(), fmp.data(), fg.data(), h_half, cl_d_half,
+    const int rc = gapro_prepare_fit_cluster(stream, (int)n, fi.data(), fmp.data(), fg.data(), h_half, cl_d_half,
                                              cl_ctl_half, &cl_blocks, &cl_members);
     if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: cluster block table upload failed");
   }
-  // grid of a ticketed kernel: twice its fits, so that an XCD (a fixed eighth of the grid) can run up to twice its share
-  auto grid_of = [&](size_t n) { return (int)(tickets ? 2 * n : n); };
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_descs, all.data(), all.size() * sizeof(gapro_fit_desc), hipMemcpyHostToDevice,
                                       stream));
   GAPRO_HIP_CHECK(ctx, hipStreamSynchronize(stream));  // `all` is pageable host memory that dies with this call
-  // The kernels go to the context's two fit streams so that the staged kernel (a few large fits, which leave
-  // most CUs idle) and the strip kernel run side by side.  No fork event is needed: `stream` has just been
-  // synchronised, so everything the kernels read is complete (and an event recorded here completes together
-  // with the NEXT dispatch of `stream` under this runtime, which would serialise the kernels again).  Both
-  // are joined back into `stream` with events.
-  bool own = !(route_flags & 2);  // debug bit 1
+  // The kernels go to the context's fit streams so that the staged kernel (a few large fits, which leave most CUs
+  // idle), the strip kernels and the others run side by side.  No fork event is needed: `stream` has just been
+  // synchronised, so everything the kernels read is complete (and an event recorded here completes together with the
+  // NEXT dispatch of `stream` under this runtime, which would serialise the kernels again).  All are joined back into
+  // `stream` with events.
+  bool own = !(route_flags & GAPRO_FIT_DBG_CALLER_STREAM);
   for (int k = 0; k < gapro_ctx::kFitStreams; ++k) own = own && ctx->fit_stream[k];
-  hipStream_t s_staged = own ? ctx->fit_stream[0] : stream;
-  hipStream_t s_strip = own ? ctx->fit_stream[1] : stream;
-  // (round 4, tried: the small-fit kernel behind the strip kernel on ITS stream, so that the two-per-CU small fits fill
-  // the end of the launch instead of competing with the whole-CU strip fits for every CU half that frees up: 341.9 /
-  // 336.5 scenes/s against 337.7 / 341.6, same box, alternating -- nothing)
-  hipStream_t s_small = own ? ctx->fit_stream[2] : stream;
-  hipStream_t s_clus = own ? ctx->fit_stream[3] : stream;
-  hipStream_t s_staged2 = own ? ctx->fit_stream[4] : stream;
   gapro_fit_timing* tm = ctx->armed_timing;
   ctx->armed_timing = nullptr;
   if (tm) {
     tm->tickets = tk;
-    tm->used[0] = !large.empty() || !staged.empty();
-    tm->used[1] = !strip.empty();
-    tm->used[2] = !small.empty();
-    tm->used[3] = !clus.empty();
-    tm->used[4] = !wave[0].empty() || !wave[1].empty() || !wave[2].empty();
+    for (bool& u : tm->used) u = false;
+    for (const FitGroup& g : grp) tm->used[g.timing] = tm->used[g.timing] || !g.descs.empty();
   }
-  bool gate_staged2 = false;
-  if (!clus.empty()) {  // first: the largest fits of the launch, each over several CUs
-    if (tm) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[6], s_clus));
+  auto on = [&](const FitGroup& g) { return own ? ctx->fit_stream[g.stream] : stream; };
+  auto ticket = [&](const FitGroup& g, int k = 0) { return tk && g.ticket >= 0 ? tk + g.ticket + k : nullptr; };
+  auto mark = [&](const FitGroup& g, int end) {  // timing event: start (0) or end (1) of the group's kernels
+    return tm ? hipEventRecord(tm->ev[2 * g.timing + end], on(g)) : hipSuccess;
+  };
+  // grid of a ticketed kernel: twice its fits, so that an XCD (a fixed eighth of the grid) can run up to twice its share
+  auto grid_of = [&](size_t n) { return (int)(tickets ? 2 * n : n); };
+  bool gate = false;
+  if (!clus.descs.empty()) {  // first: the largest fits of the launch, each over several CUs
+    GAPRO_HIP_CHECK(ctx, mark(clus, 0));
     // (Round 4, tried: holding the other kernels back until the cluster's members are resident.  They are within 1 .. 15
     // us anyway, and every cluster sits on one XCD (gapro_fit_timing_cluster_info); what makes the same cluster kernel
     // take 240 ms in one run of a step and 500 ms in the next is what runs beside it -- LABNOTES R4.4.)
-    const int rc = gapro_launch_fit_cluster(s_clus, cl_blocks, feat_dim, cl_d_half, cl_ctl_half, tk ? tk + 5 : nullptr,
+    const int rc = gapro_launch_fit_cluster(on(clus), cl_blocks, feat_dim, cl_d_half, cl_ctl_half, ticket(clus),
                                             d_feats_spp, d_idx, d_descs, d_init_mean, *opt, d_workspace, d_probs,
                                             d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
     if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: cluster kernel launch failed");
-    if (tm) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[7], s_clus));
-    GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_clus_half[cl_par], s_clus));
+    GAPRO_HIP_CHECK(ctx, mark(clus, 1));
+    GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_clus_half[cl_par], on(clus)));
     ctx->clus_half_used[cl_par] = true;
-    // gate of the two-per-CU staged launch (below): policy 2 = always behind the cluster kernel (default), 1 = only when
-    // the cluster's members fit the GPU at once, 0 = never (GAPRO_STAGED_GATE; debug bit 19 = never)
-    static int gate_policy = -1;
-    if (gate_policy < 0) {
-      const char* e = getenv("GAPRO_STAGED_GATE");
-      gate_policy = e ? atoi(e) : 2;
-    }
-    gate_staged2 = own && !(route_flags & 524288) &&
-                   (gate_policy == 2 || (gate_policy == 1 && cl_members <= ctx->n_cu));
-    if (gate_staged2) GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_gate, s_clus));
+    // gate of the two-per-CU staged launch and of the small fits (below): behind the cluster kernel
+    gate = own;
+    if (gate) GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_gate, on(clus)));
   }
-  if (tm && tm->used[0]) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[0], s_staged));
-  if (!large.empty())
-    gapro_launch_fit_large(s_staged, (int)large.size(), feat_dim, d_feats_spp, d_idx, d_descs, d_init_mean, *opt,
-                           d_workspace, d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
-  if (!staged.empty()) {
+  const bool staged_class = !large.descs.empty() || !staged.descs.empty();  // one stream, timing pair and join
+  if (staged_class) GAPRO_HIP_CHECK(ctx, mark(staged, 0));
+  if (!large.descs.empty())
+    gapro_launch_fit_large(on(large), (int)large.descs.size(), feat_dim, d_feats_spp, d_idx, d_descs + large.base,
+                           d_init_mean, *opt, d_workspace, d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status,
+                           d_fit_loss);
+  if (!staged.descs.empty()) {
     // The dynamic LDS of a launch is its largest fit's, and beyond ~72 KiB (M_p > 256 at D = 6) a CU holds ONE
     // workgroup whatever the registers allow: a launch with one such fit ran every staged fit one per CU.  So the
     // staged fits go out as two launches side by side: those whose LDS fits a CU twice in the `<4>` build (128 VGPRs,
     // two workgroups per CU: 17 % more fits/s at M <= 256 than one per CU), the larger ones in the `<2>` build (the
     // whole register file, no spills).  Either part with fewer fits than CUs takes `<2>` as well.
-    auto launch = [&](hipStream_t st, size_t first, size_t count, long long lds, bool kmaj, int tslot) -> int {
-      const bool one_per_cu = (int)count <= ctx->n_cu || lds > kTwice || (route_flags & 64);
+    auto launch = [&](hipStream_t st, size_t first, size_t count, long long lds, bool kmaj, int part) -> int {
+      const bool one_per_cu = (int)count <= ctx->n_cu || lds > kTwice;
       auto kern = kmaj ? k_svgp_fit<2, false> : one_per_cu ? k_svgp_fit<2, true> : k_svgp_fit<kWavesPerSimd, true>;
       if (lds > 48 * 1024)
         GAPRO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(kern, dim3(grid_of(count)), dim3(NT), (size_t)lds, st, (int)count, (int)feat_dim, d_feats_spp,
-                         d_idx, d_descs + large.size() + first, d_init_mean, *opt, d_workspace, d_probs, d_probs_new,
-                         d_labels, d_mu, d_var, d_fit_status, d_fit_loss, tk ? tk + tslot : nullptr);
+                         d_idx, d_descs + staged.base + first, d_init_mean, *opt, d_workspace, d_probs, d_probs_new,
+                         d_labels, d_mu, d_var, d_fit_status, d_fit_loss, ticket(staged, part));
       return GAPRO_OK;
     };
+    const size_t n = staged.descs.size();
     if (nkmaj > 0) {
-      const int rc = launch(s_staged, 0, nkmaj, lds_kmaj, true, 0);
+      const int rc = launch(on(staged), 0, nkmaj, lds_kmaj, true, 0);
       if (rc != GAPRO_OK) return rc;
     }
     if (nbig > nkmaj) {  // M_p <= kKminMaxMp with an LDS need beyond kTwice (wide features): behind the former
-      const int rc = launch(s_staged, nkmaj, nbig - nkmaj, lds_big, false, 1);
+      const int rc = launch(on(staged), nkmaj, nbig - nkmaj, lds_big, false, 1);
       if (rc != GAPRO_OK) return rc;
     }
-    if (nbig < staged.size()) {
-      hipStream_t st = nbig > 0 ? s_staged2 : s_staged;
+    if (nbig < n) {
+      constexpr int kStaged2 = 4;  // fit stream and join event of the two-per-CU launch beside the others
+      hipStream_t st = nbig > 0 && own ? ctx->fit_stream[kStaged2] : on(staged);
       // The two-per-CU staged fits are the launch's memory-bound class (3.8 FLOP/B: with the chip to themselves they
       // sit on the HBM roof), the cluster fits its latency-bound one (a chain of cluster barriers and small products
       // per Adam step).  Side by side from the start, the same cluster kernel took 230 .. 270 ms or 500 .. 800 ms
@@ -3782,88 +3733,81 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
       // the CUs beside the clusters meanwhile.  Same box, 2 x 8 steps: 361 .. 372 scenes/s with 4 or 8 hardware queues
       // (GPU_MAX_HW_QUEUES), the cluster kernel at its undisturbed time in every step; without the gate 368 / 372 with
       // the default 4 queues (the lucky mapping) and 351 .. 362 with 8.
-      if (gate_staged2) GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_gate, 0));
-      const int rc = launch(st, nbig, staged.size() - nbig, lds_rest, false, 2);
+      if (gate) GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_gate, 0));
+      const int rc = launch(st, nbig, n - nbig, lds_rest, false, 2);
       if (rc != GAPRO_OK) return rc;
-      if (st != s_staged) {  // everything staged is finished once s_staged has passed this point
-        GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[4], st));
-        GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(s_staged, ctx->ev_join[4], 0));
+      if (st != on(staged)) {  // everything staged is finished once the staged stream has passed this point
+        GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[kStaged2], st));
+        GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(on(staged), ctx->ev_join[kStaged2], 0));
       }
     }
   }
-  if (tm && tm->used[0]) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[1], s_staged));
-  if (!strip.empty()) {
+  if (staged_class) GAPRO_HIP_CHECK(ctx, mark(staged, 1));
+  if (!strip.descs.empty()) {
     auto kern = feat_dim == 6 ? k_svgp_fit_strip<6, 6> : feat_dim == 32 ? k_svgp_fit_strip<32, 32> : k_svgp_fit_strip<32, 0>;
-    if (max_lds_strip > 48 * 1024)
+    if (strip.max_lds > 48 * 1024)
       GAPRO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)max_lds_strip));
-    if (tm) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[2], s_strip));
-    hipLaunchKernelGGL(kern, dim3(grid_of(strip.size())), dim3(NT), (size_t)max_lds_strip, s_strip, (int)strip.size(),
-                       (int)feat_dim, d_feats_spp, d_idx, d_descs + large.size() + staged.size(), d_init_mean, *opt,
-                       d_workspace, d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss,
-                       tk ? tk + 3 : nullptr);
-    if (tm) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[3], s_strip));
+                                               (int)strip.max_lds));
+    GAPRO_HIP_CHECK(ctx, mark(strip, 0));
+    hipLaunchKernelGGL(kern, dim3(grid_of(strip.descs.size())), dim3(NT), (size_t)strip.max_lds, on(strip),
+                       (int)strip.descs.size(), (int)feat_dim, d_feats_spp, d_idx, d_descs + strip.base, d_init_mean,
+                       *opt, d_workspace, d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss,
+                       ticket(strip));
+    GAPRO_HIP_CHECK(ctx, mark(strip, 1));
   }
-  if (!small.empty()) {
-    // the small fits start behind the cluster kernel as well (GAPRO_SMALL_GATE=0: at once): beside the clusters run
-    // the whole-CU strip fits and the one-per-CU staged fits, and every CU half the two-per-CU staged fits leave later
-    // goes to a small fit, light on memory, instead of a second memory-bound one -- 367.8 / 367.4 / 362.6 scenes/s
-    // against 364.0 / 363.2 / 356.1, alternating on one box
-    static int gate_small = -1;
-    if (gate_small < 0) gate_small = getenv("GAPRO_SMALL_GATE") ? atoi(getenv("GAPRO_SMALL_GATE")) : 1;
-    if (gate_small && gate_staged2) GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(s_small, ctx->ev_gate, 0));
-    if (tm) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[4], s_small));
-    const int rc = gapro_launch_fit_strip_small(s_small, (int)small.size(), grid_of(small.size()), tk ? tk + 4 : nullptr,
-                                                feat_dim, (size_t)max_lds_small, d_feats_spp,
-                                                d_idx, d_descs + large.size() + staged.size() + strip.size(),
-                                                d_init_mean, opt, d_workspace, d_probs, d_probs_new, d_labels, d_mu,
-                                                d_var, d_fit_status, d_fit_loss);
+  if (!small.descs.empty()) {
+    // the small fits start behind the cluster kernel as well: beside the clusters run the whole-CU strip fits and the
+    // one-per-CU staged fits, and every CU half the two-per-CU staged fits leave later goes to a small fit, light on
+    // memory, instead of a second memory-bound one -- 367.8 / 367.4 / 362.6 scenes/s against 364.0 / 363.2 / 356.1
+    // without this gate, alternating on one box
+    if (gate) GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(on(small), ctx->ev_gate, 0));
+    GAPRO_HIP_CHECK(ctx, mark(small, 0));
+    const int rc = gapro_launch_fit_strip_small(on(small), (int)small.descs.size(), grid_of(small.descs.size()),
+                                                ticket(small), feat_dim, (size_t)small.max_lds, d_feats_spp, d_idx,
+                                                d_descs + small.base, d_init_mean, opt, d_workspace, d_probs,
+                                                d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
     if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: small-fit kernel launch failed");
-    if (tm) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[5], s_small));
+    GAPRO_HIP_CHECK(ctx, mark(small, 1));
   }
-  if (!wave[0].empty() || !wave[1].empty() || !wave[2].empty()) {
-    // One wave per fit (svgp_fit_wave.hip), one kernel per block count, side by side on their own streams; the waves
-    // of a kernel take its fits by ticket until none is left.  They touch no memory between their first and last step,
-    // so nothing holds them back: they take whatever wave slots and LDS the other kernels leave.
-    hipStream_t s_wave[3] = {own ? ctx->fit_stream[7] : stream, own ? ctx->fit_stream[6] : stream,
-                             own ? ctx->fit_stream[5] : stream};
-    const int first = !wave[2].empty() ? 2 : !wave[1].empty() ? 1 : 0;
-    if (tm) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[8], s_wave[first]));
-    for (int k = 2; k >= 0; --k) {
-      if (wave[k].empty()) continue;
-      const int slots = ctx->n_cu * gapro_fit_wave_per_cu(k + 1, feat_dim);
-      const int n_wg = (int)std::min<size_t>(wave[k].size(), (size_t)std::max(slots, 1));
-      const int rc = gapro_launch_fit_wave(s_wave[k], k + 1, (int)wave[k].size(), n_wg, tk ? tk + 8 + k : nullptr, feat_dim,
-                                           d_feats_spp, d_idx, d_descs + wave_base[k], d_init_mean, *opt, d_workspace,
-                                           d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
+  // One wave per fit (svgp_fit_wave.hip), one kernel per block count, side by side on their own streams; the waves of a
+  // kernel take its fits by ticket until none is left.  They touch no memory between their first and last step, so
+  // nothing holds them back: they take whatever wave slots and LDS the other kernels leave.  The stream of the first
+  // (largest) one collects the others.
+  int first = -1;
+  for (int g = G_WAVE3; g <= G_WAVE1 && first < 0; ++g)
+    if (!grp[g].descs.empty()) first = g;
+  if (first >= 0) {
+    const FitGroup& wf = grp[first];
+    GAPRO_HIP_CHECK(ctx, mark(wf, 0));
+    for (int g = G_WAVE3; g <= G_WAVE1; ++g) {
+      const FitGroup& w = grp[g];
+      if (w.descs.empty()) continue;
+      const int nb = G_WAVE1 + 1 - g;
+      const int slots = ctx->n_cu * gapro_fit_wave_per_cu(nb, feat_dim);
+      const int n_wg = (int)std::min<size_t>(w.descs.size(), (size_t)std::max(slots, 1));
+      const int rc = gapro_launch_fit_wave(on(w), nb, (int)w.descs.size(), n_wg, ticket(w), feat_dim, d_feats_spp,
+                                           d_idx, d_descs + w.base, d_init_mean, *opt, d_workspace, d_probs,
+                                           d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
       if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: wave kernel launch failed");
-      if (own && k != first) {  // everything wave-per-fit is finished once s_wave[first] has passed this point
-        GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[5 + k], s_wave[k]));
-        GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(s_wave[first], ctx->ev_join[5 + k], 0));
+      if (own && g != first) {
+        GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[w.join], on(w)));
+        GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(on(wf), ctx->ev_join[w.join], 0));
       }
     }
-    if (tm) GAPRO_HIP_CHECK(ctx, hipEventRecord(tm->ev[9], s_wave[first]));
+    GAPRO_HIP_CHECK(ctx, mark(wf, 1));
     if (own) {
-      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[5 + first], s_wave[first]));
-      GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_join[5 + first], 0));
+      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[wf.join], on(wf)));
+      GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_join[wf.join], 0));
     }
   }
-  if (own) {
-    if (!large.empty() || !staged.empty()) {
-      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[0], s_staged));
-      GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_join[0], 0));
-    }
-    if (!strip.empty()) {
-      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[1], s_strip));
-      GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_join[1], 0));
-    }
-    if (!small.empty()) {
-      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[2], s_small));
-      GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_join[2], 0));
-    }
-    if (!clus.empty()) {
-      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[3], s_clus));
-      GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_join[3], 0));
+  if (own) {  // the other streams, each once
+    bool joined[gapro_ctx::kFitStreams] = {};
+    for (int g = G_LARGE; g <= G_CLUSTER; ++g) {
+      const FitGroup& x = grp[g];
+      if (x.descs.empty() || joined[x.join]) continue;
+      joined[x.join] = true;
+      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[x.join], on(x)));
+      GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_join[x.join], 0));
     }
   }
   // conditioning figures, behind every kernel of the launch (they have been joined into `stream` above)

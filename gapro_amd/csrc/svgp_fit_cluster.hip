@@ -1725,9 +1725,9 @@ __global__ __launch_bounds__(NT, 2) void k_svgp_fit_cluster(const ClBlock* __res
   const ClBlock cb = blocks[blockIdx.x];
   if (cb.fit < 0) return;
   if (info && threadIdx.x == 0) atomicAdd(info, 1u);  // diagnostics (gapro_fit_timing_cluster_info)
-  // test bit 15 of gapro_fit_options.reserved: the last member of every cluster never arrives (as if it had not been
-  // given a CU) -- the others must time out and report GAPRO_ERR_TIMEOUT instead of hanging
-  if ((opt.reserved & 32768) && cb.G > 1 && cb.g == cb.G - 1) return;
+  // test bit: the last member of every cluster never arrives (as if it had not been given a CU) -- the others must time
+  // out and report GAPRO_ERR_TIMEOUT instead of hanging
+  if ((opt.reserved & GAPRO_FIT_DBG_CLUSTER_STALL) && cb.G > 1 && cb.g == cb.G - 1) return;
   const gapro_fit_desc desc = descs[cb.fit];
   Shared& sh = g_sh;
   Fit& f = sh.f;
@@ -1778,7 +1778,7 @@ __global__ __launch_bounds__(NT, 2) void k_svgp_fit_cluster(const ClBlock* __res
   // zero everything the kernel reads before writing (parameters / Adam state, padded operand tails)
   for (long long i = ct; i < lay.total; i += CT) base[i] = 0.0;
   cbar();
-  if (!(opt.reserved & 256)) detect_same_xcd();  // debug bit 8: always the full barrier
+  detect_same_xcd();
   if (info && threadIdx.x == 0 && cb.g == 0 && cb.G > 1) {  // diagnostics (gapro_fit_timing_cluster_info)
     atomicAdd(info + 2, 1u);
     if (!sh.same_xcd) atomicAdd(info + 1, 1u);
@@ -1808,16 +1808,11 @@ __global__ __launch_bounds__(NT, 2) void k_svgp_fit_cluster(const ClBlock* __res
     }
   }
   cbar();
-  // wave tiles of the M^3 products: 32 x 32, or 64 x 64 where M_p allows it (twice the FLOP per operand byte; the
-  // products of many concurrent fits stream their operands from HBM) -- debug bit 5 of gapro_fit_options.reserved
-  const bool wide = (opt.reserved & 32) && Mp % 64 == 0;
-  if (opt.precision == GAPRO_PRECISION_MIXED) {
-    if (wide) fit_body<true, 4>(opt, desc, o_probs, o_probs_new, o_labels, o_mu, o_var, &o_loss[desc.slot]);
-    else fit_body<true, 2>(opt, desc, o_probs, o_probs_new, o_labels, o_mu, o_var, &o_loss[desc.slot]);
-  } else {
-    if (wide) fit_body<false, 4>(opt, desc, o_probs, o_probs_new, o_labels, o_mu, o_var, &o_loss[desc.slot]);
-    else fit_body<false, 2>(opt, desc, o_probs, o_probs_new, o_labels, o_mu, o_var, &o_loss[desc.slot]);
-  }
+  // wave tiles of the M^3 products: 32 x 32 (64 x 64 measured no better: LABNOTES)
+  if (opt.precision == GAPRO_PRECISION_MIXED)
+    fit_body<true, 2>(opt, desc, o_probs, o_probs_new, o_labels, o_mu, o_var, &o_loss[desc.slot]);
+  else
+    fit_body<false, 2>(opt, desc, o_probs, o_probs_new, o_labels, o_mu, o_var, &o_loss[desc.slot]);
   __syncthreads();
   if (sh.g == 0 && threadIdx.x == 0) {
     int st = sh.status;
@@ -1830,33 +1825,13 @@ __global__ __launch_bounds__(NT, 2) void k_svgp_fit_cluster(const ClBlock* __res
 
 }  // namespace
 
-// Smallest padded M routed to this kernel by default (a fit below stays on one workgroup of the LDS-staged / strip
-// kernels).  Tunable for A/B runs through GAPRO_CLUSTER_MIN_MP (read once).
-int gapro_cluster_min_mp() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("GAPRO_CLUSTER_MIN_MP");
-    v = e ? atoi(e) : kClusterDefaultMinMp;
-    if (v < kClusterMinMp) v = kClusterMinMp;
-  }
-  return v;
-}
-
-// Workgroups a fit of padded size Mp is spread over by gapro_svgp_fit_batch; 0 = not a cluster fit.  `all`: every fit
-// the kernel can take (debug bit 4 of gapro_fit_options.reserved: precision sweeps through one kernel).
+// Workgroups a fit of padded size Mp is spread over by gapro_svgp_fit_batch; 0 = not a cluster fit.  By default the
+// kernel takes the fits from kClusterDefaultMinMp on (a fit below stays on one workgroup of the LDS-staged / strip
+// kernels); `all`: every fit it can take (GAPRO_FIT_DBG_CLUSTER_ALL: precision sweeps through one kernel).  A pure
+// function of Mp, never of the batch: the summation order inside a fit depends on G.
 int gapro_cluster_size(int Mp, bool all) {
-  if (!cluster_capable(Mp) || (!all && Mp < gapro_cluster_min_mp())) return 0;
-  // a pure function of Mp (never of the batch: the summation order inside a fit depends on G); the two environment
-  // variables are tuning knobs for tools/bench_fit.py
-  static double unit = 0.0;
-  static int pow2 = 1;
-  if (unit == 0.0) {
-    const char* e = getenv("GAPRO_CLUSTER_UNIT");
-    const char* r = getenv("GAPRO_CLUSTER_ROUND");
-    if (r) pow2 = strcmp(r, "ceil") != 0;
-    unit = e && atof(e) >= kClusterMinUnit ? atof(e) : 384.0;  // (the scratch planes are sized for kClusterMinUnit)
-  }
-  return cluster_g(Mp, unit, pow2 != 0);
+  if (!cluster_capable(Mp) || (!all && Mp < kClusterDefaultMinMp)) return 0;
+  return cluster_g(Mp);
 }
 
 // Internal launcher used by gapro_svgp_fit_batch (svgp_fit.hip).  `fits` = the n cluster fits' indices into the device

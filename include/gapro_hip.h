@@ -319,29 +319,32 @@ typedef struct {
   double min_variance;       /* 1e-6 gpytorch settings.min_variance */
   int32_t eval_stale_chol;   /* 0 = refactor K_ZZ with the trained parameters for prediction (default);
                                 1 = reuse the factor of the last training step */
-  int32_t reserved;          /* 0; debug bits: 1 = never route a fit to the strip-streaming kernels,
-                              * 2 = launch the fit kernels on the caller's stream (not the fit streams),
-                              * 4 = no small-fit kernel (M_p <= 64 runs the 512-thread strip kernel),
-                              * 8 = no cluster kernel (large fits stay on one workgroup),
-                              * 16 = the cluster kernel for every fit it can take (M_p >= 64, M_p % 32 == 0),
-                              * 32 = 64 x 64 wave tiles in the cluster kernel, 64 = the full-register build for every
-                              * staged launch, 128 = the staged fits as ONE launch (not split by their LDS need),
-                              * 256 = cluster barriers always with the L2 write-back, 512 = plain longest-first order
-                              * (no serpentine over the XCDs), 8192 = workgroup-tiled products through LDS in the staged
-                              * kernel at every M_p > 128 (default: M_p = 256, 384 only; bit-identical either way),
-                              * 16384 = with 8192: in the two-per-CU build only, 131072 = never (round 2's products),
-                              * 32768 = TEST: the last member of every cluster never arrives (cluster barrier timeout),
-                              * 262144 = workgroup b of a fit kernel runs fit b of its list (default: the workgroups
-                              * take the fits in the order in which they start, claim_fit in csrc/svgp_fit.hip),
-                              * 524288 = the two-per-CU staged launch is not held back behind the cluster kernel,
-                              * 1048576 = no wave-per-fit kernel (M_p <= 48 runs the small-fit strip kernel)
-                              * -- A/B switches of tools/bench_fit.py / fit_timeline.py */
+  int32_t reserved;          /* 0; debug bits GAPRO_FIT_DBG_* (below); any other bit is refused */
   int32_t psd_retries;       /* 3    gpytorch settings.cholesky_max_tries: a factorisation that meets a non-positive
                               *      pivot is repeated on K + psd_jitter 10^i I, i < psd_retries (psd_safe_cholesky,
                               *      reached from gaussian_process_utils.py:417); 0 = fail at once */
   int32_t precision;         /* GAPRO_PRECISION_*: arithmetic of the fit (0 = float64 throughout, the default) */
   double psd_jitter;         /* 1e-8 gpytorch settings.cholesky_jitter for float64 (K_ZZ is factored in double) */
 } gapro_fit_options;
+
+/* gapro_fit_options.reserved: debug bits, 0 in the product.  gapro_svgp_fit_batch refuses any bit not named here
+ * (GAPRO_ERR_BAD_ARG). */
+enum {
+  GAPRO_FIT_DBG_NO_STRIP = 1,             /* never route a fit to the strip-streaming kernels */
+  GAPRO_FIT_DBG_CALLER_STREAM = 2,        /* launch the fit kernels on the caller's stream (not the fit streams) */
+  GAPRO_FIT_DBG_NO_SMALL = 4,             /* no small-fit kernel (M_p <= 64 runs the 512-thread strip kernel) */
+  GAPRO_FIT_DBG_NO_CLUSTER = 8,           /* no cluster kernel (large fits stay on one workgroup) */
+  GAPRO_FIT_DBG_CLUSTER_ALL = 16,         /* the cluster kernel for every fit it can take (M_p >= 64, M_p % 32 == 0) */
+  GAPRO_FIT_DBG_WG_TILED_ALL = 8192,      /* workgroup-tiled products through LDS in the staged kernel at every
+                                           * M_p > 128 (default: M_p = 256, 384 only; bit-identical either way) */
+  GAPRO_FIT_DBG_CLUSTER_STALL = 32768,    /* TEST: the last member of every cluster never arrives (barrier timeout) */
+  GAPRO_FIT_DBG_WG_TILED_NONE = 131072,   /* no workgroup-tiled products (round 2's products) */
+  GAPRO_FIT_DBG_STATIC_MAP = 262144,      /* workgroup b of a fit kernel runs fit b of its list (default: the
+                                           * workgroups take the fits in the order in which they start, claim_fit in
+                                           * csrc/svgp_fit.hip) */
+  GAPRO_FIT_DBG_NO_WAVE = 1048576,        /* no wave-per-fit kernel (M_p <= 48 runs the small-fit strip kernel) */
+  GAPRO_FIT_DBG_ALL = 1 | 2 | 4 | 8 | 16 | 8192 | 32768 | 131072 | 262144 | 1048576
+};
 
 /* gapro_fit_options.precision */
 enum {

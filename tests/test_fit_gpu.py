@@ -830,6 +830,30 @@ def test_fits_taken_by_ticket_equal_the_static_block_mapping():
             np.testing.assert_array_equal(y, z)
 
 
+def test_fit_batch_refuses_retired_and_unknown_debug_bits():
+    """A debug bit of gapro_fit_options.reserved that names no switch (a retired A/B switch, or one never defined) makes
+    gapro_svgp_fit_batch fail with GAPRO_ERR_BAD_ARG and a message, instead of quietly running the default path; the
+    same pipeline fits again once the bit is cleared."""
+    import torch
+    from gapro_amd import gen_ps_utils
+    from gapro_amd._lib import GaproError
+    from gapro_amd.gaussian_process_utils import fit_gp_spp_batch
+    from gapro_amd.synth import make_gp_problem
+
+    f, b1, b2, it = make_gp_problem(7, 20, 24, 9, 6)
+    pipe = gen_ps_utils._pipeline(torch.device("cuda:0"), 3)
+    old = int(pipe.opt.reserved)
+    for bit in (32, 64, 128, 256, 512, 4096, 16384, 524288, 1 << 30):
+        try:
+            pipe.opt.reserved = old | bit
+            with pytest.raises(GaproError) as e:
+                fit_gp_spp_batch(f, [(b1, b2, it)], training_iter=3)
+        finally:
+            pipe.opt.reserved = old
+        assert e.value.code == -1 and "debug bits" in str(e.value), bit
+    assert np.isfinite(fit_gp_spp_batch(f, [(b1, b2, it)], training_iter=3)[0][3]).all()
+
+
 def test_workgroup_tiled_products_are_bit_identical_to_the_per_wave_products():
     """Round 3: the staged kernel's products through an LDS ring shared by the workgroup (default at
     M_p = 256, 384; everywhere with gapro_fit_options.reserved bit 13; nowhere with bit 17) accumulate every 16 x 16

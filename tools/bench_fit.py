@@ -106,8 +106,6 @@ def main():
     ap.add_argument("--no-small", action="store_true", help="M_p <= 64 on the 512-thread strip kernel (A/B)")
     ap.add_argument("--no-cluster", action="store_true", help="large fits stay on one workgroup (A/B)")
     ap.add_argument("--cluster-all", action="store_true", help="the cluster kernel for every fit it can take (A/B)")
-    ap.add_argument("--wide-tiles", action="store_true", help="64 x 64 wave tiles in the cluster kernel (A/B)")
-    ap.add_argument("--full-barriers", action="store_true", help="cluster barriers always with the L2 write-back (A/B)")
     ap.add_argument("--flags", type=int, default=0, help="further gapro_fit_options.reserved debug bits (A/B)")
     args = ap.parse_args()
     if args.profile:
@@ -127,10 +125,6 @@ def main():
         pipe.opt.reserved |= 8
     if args.cluster_all:
         pipe.opt.reserved |= 16
-    if args.wide_tiles:
-        pipe.opt.reserved |= 32
-    if args.full_barriers:
-        pipe.opt.reserved |= 256
     pipe.opt.reserved |= args.flags
     if args.mix:
         run_mix(pipe, args)

@@ -102,14 +102,10 @@ def main():
         if args.flags & 8 and r == 4:
             r = 1
         g = 1
-        if r == 4:  # the default policy of gapro_cluster_size (fit_layout.h)
-            unit = float(os.environ.get("GAPRO_CLUSTER_UNIT", 384))
-            work = float(lay[0]) ** 3 / unit ** 3
-            if os.environ.get("GAPRO_CLUSTER_ROUND") == "ceil":
-                g = int(min(32, max(1, np.ceil(work))))
-            else:
-                while g < 32 and g < work:
-                    g *= 2
+        if r == 4:  # gapro_cluster_size: cluster_g in fit_layout.h (work unit 384, powers of two, at most kClMaxG)
+            work = float(lay[0]) ** 3 / 384.0 ** 3
+            while g < 32 and g < work:
+                g *= 2
         rows.append((m, r, ws[o + 25], ws[o + 26], int(ws[o + 27]), max(g, 1)))
     a = np.array(rows, dtype=np.float64)
     t0 = a[:, 2].min()
