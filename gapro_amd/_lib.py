@@ -72,6 +72,16 @@ class EvalHeader(C.Structure):
     _fields_ = [("n_gt", C.c_int32), ("n_ps", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class EvalScene(C.Structure):
+    """gapro_eval_scene: one scene of a batched evaluation (gapro_eval_batch)."""
+    _fields_ = [("point_offset", C.c_int64), ("n_points", C.c_int64), ("max_gt", C.c_int32), ("max_ps", C.c_int32),
+                ("ws_offset", C.c_int64), ("row_offset", C.c_int64)]
+
+
+GAPRO_LABEL_F64, GAPRO_LABEL_I32, GAPRO_LABEL_I64 = 1, 2, 3
+GAPRO_EVAL_MAX_THRESHOLDS = 32
+
+
 class FitOptions(C.Structure):
     _fields_ = [("training_iter", C.c_int32), ("lr", C.c_double), ("jitter", C.c_double),
                 ("min_variance", C.c_double), ("eval_stale_chol", C.c_int32), ("reserved", C.c_int32),
@@ -103,6 +113,10 @@ SIGNATURES = {
     "gapro_eval_miou": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, _P,
                                   _P]),
     "gapro_eval_sem_confusion": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P]),
+    "gapro_eval_batch_workspace_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "gapro_eval_batch": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P,
+                                   C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, _P,
+                                   _P, _P]),
     "gapro_label_heuristic_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "gapro_label_heuristic": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32,
                                         C.c_int32, _P, C.c_size_t, _P, _P]),

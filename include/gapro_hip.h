@@ -212,6 +212,47 @@ int gapro_eval_miou(gapro_ctx* ctx, void* stream, int64_t n_points, const int64_
 int gapro_eval_sem_confusion(gapro_ctx* ctx, void* stream, int64_t n_points, const int64_t* d_semantic_label,
                              const int64_t* d_ps_semantic_label, int32_t num_classes, int64_t* d_conf);
 
+/* Batched pseudo-label evaluation (the reference's eval_ps_labels.py main(), :175-257): get_miou_scene and
+ * get_scene_sem_conf for a batch of scenes laid out back to back in the label arrays, unfiltered (row 0) and
+ * for K probability thresholds (row t = the points with prob >= thresholds[t-1], the reference's commented-out
+ * certain_cond filter :214-220, applied to all four arrays), in one pass over the points.  Integer atomics only:
+ * every row is bit-identical to gapro_eval_miou / gapro_eval_sem_confusion run on the filtered scene alone. */
+enum {
+  GAPRO_LABEL_F64 = 1,  /* ScanNet *_inst_nostuff.pth labels */
+  GAPRO_LABEL_I32 = 2,  /* gen_ps label files */
+  GAPRO_LABEL_I64 = 3
+};
+#define GAPRO_EVAL_MAX_THRESHOLDS 32
+
+typedef struct {
+  int64_t point_offset;  /* in : first point of the scene in the label arrays                              */
+  int64_t n_points;      /* in : may be 0                                                                  */
+  int32_t max_gt;        /* in : GT instance ids are < max_gt (>= 1); a larger id sets status[scene]       */
+  int32_t max_ps;        /* in : pseudo instance ids are < max_ps (>= 1)                                   */
+  int64_t ws_offset;     /* set by gapro_eval_batch_workspace_bytes: the scene's bytes in the workspace    */
+  int64_t row_offset;    /* set by gapro_eval_batch_workspace_bytes: the scene's first entry in d_max_iou  */
+} gapro_eval_scene;
+
+/* Fills ws_offset / row_offset of h_scenes[n_scenes] and returns the workspace size in bytes; the IoU outputs
+ * hold row_offset[last] + (n_thresholds + 1) * max_gt[last] entries (0 on a bad argument). */
+size_t gapro_eval_batch_workspace_bytes(gapro_eval_scene* h_scenes, int32_t n_scenes, int32_t n_thresholds);
+/*   in : labels of n_total_points points, each array in its own dtype code (GT: F64 / I32 / I64, pseudo: I32 /
+ *        I64); d_prob f32[n_total_points] (NULL when n_thresholds = 0); h_thresholds f32[n_thresholds],
+ *        ascending (host); scannet_remap != 0 applies sem[sem != -100] -= 2, then -1 / -2 -> 18 to the GT
+ *        semantic labels (:196-197); h_scenes as filled above, d_scenes device space for n_scenes of them.
+ *   out: d_max_iou / d_gt_cls f32 at row_offset + t * max_gt + g: scene, threshold row t, GT id g, as
+ *        gapro_eval_miou (the caller keeps the entries with class >= 0, :139);
+ *        d_conf i64[n_thresholds + 1, C, C] summed over the batch; d_kept i64[n_scenes, n_thresholds + 1]
+ *        points per scene and row; d_status i32[n_scenes] (GAPRO_ERR_BAD_ARG: an id beyond max_gt / max_ps:
+ *        that scene's IoUs are not valid).  Enqueue only. */
+int gapro_eval_batch(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro_eval_scene* h_scenes,
+                     gapro_eval_scene* d_scenes, int64_t n_total_points, int32_t sem_gt_dtype, const void* d_sem_gt,
+                     int32_t inst_gt_dtype, const void* d_inst_gt, int32_t sem_ps_dtype, const void* d_sem_ps,
+                     int32_t inst_ps_dtype, const void* d_inst_ps, const float* d_prob, int32_t n_thresholds,
+                     const float* h_thresholds, int32_t scannet_remap, int32_t num_classes, void* d_workspace,
+                     size_t workspace_bytes, float* d_max_iou, float* d_gt_cls, int64_t* d_conf, int64_t* d_kept,
+                     int32_t* d_status);
+
 /* Heuristic labelers: gen_pseudo_label (gen_ps_utils.py:485-569; rule 0 = "volume",
  * 1 = "dist", 2 = "none") and gen_pseudo_label_box2mask (:242-290; rule 3).  Membership in the INSTANCE boxes
  * (float32 box, 0.005 margin applied in float32, compared in float64), the rule for points inside several boxes,
