@@ -68,10 +68,6 @@ class InstanceHeader(C.Structure):
     _fields_ = [("instance_num", C.c_int32), ("n_boxes", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
-class EvalHeader(C.Structure):
-    _fields_ = [("n_gt", C.c_int32), ("n_ps", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
-
-
 class EvalScene(C.Structure):
     """gapro_eval_scene: one scene of a batched evaluation (gapro_eval_batch)."""
     _fields_ = [("point_offset", C.c_int64), ("n_points", C.c_int64), ("max_gt", C.c_int32), ("max_ps", C.c_int32),
@@ -109,10 +105,6 @@ SIGNATURES = {
     "gapro_instance_info_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gapro_instance_info": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, _P, _P,
                                       _P, _P]),
-    "gapro_eval_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
-    "gapro_eval_miou": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, _P,
-                                  _P]),
-    "gapro_eval_sem_confusion": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P]),
     "gapro_eval_batch_workspace_bytes": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
     "gapro_eval_batch": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P,
                                    C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, _P,

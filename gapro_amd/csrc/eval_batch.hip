@@ -1,13 +1,14 @@
-// Batched pseudo-label evaluation: the reference's eval_ps_labels.py main() (:175-257) over a batch of scenes laid
-// out back to back, with K probability thresholds in the same pass (the certain_cond filter, :214-220).
+// Pseudo-label quality evaluation: the reference's get_miou_scene / cal_iou (eval_ps_labels.py:35-42,100-147) and
+// get_scene_sem_conf (:150-172) over a batch of scenes laid out back to back, with K probability thresholds in the
+// same pass (main()'s certain_cond filter, :214-220).  A single scene is a batch of one without thresholds.
 //
 // A point of a scene falls in bin b = #{j : prob >= thresholds[j]} (thresholds ascending; bin 0 without thresholds).
-// The point pass tallies per (scene, bin) exactly what labels.hip's k_eval_pairs / k_sem_conf tally per scene:
-// (gt + 1, ps + 1) pair counts, the first point of every id, the confusion bins and the point count.  Row t of the
-// result keeps the points with bin >= t, so a suffix sum (counts) / suffix min (first points) over the bins turns the
-// bin tables into the row tables, and the finalize step is k_eval_finalize's arithmetic on them.  Integer atomics
-// only, floats only in the finalize: every row is bit-identical to the per-scene kernels run on the filtered scene,
-// whatever the batch composition.
+// One histogram pass over the points tallies per (scene, bin) the (gt + 1, ps + 1) pair counts (the intersections
+// of the reference's one-hot matrix product, :36), the first point of every id, the confusion bins and the point
+// count.  Row t of the result keeps the points with bin >= t, so a suffix sum (counts) / suffix min (first points)
+// over the bins turns the bin tables into the row tables, and the finalize step computes the IoUs from them.
+// Integer atomics only, floats only in the finalize: every row is bit-identical to the reference on the filtered
+// scene, whatever the batch composition.  Without instance arrays only the confusion and the counts are tallied.
 #include "common.h"
 
 #include <algorithm>
@@ -16,8 +17,8 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kLdsIds = 512;    // (bin, id) first-point entries kept in LDS per table, as labels.hip
-constexpr int kPairLds = 8192;  // (bin, gt, ps) pair-count bins kept in LDS, as labels.hip
+constexpr int kLdsIds = 512;    // (bin, id) first-point entries kept in LDS per table
+constexpr int kPairLds = 8192;  // (bin, gt, ps) pair-count bins kept in LDS
 constexpr int kConfLds = 2048;  // (bin, gt class, ps class) confusion bins kept in LDS (C = 19: five bins)
 constexpr int kMaxBins = GAPRO_EVAL_MAX_THRESHOLDS + 1;
 constexpr unsigned long long kKeyMax = ~0ull;
@@ -85,7 +86,8 @@ __global__ __launch_bounds__(kThreads) void k_evb_init(const gapro_eval_scene* _
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n_int; i += stride) t.pair[i] = 0;
 }
 
-// the point pass: one histogram pass per scene (blockIdx.y), LDS-privatised when the scene's tables are small
+// the point pass: one histogram pass per scene (blockIdx.y), LDS-privatised when the scene's tables are small;
+// inst_gt == NULL (then inst_ps too): a confusion-only launch, no pair or first-point tallies
 template <class TGS, class TGI, class TPS, class TPI>
 __global__ __launch_bounds__(kThreads) void k_evb_points(const gapro_eval_scene* __restrict__ scenes,
                                                          const TGS* __restrict__ sem_gt, const TGI* __restrict__ inst_gt,
@@ -106,6 +108,7 @@ __global__ __launch_bounds__(kThreads) void k_evb_points(const gapro_eval_scene*
   const bool lds_pair = (long long)B * t.nbin <= kPairLds;
   const int CC = C * C;
   const bool lds_conf = B * CC <= kConfLds;
+  const bool pairs = inst_gt != nullptr;
   for (int j = threadIdx.x; j < kLdsIds; j += kThreads) {
     s_fg[j] = kKeyMax;
     s_fp[j] = kKeyMax;
@@ -125,7 +128,7 @@ __global__ __launch_bounds__(kThreads) void k_evb_points(const gapro_eval_scene*
       for (int j = 0; j < K; ++j) b += pr >= thr.t[j] ? 1 : 0;
     }
     atomicAdd(&s_kept[b], 1);
-    // get_scene_sem_conf (eval_ps_labels.py:150-172), as k_sem_conf
+    // get_scene_sem_conf (eval_ps_labels.py:150-172): unlabeled pseudo points count as a wrong class (:157-161)
     const long long sg = remap_gt(label_at(sem_gt, gi_), remap);
     if (sg != -100) {
       long long sp = label_at(sem_ps, gi_);
@@ -136,7 +139,8 @@ __global__ __launch_bounds__(kThreads) void k_evb_points(const gapro_eval_scene*
         else atomicAdd((unsigned long long*)&conf[(long long)b * CC + x], 1ull);
       }
     }
-    // get_miou_scene's pair counts and first points (eval_ps_labels.py:101-124), as k_eval_pairs
+    if (!pairs) continue;
+    // get_miou_scene's pair counts and first points (eval_ps_labels.py:101-124); an id < 0 counts as none (:118,124)
     const long long g = label_at(inst_gt, gi_), p = label_at(inst_ps, gi_);
     if (g >= t.cap_gt || p >= t.cap_ps) {
       atomicExch(&status[scene], GAPRO_ERR_BAD_ARG);
@@ -216,7 +220,8 @@ __global__ __launch_bounds__(kThreads) void k_evb_ps_count(const gapro_eval_scen
   }
 }
 
-// per (scene, row, gt id): k_eval_finalize's arithmetic on the row's tables
+// per (scene, row, gt id): the largest inter / (|gt| + |ps| - inter + 1e-4) over the pseudo instances of the same
+// class, float32 in the reference's operation order (:36-40,131-136); class = label of the first point or -1
 template <class TGS, class TPS>
 __global__ __launch_bounds__(kThreads) void k_evb_finalize(const gapro_eval_scene* __restrict__ scenes,
                                                            const TGS* __restrict__ sem_gt, const TPS* __restrict__ sem_ps,
@@ -297,10 +302,13 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapr
                      int32_t* d_status) {
   if (!ctx) return GAPRO_ERR_BAD_ARG;
   const int K = n_thresholds, B = K + 1;
+  const bool pairs = d_inst_gt || d_inst_ps;  // false: confusion-only, the instance dtype codes are ignored
+  if (!pairs) inst_gt_dtype = inst_ps_dtype = GAPRO_LABEL_I64;
   if (n_scenes < 1 || n_scenes > 65535 || !h_scenes || !d_scenes || n_total_points < 0 || K < 0 ||
       K > GAPRO_EVAL_MAX_THRESHOLDS || (K > 0 && (!h_thresholds || (n_total_points > 0 && !d_prob))) ||
-      num_classes < 1 || num_classes > 128 || !d_workspace || !d_max_iou || !d_gt_cls || !d_conf || !d_kept ||
-      !d_status || (n_total_points > 0 && (!d_sem_gt || !d_inst_gt || !d_sem_ps || !d_inst_ps)))
+      num_classes < 1 || num_classes > 128 || !d_workspace || (pairs && (!d_max_iou || !d_gt_cls)) || !d_conf ||
+      !d_kept || !d_status ||
+      (n_total_points > 0 && (!d_sem_gt || !d_sem_ps || (pairs && (!d_inst_gt || !d_inst_ps)))))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_batch: bad argument");
   if (!with_gt_type(sem_gt_dtype, [](auto) {}) || !with_gt_type(inst_gt_dtype, [](auto) {}) ||
       !with_ps_type(sem_ps_dtype, [](auto) {}) || !with_ps_type(inst_ps_dtype, [](auto) {}))
@@ -361,17 +369,19 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapr
     hipLaunchKernelGGL(k_evb_suffix_counts, dim3(blocks_for((long long)CC + n_scenes, 1, 64)), dim3(kThreads), 0, stream,
                        (long long*)d_conf, CC, (long long*)d_kept, (int)n_scenes, B);
   }
-  hipLaunchKernelGGL(k_evb_ps_count, dim3(blocks_for((long long)B * ps_max, 1, 64), n_scenes), dim3(kThreads), 0, stream,
-                     d_scenes, d_workspace, B);
-  with_gt_type(sem_gt_dtype, [&](auto sgt) {
-    with_ps_type(sem_ps_dtype, [&](auto sps) {
-      using TGS = std::remove_const_t<std::remove_pointer_t<decltype(sgt)>>;
-      using TPS = std::remove_const_t<std::remove_pointer_t<decltype(sps)>>;
-      hipLaunchKernelGGL((k_evb_finalize<TGS, TPS>), dim3(blocks_for((long long)B * gt_max, 1, 64), n_scenes),
-                         dim3(kThreads), 0, stream, d_scenes, (const TGS*)d_sem_gt, (const TPS*)d_sem_ps,
-                         (int)(scannet_remap != 0), d_workspace, B, d_max_iou, d_gt_cls);
+  if (d_max_iou && d_gt_cls) {
+    hipLaunchKernelGGL(k_evb_ps_count, dim3(blocks_for((long long)B * ps_max, 1, 64), n_scenes), dim3(kThreads), 0,
+                       stream, d_scenes, d_workspace, B);
+    with_gt_type(sem_gt_dtype, [&](auto sgt) {
+      with_ps_type(sem_ps_dtype, [&](auto sps) {
+        using TGS = std::remove_const_t<std::remove_pointer_t<decltype(sgt)>>;
+        using TPS = std::remove_const_t<std::remove_pointer_t<decltype(sps)>>;
+        hipLaunchKernelGGL((k_evb_finalize<TGS, TPS>), dim3(blocks_for((long long)B * gt_max, 1, 64), n_scenes),
+                           dim3(kThreads), 0, stream, d_scenes, (const TGS*)d_sem_gt, (const TPS*)d_sem_ps,
+                           (int)(scannet_remap != 0), d_workspace, B, d_max_iou, d_gt_cls);
+      });
     });
-  });
+  }
   GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;
 }

@@ -1,10 +1,10 @@
-// Label-side kernels on either end of the pseudo-label path:
-//   * getInstanceInfo            reference gapro/gen_ps_utils.py:195-239  (input producer: GT boxes)
-//   * get_miou_scene / cal_iou   reference gapro/eval_ps_labels.py:35-42,100-147 (quality evaluator)
-//   * get_scene_sem_conf         reference gapro/eval_ps_labels.py:150-172
-// All three are single streaming passes over the point arrays with small per-instance tables: the tables are
-// privatised in LDS per workgroup and merged with integer atomics (min / max / add commute, so the results
-// are bit-reproducible and independent of the launch shape).
+// Label-side kernels on the input end of the pseudo-label path:
+//   * getInstanceInfo              reference gapro/gen_ps_utils.py:195-239  (input producer: GT boxes)
+//   * gen_pseudo_label / box2mask  reference gapro/gen_ps_utils.py:242-290,485-569 (heuristic labelers)
+// getInstanceInfo is a single streaming pass over the points with small per-instance tables: the tables are
+// privatised in LDS per workgroup and merged with integer atomics (min / max commute, so the results are
+// bit-reproducible and independent of the launch shape).  The quality evaluator (get_miou_scene,
+// get_scene_sem_conf) lives in eval_batch.hip.
 #include "common.h"
 
 #include <algorithm>
@@ -13,7 +13,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kLdsIds = 512;            // instance ids whose tallies fit the per-workgroup LDS table
-constexpr int kPairLds = 8192;          // (gt, ps) pair-count bins kept in LDS
 constexpr unsigned long long kKeyMax = ~0ull;
 
 inline int grid_for(long long n, int cap = 1024) {
@@ -181,151 +180,6 @@ __global__ __launch_bounds__(kThreads) void k_inst_corners(long long n, const do
       corners[6 * i + 3 + k] = on ? (float)(double_of(t.hi[3 * id + k]) - x) : -100.0f;
     }
   }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// get_miou_scene
-// ---------------------------------------------------------------------------------------------------
-struct EvalTable {
-  int* pair;                    // [(cap_gt + 1) * (cap_ps + 1)] point counts of (gt + 1, ps + 1) pairs, 0 = no id
-  unsigned long long* first_gt;  // [cap_gt] first point of a gt id
-  unsigned long long* first_ps;  // [cap_ps]
-  int* max_gt;                   // [1]
-  int* max_ps;                   // [1]
-  int* status;                   // [1]
-};
-__device__ inline EvalTable eval_table(void* ws, int cap_gt, int cap_ps) {
-  EvalTable t;
-  unsigned long long* p = (unsigned long long*)ws;
-  t.first_gt = p;
-  t.first_ps = p + cap_gt;
-  t.pair = (int*)(p + cap_gt + cap_ps);
-  t.max_gt = t.pair + (size_t)(cap_gt + 1) * (cap_ps + 1);
-  t.max_ps = t.max_gt + 1;
-  t.status = t.max_ps + 1;
-  return t;
-}
-
-__global__ __launch_bounds__(kThreads) void k_eval_init(void* ws, int cap_gt, int cap_ps) {
-  EvalTable t = eval_table(ws, cap_gt, cap_ps);
-  const long long nbin = (long long)(cap_gt + 1) * (cap_ps + 1);
-  const long long stride = (long long)gridDim.x * kThreads;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < nbin; i += stride) t.pair[i] = 0;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < cap_gt; i += stride) t.first_gt[i] = kKeyMax;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < cap_ps; i += stride) t.first_ps[i] = kKeyMax;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    *t.max_gt = -1;
-    *t.max_ps = -1;
-    *t.status = GAPRO_OK;
-  }
-}
-
-// the intersection counts of the reference's one-hot matrix product (eval_ps_labels.py:36) are the counts of
-// (gt id, pseudo id) pairs over the points: one histogram pass, LDS-privatised when the table is small
-__global__ __launch_bounds__(kThreads) void k_eval_pairs(long long n, const long long* __restrict__ inst,
-                                                         const long long* __restrict__ ps_inst, void* ws, int cap_gt,
-                                                         int cap_ps) {
-  EvalTable t = eval_table(ws, cap_gt, cap_ps);
-  __shared__ int s_pair[kPairLds];
-  __shared__ unsigned long long s_fg[kLdsIds], s_fp[kLdsIds];
-  for (int j = threadIdx.x; j < kLdsIds; j += kThreads) {
-    s_fg[j] = kKeyMax;
-    s_fp[j] = kKeyMax;
-  }
-  const int W = cap_ps + 1;
-  const long long nbin = (long long)(cap_gt + 1) * W;
-  const bool lds = nbin <= kPairLds;
-  if (lds)
-    for (int j = threadIdx.x; j < (int)nbin; j += kThreads) s_pair[j] = 0;
-  __syncthreads();
-  int mg = -1, mp = -1;
-  const long long stride = (long long)gridDim.x * kThreads;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
-    const long long g = inst[i], p = ps_inst[i];
-    if (g >= cap_gt || p >= cap_ps) {
-      atomicExch(t.status, GAPRO_ERR_BAD_ARG);
-      continue;
-    }
-    const int gi = g < 0 ? 0 : (int)g + 1, pi = p < 0 ? 0 : (int)p + 1;  // torch.where(label < 0, 0, label + 1)  :118,124
-    if (lds) atomicAdd(&s_pair[gi * W + pi], 1);
-    else atomicAdd(&t.pair[(long long)gi * W + pi], 1);
-    if (g >= 0) {
-      if (g < kLdsIds) atomicMin(&s_fg[g], (unsigned long long)i);
-      else atomicMin(&t.first_gt[g], (unsigned long long)i);
-      mg = (int)g > mg ? (int)g : mg;
-    }
-    if (p >= 0) {
-      if (p < kLdsIds) atomicMin(&s_fp[p], (unsigned long long)i);
-      else atomicMin(&t.first_ps[p], (unsigned long long)i);
-      mp = (int)p > mp ? (int)p : mp;
-    }
-  }
-  if (mg >= 0) atomicMax(t.max_gt, mg);
-  if (mp >= 0) atomicMax(t.max_ps, mp);
-  __syncthreads();
-  if (lds)
-    for (int j = threadIdx.x; j < (int)nbin; j += kThreads)
-      if (s_pair[j]) atomicAdd(&t.pair[j], s_pair[j]);
-  for (int j = threadIdx.x; j < kLdsIds; j += kThreads) {
-    if (j < cap_gt && s_fg[j] != kKeyMax) atomicMin(&t.first_gt[j], s_fg[j]);
-    if (j < cap_ps && s_fp[j] != kKeyMax) atomicMin(&t.first_ps[j], s_fp[j]);
-  }
-}
-
-// per gt id: max over the pseudo instances of the same class of inter / (|gt| + |ps| - inter + 1e-4), float32
-// in the reference's operation order (eval_ps_labels.py:36-40,131-136); class = label of the first point or -1
-__global__ __launch_bounds__(kThreads) void k_eval_finalize(void* ws, int cap_gt, int cap_ps,
-                                                            const long long* __restrict__ sem,
-                                                            const long long* __restrict__ ps_sem,
-                                                            float* __restrict__ max_iou, float* __restrict__ gt_cls,
-                                                            gapro_eval_header* __restrict__ header) {
-  EvalTable t = eval_table(ws, cap_gt, cap_ps);
-  const int n_gt = *t.max_gt + 1, n_ps = *t.max_ps + 1, W = cap_ps + 1;
-  for (int g = blockIdx.x * kThreads + threadIdx.x; g < n_gt; g += gridDim.x * kThreads) {
-    const float cg = t.first_gt[g] == kKeyMax ? -1.0f : (float)sem[t.first_gt[g]];
-    long long gt_n = 0;
-    for (int p = 0; p <= n_ps; ++p) gt_n += t.pair[(long long)(g + 1) * W + p];
-    float best = 0.0f;  // no pseudo instance at all: every IoU is 0
-    for (int p = 0; p < n_ps; ++p) {
-      const float cp = t.first_ps[p] == kKeyMax ? -1.0f : (float)ps_sem[t.first_ps[p]];
-      long long ps_n = 0;
-      for (int q = 0; q <= n_gt; ++q) ps_n += t.pair[(long long)q * W + p + 1];
-      const float inter = (float)t.pair[(long long)(g + 1) * W + p + 1];
-      const float iou = inter / ((float)gt_n + (float)ps_n - inter + 1e-4f);
-      const float v = iou * (cg == cp ? 1.0f : 0.0f);
-      best = (p == 0 || v > best) ? v : best;
-    }
-    max_iou[g] = best;
-    gt_cls[g] = cg;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    header->n_gt = n_gt;
-    header->n_ps = n_ps;
-    header->status = *t.status;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// get_scene_sem_conf
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void k_sem_conf(long long n, const long long* __restrict__ sem,
-                                                       const long long* __restrict__ ps_sem, int C,
-                                                       long long* __restrict__ conf) {
-  extern __shared__ int s_conf[];
-  for (int j = threadIdx.x; j < C * C; j += kThreads) s_conf[j] = 0;
-  __syncthreads();
-  const long long stride = (long long)gridDim.x * kThreads;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
-    const long long s = sem[i];
-    if (s == -100) continue;                                    // pos_inds  :151
-    long long p = ps_sem[i];
-    if (p == -100) p = s < 18 ? s + 1 : s - 1;                  // unlabeled pseudo points count as wrong  :157-161
-    const long long x = p + (long long)C * s;                    // :163
-    if (x >= 0 && x < (long long)C * C) atomicAdd(&s_conf[x], 1);
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < C * C; j += kThreads)
-    if (s_conf[j]) atomicAdd((unsigned long long*)&conf[j], (unsigned long long)s_conf[j]);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -569,54 +423,6 @@ int gapro_instance_info(gapro_ctx* ctx, void* stream_, int64_t n_points, const d
   GAPRO_LAUNCH_CHECK(ctx);
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(h_header_pinned, d_header, sizeof(gapro_instance_header), hipMemcpyDeviceToHost,
                                       stream));
-  return GAPRO_OK;
-}
-
-size_t gapro_eval_workspace_bytes(int32_t max_gt, int32_t max_ps) {
-  if (max_gt < 1) max_gt = 1;
-  if (max_ps < 1) max_ps = 1;
-  return align_up(((size_t)max_gt + max_ps) * sizeof(unsigned long long) +
-                      ((size_t)(max_gt + 1) * (max_ps + 1) + 3) * sizeof(int), 256);
-}
-
-int gapro_eval_miou(gapro_ctx* ctx, void* stream_, int64_t n_points, const int64_t* d_semantic_label,
-                    const int64_t* d_instance_label, const int64_t* d_ps_semantic_label,
-                    const int64_t* d_ps_instance_label, int32_t max_gt, int32_t max_ps, void* d_workspace,
-                    size_t workspace_bytes, float* d_max_iou, float* d_gt_cls, gapro_eval_header* d_header,
-                    gapro_eval_header* h_header_pinned) {
-  if (!ctx) return GAPRO_ERR_BAD_ARG;
-  if (n_points <= 0 || !d_semantic_label || !d_instance_label || !d_ps_semantic_label || !d_ps_instance_label ||
-      max_gt < 1 || max_ps < 1 || !d_workspace || !d_max_iou || !d_gt_cls || !d_header || !h_header_pinned)
-    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_miou: bad argument");
-  if (workspace_bytes < gapro_eval_workspace_bytes(max_gt, max_ps))
-    return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_eval_miou: workspace too small");
-  hipStream_t stream = (hipStream_t)stream_;
-  const long long nbin = (long long)(max_gt + 1) * (max_ps + 1);
-  hipLaunchKernelGGL(k_eval_init, dim3(grid_for(nbin, 256)), dim3(kThreads), 0, stream, d_workspace, (int)max_gt,
-                     (int)max_ps);
-  hipLaunchKernelGGL(k_eval_pairs, dim3(grid_for(n_points, 512)), dim3(kThreads), 0, stream, (long long)n_points,
-                     (const long long*)d_instance_label, (const long long*)d_ps_instance_label, d_workspace, (int)max_gt,
-                     (int)max_ps);
-  hipLaunchKernelGGL(k_eval_finalize, dim3(grid_for(max_gt, 64)), dim3(kThreads), 0, stream, d_workspace, (int)max_gt,
-                     (int)max_ps, (const long long*)d_semantic_label, (const long long*)d_ps_semantic_label, d_max_iou,
-                     d_gt_cls, d_header);
-  GAPRO_LAUNCH_CHECK(ctx);
-  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(h_header_pinned, d_header, sizeof(gapro_eval_header), hipMemcpyDeviceToHost, stream));
-  return GAPRO_OK;
-}
-
-int gapro_eval_sem_confusion(gapro_ctx* ctx, void* stream_, int64_t n_points, const int64_t* d_semantic_label,
-                             const int64_t* d_ps_semantic_label, int32_t num_classes, int64_t* d_conf) {
-  if (!ctx) return GAPRO_ERR_BAD_ARG;
-  if (n_points <= 0 || !d_semantic_label || !d_ps_semantic_label || num_classes < 1 || num_classes > 128 || !d_conf)
-    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_sem_confusion: bad argument");
-  hipStream_t stream = (hipStream_t)stream_;
-  const size_t bins = (size_t)num_classes * num_classes;
-  GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_conf, 0, bins * sizeof(int64_t), stream));
-  hipLaunchKernelGGL(k_sem_conf, dim3(grid_for(n_points, 256)), dim3(kThreads), bins * sizeof(int), stream,
-                     (long long)n_points, (const long long*)d_semantic_label, (const long long*)d_ps_semantic_label,
-                     (int)num_classes, (long long*)d_conf);
-  GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;
 }
 

@@ -2,13 +2,13 @@
 
 SURVEY.md section 8(f) row 1 ("next"): not part of the generator's hot path; wired to ``gen_ps --eval_pslabel``.
 Same call signatures as the reference (which runs them on ``.cuda()`` tensors); the work is done by the HIP
-kernels of gapro_amd/csrc/labels.hip behind ``gapro_eval_miou`` / ``gapro_eval_sem_confusion``: one histogram
-pass over the points instead of two [I, N] one-hot matrices and their product.  There is no CPU path: inputs
-are moved to the device, and without a HIP device the call raises.
+kernels of gapro_amd/csrc/eval_batch.hip behind ``gapro_eval_batch``, called for a batch of one scene: one
+histogram pass over the points instead of two [I, N] one-hot matrices and their product.  There is no CPU path:
+inputs are moved to the device, and without a HIP device the call raises.
 
-``evaluate_scenes`` is the batched form (gapro_amd/csrc/eval_batch.hip behind ``gapro_eval_batch``): a batch of
-scenes in their file dtypes, the unfiltered metrics plus any number of ``ps_prob >= tau`` filters (the reference's
-commented-out certain_cond study, :214-220), bit-identical to the two per-scene functions on the filtered arrays.
+``evaluate_scenes`` is the batched form: a batch of scenes in their file dtypes, the unfiltered metrics plus any
+number of ``ps_prob >= tau`` filters (the reference's commented-out certain_cond study, :214-220), bit-identical to
+the two per-scene functions on the filtered arrays.
 ``python -m gapro_amd.eval_ps_labels`` is the reference's stand-alone evaluation of a folder of pseudo-labels
 (main(), :175-257) on top of it:
 
@@ -30,12 +30,22 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Context, EvalHeader
+from ._lib import Context
+
+_GT_CODES = {torch.float64: _lib.GAPRO_LABEL_F64, torch.int32: _lib.GAPRO_LABEL_I32, torch.int64: _lib.GAPRO_LABEL_I64}
+_PS_CODES = {torch.int32: _lib.GAPRO_LABEL_I32, torch.int64: _lib.GAPRO_LABEL_I64}
 
 
-def _dev_long(t, device):
-    t = t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
-    return t.to(device=device, dtype=torch.int64).contiguous()
+def _as_tensor(a):
+    if isinstance(a, torch.Tensor):
+        return a.reshape(-1)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a)).reshape(-1))
+
+
+def _dev_labels(a, device, codes):
+    """The labels on the device, in their own dtype when the kernels have a code for it, else as int64."""
+    t = _as_tensor(a)
+    return t.to(device=device, dtype=t.dtype if t.dtype in codes else torch.int64).contiguous()
 
 
 def _device_of(*tensors):
@@ -53,52 +63,23 @@ def get_miou_scene(semantic_label, instance_label, ps_semantic_label, ps_instanc
     IoU = inter / (|gt| + |ps| - inter + 1e-4), float32 as in ``cal_iou`` (:35-42).  Returns a float32 device
     tensor with one entry per non-empty GT instance id, in id order."""
     dev = _device_of(semantic_label, instance_label, ps_semantic_label, ps_instance_label)
-    sem, ins = _dev_long(semantic_label, dev), _dev_long(instance_label, dev)
-    ps_sem, ps_ins = _dev_long(ps_semantic_label, dev), _dev_long(ps_instance_label, dev)
+    sem, ins = (_dev_labels(a, dev, _GT_CODES) for a in (semantic_label, instance_label))
+    ps_sem, ps_ins = (_dev_labels(a, dev, _PS_CODES) for a in (ps_semantic_label, ps_instance_label))
     n = int(ins.numel())
     if n == 0:
         return torch.zeros(0, device=dev)
-    ctx = Context.get(dev.index or 0)
-    lib = ctx.lib
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        cap_gt, cap_ps = 256, 256
-        while True:
-            ws_bytes = int(lib.gapro_eval_workspace_bytes(cap_gt, cap_ps))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            max_iou = torch.empty(cap_gt, dtype=torch.float32, device=dev)
-            gt_cls = torch.empty(cap_gt, dtype=torch.float32, device=dev)
-            d_hdr = torch.empty(C.sizeof(EvalHeader), dtype=torch.uint8, device=dev)
-            h_hdr = torch.empty(C.sizeof(EvalHeader), dtype=torch.uint8, pin_memory=True)
-            ctx.check(lib.gapro_eval_miou(ctx.handle, stream, n, sem.data_ptr(), ins.data_ptr(), ps_sem.data_ptr(),
-                                          ps_ins.data_ptr(), cap_gt, cap_ps, ws.data_ptr(), ws_bytes, max_iou.data_ptr(),
-                                          gt_cls.data_ptr(), d_hdr.data_ptr(), h_hdr.data_ptr()))
-            torch.cuda.current_stream(dev).synchronize()
-            hdr = EvalHeader.from_buffer_copy(h_hdr.numpy().tobytes())
-            if hdr.status == 0:
-                break
-            # an id beyond the table: size the tables from the data and retry
-            cap_gt = max(cap_gt, int(ins.max()) + 1)
-            cap_ps = max(cap_ps, int(ps_ins.max()) + 1)
-    n_gt = int(hdr.n_gt)
-    if n_gt <= 0:
-        return torch.zeros(0, device=dev)
-    return max_iou[:n_gt][gt_cls[:n_gt] >= 0]
+    _, max_iou, gt_cls, _, _ = _eval_batch(dev, [(n, *_id_caps([ins, ps_ins]))], sem, ins, ps_sem, ps_ins)
+    return max_iou[gt_cls >= 0]
 
 
 def get_scene_sem_conf(semantic_label, ps_semantic_label, num_classes=19):
     """Semantic confusion matrix i64[C, C] (eval_ps_labels.py:150-172); the inputs are not modified."""
     dev = _device_of(semantic_label, ps_semantic_label)
-    sem, ps_sem = _dev_long(semantic_label, dev), _dev_long(ps_semantic_label, dev)
-    conf = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=dev)
+    sem, ps_sem = _dev_labels(semantic_label, dev, _GT_CODES), _dev_labels(ps_semantic_label, dev, _PS_CODES)
     n = int(sem.numel())
     if n == 0:
-        return conf
-    ctx = Context.get(dev.index or 0)
-    with torch.cuda.device(dev):
-        ctx.check(ctx.lib.gapro_eval_sem_confusion(ctx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), n,
-                                                   sem.data_ptr(), ps_sem.data_ptr(), int(num_classes), conf.data_ptr()))
-    return conf
+        return torch.zeros((num_classes, num_classes), dtype=torch.int64, device=dev)
+    return _eval_batch(dev, [(n, 1, 1)], sem, None, ps_sem, None, num_classes=num_classes)[3][0]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -110,8 +91,6 @@ CLASSES = ("cabinet", "bed", "chair", "sofa", "table", "door", "window", "booksh
 CLASS_18 = "wall/floor"
 
 _FIELDS = ("semantic_label", "instance_label", "ps_semantic_label", "ps_instance_label", "ps_prob")
-_GT_CODES = {torch.float64: _lib.GAPRO_LABEL_F64, torch.int32: _lib.GAPRO_LABEL_I32, torch.int64: _lib.GAPRO_LABEL_I64}
-_PS_CODES = {torch.int32: _lib.GAPRO_LABEL_I32, torch.int64: _lib.GAPRO_LABEL_I64}
 
 
 class BatchEval(NamedTuple):
@@ -120,12 +99,6 @@ class BatchEval(NamedTuple):
     ious: list          # [scene][row] float32 NumPy array: get_miou_scene of the row's points
     conf: np.ndarray    # int64 [rows, C, C]: get_scene_sem_conf of the row's points, summed over the scenes
     kept: np.ndarray    # int64 [scenes, rows]: points of the row
-
-
-def _as_tensor(a):
-    if isinstance(a, torch.Tensor):
-        return a.reshape(-1)
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a)).reshape(-1))
 
 
 def _common_dtype(ts, allowed, promote):
@@ -157,6 +130,48 @@ def _id_caps(ts):
         for i, v in zip(dev_idx, m):
             caps[i] = max(1, int(v) + 1)
     return caps
+
+
+def _eval_batch(dev, sizes, sem, ins, ps_sem, ps_ins, prob=None, thresholds=(), scannet_remap=False, num_classes=19):
+    """gapro_eval_batch on label arrays already concatenated on ``dev``, each in a dtype it has a code for.
+
+    ``sizes``: (n_points, max_gt, max_ps) per scene, in array order; ``thresholds``: ascending float32 values, with
+    ``prob`` one per point.  ``ins`` and ``ps_ins`` None: the confusion matrix and the counts only, enqueued without a
+    host sync.  -> (descriptors, max_iou, gt_cls, conf, kept), device tensors (max_iou / gt_cls None without instance
+    arrays).  Raises ValueError for a scene with an instance id beyond its id table."""
+    S, K = len(sizes), len(thresholds)
+    descs = (_lib.EvalScene * S)()
+    off = 0
+    for d, (n, max_gt, max_ps) in zip(descs, sizes):
+        d.point_offset, d.n_points, d.max_gt, d.max_ps = off, n, max_gt, max_ps
+        off += n
+    ctx = Context.get(dev.index)
+    lib = ctx.lib
+    ws_bytes = int(lib.gapro_eval_batch_workspace_bytes(descs, S, K))
+    if ws_bytes == 0:
+        raise ValueError("bad id-table sizes")
+    B, pairs = K + 1, ins is not None
+    rows = int(descs[S - 1].row_offset) + B * int(descs[S - 1].max_gt)
+    h_thr = (C.c_float * K)(*[float(v) for v in thresholds]) if K else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        max_iou = torch.empty(rows, dtype=torch.float32, device=dev) if pairs else None
+        gt_cls = torch.empty(rows, dtype=torch.float32, device=dev) if pairs else None
+        conf = torch.empty((B, num_classes, num_classes), dtype=torch.int64, device=dev)
+        kept = torch.empty((S, B), dtype=torch.int64, device=dev)
+        status = torch.empty(S, dtype=torch.int32, device=dev)
+        d_descs = torch.empty(C.sizeof(descs), dtype=torch.uint8, device=dev)
+        ctx.check(lib.gapro_eval_batch(
+            ctx.handle, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), S, descs, d_descs.data_ptr(), off,
+            _GT_CODES[sem.dtype], sem.data_ptr(), _GT_CODES[ins.dtype] if pairs else 0, ptr(ins),
+            _PS_CODES[ps_sem.dtype], ps_sem.data_ptr(), _PS_CODES[ps_ins.dtype] if pairs else 0, ptr(ps_ins),
+            ptr(prob), K, h_thr, 1 if scannet_remap else 0, int(num_classes), ws.data_ptr(), ws_bytes, ptr(max_iou),
+            ptr(gt_cls), conf.data_ptr(), kept.data_ptr(), status.data_ptr()))
+        bad = torch.nonzero(status).flatten().tolist() if pairs else []
+    if bad:
+        raise ValueError("scene(s) %s hold an instance id beyond the id table" % bad)
+    return descs, max_iou, gt_cls, conf, kept
 
 
 def evaluate_scenes(scenes, prob_thresholds=(), scannet_remap=True, num_classes=19, device=None):
@@ -206,46 +221,17 @@ def evaluate_scenes(scenes, prob_thresholds=(), scannet_remap=True, num_classes=
     gt_dt = _common_dtype(cols["semantic_label"] + cols["instance_label"], _GT_CODES, torch.int64)
     ps_dt = _common_dtype(cols["ps_semantic_label"] + cols["ps_instance_label"], _PS_CODES, torch.int64)
     gt_caps, ps_caps = _id_caps(cols["instance_label"]), _id_caps(cols["ps_instance_label"])
-
-    descs = (_lib.EvalScene * S)()
-    off = 0
-    for i in range(S):
-        n = cols["semantic_label"][i].numel()
-        descs[i].point_offset, descs[i].n_points = off, n
-        descs[i].max_gt = int(caps[i][0]) if caps[i][0] is not None else gt_caps[i]
-        descs[i].max_ps = int(caps[i][1]) if caps[i][1] is not None else ps_caps[i]
-        off += n
-    ctx = Context.get(dev.index)
-    lib = ctx.lib
-    ws_bytes = int(lib.gapro_eval_batch_workspace_bytes(descs, S, K))
-    if ws_bytes == 0:
-        raise ValueError("evaluate_scenes: bad id-table sizes")
-    B = K + 1
-    rows = int(descs[S - 1].row_offset) + B * int(descs[S - 1].max_gt)
+    sizes = [(cols["semantic_label"][i].numel(), int(caps[i][0]) if caps[i][0] is not None else gt_caps[i],
+              int(caps[i][1]) if caps[i][1] is not None else ps_caps[i]) for i in range(S)]
     order = np.argsort(thr, kind="stable")
-    h_thr = (C.c_float * max(K, 1))(*[float(v) for v in thr[order]])
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
         sem, ins = (_cat(cols[f], gt_dt, dev) for f in _FIELDS[:2])
         ps_sem, ps_ins = (_cat(cols[f], ps_dt, dev) for f in _FIELDS[2:4])
         prob = _cat(cols["ps_prob"], torch.float32, dev) if K else None
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        max_iou = torch.empty(rows, dtype=torch.float32, device=dev)
-        gt_cls = torch.empty(rows, dtype=torch.float32, device=dev)
-        conf = torch.empty((B, num_classes, num_classes), dtype=torch.int64, device=dev)
-        kept = torch.empty((S, B), dtype=torch.int64, device=dev)
-        status = torch.empty(S, dtype=torch.int32, device=dev)
-        d_descs = torch.empty(C.sizeof(descs), dtype=torch.uint8, device=dev)
-        ctx.check(lib.gapro_eval_batch(
-            ctx.handle, C.c_void_p(stream.cuda_stream), S, descs, d_descs.data_ptr(), off,
-            _GT_CODES[gt_dt], sem.data_ptr(), _GT_CODES[gt_dt], ins.data_ptr(), _PS_CODES[ps_dt], ps_sem.data_ptr(),
-            _PS_CODES[ps_dt], ps_ins.data_ptr(), prob.data_ptr() if K else None, K, h_thr if K else None,
-            1 if scannet_remap else 0, int(num_classes), ws.data_ptr(), ws_bytes, max_iou.data_ptr(), gt_cls.data_ptr(),
-            conf.data_ptr(), kept.data_ptr(), status.data_ptr()))
-        max_iou, gt_cls, conf, kept, status = (t.cpu().numpy() for t in (max_iou, gt_cls, conf, kept, status))
-    bad = [i for i in range(S) if status[i] != 0]
-    if bad:
-        raise ValueError("evaluate_scenes: scene(s) %s hold an instance id beyond the id table" % bad)
+    descs, max_iou, gt_cls, conf, kept = _eval_batch(dev, sizes, sem, ins, ps_sem, ps_ins, prob, thr[order],
+                                                     scannet_remap, num_classes)
+    max_iou, gt_cls, conf, kept = (t.cpu().numpy() for t in (max_iou, gt_cls, conf, kept))
+    B = K + 1
     # kernel rows follow the ascending thresholds; the caller's row j + 1 is kernel row 1 + rank of threshold j
     perm = np.empty(B, dtype=np.int64)
     perm[0] = 0

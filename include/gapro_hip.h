@@ -189,34 +189,12 @@ int gapro_instance_info(gapro_ctx* ctx, void* stream, int64_t n_points, const do
                         double* d_cls, double* d_volume, float* d_corners, gapro_instance_header* d_header,
                         gapro_instance_header* h_header_pinned);
 
-typedef struct {
-  int32_t n_gt;          /* instance_label.max() + 1                  eval_ps_labels.py:101 */
-  int32_t n_ps;          /* ps_instance_label.max() + 1               :109 */
-  int32_t status;
-  int32_t reserved;
-} gapro_eval_header;
-
-size_t gapro_eval_workspace_bytes(int32_t max_gt, int32_t max_ps);
-/* get_miou_scene (eval_ps_labels.py:100-147, cal_iou :35-42): for every GT instance id g < n_gt the largest
- * IoU = inter / (|gt| + |ps| - inter + 1e-4) (float32, the reference's operation order) over the pseudo
- * instances whose class (label of their first point) equals the GT instance's, and that class (-1 for an
- * empty id; the caller keeps the rows with class >= 0, :139).  Labels are int64, as the reference passes.
- *   out: d_max_iou f32[max_gt], d_gt_cls f32[max_gt] (first n_gt entries), header */
-int gapro_eval_miou(gapro_ctx* ctx, void* stream, int64_t n_points, const int64_t* d_semantic_label,
-                    const int64_t* d_instance_label, const int64_t* d_ps_semantic_label,
-                    const int64_t* d_ps_instance_label, int32_t max_gt, int32_t max_ps, void* d_workspace,
-                    size_t workspace_bytes, float* d_max_iou, float* d_gt_cls, gapro_eval_header* d_header,
-                    gapro_eval_header* h_header_pinned);
-/* get_scene_sem_conf (eval_ps_labels.py:150-172): conf i64[C,C], rows = GT class, columns = pseudo class,
- * over the points with GT != -100; a pseudo label of -100 counts as a wrong class. */
-int gapro_eval_sem_confusion(gapro_ctx* ctx, void* stream, int64_t n_points, const int64_t* d_semantic_label,
-                             const int64_t* d_ps_semantic_label, int32_t num_classes, int64_t* d_conf);
-
-/* Batched pseudo-label evaluation (the reference's eval_ps_labels.py main(), :175-257): get_miou_scene and
+/* Pseudo-label evaluation (the reference's eval_ps_labels.py, :35-42,100-257): get_miou_scene and
  * get_scene_sem_conf for a batch of scenes laid out back to back in the label arrays, unfiltered (row 0) and
  * for K probability thresholds (row t = the points with prob >= thresholds[t-1], the reference's commented-out
- * certain_cond filter :214-220, applied to all four arrays), in one pass over the points.  Integer atomics only:
- * every row is bit-identical to gapro_eval_miou / gapro_eval_sem_confusion run on the filtered scene alone. */
+ * certain_cond filter :214-220, applied to all four arrays), in one pass over the points; one scene without
+ * thresholds is the per-scene evaluation.  Integer atomics only: every row is bit-identical to the reference's
+ * get_miou_scene / get_scene_sem_conf on the filtered scene alone, whatever the batch composition. */
 enum {
   GAPRO_LABEL_F64 = 1,  /* ScanNet *_inst_nostuff.pth labels */
   GAPRO_LABEL_I32 = 2,  /* gen_ps label files */
@@ -240,11 +218,17 @@ size_t gapro_eval_batch_workspace_bytes(gapro_eval_scene* h_scenes, int32_t n_sc
  *        I64); d_prob f32[n_total_points] (NULL when n_thresholds = 0); h_thresholds f32[n_thresholds],
  *        ascending (host); scannet_remap != 0 applies sem[sem != -100] -= 2, then -1 / -2 -> 18 to the GT
  *        semantic labels (:196-197); h_scenes as filled above, d_scenes device space for n_scenes of them.
- *   out: d_max_iou / d_gt_cls f32 at row_offset + t * max_gt + g: scene, threshold row t, GT id g, as
- *        gapro_eval_miou (the caller keeps the entries with class >= 0, :139);
- *        d_conf i64[n_thresholds + 1, C, C] summed over the batch; d_kept i64[n_scenes, n_thresholds + 1]
- *        points per scene and row; d_status i32[n_scenes] (GAPRO_ERR_BAD_ARG: an id beyond max_gt / max_ps:
- *        that scene's IoUs are not valid).  Enqueue only. */
+ *   out: d_max_iou / d_gt_cls f32 at row_offset + t * max_gt + g: scene, threshold row t, GT id g: the largest
+ *        IoU = inter / (|gt| + |ps| - inter + 1e-4) (float32, the reference's operation order) over the pseudo
+ *        instances whose class (label of their first point) equals the GT instance's, and that class (-1 for an
+ *        empty id; the caller keeps the entries with class >= 0, :139);
+ *        d_conf i64[n_thresholds + 1, C, C] summed over the batch (rows = GT class, columns = pseudo class,
+ *        over the points with GT != -100; a pseudo label of -100 counts as a wrong class);
+ *        d_kept i64[n_scenes, n_thresholds + 1] points per scene and row; d_status i32[n_scenes]
+ *        (GAPRO_ERR_BAD_ARG: an id beyond max_gt / max_ps: that scene's IoUs are not valid).  Enqueue only.
+ * Confusion only: with d_inst_gt and d_inst_ps both NULL, no instance tables are tallied.  d_conf and d_kept
+ * are produced as above; d_max_iou / d_gt_cls may be NULL (if given, every id reads as empty), the instance
+ * dtype codes are ignored, and max_gt = max_ps = 1 keeps the workspace at its minimum. */
 int gapro_eval_batch(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro_eval_scene* h_scenes,
                      gapro_eval_scene* d_scenes, int64_t n_total_points, int32_t sem_gt_dtype, const void* d_sem_gt,
                      int32_t inst_gt_dtype, const void* d_inst_gt, int32_t sem_ps_dtype, const void* d_sem_ps,

@@ -25,6 +25,19 @@ def test_batched_eval_abi_is_declared_exported_and_bound():
     assert C.sizeof(_lib.EvalScene) == 8 + 8 + 4 + 4 + 8 + 8
 
 
+def test_per_scene_eval_abi_is_gone():
+    """get_miou_scene / get_scene_sem_conf are one-scene calls of gapro_eval_batch: the former per-scene entry points
+    are neither declared, exported nor bound."""
+    text = open(os.path.join(ROOT, "include", "gapro_hip.h")).read()
+    lib = _lib.load()
+    for name in ("gapro_eval_workspace_bytes", "gapro_eval_miou", "gapro_eval_sem_confusion"):
+        assert not re.search(r"\b%s\b" % name, text), name
+        assert name not in _lib.SIGNATURES
+        assert not hasattr(lib, name), name
+    assert "gapro_eval_header" not in text
+    assert not hasattr(_lib, "EvalHeader")
+
+
 def test_batched_eval_workspace_plan():
     lib = _lib.load()
     d = (_lib.EvalScene * 3)()

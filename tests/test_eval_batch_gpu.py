@@ -172,6 +172,37 @@ def test_stress_large_ids_empty_pseudo_labels_no_gt_instance_and_overflow():
     np.testing.assert_array_equal(again.ious[0][0], _golden("s0_walls")["ref_ious"])
 
 
+@pytest.mark.parametrize("num_classes", [19, 128])
+def test_confusion_only_launch_matches_the_oracle(num_classes):
+    """get_scene_sem_conf is gapro_eval_batch without instance arrays: the oracle's matrix with the confusion in LDS
+    (C = 19) and beyond it (C = 128), for GT -100, pseudo -100 and labels outside [0, C), in the labels' own dtypes,
+    with the inputs left as they were."""
+    import torch
+    from gapro_amd.eval_ps_labels import get_scene_sem_conf
+    from oracle import eval_oracle as E
+
+    c = num_classes
+    rng = np.random.default_rng(c)
+    n = 200000
+    gt = rng.integers(0, c, n)
+    gt[rng.random(n) < 0.1] = -100
+    ps = rng.integers(-3, c + 3, n)
+    ps[rng.random(n) < 0.1] = -100
+    # labels outside [0, C) whose flat index gt * C + ps stays in the C * C bins (torch.bincount's domain)
+    ps[(gt != -100) & (ps != -100) & ((gt * c + ps < 0) | (gt * c + ps >= c * c))] = -100
+    unlabeled = np.full(n, -100)
+    for p_np in (ps, unlabeled):
+        ref = E.get_scene_sem_conf(torch.from_numpy(gt), torch.from_numpy(p_np), c)
+        for gt_dt, ps_dt in ((torch.int64, torch.int64), (torch.float64, torch.int32), (torch.int16, torch.int64)):
+            g, p = torch.from_numpy(gt).to(gt_dt).cuda(), torch.from_numpy(p_np).to(ps_dt).cuda()
+            g0, p0 = g.clone(), p.clone()
+            conf = get_scene_sem_conf(g, p, num_classes=c)
+            assert conf.is_cuda and conf.dtype == torch.int64 and conf.shape == (c, c)
+            assert torch.equal(conf.cpu(), ref), (gt_dt, ps_dt)
+            assert torch.equal(g, g0) and torch.equal(p, p0)
+        assert int(ref.sum()) == int((gt != -100).sum())
+
+
 def _write_layout(tmp_path):
     """The golden scenes as a ScanNet layout (synth.write_scannet_layout's file format) and their outputs as label
     files: 5-tuples, 2-tuples, one scene without a label file, one with a damaged one."""
