@@ -74,6 +74,13 @@ class EvalScene(C.Structure):
                 ("ws_offset", C.c_int64), ("row_offset", C.c_int64)]
 
 
+class EvalApScene(C.Structure):
+    """gapro_eval_ap_scene: one scene of a batched AP table launch (gapro_eval_ap_keys / gapro_eval_ap_tables)."""
+    _fields_ = [("point_offset", C.c_int64), ("n_points", C.c_int64), ("max_ps", C.c_int32), ("n_keys", C.c_int32),
+                ("ws_offset", C.c_int64), ("id_offset", C.c_int64), ("key_offset", C.c_int64),
+                ("pair_offset", C.c_int64)]
+
+
 GAPRO_LABEL_F64, GAPRO_LABEL_I32, GAPRO_LABEL_I64 = 1, 2, 3
 GAPRO_EVAL_MAX_THRESHOLDS = 32
 
@@ -109,6 +116,13 @@ SIGNATURES = {
     "gapro_eval_batch": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P,
                                    C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, _P,
                                    _P, _P]),
+    "gapro_eval_ap_workspace_bytes": (C.c_size_t, [_P, C.c_int32]),
+    "gapro_eval_ap_keys": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_int32, _P,
+                                     C.c_size_t, _P, _P]),
+    "gapro_eval_ap_pair_cells": (C.c_int64, [_P, C.c_int32]),
+    "gapro_eval_ap_tables": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_int32,
+                                       _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P,
+                                       _P]),
     "gapro_label_heuristic_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "gapro_label_heuristic": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32,
                                         C.c_int32, _P, C.c_size_t, _P, _P]),

@@ -10,6 +10,7 @@
 // Integer atomics only, floats only in the finalize: every row is bit-identical to the reference on the filtered
 // scene, whatever the batch composition.  Without instance arrays only the confusion and the counts are tallied.
 #include "common.h"
+#include "eval_labels.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -62,18 +63,6 @@ __device__ inline SceneTables scene_tables(void* ws, const gapro_eval_scene& s, 
   t.pair = (int*)(t.first_ps + (size_t)B * t.cap_ps);
   t.ps_n = t.pair + (size_t)B * t.nbin;
   return t;
-}
-
-template <class T>
-__device__ inline long long label_at(const T* a, long long i) {
-  return (long long)a[i];  // float64 labels: truncation, as the reference's .int()
-}
-
-// reference main() :196-197 (and gen_ps --eval_pslabel): sem[sem != -100] -= 2; sem[sem in (-1, -2)] = 18
-__device__ inline long long remap_gt(long long s, int remap) {
-  if (!remap || s == -100) return s;
-  s -= 2;
-  return (s == -1 || s == -2) ? 18 : s;
 }
 
 __global__ __launch_bounds__(kThreads) void k_evb_init(const gapro_eval_scene* __restrict__ scenes, void* ws, int B) {
@@ -251,25 +240,6 @@ __global__ __launch_bounds__(kThreads) void k_evb_finalize(const gapro_eval_scen
     }
     max_iou[s.row_offset + it] = best;
     gt_cls[s.row_offset + it] = cg;
-  }
-}
-
-// dtype code -> template instance
-template <class F>
-bool with_gt_type(int code, F&& f) {
-  switch (code) {
-    case GAPRO_LABEL_F64: f((const double*)nullptr); return true;
-    case GAPRO_LABEL_I32: f((const int32_t*)nullptr); return true;
-    case GAPRO_LABEL_I64: f((const int64_t*)nullptr); return true;
-    default: return false;
-  }
-}
-template <class F>
-bool with_ps_type(int code, F&& f) {
-  switch (code) {
-    case GAPRO_LABEL_I32: f((const int32_t*)nullptr); return true;
-    case GAPRO_LABEL_I64: f((const int64_t*)nullptr); return true;
-    default: return false;
   }
 }
 

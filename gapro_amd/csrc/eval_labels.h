@@ -1,0 +1,41 @@
+// Label access shared by the evaluation kernels (eval_batch.hip, eval_ap.hip): labels stay in their file dtypes,
+// one template instance per GAPRO_LABEL_* code.
+#pragma once
+#include "common.h"
+
+#include <cstdint>
+
+namespace {
+
+template <class T>
+__device__ inline long long label_at(const T* a, long long i) {
+  return (long long)a[i];  // float64 labels: truncation, as the reference's .int()
+}
+
+// reference main() :196-197 (and gen_ps --eval_pslabel): sem[sem != -100] -= 2; sem[sem in (-1, -2)] = 18
+__device__ inline long long remap_gt(long long s, int remap) {
+  if (!remap || s == -100) return s;
+  s -= 2;
+  return (s == -1 || s == -2) ? 18 : s;
+}
+
+// dtype code -> template instance
+template <class F>
+bool with_gt_type(int code, F&& f) {
+  switch (code) {
+    case GAPRO_LABEL_F64: f((const double*)nullptr); return true;
+    case GAPRO_LABEL_I32: f((const int32_t*)nullptr); return true;
+    case GAPRO_LABEL_I64: f((const int64_t*)nullptr); return true;
+    default: return false;
+  }
+}
+template <class F>
+bool with_ps_type(int code, F&& f) {
+  switch (code) {
+    case GAPRO_LABEL_I32: f((const int32_t*)nullptr); return true;
+    case GAPRO_LABEL_I64: f((const int64_t*)nullptr); return true;
+    default: return false;
+  }
+}
+
+}  // namespace

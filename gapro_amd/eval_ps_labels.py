@@ -276,10 +276,11 @@ def read_gt_labels(path):
     return arrs[2].reshape(-1), arrs[3].reshape(-1)
 
 
-def read_label_file(path, need_prob=False):
+def read_label_file(path, need_prob=False, what="--prob_thresholds"):
     """(semantic, instance, prob or None) of a pseudo-label file: [0] = semantic, [1] = instance; [2] is the per-point
     probability only when it has one entry per point (gen_ps's 5-tuple; the reference's 2-tuple has none, and an array
-    of superpoint length is not a per-point probability).  need_prob: a file without one is an error."""
+    of superpoint length is not a per-point probability).  need_prob: a file without one is an error (naming ``what``
+    needs it)."""
     arrs = _load_tuple(path)
     if len(arrs) < 2:
         raise ValueError("%s: expected (semantic, instance, ...), found %d array(s)" % (path, len(arrs)))
@@ -290,7 +291,7 @@ def read_label_file(path, need_prob=False):
     if len(arrs) > 2 and arrs[2].ndim == 1 and len(arrs[2]) == len(sem) and arrs[2].dtype.kind == "f":
         prob = arrs[2].astype(np.float32, copy=False)
     if need_prob and prob is None:
-        raise ValueError("%s: no per-point probability for --prob_thresholds" % path)
+        raise ValueError("%s: no per-point probability for %s" % (path, what))
     return sem, inst, prob
 
 
@@ -307,15 +308,41 @@ def sem_iou_from_conf(conf):
     return iou.numpy(), float(miou)
 
 
-def _read_scene(args, name, need_prob):
+def _read_scene(args, name, need_prob, what="--prob_thresholds"):
     import os.path as osp
 
     sem, inst = read_gt_labels(osp.join(args.data_root, args.split, name + "_inst_nostuff.pth"))
-    ps_sem, ps_inst, prob = read_label_file(osp.join(args.ps_folder, name + ".pth"), need_prob)
+    ps_sem, ps_inst, prob = read_label_file(osp.join(args.ps_folder, name + ".pth"), need_prob, what)
     if len(ps_sem) != len(sem):
         raise ValueError("%d pseudo labels for %d points" % (len(ps_sem), len(sem)))
     return dict(semantic_label=sem, instance_label=inst, ps_semantic_label=ps_sem, ps_instance_label=ps_inst,
                 ps_prob=prob)
+
+
+def read_scene_batches(args, present, need_prob, failed, what="--prob_thresholds"):
+    """Yields (names, scenes) per batch of ``args.batch_scenes`` of the scenes ``present`` (GT under
+    ``args.data_root`` / ``args.split``, labels in ``args.ps_folder``), read by up to 16 threads one batch ahead.  A
+    scene that cannot be read goes to ``failed[name]`` with the reason; a batch left empty is skipped."""
+    import concurrent.futures as cf
+    import os
+
+    n_threads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 16))
+    batch = max(1, int(args.batch_scenes))
+    chunks = [present[i:i + batch] for i in range(0, len(present), batch)]
+    with cf.ThreadPoolExecutor(max_workers=n_threads) as pool:
+        submit = lambda names: [(n, pool.submit(_read_scene, args, n, need_prob, what)) for n in names]  # noqa: E731
+        pending = submit(chunks[0]) if chunks else []
+        for ci in range(len(chunks)):
+            cur, pending = pending, (submit(chunks[ci + 1]) if ci + 1 < len(chunks) else [])  # read one batch ahead
+            names, scenes = [], []
+            for name, fut in cur:
+                try:
+                    scenes.append(fut.result())
+                    names.append(name)
+                except Exception as e:  # noqa: BLE001 - a damaged / unreadable scene is reported, the others go on
+                    failed[name] = "%s: %s" % (type(e).__name__, e)
+            if scenes:
+                yield names, scenes
 
 
 def _nan_to_none(v):
@@ -324,9 +351,7 @@ def _nan_to_none(v):
 
 def main(argv=None):
     import argparse
-    import concurrent.futures as cf
     import json
-    import os
     import os.path as osp
     import sys
     import time
@@ -349,38 +374,22 @@ def main(argv=None):
     present = [s for s in scanned if osp.exists(osp.join(args.ps_folder, s + ".pth"))]
     have = set(present)
     missing = [s for s in scanned if s not in have]
-    n_threads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 16))
-    batch = max(1, int(args.batch_scenes))
-    chunks = [present[i:i + batch] for i in range(0, len(present), batch)]
     rows = len(taus) + 1
     ious = [dict() for _ in range(rows)]
     conf = np.zeros((rows, 19, 19), dtype=np.int64)
     kept = np.zeros(rows, dtype=np.int64)
     evaluated, failed = [], {}
     t_eval = 0.0  # time in evaluate_scenes (upload, kernels, download): the rest of the run is reading
-    with cf.ThreadPoolExecutor(max_workers=n_threads) as pool:
-        submit = lambda names: [(n, pool.submit(_read_scene, args, n, bool(taus))) for n in names]  # noqa: E731
-        pending = submit(chunks[0]) if chunks else []
-        for ci in range(len(chunks)):
-            cur, pending = pending, (submit(chunks[ci + 1]) if ci + 1 < len(chunks) else [])  # read one batch ahead
-            names, scenes = [], []
-            for name, fut in cur:
-                try:
-                    scenes.append(fut.result())
-                    names.append(name)
-                except Exception as e:  # noqa: BLE001 - a damaged / unreadable scene is reported, the others go on
-                    failed[name] = "%s: %s" % (type(e).__name__, e)
-            if not scenes:
-                continue
-            t1 = time.perf_counter()
-            res = evaluate_scenes(scenes, taus, scannet_remap=True, num_classes=19, device=args.device)
-            t_eval += time.perf_counter() - t1
-            for name, per_row in zip(names, res.ious):
-                for r in range(rows):
-                    ious[r][name] = per_row[r]
-            conf += res.conf
-            kept += res.kept.sum(axis=0)
-            evaluated += names
+    for names, scenes in read_scene_batches(args, present, bool(taus), failed):
+        t1 = time.perf_counter()
+        res = evaluate_scenes(scenes, taus, scannet_remap=True, num_classes=19, device=args.device)
+        t_eval += time.perf_counter() - t1
+        for name, per_row in zip(names, res.ious):
+            for r in range(rows):
+                ious[r][name] = per_row[r]
+        conf += res.conf
+        kept += res.kept.sum(axis=0)
+        evaluated += names
     elapsed = time.perf_counter() - t0
 
     out = dict(data_root=args.data_root, split=args.split, ps_folder=args.ps_folder, stride=args.stride,

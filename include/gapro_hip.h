@@ -237,6 +237,56 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro
                      size_t workspace_bytes, float* d_max_iou, float* d_gt_cls, int64_t* d_conf, int64_t* d_kept,
                      int32_t* d_status);
 
+/* ScanNet instance AP of pseudo-labels (the reference's eval_ap_ps_labels.py with ISBNet's
+ * ScanNetEval.assign_instances_for_scan): the integer tables of a batch of scenes laid out back to back, in two
+ * calls with one host read of the key counts in between.  A GT point's key is the code
+ * (sem + 1) * 1000 + (inst + 1) after the optional remap; it is a GT instance when sem + 1 is in 1..18 and
+ * inst + 1 in [0, 999), else the point is void.  The matching and the AP run on the host.  Integer atomics
+ * only: every table is bit-identical to a plain tally of the scene alone, whatever the batch composition. */
+typedef struct {
+  int64_t point_offset;  /* in : first point of the scene in the label arrays                                 */
+  int64_t n_points;      /* in : may be 0                                                                     */
+  int32_t max_ps;        /* in : pseudo instance ids are -100 (none) or in [0, max_ps) (>= 1)                 */
+  int32_t n_keys;        /* in for gapro_eval_ap_tables: the scene's d_n_keys from gapro_eval_ap_keys         */
+  int64_t ws_offset;     /* set by gapro_eval_ap_workspace_bytes: the scene's bytes in the workspace          */
+  int64_t id_offset;     /* set by gapro_eval_ap_workspace_bytes: the scene's first entry in the per-id outputs */
+  int64_t key_offset;    /* set by gapro_eval_ap_pair_cells: the scene's first entry in the per-key outputs   */
+  int64_t pair_offset;   /* set by gapro_eval_ap_pair_cells: the scene's first cell in d_pair                 */
+} gapro_eval_ap_scene;
+
+/* Fills ws_offset / id_offset of h_scenes[n_scenes] and returns the workspace size in bytes (0 on a bad
+ * argument); the per-id outputs hold id_offset[last] + max_ps[last] entries. */
+size_t gapro_eval_ap_workspace_bytes(gapro_eval_ap_scene* h_scenes, int32_t n_scenes);
+/* Pass 1.  in : GT labels of n_total_points points in their dtype codes (F64 / I32 / I64); scannet_remap != 0
+ *        applies sem[sem != -100] -= 2, then -1 / -2 -> 18 (eval_ap_ps_labels.py:59-60).
+ *   out: d_n_keys i32[n_scenes] distinct GT instance keys per scene; d_status i32[n_scenes] (GAPRO_ERR_BAD_ARG:
+ *        an instance id >= 999); the key ranks in the workspace.  Enqueue only. */
+int gapro_eval_ap_keys(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro_eval_ap_scene* h_scenes,
+                       gapro_eval_ap_scene* d_scenes, int64_t n_total_points, int32_t sem_gt_dtype, const void* d_sem_gt,
+                       int32_t inst_gt_dtype, const void* d_inst_gt, int32_t scannet_remap, void* d_workspace,
+                       size_t workspace_bytes, int32_t* d_n_keys, int32_t* d_status);
+/* With n_keys set: fills key_offset / pair_offset and returns the pair cells, the sum over the scenes of
+ * (n_keys + 1) * (max_ps + 1) (0 on a bad argument); the per-key outputs hold key_offset[last] + n_keys[last]. */
+int64_t gapro_eval_ap_pair_cells(gapro_eval_ap_scene* h_scenes, int32_t n_scenes);
+/* Pass 2, on the workspace of pass 1.  in : the labels as for gapro_eval_ap_keys plus the pseudo labels (I32 /
+ *        I64) and d_prob f32[n_total_points] or NULL.
+ *   out: per key k of a scene, ascending: d_key_code i32 (class * 1000 + inst + 1), d_key_n i32 points;
+ *        per pseudo id p: d_ps_n i32 points, d_ps_label i32 = pseudo semantic label + 1 of its first point when
+ *        that is in 1..18, else 0, d_ps_void i32 points of no GT instance, d_ps_sum i64 = sum over its points of
+ *        rint(double(prob) * 2^32) (0 without d_prob);
+ *        d_pair i32 [n_keys + 1][max_ps + 1] at pair_offset: points per (key + 1, id + 1), row 0 = void, column
+ *        0 = pseudo id -100;
+ *        d_status i32[n_scenes] (GAPRO_ERR_BAD_ARG: a GT instance id >= 999, a pseudo id < 0 other than -100 or
+ *        >= max_ps, n_keys below pass 1's count, or a probability that is NaN or outside [0, 1]: that scene's
+ *        tables are not valid).  Enqueue only. */
+int gapro_eval_ap_tables(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro_eval_ap_scene* h_scenes,
+                         gapro_eval_ap_scene* d_scenes, int64_t n_total_points, int32_t sem_gt_dtype,
+                         const void* d_sem_gt, int32_t inst_gt_dtype, const void* d_inst_gt, int32_t sem_ps_dtype,
+                         const void* d_sem_ps, int32_t inst_ps_dtype, const void* d_inst_ps, const float* d_prob,
+                         int32_t scannet_remap, void* d_workspace, size_t workspace_bytes, int32_t* d_key_code,
+                         int32_t* d_key_n, int32_t* d_ps_n, int32_t* d_ps_label, int32_t* d_ps_void,
+                         int64_t* d_ps_sum, int32_t* d_pair, int32_t* d_status);
+
 /* Heuristic labelers: gen_pseudo_label (gen_ps_utils.py:485-569; rule 0 = "volume",
  * 1 = "dist", 2 = "none") and gen_pseudo_label_box2mask (:242-290; rule 3).  Membership in the INSTANCE boxes
  * (float32 box, 0.005 margin applied in float32, compared in float64), the rule for points inside several boxes,
