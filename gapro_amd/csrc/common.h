@@ -68,14 +68,34 @@ void gapro_launch_fit_large(hipStream_t stream, int n_fits, int feat_dim, const 
                             double* d_workspace, float* d_probs, float* d_probs_new, unsigned char* d_labels,
                             float* d_mu, float* d_var, int* d_fit_status, double* d_fit_loss);
 
+// svgp_fit_wg.hip: the single-workgroup kernels with 512 threads per fit -- LDS-staged k_svgp_fit<WPS, KMIN>
+// (128 < M_p <= 512) and strip-streaming k_svgp_fit_strip (M_p <= 128)
+constexpr int kWavesPerSimd = 4;  // k_svgp_fit's two-per-CU build: 2 workgroups of 8 waves per CU -> 128 VGPRs per lane
+constexpr int kKminMaxMp = 256;   // largest M_p with the copy-free product forms (k_svgp_fit's KMIN)
+long long gapro_fit_staged_lds_bytes(int m, int feat_dim);  // dynamic LDS of one fit
+bool gapro_fit_staged_ok(int m, int feat_dim);              // the staged kernel takes the fit
+long long gapro_fit_strip_lds_bytes(int m, int feat_dim);
+bool gapro_fit_strip_ok(int m, int feat_dim);
+// k_svgp_fit<wps, kmin>: <2, false>, <2, true> or <kWavesPerSimd, true>
+int gapro_launch_fit_staged(hipStream_t stream, int wps, bool kmin, int n_fits, int n_wg, unsigned* d_ticket,
+                            int feat_dim, size_t lds_bytes, const float* d_feats_spp, const int* d_idx,
+                            const gapro_fit_desc* d_descs, const double* d_init_mean, const gapro_fit_options& opt,
+                            double* d_workspace, float* d_probs, float* d_probs_new, unsigned char* d_labels,
+                            float* d_mu, float* d_var, int* d_fit_status, double* d_fit_loss);
+int gapro_launch_fit_strip(hipStream_t stream, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim,
+                           size_t lds_bytes, const float* d_feats_spp, const int* d_idx, const gapro_fit_desc* d_descs,
+                           const double* d_init_mean, const gapro_fit_options& opt, double* d_workspace,
+                           float* d_probs, float* d_probs_new, unsigned char* d_labels, float* d_mu, float* d_var,
+                           int* d_fit_status, double* d_fit_loss);
+
 // svgp_fit_small.hip: the strip kernel built with 256 threads per fit (M_p <= 64, two fits per CU)
-extern "C" int gapro_launch_fit_strip_small(void* stream, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim,
-                                            size_t lds_bytes, const float* d_feats_spp, const int32_t* d_idx,
-                                            const gapro_fit_desc* d_descs, const double* d_init_mean,
-                                            const gapro_fit_options* opt, double* d_workspace, float* d_probs,
-                                            float* d_probs_new, uint8_t* d_labels, float* d_mu, float* d_var,
-                                            int32_t* d_fit_status, double* d_fit_loss);
-extern "C" long long gapro_fit_strip_small_lds_bytes(int m, int feat_dim);
+long long gapro_fit_strip_small_lds_bytes(int m, int feat_dim);
+int gapro_launch_fit_strip_small(hipStream_t stream, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim,
+                                 size_t lds_bytes, const float* d_feats_spp, const int* d_idx,
+                                 const gapro_fit_desc* d_descs, const double* d_init_mean,
+                                 const gapro_fit_options& opt, double* d_workspace, float* d_probs, float* d_probs_new,
+                                 unsigned char* d_labels, float* d_mu, float* d_var, int* d_fit_status,
+                                 double* d_fit_loss);
 
 // svgp_fit_cluster.hip
 int gapro_cluster_size(int Mp, bool all);
@@ -115,9 +135,9 @@ int gapro_launch_fit_wave(hipStream_t stream, int nb, int n_fits, int n_wg, unsi
 // to 272 / 304 / 336 fell through to the generic kernel.
 constexpr int kPad16MaxMp = 336;
 constexpr int kPad16AlwaysMp = 128;           // up to here every multiple of 16 runs on a strip / staged / generic route
-constexpr long long kStagedMaxDynLds = 150 * 1024;  // dynamic LDS budget of the staged kernel (svgp_fit.hip kMaxDynLds)
+constexpr long long kStagedMaxDynLds = 150 * 1024;  // dynamic LDS budget of the staged kernel (fit_wg.h kMaxDynLds)
 // dynamic LDS bytes of the LDS-staged kernel (512 threads) for a PADDED size beyond kFuseMaxMp = 128:
-// Zt | Xt | max(reduction slots, Cholesky block column, operand ring); svgp_fit.hip checks this against its own
+// Zt | Xt | max(reduction slots, Cholesky block column, operand ring); fit_wg.h checks this against its own
 // staged_lds_bytes
 inline __host__ __device__ long long gapro_staged_lds_bytes_mp(int Mp, int d) {
   const long long red = 8 * 512, panel = (long long)Mp * 17 + 64 * 17, ring = 2 * 2 * 8 * (128 + 16);

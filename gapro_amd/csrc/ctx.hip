@@ -10,7 +10,7 @@ int gapro_version(void) { return GAPRO_VERSION; }
 
 // stream priorities of the fit kernels; GAPRO_FIT_PRIO="a,b,c,d,e[,f,g,h]" (0 = greatest, 1 = middle, 2 = least) overrides
 static int fit_prio(int k, int least, int greatest) {
-  // (rounds 2-3: {0, 0, 2, 0, 0}, the small fits last.  With the fits taken by ticket -- claim_fit, svgp_fit.hip -- one
+  // (rounds 2-3: {0, 0, 2, 0, 0}, the small fits last.  With the fits taken by ticket -- claim_fit, fit_wg.h -- one
   // level for all is +2.4 %: small fits beside the cluster kernel load the memory system less than staged ones)
   static int lvl[gapro_ctx::kFitStreams] = {0, 0, 0, 0, 0, 0, 0, 0};
   static bool init = false;

@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void k_peak_f64_4x4_tile(int iters, double* __
   if (s == 12345.678) sink[0] = s;
 }
 
-// The chunk loop of gemm_wg (svgp_fit.hip) piece by piece, 512 threads = one workgroup per CU: per iteration every wave
+// The chunk loop of gemm_wg (fit_wg.h) piece by piece, 512 threads = one workgroup per CU: per iteration every wave
 // reads the fragments of a 32 x 64 piece for two k-steps from LDS (6 reads each), rotates the A fragments and issues
 // 64 block instructions.  mode bit 0: + a workgroup barrier per iteration; bit 1: + two 16-byte LDS stores; bit 2: + two
 // 16-byte global loads per thread and iteration (prefetch distance two iterations); bit 3: the 16x16x4 form instead.

@@ -1,4 +1,4 @@
-// Two-phase product epilogues, shared by the single-workgroup MFMA kernels (svgp_fit.hip) and the cluster kernel.
+// Two-phase product epilogues, shared by the single-workgroup MFMA kernels (fit_wg.h) and the cluster kernel.
 #pragma once
 #include <type_traits>
 

@@ -34,30 +34,22 @@
 
 #include "common.h"
 #include "fit_layout.h"
+#include "fit_math.h"
 #include "epilogue.h"
 
 namespace {
 using namespace gapro_fit;
+using namespace gapro_fit_math;
+using gapro_mfma::d4;
 
 constexpr int NT = kClThreads;  // threads per workgroup
 constexpr int NW = NT / 64;     // waves per workgroup
 constexpr int NB = 64;          // Cholesky panel width
 constexpr int NGH = 20;
 
-typedef double d4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) double gd;
 typedef __attribute__((address_space(1))) unsigned gu32;
-typedef __attribute__((address_space(3))) double ldsd;
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) float gf;  // float32 matrices of the mixed-precision mode
-
-__constant__ double c_gh_t[10] = {0.24534070830090124, 0.7374737285453944, 1.234076215395323,  1.7385377121165861,
-                                  2.2549740020892757,  2.7888060584281305, 3.3478545673832163, 3.944764040115625,
-                                  4.603682449550744,   5.387480890011233};
-__constant__ double c_gh_w[10] = {0.4622436696006101,     0.28667550536283415,    0.1090172060200233,
-                                  0.024810520887463643,   0.0032437733422378567,  0.00022833863601635365,
-                                  7.80255647853206e-06,   1.0860693707692782e-07, 4.3993409922731747e-10,
-                                  2.2293936455341447e-13};
 
 struct Fit {
   int M, T, D, Mp;
@@ -109,47 +101,8 @@ __device__ inline void stamp(int id) {
 __device__ inline void stamp(int) {}
 #endif
 
-// ---- small helpers ---------------------------------------------------------------------------------
-__device__ inline double softplus(double x) { return log1p(exp(-fabs(x))) + fmax(x, 0.0); }
-__device__ inline double sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
-__device__ inline void log_ndtr_ratio(double z, double* lp, double* r) {
-  const double rs2 = 0.70710678118654752440;
-  if (z < 0.0) {
-    const double ex = erfcx(-z * rs2);
-    *lp = log(0.5 * ex) - 0.5 * z * z;
-    *r = 0.79788456080286535588 / ex;
-  } else {
-    const double tail = 0.5 * erfc(z * rs2);
-    *lp = log1p(-tail);
-    *r = exp(-0.5 * z * z) * 0.39894228040143267794 / (1.0 - tail);
-  }
-}
-__device__ inline double lane_bcast(double v, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
-__device__ inline int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-template <typename T>
-__device__ inline T* uni_ptr(T* p) {
-  const unsigned long long a = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  return (T*)(((unsigned long long)hi << 32) | lo);
-}
-__device__ inline double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ inline double block_sum(double v) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) g_sh.redw[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < NW; ++w) t += g_sh.redw[w];
-  return t;
-}
+// ---- small helpers (the scalar ones: fit_math.h) -------------------------------------------------
+__device__ inline double block_sum(double v) { return block_sum_shfl<NW>(v, g_sh.redw); }
 
 // cluster-wide thread / wave coordinates
 __device__ inline int cl_tid() { return g_sh.g * NT + (int)threadIdx.x; }
@@ -247,7 +200,7 @@ __device__ __noinline__ void cl_reduce(double (&v)[K]) {
 //   C[i][j] = sum_{k in [klo,khi)} P[k][i] * Q[k][j] (* qscale[k] if SCALE);  P, Q row-major in k with leading
 //   dimension ld; each wave owns (16 TU) x (16 TU) output tiles; `lower_only` enumerates tiles ti >= tj.
 //   kr(i0, j0, &klo, &khi): contraction range (multiples of 8); epi(i, j, tile): one 16 x 16 result in C layout.
-//   Two register blocks of KS k-steps alternate with no guard in the steady-state body (see svgp_fit.hip).
+//   Two register blocks of KS k-steps alternate with no guard in the steady-state body (see fit_wg.h).
 //   EP / EQ: element types of P and Q in memory (gd = float64, gf = float32: the mixed-precision mode's float32
 //   matrices feeding a float64 product are converted when a fragment is consumed, not when it is loaded).
 // ORD: tile enumeration, heaviest contraction range first for the product's kr; the cluster's waves take the tiles of
@@ -532,7 +485,7 @@ __device__ inline double sqdist(const gd* a, const gd* b, int D) {
 
 // ---- Cholesky ---------------------------------------------------------------------------------------
 // 16 x 16 diagonal block at blk[16 kb.., 16 kb..] (LDS, row stride RS): L_kk in place (upper zeroed) and
-// Dinv = L_kk^-1 in g_sh.dinv; one wave, rows in registers, pivots by v_readlane (as svgp_fit.hip).
+// Dinv = L_kk^-1 in g_sh.dinv; one wave, rows in registers, pivots by v_readlane (as fit_wg.h).
 __device__ __noinline__ void diag16(ldsd* blk, int RS, int kb) {
   const int lane = threadIdx.x & 63, r = lane & 15;
   ldsd* base = blk + (16 * kb) * RS + 16 * kb;
@@ -1143,11 +1096,11 @@ __device__ __noinline__ void kernel_grads(const gd* __restrict__ G, const gd* __
     }
 #pragma unroll
     for (int r = 0; r < kRowBlock; ++r) {
-      const double wsum_d = wave_sum((double)wsum[r]);
+      const double wsum_d = wave_sum_shfl((double)wsum[r]);
 #pragma unroll
       for (int d = 0; d < DMAX; ++d) {
         if (d < D && i0 + r < M) {
-          const double a = wave_sum((double)acc[r][d]);
+          const double a = wave_sum_shfl((double)acc[r][d]);
           if (lane == 0) {
             const double gz = -inv_l2 * (wsum_d * (double)(R)zl[kRowBlock * d + r] - a);
             f.gZ[(size_t)(i0 + r) * D + d] = MX ? (double)(float)gz : gz;
@@ -1206,7 +1159,7 @@ __device__ __noinline__ void kernel_grads_deep(gd* __restrict__ G, const gd* __r
     }
 #pragma unroll
     for (int r = 0; r < kRowBlock; ++r) {
-      const double wsum_d = wave_sum((double)wsum[r]);
+      const double wsum_d = wave_sum_shfl((double)wsum[r]);
       if (lane == 0 && i0 + r < M) wsum_v[i0 + r] = wsum_d;
     }
   }
@@ -1302,7 +1255,7 @@ __device__ __noinline__ void fit_body(const gapro_fit_options& opt, const gapro_
     }
     __syncthreads();
   };
-  // gpytorch's psd_safe_cholesky around the factorisation (see svgp_fit.hip: cholesky_psd_safe)
+  // gpytorch's psd_safe_cholesky around the factorisation (see fit_wg.h: cholesky_psd_safe)
   auto factorize = [&]() {
     double extra = 0.0;
     for (int attempt = 0;; ++attempt) {
@@ -1358,9 +1311,9 @@ __device__ __noinline__ void fit_body(const gapro_fit_options& opt, const gapro_
           if (q < NGH / 2) {
             const double t = c_gh_t[q], w = c_gh_w[q];
             double lp, r;
-            log_ndtr_ratio(y * (mu - sd * t), &lp, &r);
+            log_ndtr_ratio_branchy(y * (mu - sd * t), &lp, &r);
             E += w * lp; dmu += w * r; dvar -= w * t * r;
-            log_ndtr_ratio(y * (mu + sd * t), &lp, &r);
+            log_ndtr_ratio_branchy(y * (mu + sd * t), &lp, &r);
             E += w * lp; dmu += w * r; dvar += w * t * r;
           }
         }
@@ -1566,7 +1519,7 @@ __device__ __noinline__ void fit_body(const gapro_fit_options& opt, const gapro_
     }
     // G_Kzz (unsymmetrised) = L^-T Pm L^-1, associated as L^-T (Pm L^-1): W = Pm L^-1 is a product of two
     // lower-triangular matrices (M^3 / 3, lower itself), S = L^-T W costs 2 M^3 / 3 -- 1.0 M^3 where (L^-T Pm) L^-1
-    // spends 2/3 + 1 (svgp_fit.hip has the same order).
+    // spends 2/3 + 1 (fit_staged.h has the same order).
     // W = Pm L^-1 (lower tiles only; zeros above the diagonal inside them) -> BMT buffer.  S reads W[k][j] for
     // k >= max(i0, j0) only, i.e. lower tiles: what the upper tiles of the buffer hold does not matter.
     // (j0 <= k < i0 + tile: Pm^T[k][i] = 0 for k > i, L^-1[k][j] = 0 for k < j)

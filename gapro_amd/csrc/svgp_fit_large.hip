@@ -1,6 +1,6 @@
 // Generic (any M) variant of the batched SVGP fit: every matrix lives in the global-memory workspace,
 // nothing is staged in LDS.  It is the first correct kernel of round 1, kept as the fallback for fits
-// whose working set does not fit the LDS-staged kernel of svgp_fit.hip (M > 512 or very wide features).
+// whose working set does not fit the LDS-staged kernel of fit_staged.h (M > 512 or very wide features).
 // Same arithmetic, same workspace layout, same results to rounding.
 //
 // Replaces reference gapro/gaussian_process_utils.py:382-445 (fit_gp_spp) and the gpytorch objects
@@ -28,25 +28,16 @@
 
 #include "common.h"
 #include "fit_layout.h"
+#include "fit_math.h"
 
 namespace {
 using namespace gapro_fit;
+using namespace gapro_fit_math;
+using gapro_mfma::d4;
 
 constexpr int NT = 512;       // threads per fit
 constexpr int NW = NT / 64;   // waves per fit
 constexpr int NGH = 20;       // Gauss-Hermite nodes (gpytorch settings.num_gauss_hermite_locs)
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-// numpy.polynomial.hermite.hermgauss(20): positive nodes (ascending) and their weights; the rule is
-// symmetric.  Printed with repr() from NumPy 2.2.
-__constant__ double c_gh_t[10] = {0.24534070830090124, 0.7374737285453944, 1.234076215395323,  1.7385377121165861,
-                                  2.2549740020892757,  2.7888060584281305, 3.3478545673832163, 3.944764040115625,
-                                  4.603682449550744,   5.387480890011233};
-__constant__ double c_gh_w[10] = {0.4622436696006101,     0.28667550536283415,    0.1090172060200233,
-                                  0.024810520887463643,   0.0032437733422378567,  0.00022833863601635365,
-                                  7.80255647853206e-06,   1.0860693707692782e-07, 4.3993409922731747e-10,
-                                  2.2293936455341447e-13};
 
 
 // ---- workspace layout (doubles) -------------------------------------------------------------------
@@ -60,39 +51,9 @@ struct Fit {
   double *X, *Z, *mZ, *vZ, *gZ, *Xt, *dinv, *dinvT, *scal;
 };
 
-// ---- small helpers ---------------------------------------------------------------------------------
-__device__ inline double softplus(double x) { return log1p(exp(-fabs(x))) + fmax(x, 0.0); }
-__device__ inline double sigmoid(double x) { return 1.0 / (1.0 + exp(-x)); }
-
-// log Phi(z) and r(z) = phi(z)/Phi(z), both tails stable (same branches as oracle/svgp_oracle.py).
-__device__ inline void log_ndtr_ratio(double z, double* lp, double* r) {
-  const double rs2 = 0.70710678118654752440;
-  if (z < 0.0) {
-    const double ex = erfcx(-z * rs2);
-    *lp = log(0.5 * ex) - 0.5 * z * z;
-    *r = 0.79788456080286535588 / ex;  // sqrt(2/pi) / erfcx
-  } else {
-    const double tail = 0.5 * erfc(z * rs2);
-    *lp = log1p(-tail);
-    *r = exp(-0.5 * z * z) * 0.39894228040143267794 / (1.0 - tail);
-  }
-}
-
-__device__ inline double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
+// ---- small helpers (the scalar ones: fit_math.h) -------------------------------------------------
 // Deterministic block sum (fixed tree), result broadcast to every thread.
-__device__ inline double block_sum(double v, double* sh /* >= NW doubles */) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < NW; ++w) t += sh[w];
-  return t;
-}
+__device__ inline double block_sum(double v, double* sh /* >= NW doubles */) { return block_sum_shfl<NW>(v, sh); }
 
 // ---- TN-form MFMA product ---------------------------------------------------------------------------
 //   C[i][j] = sum_{k in [klo,khi)} P[k][i] * (Q[k][j] * qscale(k)),  ld = leading dimension of P and Q
@@ -489,7 +450,7 @@ __device__ void fit_body(const Fit& f, const gapro_fit_options& opt, Shared& sh,
   auto factorize = [&]() {
     stamp(19);
     // psd_safe_cholesky of gpytorch: repeat on K + psd_jitter 10^i I (i < psd_retries) before giving up; see the
-    // comment at GAPRO_PSD_SAFE_CHOLESKY in svgp_fit.hip
+    // comment at GAPRO_PSD_SAFE_CHOLESKY in fit_wg.h
     double extra = 0.0;
     for (int attempt = 0;; ++attempt) {
       build_kzz(f, sh.s, sh.inv_l2, jitter + extra);
@@ -541,9 +502,9 @@ __device__ void fit_body(const Fit& f, const gapro_fit_options& opt, Shared& sh,
         for (int q = 0; q < NGH / 2; ++q) {
           const double t = c_gh_t[q], w = c_gh_w[q];
           double lp, r;
-          log_ndtr_ratio(y * (mu - sd * t), &lp, &r);
+          log_ndtr_ratio_branchy(y * (mu - sd * t), &lp, &r);
           E += w * lp; dmu += w * r; dvar -= w * t * r;
-          log_ndtr_ratio(y * (mu + sd * t), &lp, &r);
+          log_ndtr_ratio_branchy(y * (mu + sd * t), &lp, &r);
           E += w * lp; dmu += w * r; dvar += w * t * r;
         }
         const double ipi = 0.56418958354775628695;  // 1/sqrt(pi)
@@ -610,7 +571,7 @@ __device__ void fit_body(const Fit& f, const gapro_fit_options& opt, Shared& sh,
     __syncthreads();
     stamp(10);
     // G_Kzz (unsymmetrised) = L^-T Pm L^-1, Pm = Phi(tril(L^T G_L)), associated as L^-T (Pm L^-1) like the MFMA kernels
-    // (svgp_fit.hip): W = Pm L^-1 is lower (M^3 / 3), S = L^-T W costs 2 M^3 / 3.
+    // (fit_staged.h): W = Pm L^-1 is lower (M^3 / 3), S = L^-T W costs 2 M^3 / 3.
     // Pm^T -> GA buffer   (k >= i0 on lower tiles)
     double* PmT = GA;
     gemm_tn<TU>(mt, mt, true, f.mat[B_L], GL, Mp, [=](int i0, int, int* lo, int* hi) { *lo = i0; *hi = Mp; },

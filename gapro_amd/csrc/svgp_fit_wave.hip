@@ -1,13 +1,13 @@
 // One WAVE per GP fit (gfx950): the small fits of a launch, M_p = 16 NB <= 48, with the whole Adam loop on one wavefront.
 //
 // Why: a fit of M <= 48 points has 0.3 .. 1 MFLOP per Adam step -- microseconds of matrix work --
-// and the workgroup-per-fit kernels of svgp_fit.hip spend 30 .. 100 us on it: ~25 barrier-separated phases per strip
+// and the workgroup-per-fit kernels of fit_staged.h / fit_strip.h spend 30 .. 100 us on it: ~25 barrier-separated phases per strip
 // whose operands make a round trip through the HBM workspace, one wave factoring the 16 x 16 diagonal blocks while the
 // others wait.  Here a fit is ONE wave: no workgroup barrier exists, no intermediate ever leaves the CU, and a CU
 // hosts eight fits (NB <= 2: 256 registers per lane, two waves per SIMD) or four (NB = 3: the whole register file)
 // whose serial chains (diagonal blocks, likelihood) overlap on the four SIMDs.
 //
-// Same arithmetic as svgp_fit.hip (reference gapro/gaussian_process_utils.py:11-25, 382-445 and the gpytorch objects
+// Same arithmetic as fit_staged.h (reference gapro/gaussian_process_utils.py:11-25, 382-445 and the gpytorch objects
 // behind it; oracle/svgp_oracle.py): whitened SVGP classifier, Z = X initially, 50 Adam steps on
 // {Z, m, tril(L_S), c, rho_s, rho_l}, 20-point Gauss-Hermite Bernoulli likelihood, psd_safe_cholesky retries, then
 // mu, sigma^2, Phi(mu / sqrt(1 + sigma^2)) for the test points.  float64 throughout.
@@ -26,7 +26,7 @@
 //
 // Per Adam step (U = L^T upper tiles, LI = L^-1, LIT = LI^T):
 //   U        left-looking block Cholesky of K_ZZ + jitter I in registers; diagonal blocks factored and inverted by the
-//            readlane chain of svgp_fit.hip's diag_factor_invert (through one LDS tile for the row-per-lane layout)
+//            readlane chain of fit_wg.h's diag_factor_invert (through one LDS tile for the row-per-lane layout)
 //   LI, LIT  block forward substitution, both orientations from the same partial sums
 //   KX; A = LI KX, At;  B = L_S^T A (transient: column sums only);  mu, var;  likelihood -> g_mu, g_v
 //   B, Bt again;  G_LS = tril(At^T GBt);  G_A = m g_mu^T + L_S GB - 2 A diag(g_v), G_At;  Adam on L_S
@@ -44,7 +44,6 @@ namespace {
 using namespace gapro_fit;
 using namespace gapro_fit_math;
 using gapro_mfma::d4;
-typedef __attribute__((address_space(3))) double ldsd;
 
 constexpr int kTS = 16 * 17;  // doubles of one LDS tile (row stride 17)
 
@@ -111,7 +110,7 @@ struct LpR {
 };
 __device__ __noinline__ LpR nl_log_ndtr_ratio(double z) {
   LpR o;
-  log_ndtr_ratio(z, &o.lp, &o.r);
+  log_ndtr_ratio_erfcx(z, &o.lp, &o.r);
   return o;
 }
 // r(z) = phi(z) / Phi(z) alone: the 49 steps whose ELBO value nobody reads need no log Phi (same bits as the r above)
@@ -123,7 +122,7 @@ __device__ __noinline__ double nl_ndtr_ratio(double z) {
 }
 
 // Factor the symmetric 16 x 16 block S = L L^T and invert L: Dinv = L^-1 and Dinv^T as accumulator-layout tiles.  The
-// elimination is svgp_fit.hip's diag_factor_invert: lane r (mod 16) holds row r, pivots and multipliers travel by
+// elimination is fit_wg.h's diag_factor_invert: lane r (mod 16) holds row r, pivots and multipliers travel by
 // v_readlane; the inverse is a forward substitution, one column per lane, reading L as LDS broadcasts.  Returns
 // bad: a pivot was not positive (psd_safe_cholesky's retry condition).
 // The elementwise, transcendental-heavy pieces of a step (this one, rbf_tile, lik_column, adam_ls_tile) are functions
@@ -544,10 +543,10 @@ __device__ inline void fit_wave(ldsd* L, const gapro_fit_desc& desc, const gapro
     }
 
     // ---- the training points in blocks of 16 columns: everything between KX and the gradient sums is column-wise
-    // (the strip idea of svgp_fit.hip), so only the M x M sums G_LS, Pm^T and R live across the blocks
+    // (the strip idea of fit_strip.h), so only the M x M sums G_LS, Pm^T and R live across the blocks
     d4 GLS[NL], PmT[NL];
     double gm_part[NB];
-    // G_Z[k][d] = -sum_n W[k][n] (Z_k[d] - P_n[d]) / l^2 in the DIFFERENCE form, like svgp_fit.hip: as a product
+    // G_Z[k][d] = -sum_n W[k][n] (Z_k[d] - P_n[d]) / l^2 in the DIFFERENCE form, like fit_wg.h: as a product
     // (rowsum_k Z_k - W P) it loses digits to cancellation, and on tiny fits (M = 3) Adam turns that into 5e-6 in mu.
     // This lane accumulates column k = 16 kb + lr over the rows n of transposed tiles (n-major: W^T, or the symmetric
     // W_zz as it is); the four row groups are summed at the end.
@@ -722,8 +721,8 @@ __device__ inline void fit_wave(ldsd* L, const gapro_fit_desc& desc, const gapro
         MLS[t][r] = gMLS[(4 * t + r) * 64 + lane];
         VLS[t][r] = gVLS[(4 * t + r) * 64 + lane];
       }
-    const double g_c = uni_d(wave_sum(gc_part));
-    const double gv_sum = uni_d(wave_sum(gvs_part));
+    const double g_c = uni_d(wave_sum_dpp(gc_part));
+    const double gv_sum = uni_d(wave_sum_dpp(gvs_part));
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
       const double p = red_lq(gm_part[i]);
@@ -732,7 +731,7 @@ __device__ inline void fit_wave(ldsd* L, const gapro_fit_desc& desc, const gapro
 
     // ---- ELBO value of the last step (parameters before their update)
     if (last) {
-      const double e_sum = wave_sum(e_part);
+      const double e_sum = wave_sum_dpp(e_part);
       double kl_part = 0.0;
 #pragma unroll
       for (int i = 0; i < NB; ++i)
@@ -749,7 +748,7 @@ __device__ inline void fit_wave(ldsd* L, const gapro_fit_desc& desc, const gapro
           }
         }
       if (lane < M) kl_part += vm[lane] * vm[lane];
-      const double kl = 0.5 * (wave_sum(kl_part) - Nd);
+      const double kl = 0.5 * (wave_sum_dpp(kl_part) - Nd);
       last_loss = -(e_sum / Nd - kl / Nd);
     }
     wsync();  // every read of L_S of this step is done
@@ -838,8 +837,8 @@ __device__ inline void fit_wave(ldsd* L, const gapro_fit_desc& desc, const gapro
         }
       }
     }
-    gs = uni_d(wave_sum(gs) + gv_sum);
-    gl = uni_d(wave_sum(gl) / (ell * ell * ell));
+    gs = uni_d(wave_sum_dpp(gs) + gv_sum);
+    gl = uni_d(wave_sum_dpp(gl) / (ell * ell * ell));
     stamp(10);
 
     // ---- Adam on Z: the four row groups of column k are summed; row group lq then updates d = lq, lq + 4, ...

@@ -416,7 +416,7 @@ enum {
   GAPRO_FIT_DBG_WG_TILED_NONE = 131072,   /* no workgroup-tiled products (round 2's products) */
   GAPRO_FIT_DBG_STATIC_MAP = 262144,      /* workgroup b of a fit kernel runs fit b of its list (default: the
                                            * workgroups take the fits in the order in which they start, claim_fit in
-                                           * csrc/svgp_fit.hip) */
+                                           * csrc/fit_wg.h) */
   GAPRO_FIT_DBG_NO_WAVE = 1048576,        /* no wave-per-fit kernel (M_p <= 48 runs the small-fit strip kernel) */
   GAPRO_FIT_DBG_ALL = 1 | 2 | 4 | 8 | 16 | 8192 | 32768 | 131072 | 262144 | 1048576
 };

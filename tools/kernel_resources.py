@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Register / spill / LDS table of every kernel of a HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
 
-    python tools/kernel_resources.py gapro_amd/csrc/svgp_fit.hip [-DGAPRO_NT=256 ...]
+    python tools/kernel_resources.py gapro_amd/csrc/svgp_fit_wg.hip [-DGAPRO_PROFILE ...]
 """
 import re
 import subprocess
