@@ -15,7 +15,7 @@ _EXPORTS = {
     "gen_ps_utils": ("batch_giou_cross", "gen_pseudo_label", "gen_pseudo_label_box2mask",
                      "gen_pseudo_label_gaussian_process", "gen_pseudo_label_gaussian_process_batch", "getInstanceInfo",
                      "getInstanceInfo_device", "is_box1_in_box2"),
-    "gaussian_process_utils": ("fit_gp_spp", "fit_gp_spp_batch"),
+    "gaussian_process_utils": ("fit_gp_spp", "fit_gp_spp_batch", "predict_gp_batch", "GPModel"),
     "scannet_planes": ("get_wall_boxes",),
 }
 __all__ = [n for names in _EXPORTS.values() for n in names]
@@ -28,7 +28,7 @@ def __getattr__(name):
             globals()[name] = value
             return value
     if name in _EXPORTS or name in ("gen_ps", "pipeline", "synth", "_lib", "pth_io", "feeder", "dist_utils",
-                                    "consumer_ops", "eval_ps_labels"):
+                                    "consumer_ops", "eval_ps_labels", "gp_model"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 

@@ -47,6 +47,12 @@ class FitDesc(C.Structure):
                 ("ws_offset", C.c_int64)]
 
 
+class PredictDesc(C.Structure):
+    """gapro_predict_desc: one model of a gapro_svgp_predict_batch launch."""
+    _fields_ = [("state_offset", C.c_int64), ("row_offset", C.c_int64), ("out_offset", C.c_int64), ("t", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class SceneTask(C.Structure):
     """gapro_scene_task: the device pointers of one scene of a batched partition call."""
     _fields_ = [("n_points", C.c_int64), ("coords", C.c_void_p), ("feats", C.c_void_p), ("spp", C.c_void_p),
@@ -143,6 +149,13 @@ SIGNATURES = {
                                        C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "gapro_svgp_fit_batch_ex": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.POINTER(FitOptions), _P,
                                           C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gapro_gp_state_doubles": (C.c_int64, [C.c_int32, C.c_int32]),
+    "gapro_gp_state_plan": (C.c_int64, [_P, C.c_int32, C.c_int32, _P]),
+    "gapro_svgp_fit_batch_state": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.POINTER(FitOptions), _P,
+                                             C.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t]),
+    "gapro_svgp_predict_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, _P]),
+    "gapro_svgp_predict_batch": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P,
+                                           C.POINTER(FitOptions), _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
     "gapro_fit_workspace_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P]),
     "gapro_fit_route": (C.c_int, [C.c_int32, C.c_int32]),
     "gapro_fit_padded_m": (C.c_int, [C.c_int32, C.c_int32]),
@@ -278,7 +291,10 @@ def load() -> C.CDLL:
         try:
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
         except AttributeError:
-            if os.path.abspath(LIB_PATH) == os.path.abspath(default) or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):
+            variant = os.path.abspath(LIB_PATH) != os.path.abspath(default)
+            if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state")):
+                continue  # an older build under A/B comparison: it has no model export (a call raises AttributeError)
+            if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):
                 raise
             if host_only is None:
                 host_only = C.CDLL(default)

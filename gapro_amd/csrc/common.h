@@ -43,6 +43,9 @@ struct gapro_ctx {
   static constexpr unsigned kTicketSets = 64, kTicketsPerSet = 16;
   unsigned* d_tickets = nullptr;
   unsigned ticket_seq = 0;
+  // gapro_svgp_fit_batch_state: the launch's state offsets by fit slot (device copy, grown on demand)
+  long long* d_state_off = nullptr;
+  size_t state_off_cap = 0;
   // single-scene partition calls stage their one-task batch through this ring (pinned host + device mirror);
   // a slot is reused after kTaskRing further calls, long after the stream has consumed it
   gapro_scene_task* h_task_ring = nullptr;

@@ -15,6 +15,17 @@ enum ScalId { S_C = 0, S_RS, S_RL, S_MC, S_MRS, S_MRL, S_VC, S_VRS, S_VRL, S_LOS
 
 inline __host__ __device__ int round_up(int x, int a) { return (x + a - 1) / a * a; }
 
+// Set by gapro_svgp_fit_batch_state in the copy of gapro_fit_options.reserved it hands to the wave-per-fit kernel (never
+// by a caller: the public entry points refuse the bit): the kernel, which trains Z, m and tril(L_S) on chip, then leaves
+// them in the fit's workspace slab where the other kernels keep theirs (Z [M_p][D] behind X, V_M, B_LS row-major).
+constexpr int kFitOptKeepState = 1 << 30;
+// Exported model of one fit (gapro_gp_state_doubles): header of kStateHeader doubles, Z [M][D], mean [M], tril(L_S) [M][M]
+constexpr int kStateHeader = 8;
+enum StateHdr { SH_M = 0, SH_D, SH_STATUS, SH_JITTER, SH_C, SH_RS, SH_RL, SH_RESERVED };
+inline __host__ __device__ long long state_doubles(int m, int d) {
+  return kStateHeader + (long long)m * d + m + (long long)m * m;
+}
+
 // Fits run by the cluster kernel (svgp_fit_cluster.hip: one fit over G workgroups) exchange partial sums through a
 // scratch region at the end of their workspace: 3 column-partial planes of max(G * 512, Mp) doubles + 2 x 16 scalar
 // slots per member, then the transposed copies Zt[D][Mp], Xt[D][Mp] of the inducing / training points.

@@ -41,6 +41,50 @@ __global__ __launch_bounds__(256) void k_fit_cond(int n_fits, int D, const gapro
   }
 }
 
+// Trained model of every fit of a launch (gapro_svgp_fit_batch_state), gathered behind the fit kernels like the figures
+// above.  Every route leaves its final parameters at the same places of the fit's slab: Z [M_p][D] behind X (the strip
+// and staged kernels update it together with their LDS copy, fit_wg.h), the mean in V_M, tril(L_S) row-major in B_LS
+// (float32 in the first half of the slot where the cluster kernel ran the fit in GAPRO_PRECISION_MIXED), c, rho_s,
+// rho_l and the status in the scalar tail; the wave-per-fit kernel writes them there on its way out when asked.  One
+// workgroup per fit copies the M real rows into the route-independent state layout of include/gapro_hip.h.
+// [f32_lo, f32_hi): the launch's cluster fits when their L_S is float32.
+__global__ __launch_bounds__(256) void k_gp_state_export(int D, const gapro_fit_desc* __restrict__ descs,
+                                                         const double* __restrict__ ws, double* __restrict__ state,
+                                                         const long long* __restrict__ state_off, double jitter,
+                                                         int f32_lo, int f32_hi) {
+  const gapro_fit_desc d = descs[blockIdx.x];
+  const int M = d.m1 + d.m2;
+  const Layout lay = make_layout(M, d.t, D);
+  const double* base = ws + d.ws_offset;
+  double* out = state + state_off[d.slot];
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    const double* scal = base + lay.scal;
+    out[SH_M] = (double)M;
+    out[SH_D] = (double)D;
+    out[SH_STATUS] = scal[S_STATUS];
+    out[SH_JITTER] = jitter;
+    out[SH_C] = scal[S_C];
+    out[SH_RS] = scal[S_RS];
+    out[SH_RL] = scal[S_RL];
+    out[SH_RESERVED] = 0.0;
+  }
+  const double* Z = base + lay.xz + (long long)lay.Mp * D;
+  double* oz = out + kStateHeader;
+  for (int e = tid; e < M * D; e += 256) oz[e] = Z[e];
+  const double* vm = base + lay.vec + (long long)V_M * lay.Mp;
+  double* om = oz + (long long)M * D;
+  for (int e = tid; e < M; e += 256) om[e] = vm[e];
+  const double* LS = base + lay.mat + (long long)B_LS * lay.Mp * lay.Mp;
+  const bool f32 = (int)blockIdx.x >= f32_lo && (int)blockIdx.x < f32_hi;
+  double* ol = om + M;
+  for (long long e = tid; e < (long long)M * M; e += 256) {
+    const int i = (int)(e / M), j = (int)(e - (long long)i * M);
+    const long long src = (long long)i * lay.Mp + j;
+    ol[e] = j <= i ? (f32 ? (double)((const float*)LS)[src] : LS[src]) : 0.0;
+  }
+}
+
 // 0 = strip-streaming kernel, 1 = LDS-staged kernel, 2 = generic kernel, 3 = strip-streaming kernel of the small-fit
 // translation unit (M_p <= 64: 256 threads per fit, two fits per CU), 4 = cluster kernel (one fit over several
 // workgroups), 5 = the wave-per-fit kernel (svgp_fit_wave.hip: M_p <= 48 at feat_dim 6).  flags:
@@ -129,11 +173,37 @@ int gapro_svgp_fit_batch(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32_t 
                                  d_fit_loss, nullptr);
 }
 
+int64_t gapro_gp_state_doubles(int32_t m, int32_t feat_dim) {
+  if (m <= 0 || feat_dim <= 0) return 0;
+  return state_doubles(m, feat_dim);
+}
+
+int64_t gapro_gp_state_plan(const gapro_fit_desc* h_descs, int32_t n_fits, int32_t feat_dim, int64_t* h_state_offsets) {
+  if (!h_descs || !h_state_offsets || n_fits < 0) return 0;
+  int64_t off = 0;
+  for (int i = 0; i < n_fits; ++i) {
+    h_state_offsets[i] = off;
+    off += gapro_gp_state_doubles(h_descs[i].m1 + h_descs[i].m2, feat_dim);
+  }
+  return off * (int64_t)sizeof(double);
+}
+
 int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32_t feat_dim, const float* d_feats_spp,
                             const int32_t* d_idx, const gapro_fit_desc* h_descs, gapro_fit_desc* d_descs,
                             const double* d_init_mean, const gapro_fit_options* opt, double* d_workspace,
                             size_t workspace_bytes, float* d_probs, float* d_probs_new, uint8_t* d_labels, float* d_mu,
                             float* d_var, int32_t* d_fit_status, double* d_fit_loss, double* d_fit_cond) {
+  return gapro_svgp_fit_batch_state(ctx, stream_, n_fits, feat_dim, d_feats_spp, d_idx, h_descs, d_descs, d_init_mean,
+                                    opt, d_workspace, workspace_bytes, d_probs, d_probs_new, d_labels, d_mu, d_var,
+                                    d_fit_status, d_fit_loss, d_fit_cond, nullptr, nullptr, 0);
+}
+
+int gapro_svgp_fit_batch_state(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32_t feat_dim,
+                               const float* d_feats_spp, const int32_t* d_idx, const gapro_fit_desc* h_descs,
+                               gapro_fit_desc* d_descs, const double* d_init_mean, const gapro_fit_options* opt,
+                               double* d_workspace, size_t workspace_bytes, float* d_probs, float* d_probs_new,
+                               uint8_t* d_labels, float* d_mu, float* d_var, int32_t* d_fit_status, double* d_fit_loss,
+                               double* d_fit_cond, double* d_state, const int64_t* h_state_offsets, size_t state_bytes) {
   if (!ctx) return GAPRO_ERR_BAD_ARG;
   if (n_fits == 0) return GAPRO_OK;
   if (n_fits < 0 || feat_dim <= 0 || !d_feats_spp || !d_idx || !h_descs || !d_descs || !opt || !d_workspace ||
@@ -190,6 +260,23 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
   if ((size_t)need > workspace_bytes)
     return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_svgp_fit_batch: workspace too small (%lld > %zu)", need,
                       workspace_bytes);
+  if (d_state) {  // every fit's state inside the caller's buffer; the offsets go up with the descriptors (below)
+    if (!h_state_offsets) return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch_state: no state offsets");
+    for (int i = 0; i < n_fits; ++i) {
+      const long long end = h_state_offsets[i] + state_doubles(h_descs[i].m1 + h_descs[i].m2, feat_dim);
+      if (h_state_offsets[i] < 0 || (unsigned long long)end * 8ULL > state_bytes)
+        return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_svgp_fit_batch_state: state of fit %d ends at %lld bytes of %zu",
+                          i, end * 8LL, state_bytes);
+    }
+    if ((size_t)n_fits > ctx->state_off_cap) {
+      if (ctx->d_state_off) (void)hipFree(ctx->d_state_off);
+      ctx->d_state_off = nullptr;
+      ctx->state_off_cap = 0;
+      const size_t cap = std::max<size_t>(1024, 2 * (size_t)n_fits);
+      GAPRO_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_state_off, cap * sizeof(long long)));
+      ctx->state_off_cap = cap;
+    }
+  }
   auto by_cost = [](const gapro_fit_desc& a, const gapro_fit_desc& b) { return a.m1 + a.m2 > b.m1 + b.m2; };
   for (FitGroup& g : grp) std::stable_sort(g.descs.begin(), g.descs.end(), by_cost);
   // the staged fits whose LDS fits a CU twice and the larger ones are two launches (see below)
@@ -294,6 +381,9 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
   }
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_descs, all.data(), all.size() * sizeof(gapro_fit_desc), hipMemcpyHostToDevice,
                                       stream));
+  if (d_state)
+    GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_state_off, h_state_offsets, (size_t)n_fits * sizeof(long long),
+                                        hipMemcpyHostToDevice, stream));
   GAPRO_HIP_CHECK(ctx, hipStreamSynchronize(stream));  // `all` is pageable host memory that dies with this call
   // The kernels go to the context's fit streams so that the staged kernel (a few large fits, which leave most CUs
   // idle), the strip kernels and the others run side by side.  No fork event is needed: `stream` has just been
@@ -413,6 +503,8 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
   int first = -1;
   for (int g = G_WAVE3; g <= G_WAVE1 && first < 0; ++g)
     if (!grp[g].descs.empty()) first = g;
+  gapro_fit_options wave_opt = *opt;  // the wave kernel keeps its model on chip: it writes it out only when asked
+  if (d_state) wave_opt.reserved |= kFitOptKeepState;
   if (first >= 0) {
     const FitGroup& wf = grp[first];
     GAPRO_HIP_CHECK(ctx, mark(wf, 0));
@@ -423,7 +515,7 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
       const int slots = ctx->n_cu * gapro_fit_wave_per_cu(nb, feat_dim);
       const int n_wg = (int)std::min<size_t>(w.descs.size(), (size_t)std::max(slots, 1));
       const int rc = gapro_launch_fit_wave(on(w), nb, (int)w.descs.size(), n_wg, ticket(w), feat_dim, d_feats_spp,
-                                           d_idx, d_descs + w.base, d_init_mean, *opt, d_workspace, d_probs,
+                                           d_idx, d_descs + w.base, d_init_mean, wave_opt, d_workspace, d_probs,
                                            d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
       if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: wave kernel launch failed");
       if (own && g != first) {
@@ -451,6 +543,12 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream_, int32_t n_fits, int32
   if (d_fit_cond)
     hipLaunchKernelGGL(k_fit_cond, dim3((n_fits + 3) / 4), dim3(256), 0, stream, (int)n_fits, (int)feat_dim, d_descs,
                        d_workspace, d_fit_cond);
+  if (d_state) {
+    const bool f32 = opt->precision == GAPRO_PRECISION_MIXED;
+    const int lo = f32 ? (int)clus.base : 0, hi = f32 ? (int)(clus.base + clus.descs.size()) : 0;
+    hipLaunchKernelGGL(k_gp_state_export, dim3(n_fits), dim3(256), 0, stream, (int)feat_dim, d_descs, d_workspace,
+                       d_state, ctx->d_state_off, opt->jitter, lo, hi);
+  }
   GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;
 }

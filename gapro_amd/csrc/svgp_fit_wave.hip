@@ -987,6 +987,21 @@ __device__ inline void fit_wave(ldsd* L, const gapro_fit_desc& desc, const gapro
     const int kb = lane >> 4, j = lane & 15;
     (wbase + lay.dinv)[(size_t)kb * 256 + 17 * j] = LIm[lt(kb, kb) * kTS + j * 17 + j];
   }
+  // the trained model, for gapro_svgp_fit_batch_state only: Z, m and tril(L_S) never left the CU, so they go to the
+  // slab places the workgroup kernels train theirs in (the export kernel of svgp_fit.hip reads every route there)
+  if (opt.reserved & kFitOptKeepState) {
+    double* Zs = wbase + lay.xz + (long long)lay.Mp * DC;
+    for (int e = lane; e < M * DC; e += 64) {
+      const int i = e / DC, d = e - i * DC;
+      Zs[e] = Zt[d * Mp + i];
+    }
+    if (lane < M) (wbase + lay.vec + (long long)V_M * lay.Mp)[lane] = vm[lane];
+    double* LSs = wbase + lay.mat + (long long)B_LS * lay.Mp * lay.Mp;
+    for (int e = lane; e < M * M; e += 64) {
+      const int i = e / M, j = e - i * M;
+      LSs[(long long)i * lay.Mp + j] = j <= i ? LS[lt(i >> 4, j >> 4) * kTS + (i & 15) * 17 + (j & 15)] : 0.0;
+    }
+  }
   if (lane == 0) {
     if (status == GAPRO_OK && !isfinite(last_loss) && opt.training_iter > 0) status = GAPRO_ERR_NOT_FINITE;
     o_status[desc.slot] = status;

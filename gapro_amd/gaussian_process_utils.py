@@ -12,10 +12,11 @@ import torch
 
 from ._lib import FitDesc
 from .gen_ps_utils import _pick_device, _pipeline
+from .gp_model import GPModel, load_models, save_models  # noqa: F401  (re-exported: the models of return_models=True)
 
 
 def fit_gp_spp_batch(feats_spp, problems, training_iter=50, init_mean=None, device=None, keep_debug=False,
-                     return_status=False, reproducibility_probe=False, **pipe_kw):
+                     return_status=False, reproducibility_probe=False, return_models=False, **pipe_kw):
     """Fit many independent GPs in one launch.
 
     feats_spp  f32[S,D] (torch or numpy); problems = list of (b1_inds, b2_inds, intersect_inds).
@@ -29,6 +30,8 @@ def fit_gp_spp_batch(feats_spp, problems, training_iter=50, init_mean=None, devi
     with ``reproducibility_probe=True`` (implies keep_debug; twice the work) ``repro_dv`` / ``repro_dp``: how far each
     fit's sigma^2 (relative) and p (absolute) move when the jitter on K_ZZ is scaled by (1 + 1e-11) -- beyond
     pipeline.REPRO_SOFT (1e-5) a fit's variances are reproducible by no float64 implementation to 1e-4.
+    With ``return_models=True`` one more value follows the list of outputs: the list of trained ``GPModel`` (one per
+    problem; predict_gp_batch evaluates them at other inputs).  The other results are the same bits either way.
     """
     dev = _pick_device(feats_spp, device)
     pipe = _pipeline(dev, training_iter, **pipe_kw)
@@ -58,7 +61,7 @@ def fit_gp_spp_batch(feats_spp, problems, training_iter=50, init_mean=None, devi
     h_init = np.concatenate(init) if init else None
     keep_debug = keep_debug or reproducibility_probe
     res = pipe.fit_descs(f, descs, n, h_idx, oo, init_mean=h_init, keep_debug=keep_debug,
-                         raise_on_failure=not return_status)
+                         raise_on_failure=not return_status, keep_models=return_models)
     if reproducibility_probe:
         res["repro_dv"], res["repro_dp"] = pipe.reproducibility_probe(f, descs, n, h_idx, oo, res=res, init_mean=h_init)
     outs = []
@@ -66,9 +69,47 @@ def fit_gp_spp_batch(feats_spp, problems, training_iter=50, init_mean=None, devi
         a, b = descs[i].out_offset, descs[i].out_offset + descs[i].t
         outs.append((res["probs"][a:b], res["probs_new"][a:b], res["labels"][a:b].astype(bool), res["mu"][a:b],
                      res["var"][a:b]))
-    if return_status:
-        return (outs, res, res["status"]) if keep_debug else (outs, res["status"])
-    return (outs, res) if keep_debug else outs
+    ret = (outs,) + ((res["models"][:n],) if return_models else ()) + ((res,) if keep_debug else ()) + \
+        ((res["status"],) if return_status else ())
+    return ret if len(ret) > 1 else outs
+
+
+def predict_gp_batch(models, feats, rows, device=None, return_status=False, **pipe_kw):
+    """Posterior of trained models at other inputs: model i at ``feats[rows[i]]``.
+
+    models  list of GPModel (fit_gp_spp_batch(..., return_models=True), GPModel.load, ...);
+    feats   f32[R, D] torch or NumPy -- pooled superpoint features or per-point features alike;
+    rows    one index vector per model (any order, repeats allowed, may be empty).
+    Returns, per model, the reference's 5-tuple (pred_probs f32[T], pred_probs_new f32[T], pred_labels bool[T],
+    pred_mu f32[T], pred_variance f32[T]) as NumPy arrays, like fit_gp_spp_batch.  K_ZZ is factored afresh from the
+    model (psd_safe_cholesky's retry rule) with the model's own variational jitter.  A feature width that differs
+    from a model's, a model of a failed fit, or non-finite features raise ValueError / GaproError; with
+    ``return_status=True`` nothing is raised for them, the per-model gapro_status array is the last value and the
+    other models' results are intact.
+    """
+    models = list(models)
+    D = int(feats.shape[1]) if getattr(feats, "ndim", 0) == 2 else -1
+    if D < 0:
+        raise ValueError("predict_gp_batch: feats must be [R, D]")
+    if not return_status:  # before a device is touched
+        for i, mo in enumerate(models):
+            if mo.d != D:
+                raise ValueError("predict_gp_batch: model %d was trained at feature width %d, the features have %d"
+                                 % (i, mo.d, D))
+    if len(rows) != len(models):
+        raise ValueError("predict_gp_batch: %d models but %d row vectors" % (len(models), len(rows)))
+    dev = _pick_device(feats, device)
+    pipe = _pipeline(dev, 50, **pipe_kw)
+    f = feats if isinstance(feats, torch.Tensor) else torch.from_numpy(np.asarray(feats))
+    f = f.to(device=dev, dtype=torch.float32).contiguous()
+    rows = [r.cpu().numpy() if isinstance(r, torch.Tensor) else np.asarray(r) for r in rows]
+    res = pipe.predict_models(models, f, rows, raise_on_failure=not return_status)
+    outs, off = [], res["offsets"]
+    for i in range(len(models)):
+        a, b = int(off[i]), int(off[i + 1])
+        outs.append((res["probs"][a:b], res["probs_new"][a:b], res["labels"][a:b].astype(bool), res["mu"][a:b],
+                     res["var"][a:b]))
+    return (outs, res["status"]) if return_status else outs
 
 
 def fit_gp_spp(coords_float_spp, feats_spp, b1_inds, b2_inds, intersect_inds, training_iter=50, *,

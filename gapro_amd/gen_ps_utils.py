@@ -45,6 +45,7 @@ def gen_pseudo_label_gaussian_process(
     thresh_spp_occu=0.8,
     *,
     broadcast_mu_var=False,
+    return_models=False,
     device=None,
     init_mean_std=0.0,
     seed=0,
@@ -55,6 +56,10 @@ def gen_pseudo_label_gaussian_process(
 
     broadcast_mu_var  return mu/var broadcast to point length (what the ISBNet/SPFormer loaders index,
                       SURVEY Q2) instead of the reference generator's superpoint length.
+    return_models     one more value after the 5-tuple: an object with ``feats_spp`` f32[S, D] (the pooled features,
+                      NumPy) and ``fits``, the scene's GP fits in schedule order as (b1, b2, train superpoint ranks,
+                      test superpoint ranks, GPModel) -- gaussian_process_utils.predict_gp_batch evaluates the models
+                      at other inputs, e.g. every point's own features.  The 5-tuple is the same bits either way.
     init_mean_std     std of the random initial variational mean (gpytorch uses 1e-3 with an unseeded
                       RNG; 0 = deterministic zeros), ``seed`` seeds it.
     eval_stale_chol   predict with the Cholesky factor of the last training step.
@@ -64,14 +69,24 @@ def gen_pseudo_label_gaussian_process(
     job = make_job(coords_float, mask_feats, spp, instance_cls, instance_box, instance_box_volume, wall_box,
                    wall_box_volume, instance_classes, ground_h, thresh_spp_occu, device=dev)
     pipe = _pipeline(dev, training_iter, init_mean_std=init_mean_std, seed=seed, eval_stale_chol=eval_stale_chol)
-    sem, ins, prob, mu, var = pipe.run([job])[0]
+    sem, ins, prob, mu, var = pipe.run([job], keep_models=return_models)[0]
     if broadcast_mu_var:
         idx = job.spp_inv.long()
         mu, var = mu[idx], var[idx]
     outs = (sem, ins, prob, mu, var)
     if was_cpu:
         outs = tuple(o.cpu() for o in outs)
+    if return_models:
+        outs = outs + (SceneModels(job.feats_spp, job.fits),)
     return outs
+
+
+class SceneModels:
+    """The trained GPs of one scene (gen_pseudo_label_gaussian_process(..., return_models=True))."""
+
+    def __init__(self, feats_spp, fits):
+        self.feats_spp = feats_spp  # f32[S, D] pooled superpoint features
+        self.fits = fits            # [(b1, b2, train ranks, test ranks, GPModel)] in schedule order
 
 
 def gen_pseudo_label_gaussian_process_batch(scenes, training_iter=50, device=None, **pipe_kw):

@@ -25,7 +25,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import Context, FitDesc, SceneHeader, SceneTask, ScheduleCounts
+from ._lib import Context, FitDesc, PredictDesc, SceneHeader, SceneTask, ScheduleCounts
+from .gp_model import GPModel, SceneFit
 
 
 # A fit is "soft" when its outputs move by more than this (sigma^2 relative, p absolute) when the jitter on K_ZZ's diagonal
@@ -47,6 +48,12 @@ def _to_np(x, dtype):
     if hasattr(x, "detach"):  # torch.Tensor
         x = x.detach().cpu().numpy()
     return np.ascontiguousarray(np.asarray(x), dtype=dtype)
+
+
+def _host(x) -> np.ndarray:
+    """Blocking device -> host copy of a backend buffer (torch tensor or devmem.DevBuf) as a NumPy array."""
+    h = x.cpu()
+    return h if isinstance(h, np.ndarray) else h.numpy()
 
 
 class LazyViews(dict):
@@ -102,6 +109,10 @@ class SceneJob:
     out_base: int = 0
     outputs: Optional[tuple] = None
     error: Optional[Exception] = None  # why the scene could not be processed (Pipeline.strict = False)
+    # Pipeline.run(..., keep_models=True): pooled features f32[S, D] (NumPy) and the scene's fits in schedule order as
+    # (b1, b2, train superpoint ranks [b1_inds | b2_inds], test superpoint ranks, GPModel)
+    feats_spp: Optional[np.ndarray] = None
+    fits: Optional[list] = None
     scene_key: int = 0  # stable id of the scene (e.g. crc32 of the scan name): seeds the optional initial-mean noise
 
     @property
@@ -491,10 +502,12 @@ class Pipeline:
         job.counts = cnt
 
     # ------------------------------------------------------------------ run
-    def run(self, jobs: Sequence[SceneJob], keep_debug: bool = False):
+    def run(self, jobs: Sequence[SceneJob], keep_debug: bool = False, keep_models: bool = False):
         """Process a batch of scenes; fills job.outputs = (sem i32[N], inst i32[N], prob f32[N], mu f32[S],
-        var f32[S]) as device tensors (same lengths as the reference returns)."""
-        return self._finish(self._start(jobs, keep_debug))
+        var f32[S]) as device tensors (same lengths as the reference returns).  With ``keep_models`` every
+        job also gets ``feats_spp`` and ``fits`` (see SceneJob): the trained GP of every box pair, for predictions at
+        other inputs (predict_models).  The outputs are the same bits either way."""
+        return self._finish(self._start(jobs, keep_debug, keep_models))
 
     kSlots = 3  # pipeline streams = slots of per-batch buffers (see _stream_batches)
 
@@ -674,9 +687,10 @@ class Pipeline:
             self._pin_cache[tag] = buf
         return buf
 
-    def _start(self, jobs: Sequence[SceneJob], keep_debug: bool = False):
+    def _start(self, jobs: Sequence[SceneJob], keep_debug: bool = False, keep_models: bool = False):
         """Stages A-D: everything up to and including the (asynchronous) fit launch."""
         state = self._partition(jobs, keep_debug)
+        state["keep_models"] = keep_models
         self._schedule_all(state)
         self._launch(state)
         return state
@@ -766,7 +780,8 @@ class Pipeline:
         if state["n_fits"]:
             state["pending"] = self.fit_launch(state["feats_spp_all"], state["descs"], state["n_fits"], state["h_idx"],
                                                state["n_out"], keep_debug=state["keep_debug"], slot=state["slot"],
-                                               scene_keys=[j.scene_key for j in state["jobs"]])
+                                               scene_keys=[j.scene_key for j in state["jobs"]],
+                                               keep_models=state.get("keep_models", False))
         state["mark"]("D launched")
 
     def _finish(self, state, sync: bool = True):
@@ -783,6 +798,18 @@ class Pipeline:
             res = self._retry_timeouts(res, state["feats_spp_all"], state["descs"], state["h_idx"], state["n_out"],
                                        slot=state["slot"], scene_keys=[j.scene_key for j in jobs])
         _mark("D fit")
+        if state.get("keep_models"):
+            feats_all = _host(state["feats_spp_all"])
+            descs, h_idx = state.get("descs"), state.get("h_idx")
+            for job in jobs:
+                job.feats_spp = feats_all[job.feats_row_base:job.feats_row_base + job.n_spps].copy()
+                job.fits = []
+                for k in range(job.fit_base, job.fit_base + job.counts.n_fits):
+                    d = descs[k]
+                    io, m = int(d.idx_offset), int(d.m1 + d.m2)
+                    job.fits.append(SceneFit(int(d.b1), int(d.b2), h_idx[io:io + m] - job.feats_row_base,
+                                             h_idx[io + m:io + m + int(d.t)] - job.feats_row_base, res["models"][k],
+                                             int(d.m1)))
         if res is not None and (res["status"] != 0).any():
             # per-fit status -> per-scene failure: only the scenes that own a failed fit are lost
             for job in jobs:
@@ -868,12 +895,88 @@ class Pipeline:
                 j.outputs = None
         return [j.outputs if j.error is None else None for j in state["all_jobs"]]
 
+    # ------------------------------------------------------------------ prediction from kept models
+    def predict_models(self, models: Sequence[GPModel], feats, rows: Sequence, raise_on_failure: bool = True):
+        """Posterior of every model at its own rows of ``feats`` (device f32[R, D]): one gapro_svgp_predict_batch
+        launch.  ``rows[i]`` indexes ``feats`` (any order, repeats allowed).  Returns a dict like fit_collect's: probs,
+        probs_new, mu, var f32 and labels u8 over all rows (model i at [offsets[i], offsets[i + 1])) and a per-model
+        ``status``.  A model of a failed fit, or of another feature width, is refused: ValueError with
+        ``raise_on_failure``, otherwise status BAD_ARG / the fit's own status for that model alone."""
+        lib, ctx, be = self.lib, self.ctx, self.be
+        n = len(models)
+        D, R = int(feats.shape[1]), int(feats.shape[0])
+        rows = [np.ascontiguousarray(_to_np(r, np.int64).reshape(-1)) for r in rows]
+        if len(rows) != n:
+            raise ValueError("predict_models: %d models but %d row vectors" % (n, len(rows)))
+        pre = np.zeros(n, dtype=np.int32)
+        for i, (mo, r) in enumerate(zip(models, rows)):
+            if mo.d != D:
+                if raise_on_failure:
+                    raise ValueError("predict_models: model %d was trained at feature width %d, the features have %d"
+                                     % (i, mo.d, D))
+                pre[i] = -1
+            elif mo.status != 0:
+                if raise_on_failure:
+                    raise ValueError("predict_models: model %d comes from a failed fit (status %d)" % (i, mo.status))
+                pre[i] = mo.status
+            if len(r) and (r.min() < 0 or r.max() >= R):
+                raise ValueError("predict_models: rows of model %d reach outside the %d feature rows" % (i, R))
+        live = [i for i in range(n) if pre[i] == 0]
+        offsets = np.zeros(n + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([len(r) for r in rows])
+        tot = int(offsets[-1])
+        res = dict(probs=np.zeros(tot, np.float32), probs_new=np.zeros(tot, np.float32), mu=np.zeros(tot, np.float32),
+                   var=np.zeros(tot, np.float32), labels=np.zeros(tot, np.uint8), status=pre.copy(), offsets=offsets)
+        if not live:
+            return res
+        nl = len(live)
+        states = [models[i].to_state() for i in live]
+        descs = (PredictDesc * nl)()
+        h_m = np.array([models[i].m for i in live], dtype=np.int32)
+        so = ro = 0
+        for k, i in enumerate(live):
+            d = descs[k]
+            d.state_offset, d.row_offset, d.out_offset, d.t, d.reserved = so, ro, ro, len(rows[i]), 0
+            so += len(states[k])
+            ro += len(rows[i])
+        no = max(ro, 1)
+        d_state = be.from_numpy(np.concatenate(states))
+        h_rows = np.concatenate([rows[i] for i in live]).astype(np.int32) if ro else np.zeros(1, np.int32)
+        d_rows = be.from_numpy(h_rows)
+        ws_bytes = int(lib.gapro_svgp_predict_workspace_bytes(nl, D, _ptr(h_m)))
+        ws = be.empty(ws_bytes)
+        out = be.empty(no * 17)  # probs f32 | probs_new f32 | mu f32 | var f32 | labels u8, as in fit_launch
+        stat = be.empty(nl * 4)
+        ctx.check(lib.gapro_svgp_predict_batch(
+            ctx.handle, self._sh(), nl, D, _ptr(d_state), _ptr(h_m), C.cast(descs, C.c_void_p), _ptr(feats), R,
+            _ptr(d_rows), C.byref(self.opt), _ptr(ws), ws_bytes, _ptr(out[0:4 * no]), _ptr(out[4 * no:8 * no]),
+            _ptr(out[16 * no:17 * no]), _ptr(out[8 * no:12 * no]), _ptr(out[12 * no:16 * no]), _ptr(stat)))
+        raw = _host(out)
+        st = _host(stat).view(np.int32)
+        flat = dict(probs=raw[0:4 * no].view(np.float32), probs_new=raw[4 * no:8 * no].view(np.float32),
+                    mu=raw[8 * no:12 * no].view(np.float32), var=raw[12 * no:16 * no].view(np.float32),
+                    labels=raw[16 * no:17 * no])
+        ro = 0
+        for k, i in enumerate(live):
+            t = len(rows[i])
+            res["status"][i] = st[k]
+            if st[k] != _lib.GAPRO_ERR_CHOLESKY:
+                for key in flat:
+                    res[key][offsets[i]:offsets[i] + t] = flat[key][ro:ro + t]
+            ro += t
+        if raise_on_failure and (res["status"] != 0).any():
+            bad = int(np.nonzero(res["status"])[0][0])
+            raise _lib.GaproError(int(res["status"][bad]), "prediction of model %d of %d failed" % (bad, n))
+        return res
+
     # ------------------------------------------------------------------ stage D
     def fit_descs(self, feats_spp, descs, n_fits: int, h_idx: np.ndarray, n_out: int,
-                  init_mean: Optional[np.ndarray] = None, keep_debug: bool = False, raise_on_failure: bool = True):
-        """Launch a batch of fits and wait for the results (numpy arrays)."""
-        res = self.fit_collect(self.fit_launch(feats_spp, descs, n_fits, h_idx, n_out, init_mean, keep_debug),
-                               raise_on_failure=False)
+                  init_mean: Optional[np.ndarray] = None, keep_debug: bool = False, raise_on_failure: bool = True,
+                  keep_models: bool = False):
+        """Launch a batch of fits and wait for the results (numpy arrays); with ``keep_models`` also res["models"], the
+        trained GPModel of every fit."""
+        res = self.fit_collect(self.fit_launch(feats_spp, descs, n_fits, h_idx, n_out, init_mean, keep_debug,
+                                               keep_models=keep_models), raise_on_failure=False)
         res = self._retry_timeouts(res, feats_spp, descs, h_idx, n_out, init_mean=init_mean)
         if raise_on_failure and (res["status"] != 0).any():
             bad = int(np.nonzero(res["status"])[0][0])
@@ -934,7 +1037,8 @@ class Pipeline:
         self.profile_fit = False  # the retry is not a step of whoever is timing the launches
         try:
             r2 = self.fit_collect(self.fit_launch(feats_spp, sub, len(bad), h_idx, n_out, init_mean, slot=slot + "retry",
-                                                  scene_keys=scene_keys), raise_on_failure=False)
+                                                  scene_keys=scene_keys, keep_models="models" in res),
+                                  raise_on_failure=False)
         finally:
             self.opt.reserved, self.profile_fit = old, prof
             with self._ws_lock:
@@ -947,13 +1051,15 @@ class Pipeline:
             res["status"][i] = r2["status"][k]
             res["loss"][i] = r2["loss"][k]
             res["cond"][i] = r2["cond"][k]
+            if "models" in res:
+                res["models"][int(i)] = r2["models"][k]
         self.timeout_retries += len(bad)
         res["retried"] = [int(i) for i in bad]
         return res
 
     def fit_launch(self, feats_spp, descs, n_fits: int, h_idx: np.ndarray, n_out: int,
                    init_mean: Optional[np.ndarray] = None, keep_debug: bool = False, slot: str = "s0",
-                   scene_keys: Optional[Sequence[int]] = None):
+                   scene_keys: Optional[Sequence[int]] = None, keep_models: bool = False):
         lib, ctx, be = self.lib, self.ctx, self.be
         D = int(feats_spp.shape[1])
         ws_bytes = int(lib.gapro_fit_plan_workspace(C.cast(descs, C.c_void_p), n_fits, D))
@@ -1004,11 +1110,22 @@ class Pipeline:
         if prev is not None:
             be.current_stream().wait_event(prev)
         # (_ex: the per-fit conditioning figure travels with the status)
-        ctx.check(lib.gapro_svgp_fit_batch_ex(
-            ctx.handle, self._sh(), n_fits, D, _ptr(feats_spp), _ptr(d_idx), C.cast(descs, C.c_void_p),
-            _ptr(d_descs), _ptr(d_init),
-            C.byref(self.opt), _ptr(ws), ws_bytes, _ptr(probs), _ptr(probs_new), _ptr(labels), _ptr(mu), _ptr(var),
-            _ptr(status), _ptr(loss), _ptr(cond)))
+        d_state = state_off = None
+        if not keep_models:
+            ctx.check(lib.gapro_svgp_fit_batch_ex(
+                ctx.handle, self._sh(), n_fits, D, _ptr(feats_spp), _ptr(d_idx), C.cast(descs, C.c_void_p),
+                _ptr(d_descs), _ptr(d_init),
+                C.byref(self.opt), _ptr(ws), ws_bytes, _ptr(probs), _ptr(probs_new), _ptr(labels), _ptr(mu), _ptr(var),
+                _ptr(status), _ptr(loss), _ptr(cond)))
+        else:  # the same launch, and behind it the trained model of every fit in one route-independent layout
+            state_off = np.zeros(max(n_fits, 1), dtype=np.int64)
+            state_bytes = int(lib.gapro_gp_state_plan(C.cast(descs, C.c_void_p), n_fits, D, _ptr(state_off)))
+            d_state = be.empty(max(state_bytes, 8))
+            ctx.check(lib.gapro_svgp_fit_batch_state(
+                ctx.handle, self._sh(), n_fits, D, _ptr(feats_spp), _ptr(d_idx), C.cast(descs, C.c_void_p),
+                _ptr(d_descs), _ptr(d_init),
+                C.byref(self.opt), _ptr(ws), ws_bytes, _ptr(probs), _ptr(probs_new), _ptr(labels), _ptr(mu), _ptr(var),
+                _ptr(status), _ptr(loss), _ptr(cond), _ptr(d_state), _ptr(state_off), state_bytes))
         if self.profile_fit:
             each = fit_flops_each(descs, n_fits, D, int(self.opt.training_iter))
             raw = _desc_table(descs, n_fits)
@@ -1044,6 +1161,10 @@ class Pipeline:
         h_stat = self._pinned(slot + "fit_stat", n_fits * 20)
         h_out[:no * 17].copy_(out, non_blocking=True)
         h_stat[:n_fits * 20].copy_(stat, non_blocking=True)
+        h_state = None
+        if d_state is not None:
+            h_state = self._pinned(slot + "fit_state", max(state_bytes, 8))
+            h_state[:max(state_bytes, 8)].copy_(d_state, non_blocking=True)
         done = be.event()
         done.record(be.current_stream())
         # The next launch stays ordered behind the result COPIES of this one, as in round 3.  ADVICE r03 suggested the
@@ -1052,9 +1173,10 @@ class Pipeline:
         # launch's descriptor upload and first workgroups then compete with this launch's copies and the host work
         # that follows them.  GAPRO_SERIALIZE_ON_KERNELS=1 selects the variant (A/B only).
         self._last_fit_done = kern_done if os.environ.get("GAPRO_SERIALIZE_ON_KERNELS") else done
-        keep = (d_descs, d_idx, d_init, ws, out, stat, feats_spp)  # alive until the launch has finished
+        keep = (d_descs, d_idx, d_init, ws, out, stat, feats_spp, d_state)  # alive until the launch has finished
         return dict(done=done, h_out=h_out, h_stat=h_stat, no=no, n_fits=n_fits, ws_bytes=ws_bytes, keep=keep,
-                    ws=ws if keep_debug else None, descs=descs if keep_debug else None)
+                    ws=ws if keep_debug else None, descs=descs if keep_debug else None, h_state=h_state,
+                    state_off=state_off, state_bytes=state_bytes if d_state is not None else 0)
 
     def fit_collect(self, p, raise_on_failure: bool = True):
         """Results of a launch.  The library reports a gapro_status per fit and never fails the batch; with
@@ -1073,6 +1195,10 @@ class Pipeline:
                    labels=raw[16 * no:17 * no].copy(), loss=st_raw[0:8 * n_fits].view(np.float64).copy(), status=st,
                    # (max L_jj / min L_jj)^2 of every fit's last factorisation (a diagnostic: see reproducibility_probe)
                    cond=st_raw[8 * n_fits:16 * n_fits].view(np.float64).copy(), ws_bytes=p["ws_bytes"])
+        if p.get("h_state") is not None:
+            flat = p["h_state"].numpy()[:p["state_bytes"]].view(np.float64)
+            off = p["state_off"]
+            res["models"] = [GPModel.from_state(flat[int(off[i]):]) for i in range(n_fits)]
         if p["ws"] is not None:
             res["workspace"] = p["ws"].clone()  # the slot's workspace is reused by the next launch
             res["descs"] = p["descs"]

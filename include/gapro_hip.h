@@ -469,6 +469,61 @@ int gapro_svgp_fit_batch_ex(gapro_ctx* ctx, void* stream, int32_t n_fits, int32_
                             size_t workspace_bytes, float* d_probs, float* d_probs_new, uint8_t* d_labels,
                             float* d_mu, float* d_var, int32_t* d_fit_status, double* d_fit_loss, double* d_fit_cond);
 
+/* ------------------------------------------------------------------------------------------
+ * The trained models of a fit launch, and predictions from them at other inputs.
+ *
+ * State of one fit with M = m1 + m2 inducing points at feature width D: gapro_gp_state_doubles(M, D) =
+ * 8 + M D + M + M M doubles, the same layout whatever kernel trained the fit and whatever `precision` it ran in:
+ *   [0] M   [1] D   [2] the fit's gapro_status (0 = ok; a failed fit leaves a state that says so)
+ *   [3] variational jitter the fit was trained with (gapro_fit_options.jitter)
+ *   [4] c (constant mean)   [5] rho_s (raw output scale)   [6] rho_l (raw length scale)   [7] 0 (reserved)
+ *   Z f64[M, D] row-major | variational mean f64[M] | tril(L_S) f64[M, M] row-major, upper part zero
+ * Output scale and length scale are softplus(rho_s), softplus(rho_l).  Unpadded: M = 50 exports 50 rows.
+ * ---------------------------------------------------------------------------------------- */
+int64_t gapro_gp_state_doubles(int32_t m, int32_t feat_dim);
+/* h_state_offsets[i] (in doubles) for fit i of h_descs, packed in order; returns the total size in BYTES. */
+int64_t gapro_gp_state_plan(const gapro_fit_desc* h_descs, int32_t n_fits, int32_t feat_dim, int64_t* h_state_offsets);
+/* gapro_svgp_fit_batch_ex with the trained models kept: when the launch has finished, d_state + h_state_offsets[i]
+ * holds the state of fit i (h_descs order).  d_state == NULL is exactly gapro_svgp_fit_batch_ex; with a state buffer
+ * the launch's outputs, statuses and losses are the same bits.  state_bytes = size of d_state (GAPRO_ERR_WORKSPACE if a
+ * state would end beyond it).  Launches that keep states must be issued on one stream per context. */
+int gapro_svgp_fit_batch_state(gapro_ctx* ctx, void* stream, int32_t n_fits, int32_t feat_dim,
+                               const float* d_feats_spp, const int32_t* d_idx, const gapro_fit_desc* h_descs,
+                               gapro_fit_desc* d_descs, const double* d_init_mean, const gapro_fit_options* opt,
+                               double* d_workspace, size_t workspace_bytes, float* d_probs, float* d_probs_new,
+                               uint8_t* d_labels, float* d_mu, float* d_var, int32_t* d_fit_status, double* d_fit_loss,
+                               double* d_fit_cond, double* d_state, const int64_t* h_state_offsets, size_t state_bytes);
+
+/* One model of a predict launch: its state at d_state + state_offset (doubles); test row r of the model is the feature
+ * row d_rows[row_offset + r], r < t; its five outputs go to [out_offset, out_offset + t). */
+typedef struct {
+  int64_t state_offset;
+  int64_t row_offset;
+  int64_t out_offset;
+  int32_t t;
+  int32_t reserved;      /* 0 */
+} gapro_predict_desc;
+
+/* Bytes of device workspace a predict launch of n_models models needs; h_m[i] = M of model i. */
+size_t gapro_svgp_predict_workspace_bytes(int32_t n_models, int32_t feat_dim, const int32_t* h_m);
+/* Posterior of every model at its test rows (gaussian_process_utils.py:426-438 with the model's own parameters):
+ *   K_ZZ + jitter I is factored FRESH from the state (psd_safe_cholesky's retry rule: opt->psd_retries, opt->psd_jitter;
+ *   a state exported from an eval_stale_chol = 1 launch therefore predicts with the fresh factor, not the stale one),
+ *   A = L^-1 k(Z, x), mu = A^T m + c, var = max(s + jitter + |L_S^T A|^2 - |A|^2, opt->min_variance),
+ *   p = Phi(mu / sqrt(1 + var)), label = (float)p >= 0.5f, probs_new = label ? p : 1 - p; float64, rounded to float32 once.
+ * The variational jitter is the MODEL's (state header [3]); min_variance and the retry settings come from `opt`.
+ * h_m[i] / h_descs[i]: M and descriptor of model i (host).  d_feats f32[n_feat_rows, feat_dim]; d_rows i32 (rows may
+ * repeat, any order).  d_status i32[n_models]: GAPRO_OK, the state's own status if its fit had failed (nothing is
+ * written for that model), GAPRO_ERR_BAD_ARG (state of another M / D, or a row outside [0, n_feat_rows)),
+ * GAPRO_ERR_CHOLESKY (nothing written), GAPRO_ERR_NOT_FINITE (a non-finite result).  A model never affects another, and
+ * a row's result does not depend on which models or rows share the launch.  t = 0 is a no-op for that model.  The call
+ * synchronises the stream once (descriptor upload), then only enqueues. */
+int gapro_svgp_predict_batch(gapro_ctx* ctx, void* stream, int32_t n_models, int32_t feat_dim, const double* d_state,
+                             const int32_t* h_m, const gapro_predict_desc* h_descs, const float* d_feats,
+                             int64_t n_feat_rows, const int32_t* d_rows, const gapro_fit_options* opt,
+                             void* d_workspace, size_t workspace_bytes, float* d_probs, float* d_probs_new,
+                             uint8_t* d_labels, float* d_mu, float* d_var, int32_t* d_status);
+
 /* Which kernel gapro_svgp_fit_batch routes a fit of m = m1 + m2 inducing points to: 0 = strip-streaming
  * kernel (64 < M_p <= 128), 1 = LDS-staged kernel (128 < M_p < 512 while Z and X fit the LDS: M_p <= 192 at
  * feat_dim 32), 2 = generic kernel (feat_dim > 32), 3 = the small-fit strip kernel (M_p <= 64: 256 threads per fit,
