@@ -97,6 +97,19 @@ class FitOptions(C.Structure):
                 ("psd_retries", C.c_int32), ("precision", C.c_int32), ("psd_jitter", C.c_double)]
 
 
+# debug bits of FitOptions.reserved: the GAPRO_FIT_DBG_* enumerators of include/gapro_hip.h, which says what each does
+FIT_DBG_NO_STRIP = 1
+FIT_DBG_CALLER_STREAM = 2
+FIT_DBG_NO_SMALL = 4
+FIT_DBG_NO_CLUSTER = 8
+FIT_DBG_CLUSTER_ALL = 16
+FIT_DBG_WG_TILED_ALL = 8192
+FIT_DBG_CLUSTER_STALL = 32768
+FIT_DBG_WG_TILED_NONE = 131072
+FIT_DBG_STATIC_MAP = 262144
+FIT_DBG_NO_WAVE = 1048576
+
+
 # name -> (restype, argtypes); every symbol of include/gapro_hip.h
 _P = C.c_void_p
 SIGNATURES = {
@@ -158,6 +171,7 @@ SIGNATURES = {
                                            C.POINTER(FitOptions), _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
     "gapro_fit_workspace_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P]),
     "gapro_fit_route": (C.c_int, [C.c_int32, C.c_int32]),
+    "gapro_fit_route_flags": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "gapro_fit_padded_m": (C.c_int, [C.c_int32, C.c_int32]),
     "gapro_fit_timing_create": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "gapro_fit_timing_destroy": (None, [_P]),

@@ -555,6 +555,10 @@ int gapro_svgp_fit_batch_state(gapro_ctx* ctx, void* stream_, int32_t n_fits, in
 
 int gapro_fit_route(int32_t m, int32_t feat_dim) { return fit_route(m, feat_dim, 0); }
 
+int gapro_fit_route_flags(int32_t m, int32_t feat_dim, int32_t flags) {
+  return (flags & ~GAPRO_FIT_DBG_ALL) ? (int)GAPRO_ERR_BAD_ARG : fit_route(m, feat_dim, flags);
+}
+
 int gapro_fit_padded_m(int32_t m, int32_t feat_dim) { return gapro_pad_m(m, feat_dim); }
 
 int gapro_fit_timing_create(gapro_ctx* ctx, gapro_fit_timing** out) {

@@ -29,7 +29,7 @@ def fit_gp_spp_batch(feats_spp, problems, training_iter=50, init_mean=None, devi
     The raw result dict carries ``cond``, a per-fit conditioning figure of the last Cholesky factor (a diagnostic), and
     with ``reproducibility_probe=True`` (implies keep_debug; twice the work) ``repro_dv`` / ``repro_dp``: how far each
     fit's sigma^2 (relative) and p (absolute) move when the jitter on K_ZZ is scaled by (1 + 1e-11) -- beyond
-    pipeline.REPRO_SOFT (1e-5) a fit's variances are reproducible by no float64 implementation to 1e-4.
+    fit_runner.REPRO_SOFT (1e-5) a fit's variances are reproducible by no float64 implementation to 1e-4.
     With ``return_models=True`` one more value follows the list of outputs: the list of trained ``GPModel`` (one per
     problem; predict_gp_batch evaluates them at other inputs).  The other results are the same bits either way.
     """

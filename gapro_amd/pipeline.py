@@ -17,43 +17,16 @@ which then never import torch -- round 6).
 from __future__ import annotations
 
 import os
-import sys
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import Callable, Optional, Sequence
 
 import numpy as np
 
 from . import _lib
-from ._lib import Context, FitDesc, PredictDesc, SceneHeader, SceneTask, ScheduleCounts
-from .gp_model import GPModel, SceneFit
-
-
-# A fit is "soft" when its outputs move by more than this (sigma^2 relative, p absolute) when the jitter on K_ZZ's diagonal
-# is scaled by (1 + 1e-11) (Pipeline.reproducibility_probe): fifty Adam steps amplify last-bit differences ~1e9-fold on
-# such a fit, in ANY float64 implementation.  Measured on the S3DIS-shaped test scene's 66 fits: the
-# two soft ones move by 6.4e-5 / 6.8e-4, every other fit by 8e-8 .. 1.2e-6
-REPRO_SOFT = 1.0e-5
-
-
-def _ptr(t) -> C.c_void_p:
-    if t is None:
-        return C.c_void_p(0)
-    if hasattr(t, "data_ptr"):  # torch.Tensor / devmem buffer
-        return C.c_void_p(t.data_ptr())
-    return C.c_void_p(t.ctypes.data)
-
-
-def _to_np(x, dtype):
-    if hasattr(x, "detach"):  # torch.Tensor
-        x = x.detach().cpu().numpy()
-    return np.ascontiguousarray(np.asarray(x), dtype=dtype)
-
-
-def _host(x) -> np.ndarray:
-    """Blocking device -> host copy of a backend buffer (torch tensor or devmem.DevBuf) as a NumPy array."""
-    h = x.cpu()
-    return h if isinstance(h, np.ndarray) else h.numpy()
+from ._lib import FitDesc, SceneHeader, SceneTask, ScheduleCounts
+from .fit_runner import FitRunner, PendingFit, _host, _ptr, _to_np
+from .gp_model import SceneFit
 
 
 class LazyViews(dict):
@@ -168,153 +141,45 @@ def make_job(coords_float, mask_feats, spp, instance_cls, instance_box, instance
                     int(instance_classes), float(ground_h), float(thresh_spp_occu), scene_key=int(scene_key))
 
 
-def _desc_table(descs, n_fits: int) -> np.ndarray:
-    return np.frombuffer(descs, dtype=np.int32, count=n_fits * (C.sizeof(FitDesc) // 4)).reshape(n_fits, -1)
+@dataclass
+class BatchState:
+    """A batch on its way through the stages: _partition creates it, _schedule_all and _launch fill it, _finish ends it."""
+    jobs: list  # the scenes that passed stage A
+    all_jobs: list  # every scene of the batch, rejected ones included
+    stream: object
+    slot: str  # name of the stream's buffers (pinned staging, workspace)
+    mark: Callable  # _marker of the batch
+    tasks: object  # gapro_scene_task array (host) and its device mirror
+    d_tasks: object
+    keep_debug: bool = False
+    keep_models: bool = False
+    feats_spp_all: object = None  # stage B: pooled features f32[sum S, D] of every scene
+    n_fits: int = 0  # stage C: the fit descriptors of the whole batch and their index array
+    n_out: int = 0
+    descs: object = None
+    h_idx: Optional[np.ndarray] = None
+    pending: Optional[PendingFit] = None  # stage D: the launch in flight
 
 
-def fit_flops_each(descs, n_fits: int, feat_dim: int, training_iter: int) -> np.ndarray:
-    """Algorithmic FLOPs of every fit of a batch, SURVEY.md section 8(d):
-    F_fit = I (8.33 M^3 + 12 D M^2) + (M^3/3 + 2 M^2 T + 2 D (M^2 + M T)),  M = m1 + m2."""
-    if n_fits <= 0:
-        return np.zeros(0)
-    raw = _desc_table(descs, n_fits)
-    m = (raw[:, 0] + raw[:, 1]).astype(np.float64)
-    t = raw[:, 2].astype(np.float64)
-    d = float(feat_dim)
-    return training_iter * (8.33 * m**3 + 12.0 * d * m * m) + (m**3 / 3.0 + 2.0 * m * m * t + 2.0 * d * (m * m + m * t))
-
-
-def fit_flops(descs, n_fits: int, feat_dim: int, training_iter: int) -> float:
-    return float(fit_flops_each(descs, n_fits, feat_dim, training_iter).sum())
-
-
-class FitTiming:
-    """Device-side timing of one fit launch (gapro_fit_timing): HIP events recorded by the library on the
-    streams its kernels run on.  read() blocks until the launch has finished."""
-
-    def __init__(self, ctx, handle, flops_strip, flops_staged, flops_small, m, flops_cluster=0.0, flops_wave=0.0):
-        self.ctx, self.handle = ctx, handle
-        self.flops_strip, self.flops_staged, self.flops_small, self.m = flops_strip, flops_staged, flops_small, m
-        self.flops_cluster, self.flops_wave = flops_cluster, flops_wave
-        self.ms = None
-
-    @property
-    def flops(self):
-        return self.flops_strip + self.flops_staged + self.flops_small + self.flops_cluster + self.flops_wave
-
-    def read(self):
-        """(staged kernel ms, strip kernel ms, first start -> last end ms, small-fit strip kernel ms, cluster kernel
-        ms, wave-per-fit kernels ms); the span covers all of them"""
-        if self.ms is None:
-            out = (C.c_float * 5)()
-            self.ctx.check(self.ctx.lib.gapro_fit_timing_read(self.ctx.handle, self.handle, out))
-            w = C.c_float(0.0)
-            self.ctx.check(self.ctx.lib.gapro_fit_timing_read_wave(self.ctx.handle, self.handle, C.byref(w)))
-            self.ms = (float(out[0]), float(out[1]), float(out[2]), float(out[3]), float(out[4]), float(w.value))
-        return self.ms
-
-    def cluster_info(self):
-        """(clusters of more than one workgroup, those whose members did not share an XCD, member workgroups) of this
-        launch's cluster kernel; read before 64 further launches."""
-        out = (C.c_int32 * 3)()
-        self.ctx.check(self.ctx.lib.gapro_fit_timing_cluster_info(self.ctx.handle, self.handle, out))
-        return int(out[0]), int(out[1]), int(out[2])
-
-    def offsets(self, ref):
-        """(first kernel start, last kernel end) of this launch in ms after the start of launch `ref`."""
-        out = (C.c_float * 2)()
-        self.ctx.check(self.ctx.lib.gapro_fit_timing_offsets(self.ctx.handle, ref.handle, self.handle, out))
-        return float(out[0]), float(out[1])
-
-    def close(self):
-        if self.handle is not None:
-            self.ctx.lib.gapro_fit_timing_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001 - interpreter shutdown
-            pass
-
-
-class Pipeline:
+class Pipeline(FitRunner):
     def __init__(self, device=0, training_iter=50, init_mean_std=0.0, seed=0, eval_stale_chol=False,
                  spp_range_cap=None, force_staged=False, precision="f64", cluster_all=False, backend="torch"):
-        from .devmem import make_backend
-
-        if not isinstance(device, int):
-            import torch
-
-            device = torch.device(device).index or 0
-        # backend: "torch" (tensors in, tensors out) or "native" (the library's arena, no torch in the process);
-        # either raises when there is no HIP device -- there is no CPU fallback
-        self.be = make_backend(backend, device)
-        self.device = self.be.device
-        self.ctx = self.be.ctx
-        self.lib = self.ctx.lib
-        self.opt = _lib.default_fit_options(training_iter)
-        self.opt.eval_stale_chol = 1 if eval_stale_chol else 0
-        # reserved: 0 default dispatch (strip-streaming kernel for M_p <= 128, LDS-staged kernel up to 512, generic
-        # kernel beyond); 1 = never the strip kernel (A/B runs, tests)
-        self.opt.reserved = 1 if force_staged else 0
-        # precision: "f64" (default, float64 throughout) or "mixed" (the reference's float32 / float64 split, run by
-        # the cluster kernel; fits routed elsewhere stay float64).  cluster_all: the cluster kernel for every fit it
-        # can take (precision sweeps, A/B runs)
-        if precision not in ("f64", "mixed"):
-            raise ValueError("precision must be 'f64' or 'mixed'")
-        self.opt.precision = 1 if precision == "mixed" else 0
-        if cluster_all:
-            self.opt.reserved |= 16
-        # A/B runs and tests only: further debug bits of gapro_fit_options.reserved (include/gapro_hip.h) from the
-        # environment.  Never silent (ADVICE r03): a leaked variable changes the routing of every fit.
-        env_flags = os.environ.get("GAPRO_FIT_FLAGS", "").strip()
-        if env_flags:
-            try:
-                bits = int(env_flags, 0)
-            except ValueError:
-                raise ValueError("GAPRO_FIT_FLAGS=%r is not an integer (debug bits of gapro_fit_options.reserved)"
-                                 % env_flags) from None
-            if bits:
-                print("[gapro_amd] GAPRO_FIT_FLAGS=0x%x: debug routing bits are ORed into every fit launch of this "
-                      "process (measurement / test setting, not a product mode)" % bits, file=sys.stderr)
-            self.opt.reserved |= bits
-        # a fit that comes back GAPRO_ERR_TIMEOUT (a cluster member was not resident in time: transient, unlike a failed
-        # factorisation) is run once more on the single-workgroup route before its scene is given up (VERDICT r03 7)
-        self.retry_timeouts = True
-        self.timeout_retries = 0  # fits that went through the retry, over the life of this object
-
-        self.init_mean_std = float(init_mean_std)
-        self.seed = int(seed)
+        super().__init__(device, training_iter, init_mean_std, seed, eval_stale_chol, force_staged, precision,
+                         cluster_all, backend)
         self.spp_range_cap = spp_range_cap
         # strict: a scene that cannot be processed (non-finite input, id range beyond the rank table, a GP fit that
         # fails after the jitter retries) raises, as the reference would.  The gen_ps driver clears it: the scene's
         # outputs come back as None with job.error set, and the other scenes of the batch are unaffected.
         self.strict = True
         self.last_stats = {}
-        self.trace = None  # set to a list to collect (time, batch id, stage) host timestamps
-        self.workspace_headroom = 1.3  # growth factor of the fit workspaces over the need that triggers it
-        self.serialize_fits = not os.environ.get("GAPRO_OVERLAP_FITS")  # fit launches never overlap (see fit_launch)
-        self._last_fit_done = None
-        import threading
-
-        self._ws_lock = threading.Lock()
-        # optional HIP-event timing of the fit launches (bench.py): list of (start_event, end_event, flops)
-        self.profile_fit = False
-        self.fit_events = []
         # with profile_fit: torch events (current stream = the stream the kernels are launched on) around the batched
         # partition calls: dicts with 'prepare', 'pool', 'broadcast' -> (start, end) and the points they cover
         self.part_events = []
         self.profile_stages = False  # bench.py --stage-times: synchronising per-stage wall clock
         self.stage_times = {}
-        self._pin_cache = {}
         self._pin_events = {}
-        self._ws = {}  # slot -> fit workspace (device, float64)
         self._keep = {}
 
-    def _sh(self) -> C.c_void_p:
-        """raw handle of the backend's current stream"""
-        return C.c_void_p(self.be.current_stream().cuda_stream)
 
     # ------------------------------------------------------------------ batched partition plumbing
     def _task_array(self, jobs: Sequence[SceneJob]):
@@ -527,7 +392,6 @@ class Pipeline:
 
         Same results as run() batch by batch."""
         self._ensure_streams()
-        outs = []
         # inputs produced on the caller's stream are ordered before both pipeline streams ONCE: an event on
         # the (legacy default) stream recorded per batch would also wait for every blocking stream
         ready = self.be.current_stream().record_event()
@@ -537,78 +401,6 @@ class Pipeline:
         for st in self._streams:
             self.be.current_stream().wait_stream(st)
         return outs
-
-    def warmup(self):
-        """One small launch through every fit kernel family and the result path (a driver calls this while its first
-        scenes are being read): the first launch of a process pays for code-object loading, kernel attributes and the
-        allocator's first blocks -- ~0.2 s that would otherwise sit in front of the first batch."""
-        rng = np.random.default_rng(0)
-        sizes = [4, 12, 20, 30, 50, 75, 150, 280]
-        feats = self.be.from_numpy(rng.normal(size=(2 * sum(sizes), 6)).astype(np.float32))
-        descs = (FitDesc * len(sizes))()
-        idx, io, oo, base = [], 0, 0, 0
-        for k, m in enumerate(sizes):
-            d = descs[k]
-            d.m1, d.m2, d.t, d.b1, d.b2, d.scene = m, m, 4, 0, 1, 0
-            d.idx_offset, d.out_offset, d.ws_offset = io, oo, 0
-            idx.append(np.arange(base, base + 2 * m, dtype=np.int32))
-            idx.append(np.arange(base, base + 4, dtype=np.int32))
-            io += 2 * m + 4
-            oo += 4
-            base += 2 * m
-        it, prof = self.opt.training_iter, self.profile_fit
-        self.opt.training_iter, self.profile_fit = 2, False
-        try:
-            self.fit_descs(feats, descs, len(sizes), np.concatenate(idx), oo, raise_on_failure=False)
-        finally:
-            self.opt.training_iter, self.profile_fit = it, prof
-
-    def prealloc_workspace(self, n_bytes: int, slot: str = "shared"):
-        """Allocate the fit workspace ahead of its first use (a driver calls this from a helper thread while the first
-        scenes are still being read: the hipMalloc + clear of ~25 GB takes 1.2 .. 2.4 s, a third of what a worker needs
-        for the whole ScanNet train split).  A later need beyond this size grows it as usual."""
-        with self.be.device_ctx():
-            self._workspace(slot, max(1, int(n_bytes) // 8), headroom=1.0)
-
-    def _workspace(self, slot: str, n_doubles: int, headroom: Optional[float] = None):
-        """Grow-only fit workspace per pipeline slot.  Every registered slot grows together and new memory is
-        touched once here: a slot first used inside a timed region would otherwise pay the allocation and the
-        first-touch mapping of several GB inside its fit kernel."""
-        with self._ws_lock:
-            return self._workspace_locked(slot, n_doubles, headroom)
-
-    def _workspace_locked(self, slot: str, n_doubles: int, headroom: Optional[float]):
-        self._ws.setdefault(slot, None)
-        cur = self._ws[slot]
-        if cur is None or cur.numel() < n_doubles:
-            if self._last_fit_done is not None:
-                # a launch that may still be running works in the memory about to be released (the fit kernels run on
-                # library-owned streams the caching allocator knows nothing about)
-                self._last_fit_done.synchronize()
-            # 30 % headroom: the need of a batch of 256 scenes varies by ~10 %, and growing means a hipMalloc of
-            # 10 .. 20 GB per slot plus its fill behind the running fit kernels -- 2 s on a freshly booted box, inside
-            # whatever step first exceeds the old size (bench.py's sporadic 980 ms steps against 760 ms launches)
-            size = int(n_doubles * (self.workspace_headroom if headroom is None else headroom)) + 1024
-            if slot.endswith("retry"):  # a handful of timed-out fits (ADVICE r04): exactly their need, for one launch
-                self._ws[slot] = self.be.zeros(n_doubles + 1024, self.be.f64)
-                self.be.current_stream().synchronize()
-                return self._ws[slot][:n_doubles]
-            if self.trace is not None:
-                import time as _time
-                self.trace.append((_time.perf_counter(), 0, "workspace grows to %.1f GB per slot" % (size * 8 / 1e9)))
-            for k in list(self._ws):  # the requested slot, and every slot that is in use (they grow together)
-                if k != slot and (self._ws[k] is None or k.endswith("retry")):
-                    continue
-                if self._ws[k] is None or self._ws[k].numel() < size:
-                    self._ws[k] = None  # release before growing
-                    self._ws[k] = self.be.zeros(size, self.be.f64)
-            # the fill runs on the allocating thread's stream; the fit kernels that use this memory run on other
-            # streams (another pipeline slot's, the library's): nobody may get the tensor before the fill is done
-            self.be.current_stream().synchronize()
-            if self.trace is not None:
-                import time as _time
-                self.trace.append((_time.perf_counter(), 0, "workspace ready"))
-        return self._ws[slot][:n_doubles]
 
     def run_stream(self, batches):
         """run_pipelined for an ITERATOR of batches (e.g. a dataset being read from disk): yields the outputs of
@@ -658,7 +450,6 @@ class Pipeline:
         on(0, self._launch, cur_state)
         nxt = on(1, next, it, None)
         prev_state = None
-        finish_late = bool(os.environ.get("GAPRO_FINISH_LATE"))  # A/B: round 5's order (merge after the pull)
         while cur_state is not None:
             nxt_state = on(i + 1, self._partition, nxt, False) if nxt is not None else None
             if i > 0:
@@ -668,29 +459,19 @@ class Pipeline:
             # scenes), the schedule of the next batch.  The merge comes FIRST (round 6): fit(i-1) has ended -- the
             # partition kernels above only ran once it had drained -- and the pull can block for a whole batch of
             # reads, which in a worker's first second kept finished labels waiting for 0.3 .. 0.5 s
-            if prev_state is not None and not finish_late:
+            if prev_state is not None:
                 yield on(i - 1, self._finish, prev_state, False)
             nxt = on(i + 2, next, it, None) if nxt is not None else None
             if nxt_state is not None:
                 on(i + 1, self._schedule_all, nxt_state)
-            if prev_state is not None and finish_late:
-                yield on(i - 1, self._finish, prev_state, False)
             prev_state, cur_state = cur_state, nxt_state
             i += 1
         yield on(i - 1, self._finish, prev_state, True)
 
-    def _pinned(self, tag: str, nbytes: int):
-        """Growable page-locked staging buffers, reused across batches (hipHostMalloc is slow)."""
-        buf = self._pin_cache.get(tag)
-        if buf is None or buf.numel() < nbytes:
-            buf = self.be.pinned(max(nbytes, 1 << 16))
-            self._pin_cache[tag] = buf
-        return buf
-
     def _start(self, jobs: Sequence[SceneJob], keep_debug: bool = False, keep_models: bool = False):
         """Stages A-D: everything up to and including the (asynchronous) fit launch."""
         state = self._partition(jobs, keep_debug)
-        state["keep_models"] = keep_models
+        state.keep_models = keep_models
         self._schedule_all(state)
         self._launch(state)
         return state
@@ -721,8 +502,7 @@ class Pipeline:
         jobs = [j for j in all_jobs if j.error is None]
         _mark("A prepare")
         if not jobs:
-            return dict(jobs=[], all_jobs=all_jobs, stream=stream, keep_debug=keep_debug, mark=_mark, slot=slot,
-                        pending=None, n_fits=0, n_out=0, tasks=tasks, d_tasks=d_tasks, feats_spp_all=None)
+            return BatchState([], all_jobs, stream, slot, _mark, tasks, d_tasks, keep_debug)
         D = int(jobs[0].feats.shape[1])
         base = 0
         for job in jobs:
@@ -737,13 +517,12 @@ class Pipeline:
         self._pool_all(jobs, tasks, d_tasks, feats_spp_all, stage)
         stream.synchronize()  # one sync: pooled tables of every scene are on the host
         _mark("B pool")
-        return dict(jobs=jobs, all_jobs=all_jobs, stream=stream, keep_debug=keep_debug, mark=_mark,
-                    feats_spp_all=feats_spp_all, slot=slot, pending=None, n_fits=0, n_out=0, tasks=tasks, d_tasks=d_tasks)
+        return BatchState(jobs, all_jobs, stream, slot, _mark, tasks, d_tasks, keep_debug, feats_spp_all=feats_spp_all)
 
-    def _schedule_all(self, state):
+    def _schedule_all(self, state: BatchState):
         """Stage C (host only): static pair schedule of every scene, fit descriptors of the whole batch."""
         lib = self.lib
-        jobs, _mark = state["jobs"], state["mark"]
+        jobs, _mark = state.jobs, state.mark
         if not jobs:
             return
         # one host thread per scene (gapro_schedule_build is host C++ behind ctypes: no GIL): 256 scenes took 0.45 s on
@@ -773,34 +552,33 @@ class Pipeline:
             io += job.counts.n_fit_idx
             oo += job.counts.n_fit_out
         _mark("C export")
-        state.update(n_fits=n_fits, n_out=n_out, descs=descs, h_idx=h_idx)
+        state.n_fits, state.n_out, state.descs, state.h_idx = n_fits, n_out, descs, h_idx
 
-    def _launch(self, state):
+    def _launch(self, state: BatchState):
         """Stage D: one (asynchronous) launch for every fit of every scene."""
-        if state["n_fits"]:
-            state["pending"] = self.fit_launch(state["feats_spp_all"], state["descs"], state["n_fits"], state["h_idx"],
-                                               state["n_out"], keep_debug=state["keep_debug"], slot=state["slot"],
-                                               scene_keys=[j.scene_key for j in state["jobs"]],
-                                               keep_models=state.get("keep_models", False))
-        state["mark"]("D launched")
+        if state.n_fits:
+            state.pending = self.fit_launch(state.feats_spp_all, state.descs, state.n_fits, state.h_idx, state.n_out,
+                                            keep_debug=state.keep_debug, slot=state.slot,
+                                            scene_keys=[j.scene_key for j in state.jobs], keep_models=state.keep_models)
+        state.mark("D launched")
 
-    def _finish(self, state, sync: bool = True):
+    def _finish(self, state: BatchState, sync: bool = True):
         """Stages E-F: wait for the fit results, ordered merge on the host, broadcast on the device.  With
         sync=False the broadcast kernels are only enqueued (the outputs are ordered on the current stream)."""
         lib, ctx, be = self.lib, self.ctx, self.be
-        jobs, keep_debug, _mark = state["jobs"], state["keep_debug"], state["mark"]
+        jobs, keep_debug, _mark = state.jobs, state.keep_debug, state.mark
         _mark("finish")
         if not jobs:  # every scene of the batch was rejected (non-strict mode)
             self.last_stats = dict(n_fits=0, n_fit_out=0, fit=None)
-            return [None for _ in state["all_jobs"]]
-        res = self.fit_collect(state["pending"], raise_on_failure=False) if state["pending"] is not None else None
+            return [None for _ in state.all_jobs]
+        res = self.fit_collect(state.pending, raise_on_failure=False) if state.pending is not None else None
         if res is not None:
-            res = self._retry_timeouts(res, state["feats_spp_all"], state["descs"], state["h_idx"], state["n_out"],
-                                       slot=state["slot"], scene_keys=[j.scene_key for j in jobs])
+            res = self._retry_timeouts(res, state.feats_spp_all, state.descs, state.h_idx, state.n_out,
+                                       slot=state.slot, scene_keys=[j.scene_key for j in jobs])
         _mark("D fit")
-        if state.get("keep_models"):
-            feats_all = _host(state["feats_spp_all"])
-            descs, h_idx = state.get("descs"), state.get("h_idx")
+        if state.keep_models:
+            feats_all = _host(state.feats_spp_all)
+            descs, h_idx = state.descs, state.h_idx
             for job in jobs:
                 job.feats_spp = feats_all[job.feats_row_base:job.feats_row_base + job.n_spps].copy()
                 job.fits = []
@@ -821,14 +599,13 @@ class Pipeline:
             if self.strict:
                 raise next(j.error for j in jobs if j.error is not None)
         tot_s = sum(job.n_spps for job in jobs)
-        tables = self._pinned(state["slot"] + "labels", tot_s * 20)
-        busy = self._pin_events.pop(state["slot"] + "labels", None)
+        tables = self._pinned(state.slot + "labels", tot_s * 20)
+        busy = self._pin_events.pop(state.slot + "labels", None)
         if busy is not None:
             busy.synchronize()  # the previous batch of this slot has uploaded its label tables
         d_tables = be.empty(tot_s * 20)
         tab_np = tables.numpy()
-        views, off = [], 0
-        offs = []
+        offs, off = [], 0
         for job in jobs:
             offs.append(off)
             off += 20 * job.n_spps
@@ -860,13 +637,12 @@ class Pipeline:
         else:
             for arg in zip(jobs, offs):
                 merge_one(arg)
-        views = offs
         d_tables.copy_(tables[:tot_s * 20], non_blocking=True)  # one H2D copy for the whole batch
-        self._pin_events[state["slot"] + "labels"] = be.current_stream().record_event()
-        tasks, d_tasks = state["tasks"], state["d_tasks"]
+        self._pin_events[state.slot + "labels"] = be.current_stream().record_event()
+        tasks, d_tasks = state.tasks, state.d_tasks
         out_off, out_tot = self._carve([12 * job.n_points for job in jobs], 16)
         d_out = be.empty(out_tot)  # [sem | inst | prob] per scene
-        for t, job, off, oo in zip(tasks, jobs, views, out_off):
+        for t, job, off, oo in zip(tasks, jobs, offs, out_off):
             S, n = job.n_spps, job.n_points
             sem = d_out[oo:oo + 4 * n].view(be.i32)
             ins = d_out[oo + 4 * n:oo + 8 * n].view(be.i32)
@@ -885,322 +661,13 @@ class Pipeline:
                                                    C.cast(tasks, C.c_void_p), _ptr(d_tasks)))
         self._part_event_end(ev)
         # the task array must outlive the (possibly delayed) upload enqueued above
-        self._keep[state["slot"]] = (tasks, d_tasks)
+        self._keep[state.slot] = (tasks, d_tasks)
         if sync:
             be.current_stream().synchronize()
         _mark("E+F merge/broadcast")
-        self.last_stats = dict(n_fits=state["n_fits"], n_fit_out=state["n_out"], fit=res)
+        self.last_stats = dict(n_fits=state.n_fits, n_fit_out=state.n_out, fit=res)
         for j in jobs:
             if j.error is not None:  # merged from a failed fit's garbage: not a result
                 j.outputs = None
-        return [j.outputs if j.error is None else None for j in state["all_jobs"]]
+        return [j.outputs if j.error is None else None for j in state.all_jobs]
 
-    # ------------------------------------------------------------------ prediction from kept models
-    def predict_models(self, models: Sequence[GPModel], feats, rows: Sequence, raise_on_failure: bool = True):
-        """Posterior of every model at its own rows of ``feats`` (device f32[R, D]): one gapro_svgp_predict_batch
-        launch.  ``rows[i]`` indexes ``feats`` (any order, repeats allowed).  Returns a dict like fit_collect's: probs,
-        probs_new, mu, var f32 and labels u8 over all rows (model i at [offsets[i], offsets[i + 1])) and a per-model
-        ``status``.  A model of a failed fit, or of another feature width, is refused: ValueError with
-        ``raise_on_failure``, otherwise status BAD_ARG / the fit's own status for that model alone."""
-        lib, ctx, be = self.lib, self.ctx, self.be
-        n = len(models)
-        D, R = int(feats.shape[1]), int(feats.shape[0])
-        rows = [np.ascontiguousarray(_to_np(r, np.int64).reshape(-1)) for r in rows]
-        if len(rows) != n:
-            raise ValueError("predict_models: %d models but %d row vectors" % (n, len(rows)))
-        pre = np.zeros(n, dtype=np.int32)
-        for i, (mo, r) in enumerate(zip(models, rows)):
-            if mo.d != D:
-                if raise_on_failure:
-                    raise ValueError("predict_models: model %d was trained at feature width %d, the features have %d"
-                                     % (i, mo.d, D))
-                pre[i] = -1
-            elif mo.status != 0:
-                if raise_on_failure:
-                    raise ValueError("predict_models: model %d comes from a failed fit (status %d)" % (i, mo.status))
-                pre[i] = mo.status
-            if len(r) and (r.min() < 0 or r.max() >= R):
-                raise ValueError("predict_models: rows of model %d reach outside the %d feature rows" % (i, R))
-        live = [i for i in range(n) if pre[i] == 0]
-        offsets = np.zeros(n + 1, dtype=np.int64)
-        offsets[1:] = np.cumsum([len(r) for r in rows])
-        tot = int(offsets[-1])
-        res = dict(probs=np.zeros(tot, np.float32), probs_new=np.zeros(tot, np.float32), mu=np.zeros(tot, np.float32),
-                   var=np.zeros(tot, np.float32), labels=np.zeros(tot, np.uint8), status=pre.copy(), offsets=offsets)
-        if not live:
-            return res
-        nl = len(live)
-        states = [models[i].to_state() for i in live]
-        descs = (PredictDesc * nl)()
-        h_m = np.array([models[i].m for i in live], dtype=np.int32)
-        so = ro = 0
-        for k, i in enumerate(live):
-            d = descs[k]
-            d.state_offset, d.row_offset, d.out_offset, d.t, d.reserved = so, ro, ro, len(rows[i]), 0
-            so += len(states[k])
-            ro += len(rows[i])
-        no = max(ro, 1)
-        d_state = be.from_numpy(np.concatenate(states))
-        h_rows = np.concatenate([rows[i] for i in live]).astype(np.int32) if ro else np.zeros(1, np.int32)
-        d_rows = be.from_numpy(h_rows)
-        ws_bytes = int(lib.gapro_svgp_predict_workspace_bytes(nl, D, _ptr(h_m)))
-        ws = be.empty(ws_bytes)
-        out = be.empty(no * 17)  # probs f32 | probs_new f32 | mu f32 | var f32 | labels u8, as in fit_launch
-        stat = be.empty(nl * 4)
-        ctx.check(lib.gapro_svgp_predict_batch(
-            ctx.handle, self._sh(), nl, D, _ptr(d_state), _ptr(h_m), C.cast(descs, C.c_void_p), _ptr(feats), R,
-            _ptr(d_rows), C.byref(self.opt), _ptr(ws), ws_bytes, _ptr(out[0:4 * no]), _ptr(out[4 * no:8 * no]),
-            _ptr(out[16 * no:17 * no]), _ptr(out[8 * no:12 * no]), _ptr(out[12 * no:16 * no]), _ptr(stat)))
-        raw = _host(out)
-        st = _host(stat).view(np.int32)
-        flat = dict(probs=raw[0:4 * no].view(np.float32), probs_new=raw[4 * no:8 * no].view(np.float32),
-                    mu=raw[8 * no:12 * no].view(np.float32), var=raw[12 * no:16 * no].view(np.float32),
-                    labels=raw[16 * no:17 * no])
-        ro = 0
-        for k, i in enumerate(live):
-            t = len(rows[i])
-            res["status"][i] = st[k]
-            if st[k] != _lib.GAPRO_ERR_CHOLESKY:
-                for key in flat:
-                    res[key][offsets[i]:offsets[i] + t] = flat[key][ro:ro + t]
-            ro += t
-        if raise_on_failure and (res["status"] != 0).any():
-            bad = int(np.nonzero(res["status"])[0][0])
-            raise _lib.GaproError(int(res["status"][bad]), "prediction of model %d of %d failed" % (bad, n))
-        return res
-
-    # ------------------------------------------------------------------ stage D
-    def fit_descs(self, feats_spp, descs, n_fits: int, h_idx: np.ndarray, n_out: int,
-                  init_mean: Optional[np.ndarray] = None, keep_debug: bool = False, raise_on_failure: bool = True,
-                  keep_models: bool = False):
-        """Launch a batch of fits and wait for the results (numpy arrays); with ``keep_models`` also res["models"], the
-        trained GPModel of every fit."""
-        res = self.fit_collect(self.fit_launch(feats_spp, descs, n_fits, h_idx, n_out, init_mean, keep_debug,
-                                               keep_models=keep_models), raise_on_failure=False)
-        res = self._retry_timeouts(res, feats_spp, descs, h_idx, n_out, init_mean=init_mean)
-        if raise_on_failure and (res["status"] != 0).any():
-            bad = int(np.nonzero(res["status"])[0][0])
-            raise _lib.GaproError(int(res["status"][bad]), "fit %d of %d failed" % (bad, n_fits))
-        return res
-
-    def reproducibility_probe(self, feats_spp, descs, n_fits: int, h_idx: np.ndarray, n_out: int, res=None,
-                              init_mean: Optional[np.ndarray] = None, rel: float = 1e-11):
-        """How far do a fit's outputs move when nothing but rounding-sized quantities change?  The same fits once more
-        with the jitter on K_ZZ's diagonal scaled by (1 + rel) -- 1e-15 absolute on entries of size 0.7, a few ulps --
-        compared with `res` (the unperturbed run; computed here when not given).  Returns (dv, dp) per fit: the largest
-        relative change of sigma^2 and absolute change of p over the fit's test superpoints.  Well-behaved fits come
-        back at 1e-7 .. 1e-6 (float32 output rounding and a little more); a fit beyond REPRO_SOFT amplifies last-bit differences ~1e9-fold over
-        its fifty Adam steps, and NO float64 implementation reproduces its sigma^2 to north_star's 1e-4 -- the reference
-        against itself on another BLAS included (on the S3DIS-shaped test scene: 2 of 66 fits, the
-        two the oracle's own implementations disagree on).  Twice the work of the fits: a caller's choice
-        (fit_gp_spp_batch(..., reproducibility_probe=True)), not the default.  (Perturbing the initial variational mean
-        instead is useless as a probe: at 1e-13 it moves EVERY fit's sigma^2 by 1e-4 .. 9e-2 -- the optimisation is
-        that sensitive to its starting point, which is why the reference's unseeded 1e-3 * randn start is switched off
-        by default -- LABNOTES R6.)"""
-        if res is None:
-            res = self.fit_descs(feats_spp, descs, n_fits, h_idx, n_out, init_mean=init_mean, raise_on_failure=False)
-        jit = float(self.opt.jitter)
-        self.opt.jitter = jit * (1.0 + rel)
-        try:
-            r2 = self.fit_descs(feats_spp, descs, n_fits, h_idx, n_out, init_mean=init_mean, raise_on_failure=False)
-        finally:
-            self.opt.jitter = jit
-        dv, dp = np.zeros(n_fits), np.zeros(n_fits)
-        for k in range(n_fits):
-            d = descs[k]
-            a, b = int(d.out_offset), int(d.out_offset) + int(d.t)
-            if b > a:
-                v1, v2 = res["var"][a:b].astype(np.float64), r2["var"][a:b].astype(np.float64)
-                dv[k] = float(np.max(np.abs(v1 - v2) / np.maximum(np.abs(v1), 1e-30)))
-                dp[k] = float(np.max(np.abs(res["probs"][a:b].astype(np.float64) - r2["probs"][a:b].astype(np.float64))))
-        return dv, dp
-
-    def _retry_timeouts(self, res, feats_spp, descs, h_idx, n_out, init_mean=None, slot="s0", scene_keys=None):
-        """Fits whose status is GAPRO_ERR_TIMEOUT are launched once more with the cluster kernel switched off (debug
-        bit 3 of gapro_fit_options.reserved: the LDS-staged kernel up to M_p = 512, the generic kernel beyond -- one
-        workgroup each, no cross-workgroup barrier that could time out) and their outputs, status and loss replace the
-        first attempt's.  A timeout says that a member of the fit's cluster was not given a CU within
-        GAPRO_CLUSTER_BARRIER_TIMEOUT_MS; the arithmetic never ran to an end, so there is nothing deterministic about
-        the failure and the second attempt computes what the first one would have (the per-fit result does not
-        depend on the kernel beyond float64 round-off: tests/test_fit_gpu.py).  Same descriptors, same index array,
-        same output offsets; only the workspace is the retry's own."""
-        bad = np.nonzero(res["status"] == _lib.GAPRO_ERR_TIMEOUT)[0]
-        if not len(bad) or not self.retry_timeouts:
-            return res
-        sub = (FitDesc * len(bad))()
-        for k, i in enumerate(bad):
-            C.memmove(C.byref(sub, k * C.sizeof(FitDesc)), C.byref(descs, int(i) * C.sizeof(FitDesc)), C.sizeof(FitDesc))
-        print("[gapro_amd] %d GP fit(s) timed out at a cluster barrier; retrying them on one workgroup each"
-              % len(bad), file=sys.stderr)
-        old, prof = self.opt.reserved, self.profile_fit
-        self.opt.reserved = (int(old) | 8) & ~32768
-        self.profile_fit = False  # the retry is not a step of whoever is timing the launches
-        try:
-            r2 = self.fit_collect(self.fit_launch(feats_spp, sub, len(bad), h_idx, n_out, init_mean, slot=slot + "retry",
-                                                  scene_keys=scene_keys, keep_models="models" in res),
-                                  raise_on_failure=False)
-        finally:
-            self.opt.reserved, self.profile_fit = old, prof
-            with self._ws_lock:
-                self._ws.pop(slot + "retry", None)  # its workspace goes back to the allocator
-        for k, i in enumerate(bad):
-            d = descs[int(i)]
-            a, b = int(d.out_offset), int(d.out_offset) + int(d.t)
-            for key in ("probs", "probs_new", "mu", "var", "labels"):
-                res[key][a:b] = r2[key][a:b]
-            res["status"][i] = r2["status"][k]
-            res["loss"][i] = r2["loss"][k]
-            res["cond"][i] = r2["cond"][k]
-            if "models" in res:
-                res["models"][int(i)] = r2["models"][k]
-        self.timeout_retries += len(bad)
-        res["retried"] = [int(i) for i in bad]
-        return res
-
-    def fit_launch(self, feats_spp, descs, n_fits: int, h_idx: np.ndarray, n_out: int,
-                   init_mean: Optional[np.ndarray] = None, keep_debug: bool = False, slot: str = "s0",
-                   scene_keys: Optional[Sequence[int]] = None, keep_models: bool = False):
-        lib, ctx, be = self.lib, self.ctx, self.be
-        D = int(feats_spp.shape[1])
-        ws_bytes = int(lib.gapro_fit_plan_workspace(C.cast(descs, C.c_void_p), n_fits, D))
-        if init_mean is None and self.init_mean_std > 0.0:
-            # gpytorch: variational mean <- 0 + mean_init_std * randn on first call (SURVEY B.1, Q1).  The noise of a
-            # fit is a function of (seed, scene key, box pair) only, so a scene's result depends neither on the
-            # batch it travels in nor on its position there, and a resumed run reproduces it.
-            init_mean = np.zeros(len(h_idx))
-            for k in range(n_fits):
-                d = descs[k]
-                key = int(scene_keys[d.scene]) if scene_keys is not None else int(d.scene)
-                rng = np.random.default_rng([self.seed, key & 0xFFFFFFFF, int(d.b1), int(d.b2)])
-                m = int(d.m1 + d.m2)
-                init_mean[d.idx_offset:d.idx_offset + m] = self.init_mean_std * rng.standard_normal(m)
-        d_descs = be.empty(n_fits * C.sizeof(FitDesc))
-        d_idx = be.from_numpy(h_idx)
-        d_init = be.from_numpy(np.ascontiguousarray(init_mean, dtype=np.float64)) if init_mean is not None else None
-        # ONE workspace for all pipeline slots while launches are serialised (round 4): launch i + 1 starts on the device
-        # when launch i has ended, nothing on the host reads a workspace (results leave through `out` / `stat`), and every
-        # kernel initialises what it reads -- slots were already reused by other fits every third launch.  A worker's
-        # first batches no longer pay three hipMallocs of ~18 GB (~2 s each: the driver clears VRAM on allocation; a
-        # 1201-scene job is 3.5 s of GPU work), and a 256-scene pipeline holds 14 GB of workspace instead of 42.
-        # Tests that inspect trained parameters (keep_debug) and overlapping launches keep a workspace per slot.
-        ws_slot = "shared" if (self.serialize_fits and not keep_debug and not slot.endswith("retry")) else slot
-        ws = self._workspace(ws_slot, ws_bytes // 8)
-        no = max(n_out, 1)
-        # per-test-superpoint outputs in one device block: probs f32 | probs_new f32 | mu f32 | var f32 | labels u8
-        out = be.empty(no * 17)
-        probs = out[0:4 * no].view(be.f32)
-        probs_new = out[4 * no:8 * no].view(be.f32)
-        mu = out[8 * no:12 * no].view(be.f32)
-        var = out[12 * no:16 * no].view(be.f32)
-        labels = out[16 * no:17 * no]
-        stat = be.empty(n_fits * 20)  # loss f64[n] | cond f64[n] | status i32[n]
-        loss = stat[0:8 * n_fits].view(be.f64)
-        cond = stat[8 * n_fits:16 * n_fits].view(be.f64)
-        status = stat[16 * n_fits:20 * n_fits].view(be.i32)
-        if self.profile_fit:
-            tm = C.c_void_p()
-            ctx.check(lib.gapro_fit_timing_create(ctx.handle, C.byref(tm)))
-            ctx.check(lib.gapro_fit_timing_arm(ctx.handle, tm))
-        # One fit launch at a time.  The software pipeline launches fit(i) when the partition kernels of batch i+1 have
-        # completed, and those normally complete when fit(i-1) drains -- but now and then they slip in earlier, fit(i)
-        # is enqueued with most of fit(i-1) still to run, and the members of its cluster fits become resident one by
-        # one as CUs free up, spinning at their first barrier for hundreds of ms on CUs that fit(i-1) could use
-        # (bench.py --steps 20: cluster kernels of 1.2 .. 1.5 s beside the usual 0.23 s, launches 12 % longer).
-        prev = self._last_fit_done if self.serialize_fits else None
-        if prev is not None:
-            be.current_stream().wait_event(prev)
-        # (_ex: the per-fit conditioning figure travels with the status)
-        d_state = state_off = None
-        if not keep_models:
-            ctx.check(lib.gapro_svgp_fit_batch_ex(
-                ctx.handle, self._sh(), n_fits, D, _ptr(feats_spp), _ptr(d_idx), C.cast(descs, C.c_void_p),
-                _ptr(d_descs), _ptr(d_init),
-                C.byref(self.opt), _ptr(ws), ws_bytes, _ptr(probs), _ptr(probs_new), _ptr(labels), _ptr(mu), _ptr(var),
-                _ptr(status), _ptr(loss), _ptr(cond)))
-        else:  # the same launch, and behind it the trained model of every fit in one route-independent layout
-            state_off = np.zeros(max(n_fits, 1), dtype=np.int64)
-            state_bytes = int(lib.gapro_gp_state_plan(C.cast(descs, C.c_void_p), n_fits, D, _ptr(state_off)))
-            d_state = be.empty(max(state_bytes, 8))
-            ctx.check(lib.gapro_svgp_fit_batch_state(
-                ctx.handle, self._sh(), n_fits, D, _ptr(feats_spp), _ptr(d_idx), C.cast(descs, C.c_void_p),
-                _ptr(d_descs), _ptr(d_init),
-                C.byref(self.opt), _ptr(ws), ws_bytes, _ptr(probs), _ptr(probs_new), _ptr(labels), _ptr(mu), _ptr(var),
-                _ptr(status), _ptr(loss), _ptr(cond), _ptr(d_state), _ptr(state_off), state_bytes))
-        if self.profile_fit:
-            each = fit_flops_each(descs, n_fits, D, int(self.opt.training_iter))
-            raw = _desc_table(descs, n_fits)
-            m = (raw[:, 0] + raw[:, 1]).copy()
-            route = {int(v): int(lib.gapro_fit_route(int(v), D)) for v in np.unique(m)}
-            flags = int(self.opt.reserved)
-            r = np.array([route[int(v)] for v in m])
-            if flags & 16:
-                for v in np.unique(m):
-                    mp = int(lib.gapro_fit_padded_m(int(v), D))
-                    if mp >= 64 and mp % 32 == 0 and D <= 32:
-                        r[m == v] = 4
-            if flags & 8:  # no cluster kernel: those fits run where they ran in round 1
-                for v in np.unique(m[r == 4]):
-                    r[m == v] = 1 if int(v) <= 512 and D <= 32 else 2
-            if flags & (1 << 20):  # no wave-per-fit kernel
-                r[r == 5] = 3
-            if flags & 4:
-                r[r == 3] = 0
-            if flags & 1:
-                r[(r == 0) | (r == 3)] = 1
-            is_strip, is_small, is_clus, is_wave = r == 0, r == 3, r == 4, r == 5
-            self.fit_events.append(FitTiming(ctx, tm, float(each[is_strip].sum()),
-                                             float(each[~(is_strip | is_small | is_clus | is_wave)].sum()),
-                                             float(each[is_small].sum()), m, float(each[is_clus].sum()),
-                                             float(each[is_wave].sum())))
-            self.last_fit_m = m
-        # the next launch is ordered behind THIS launch's kernels only, not behind the copies below (ADVICE r03)
-        kern_done = be.event()
-        kern_done.record(be.current_stream())
-        # results travel to pinned host memory on the same stream; nobody waits here
-        h_out = self._pinned(slot + "fit_out", no * 17)
-        h_stat = self._pinned(slot + "fit_stat", n_fits * 20)
-        h_out[:no * 17].copy_(out, non_blocking=True)
-        h_stat[:n_fits * 20].copy_(stat, non_blocking=True)
-        h_state = None
-        if d_state is not None:
-            h_state = self._pinned(slot + "fit_state", max(state_bytes, 8))
-            h_state[:max(state_bytes, 8)].copy_(d_state, non_blocking=True)
-        done = be.event()
-        done.record(be.current_stream())
-        # The next launch stays ordered behind the result COPIES of this one, as in round 3.  ADVICE r03 suggested the
-        # kernels' end instead (so that the host blocks for less inside the next gapro_svgp_fit_batch); measured, same
-        # box, alternating, 10 steps: 322.8 / 327.3 scenes/s with it against 331.3 / 336.7 without (-2.7 %): the next
-        # launch's descriptor upload and first workgroups then compete with this launch's copies and the host work
-        # that follows them.  GAPRO_SERIALIZE_ON_KERNELS=1 selects the variant (A/B only).
-        self._last_fit_done = kern_done if os.environ.get("GAPRO_SERIALIZE_ON_KERNELS") else done
-        keep = (d_descs, d_idx, d_init, ws, out, stat, feats_spp, d_state)  # alive until the launch has finished
-        return dict(done=done, h_out=h_out, h_stat=h_stat, no=no, n_fits=n_fits, ws_bytes=ws_bytes, keep=keep,
-                    ws=ws if keep_debug else None, descs=descs if keep_debug else None, h_state=h_state,
-                    state_off=state_off, state_bytes=state_bytes if d_state is not None else 0)
-
-    def fit_collect(self, p, raise_on_failure: bool = True):
-        """Results of a launch.  The library reports a gapro_status per fit and never fails the batch; with
-        raise_on_failure (the fit_gp_spp API: gpytorch raises NotPSDError / NanError there) the first failed fit
-        raises, otherwise the caller reads res["status"]."""
-        p["done"].synchronize()
-        no, n_fits = p["no"], p["n_fits"]
-        raw = p["h_out"].numpy()
-        st_raw = p["h_stat"].numpy()
-        st = st_raw[16 * n_fits:20 * n_fits].view(np.int32).copy()
-        if raise_on_failure and (st != 0).any():
-            bad = int(np.nonzero(st)[0][0])
-            raise _lib.GaproError(int(st[bad]), "fit %d of %d failed" % (bad, n_fits))
-        res = dict(probs=raw[0:4 * no].view(np.float32).copy(), probs_new=raw[4 * no:8 * no].view(np.float32).copy(),
-                   mu=raw[8 * no:12 * no].view(np.float32).copy(), var=raw[12 * no:16 * no].view(np.float32).copy(),
-                   labels=raw[16 * no:17 * no].copy(), loss=st_raw[0:8 * n_fits].view(np.float64).copy(), status=st,
-                   # (max L_jj / min L_jj)^2 of every fit's last factorisation (a diagnostic: see reproducibility_probe)
-                   cond=st_raw[8 * n_fits:16 * n_fits].view(np.float64).copy(), ws_bytes=p["ws_bytes"])
-        if p.get("h_state") is not None:
-            flat = p["h_state"].numpy()[:p["state_bytes"]].view(np.float64)
-            off = p["state_off"]
-            res["models"] = [GPModel.from_state(flat[int(off[i]):]) for i in range(n_fits)]
-        if p["ws"] is not None:
-            res["workspace"] = p["ws"].clone()  # the slot's workspace is reused by the next launch
-            res["descs"] = p["descs"]
-        p["keep"] = None
-        return res

@@ -532,6 +532,9 @@ int gapro_svgp_predict_batch(gapro_ctx* ctx, void* stream, int32_t n_models, int
  * feat_dim 6: one wavefront trains one fit, eight / four fits per CU, nothing leaves the CU between the first and the
  * last Adam step).  M_p = m padded to the MFMA tile. */
 int gapro_fit_route(int32_t m, int32_t feat_dim);
+/* The same for a launch whose gapro_fit_options.reserved holds `flags` (GAPRO_FIT_DBG_* bits; gapro_fit_route is
+ * flags = 0).  A bit outside GAPRO_FIT_DBG_ALL returns GAPRO_ERR_BAD_ARG, as the launch refuses it. */
+int gapro_fit_route_flags(int32_t m, int32_t feat_dim, int32_t flags);
 /* Padded size M_p of a fit's M x M matrices (a multiple of 16; of 32 where the kernel that takes the fit needs it):
  * a function of (M, D) only, never of the routing options.  The workspace layout is built on it. */
 int gapro_fit_padded_m(int32_t m, int32_t feat_dim);

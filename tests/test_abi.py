@@ -96,3 +96,41 @@ def test_padding_and_route_agree_for_every_size_and_feature_width():
         assert lib.gapro_fit_padded_m(m, 32) == mp, m
         assert lib.gapro_fit_route(m, 32) == (1 if mp <= 208 else 4), m
     assert [lib.gapro_fit_padded_m(m, 6) for m in (130, 200, 230, 260, 300, 330, 340)] == [144, 208, 256, 272, 304, 336, 352]
+
+
+def _dbg_enumerators():
+    text = open(os.path.join(ROOT, "include", "gapro_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return dict(re.findall(r"\bGAPRO_FIT_DBG_([A-Z_]+)\s*=\s*([0-9| ]+)", text))
+
+
+def test_debug_bit_names_match_the_header():
+    enum = _dbg_enumerators()
+    all_bits = sum(int(v) for v in enum.pop("ALL").split("|"))  # distinct powers of two
+    assert len(enum) == 10
+    for name, value in enum.items():
+        assert getattr(_lib, "FIT_DBG_" + name) == int(value), name
+    assert sorted(n[8:] for n in dir(_lib) if n.startswith("FIT_DBG_")) == sorted(enum)
+    union = 0
+    for name in enum:
+        union |= getattr(_lib, "FIT_DBG_" + name)
+    assert union == all_bits
+
+
+def test_route_with_flags_agrees_with_the_plain_route_and_honours_every_routing_bit():
+    """gapro_fit_route_flags is the launch's own router: flags = 0 is gapro_fit_route, a bit that switches a kernel off
+    never yields that kernel's route, and NO_WAVE alone sends exactly the wave kernel's sizes to the small-fit kernel."""
+    lib = _lib.load()
+    forbids = {_lib.FIT_DBG_NO_WAVE: (5,), _lib.FIT_DBG_NO_CLUSTER: (4,), _lib.FIT_DBG_NO_STRIP: (0, 3),
+               _lib.FIT_DBG_NO_SMALL: (3,)}
+    for d in (6, 16, 32, 40):
+        for m in range(2, 1200):
+            r0 = lib.gapro_fit_route(m, d)
+            assert lib.gapro_fit_route_flags(m, d, 0) == r0, (m, d)
+            for bit, routes in forbids.items():
+                r = lib.gapro_fit_route_flags(m, d, bit)
+                assert 0 <= r <= 5 and r not in routes, (m, d, bit, r)
+            if r0 == 5:
+                assert lib.gapro_fit_route_flags(m, d, _lib.FIT_DBG_NO_WAVE) == 3, (m, d)
+    for bad in (32, 64, 1 << 21, 1 << 30, 8 | 4096):  # as the launch refuses them
+        assert lib.gapro_fit_route_flags(100, 6, bad) == -1  # GAPRO_ERR_BAD_ARG

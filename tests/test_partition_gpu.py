@@ -141,7 +141,7 @@ def test_partition_batch_of_ragged_scenes_matches_oracle():
 def test_single_scene_c_entry_points_match_the_batched_ones():
     """gapro_partition_prepare / _pool / gapro_broadcast_labels (one-scene ABI) against the batched path."""
     import torch
-    from gapro_amd.pipeline import _ptr
+    from gapro_amd.fit_runner import _ptr
 
     kw = _synth_kw(21, 20000)
     pipe, job = _run_partition(kw)  # batched path

@@ -158,7 +158,7 @@ def test_s3dis_shaped_scene_matches_oracle():
     from gapro_amd._lib import Context
     from gapro_amd.gaussian_process_utils import fit_gp_spp_batch
     from gapro_amd.gen_ps_utils import getInstanceInfo
-    from gapro_amd.pipeline import REPRO_SOFT
+    from gapro_amd.fit_runner import REPRO_SOFT
     from gapro_amd.synth import make_scene
 
     sc = make_scene(seed=7, n_points=1_000_000, n_objects=40, with_walls_json=False, obj_patch=60, plane_patch=400)

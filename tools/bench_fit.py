@@ -12,29 +12,30 @@ import numpy as np
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
 import torch  # noqa: E402
 
-from gapro_amd._lib import FitDesc  # noqa: E402
-from gapro_amd.pipeline import Pipeline, fit_flops  # noqa: E402
+from gapro_amd import _lib  # noqa: E402
+from gapro_amd.pipeline import Pipeline  # noqa: E402
 from gapro_amd.synth import make_gp_problem  # noqa: E402
 
 
-def build_mix(mix, args):
+def build_mix(mix, args, n_distinct=4):
+    """Descriptors of one launch: per 'M:count' group, `count` fits cycling through n_distinct problems of size M."""
     groups = [(int(a.split(":")[0]), int(a.split(":")[1])) for a in mix.split(",")]
     feats_l, sel = [], []
     base = 0
     for m, cnt in groups:
-        for i in range(4):
+        for i in range(n_distinct):
             f, b1, b2, it = make_gp_problem(i, m // 2, m - m // 2, args.t, args.d)
             feats_l.append(f)
             sel.append((m, b1 + base, b2 + base, it + base))
             base += len(f)
     feats = torch.from_numpy(np.concatenate(feats_l)).cuda()
     n = sum(c for _, c in groups)
-    descs = (FitDesc * n)()
+    descs = (_lib.FitDesc * n)()
     idx = []
     io = oo = k = 0
     for gi, (m, cnt) in enumerate(groups):
         for i in range(cnt):
-            _, b1, b2, it = sel[4 * gi + i % 4]
+            _, b1, b2, it = sel[n_distinct * gi + i % n_distinct]
             d = descs[k]
             d.m1, d.m2, d.t = len(b1), len(b2), len(it)
             d.idx_offset, d.out_offset = io, oo
@@ -67,24 +68,25 @@ def run_two_streams(pipe, args):
         print("%s: %-12s %.2f ms" % (args.mix, mode, dt))
 
 
+def time_launches(pipe, batch, reps, stream=None, **kw):
+    """Median device span (ms) of `reps` launches after a warm-up one, the launch's FLOPs, the last result."""
+    pipe.profile_fit = True
+    times = []
+    for r in range(reps + 1):
+        pipe.fit_events = []
+        with torch.cuda.stream(stream or torch.cuda.current_stream()):
+            res = pipe.fit_descs(*batch, **kw)
+        torch.cuda.synchronize()
+        times.append(pipe.fit_events[0].read()[2])
+    return float(np.median(times[1:])), pipe.fit_events[0].flops, res
+
+
 def run_mix(pipe, args):
     if ";" in args.mix:
         return run_two_streams(pipe, args)
-    feats, descs, n, h_idx, oo = build_mix(args.mix, args)
-    pipe.profile_fit = True
-    times = []
-    for r in range(args.reps + 1):
-        pipe.fit_events = []
-        with torch.cuda.stream(torch.cuda.Stream() if args.own_stream else torch.cuda.current_stream()):
-            pipe.fit_descs(feats, descs, n, h_idx, oo)
-        torch.cuda.synchronize()
-        ev = pipe.fit_events[0]
-        fl = ev.flops
-        if r > 0:
-            times.append(ev.read()[2])
-        else:
-            ev.read()
-    ms = float(np.median(times))
+    batch = build_mix(args.mix, args)
+    n = batch[2]
+    ms, fl, _ = time_launches(pipe, batch, args.reps, torch.cuda.Stream() if args.own_stream else None)
     print("mix %s fork=%s : %9.2f ms/launch  %9.1f fits/s  %7.3f TFLOP/s" % (args.mix, not args.no_fork, ms,
                                                                            n / (ms * 1e-3), fl / (ms * 1e-3) / 1e12))
 
@@ -108,63 +110,20 @@ def main():
     ap.add_argument("--cluster-all", action="store_true", help="the cluster kernel for every fit it can take (A/B)")
     ap.add_argument("--flags", type=int, default=0, help="further gapro_fit_options.reserved debug bits (A/B)")
     args = ap.parse_args()
-    if args.profile:
+    if args.profile or args.lib:
         import os
-        from gapro_amd import _lib
-        _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), "libgapro_hip_prof.so")
-    if args.lib:
-        import os
-        from gapro_amd import _lib
-        _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), args.lib)
-    pipe = Pipeline(device=0, training_iter=args.iters, force_staged=args.force_staged)
-    if args.no_fork:
-        pipe.opt.reserved |= 2
-    if args.no_small:
-        pipe.opt.reserved |= 4
-    if args.no_cluster:
-        pipe.opt.reserved |= 8
-    if args.cluster_all:
-        pipe.opt.reserved |= 16
-    pipe.opt.reserved |= args.flags
+        _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), args.lib or "libgapro_hip_prof.so")
+    pipe = Pipeline(device=0, training_iter=args.iters, force_staged=args.force_staged, cluster_all=args.cluster_all)
+    named = ((args.no_fork, _lib.FIT_DBG_CALLER_STREAM), (args.no_small, _lib.FIT_DBG_NO_SMALL),
+             (args.no_cluster, _lib.FIT_DBG_NO_CLUSTER))
+    pipe.opt.reserved |= args.flags | sum(bit for on, bit in named if on)
     if args.mix:
         run_mix(pipe, args)
         return
     for m in [int(s) for s in args.sizes.split(",")]:
-        m1 = m // 2
-        m2 = m - m1
-        n_distinct = 8
-        feats_l, probs = [], []
-        base = 0
-        for i in range(n_distinct):
-            f, b1, b2, it = make_gp_problem(i, m1, m2, args.t, args.d)
-            feats_l.append(f)
-            probs.append((b1 + base, b2 + base, it + base))
-            base += len(f)
-        feats = torch.from_numpy(np.concatenate(feats_l)).cuda()
         n = args.fits
-        descs = (FitDesc * n)()
-        idx = []
-        io = oo = 0
-        for i in range(n):
-            b1, b2, it = probs[i % n_distinct]
-            d = descs[i]
-            d.m1, d.m2, d.t = len(b1), len(b2), len(it)
-            d.idx_offset, d.out_offset = io, oo
-            idx += [b1, b2, it]
-            io += len(b1) + len(b2) + len(it)
-            oo += len(it)
-        h_idx = np.concatenate(idx).astype(np.int32)
-        pipe.profile_fit = True
-        times = []
-        for r in range(args.reps + 1):
-            pipe.fit_events = []
-            res = pipe.fit_descs(feats, descs, n, h_idx, oo, keep_debug=args.profile)
-            torch.cuda.synchronize()
-            ev = pipe.fit_events[0]
-            fl = ev.flops
-            if r > 0:
-                times.append(ev.read()[2])
-        ms = float(np.median(times))
+        ms, fl, res = time_launches(pipe, build_mix("%d:%d" % (m, n), args, n_distinct=8), args.reps,
+                                    keep_debug=args.profile)
         tf = fl / (ms * 1e-3) / 1e12
         print("M=%4d T=%3d D=%2d fits=%4d iters=%d : %9.2f ms/launch  %9.1f fits/s  %7.3f TFLOP/s  (%.2f%% of 78.6)  "
               "per-fit-step %.1f us (at %d concurrent)" % (m, args.t, args.d, n, args.iters, ms, n / (ms * 1e-3), tf,
@@ -172,7 +131,6 @@ def main():
                                                           max(1, (n + 255) // 256), min(n, 256)), flush=True)
         if args.profile:
             import ctypes as C
-            from gapro_amd import _lib
             lay = (C.c_int64 * 8)()
             _lib.load().gapro_fit_workspace_layout(m, args.t, args.d, C.cast(lay, C.c_void_p))
             scal, total = int(lay[6]), int(lay[7])
@@ -181,17 +139,16 @@ def main():
             names = ["chol:update", "chol:rest", "inv", "kx", "A+BMT+meanvar", "chol:diag", "quad/kl", "Gm+GA",
                      "GLS+adam", "Pm(-GA A^T)", "GKX", "-", "W", "S", "kgrads+adamZ", "-", "adam", "predict", "chol:panel",
                      "misc"]
-            route = _lib.load().gapro_fit_route(m, args.d)
-            if not args.force_staged and route in (0, 3):
+            route = _lib.load().gapro_fit_route_flags(m, args.d, pipe.opt.reserved)  # where this launch really ran
+            if route in (0, 3):
                 names = ["chol:update", "chol:rest", "inv", "s:fill", "s:A", "chol:diag", "post-strips", "s:B",
                          "GLS+adam", "s:meanvar", "s:lik", "s:scale+GLSacc", "s:GA", "tail", "kgrads+adamZ",
                          "s:GKX+PmAcc", "adam", "predict", "s:kgrad-zx (D = 6) / GKXTstore", "misc", "kg:loop", "kg:sums", "(diag:factor", "(diag:inverse",
                          "(diag:stores", "x25", "x26", "x27"]
-            if route == 5 and not (args.flags & (1 << 20)):
+            if route == 5:
                 names = ["hypers", "chol+inv", "kx", "A+colsums", "lik", "At+GLS+Gm", "GB+GA+PmT", "zx grads", "sums+loss",
                          "adamLS", "W+S+Wzz", "adamZ+m+scal", "predict"] + ["-"] * 15
-            from gapro_amd import _lib as _l
-            if (route == 4 or args.cluster_all) and not args.no_cluster:
+            if route == 4:
                 names = ["kzz", "chol:diag(leader)", "chol:panel", "chol:trailing", "inverse", "kx", "fwd:colpart",
                          "-", "chol:flag", "quad+kl", "Gm+GA", "GLS+adamLS+GKX+Pm", "-", "-", "W", "S", "kgrads(fused)", "-",
                          "adam", "predict", "fwd:A", "fwd:B", "-", "-", "-", "-", "-", "-"]

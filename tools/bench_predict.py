@@ -22,7 +22,7 @@ import torch  # noqa: E402
 from gapro_amd._lib import PredictDesc  # noqa: E402
 from gapro_amd.gaussian_process_utils import fit_gp_spp_batch  # noqa: E402
 from gapro_amd.gen_ps_utils import _pipeline  # noqa: E402
-from gapro_amd.pipeline import _ptr  # noqa: E402
+from gapro_amd.fit_runner import ROW_FIELDS, _ptr, block_bytes, block_views  # noqa: E402
 from gapro_amd.synth import make_gp_problem  # noqa: E402
 
 PEAK_TFLOPS, PEAK_TBS = 78.6, 6.3
@@ -50,15 +50,15 @@ def time_launch(pipe, models, feats, rows, window):
     d_rows = torch.from_numpy(np.concatenate(rows).astype(np.int32)).cuda()
     ws_bytes = int(lib.gapro_svgp_predict_workspace_bytes(n, D, _ptr(h_m)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
-    out = torch.empty(no * 17, dtype=torch.uint8, device="cuda")
+    out = block_views(ROW_FIELDS, pipe.be.empty(block_bytes(ROW_FIELDS, no)), no, pipe.be)
     stat = torch.empty(n, dtype=torch.int32, device="cuda")
 
     def launch():
         ctx.check(lib.gapro_svgp_predict_batch(
             ctx.handle, C.c_void_p(torch.cuda.current_stream().cuda_stream), n, D, _ptr(d_state), _ptr(h_m),
             C.cast(descs, C.c_void_p), _ptr(feats), R, _ptr(d_rows), C.byref(pipe.opt), _ptr(ws), ws_bytes,
-            _ptr(out[0:4 * no]), _ptr(out[4 * no:8 * no]), _ptr(out[16 * no:17 * no]), _ptr(out[8 * no:12 * no]),
-            _ptr(out[12 * no:16 * no]), _ptr(stat)))
+            _ptr(out["probs"]), _ptr(out["probs_new"]), _ptr(out["labels"]), _ptr(out["mu"]), _ptr(out["var"]),
+            _ptr(stat)))
 
     launch()
     torch.cuda.synchronize()

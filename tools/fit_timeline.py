@@ -41,7 +41,6 @@ def main():
     args = ap.parse_args()
     _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), args.lib)
     prof = "prof" in args.lib
-    from gapro_amd._lib import FitDesc
     from gapro_amd.pipeline import Pipeline
     from gapro_amd.synth import make_gp_problem
 
@@ -61,7 +60,7 @@ def main():
         base += len(f)
     feats = torch.from_numpy(np.concatenate(feats_l)).cuda()
     n = len(ms)
-    descs = (FitDesc * n)()
+    descs = (_lib.FitDesc * n)()
     idx, io, oo = [], 0, 0
     for i, m in enumerate(ms):
         b1, b2, it = probs[int(m)]
@@ -98,9 +97,7 @@ def main():
         m = int(ms[i])
         lib.gapro_fit_workspace_layout(m, args.t, args.d, C.cast(lay, C.c_void_p))
         o = int(dd[i].ws_offset) + int(lay[6]) + 24
-        r = int(lib.gapro_fit_route(m, args.d))
-        if args.flags & 8 and r == 4:
-            r = 1
+        r = int(lib.gapro_fit_route_flags(m, args.d, pipe.opt.reserved))
         g = 1
         if r == 4:  # gapro_cluster_size: cluster_g in fit_layout.h (work unit 384, powers of two, at most kClMaxG)
             work = float(lay[0]) ** 3 / 384.0 ** 3

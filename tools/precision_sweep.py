@@ -49,7 +49,7 @@ def main():
     import torch
 
     from gapro_amd.gaussian_process_utils import fit_gp_spp_batch
-    from gapro_amd.pipeline import fit_flops_each
+    from gapro_amd.fit_runner import fit_flops_each
     from gapro_amd.synth import make_gp_problem
     from oracle import svgp_oracle as so
 

@@ -24,7 +24,8 @@ def main():
     import concurrent.futures as cf
 
     import bench
-    from gapro_amd.pipeline import REPRO_SOFT, Pipeline, make_job
+    from gapro_amd.fit_runner import REPRO_SOFT
+    from gapro_amd.pipeline import Pipeline, make_job
 
     with cf.ProcessPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as ex:
         kws = list(ex.map(bench._scene_task, [(s, 150000, 6, "stream", None) for s in range(args.scenes)]))
@@ -34,14 +35,14 @@ def main():
         jobs = [make_job(**{k: v for k, v in kw.items()}) for kw in kws[b0:b0 + args.batch]]
         state = pipe._partition(jobs)
         pipe._schedule_all(state)
-        n = state["n_fits"]
+        n = state.n_fits
         if not n:
             continue
-        dv, dp = pipe.reproducibility_probe(state["feats_spp_all"], state["descs"], n, state["h_idx"], state["n_out"])
+        dv, dp = pipe.reproducibility_probe(state.feats_spp_all, state.descs, n, state.h_idx, state.n_out)
         dv_all.append(dv)
         dp_all.append(dp)
-        m_all.append(np.array([state["descs"][k].m1 + state["descs"][k].m2 for k in range(n)]))
-        for j in state["jobs"]:
+        m_all.append(np.array([state.descs[k].m1 + state.descs[k].m2 for k in range(n)]))
+        for j in state.jobs:
             pipe.lib.gapro_schedule_free(j.schedule)
     dv, dp, m = np.concatenate(dv_all), np.concatenate(dp_all), np.concatenate(m_all)
     mv = np.maximum(dv, dp)
