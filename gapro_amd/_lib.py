@@ -53,6 +53,17 @@ class PredictDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class TrainsetDesc(C.Structure):
+    """gapro_trainset_desc: one point-level problem of gapro_trainset_count / gapro_trainset_fill."""
+    _fields_ = [("idx_offset", C.c_int64), ("n1", C.c_int32), ("n2", C.c_int32), ("t", C.c_int32), ("m1", C.c_int32),
+                ("m2", C.c_int32), ("reserved", C.c_int32), ("row_offset", C.c_int64)]
+
+
+TRAINSET_POOL, TRAINSET_NEAREST = 0, 1
+TRAINSET_MAX_NEAREST = 1024
+TRAINSET_MAX_LIST_FACTOR = 2  # a list holds at most so many times N entries (the exact sums' headroom)
+
+
 class SceneTask(C.Structure):
     """gapro_scene_task: the device pointers of one scene of a batched partition call."""
     _fields_ = [("n_points", C.c_int64), ("coords", C.c_void_p), ("feats", C.c_void_p), ("spp", C.c_void_p),
@@ -169,6 +180,11 @@ SIGNATURES = {
     "gapro_svgp_predict_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, _P]),
     "gapro_svgp_predict_batch": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P,
                                            C.POINTER(FitOptions), _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
+    "gapro_trainset_workspace_bytes": (C.c_size_t, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "gapro_trainset_count": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_size_t,
+                                       _P, _P]),
+    "gapro_trainset_fill": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, _P, _P,
+                                      _P, C.c_int32, C.c_int32, _P, _P, C.c_size_t, C.c_int64, _P, _P, _P]),
     "gapro_fit_workspace_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P]),
     "gapro_fit_route": (C.c_int, [C.c_int32, C.c_int32]),
     "gapro_fit_route_flags": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
@@ -306,8 +322,10 @@ def load() -> C.CDLL:
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
         except AttributeError:
             variant = os.path.abspath(LIB_PATH) != os.path.abspath(default)
-            if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state")):
-                continue  # an older build under A/B comparison: it has no model export (a call raises AttributeError)
+            if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state",
+                                            "gapro_trainset_")):
+                continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
+                #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):
                 raise
             if host_only is None:

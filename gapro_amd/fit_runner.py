@@ -1,5 +1,6 @@
 """The fit launcher on one GPU: every GP fit of a batch in ONE gapro_svgp_fit_batch launch (fit_launch / fit_collect /
-fit_descs), the posterior of kept models at other inputs (predict_models), and what goes with them: grow-only
+fit_descs), the posterior of kept models at other inputs (predict_models), point-level fits whose training sets are
+assembled on the device (train_sets / fit_points), and what goes with them: grow-only
 workspaces, pinned staging, the timeout retry, the reproducibility probe, the FLOP accounting of a launch.  Nothing here
 knows what a scene is: pipeline.py's Pipeline derives from FitRunner and adds the scene path.  Device memory, streams
 and events come from a backend (devmem.py).
@@ -18,7 +19,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import FitDesc, PredictDesc
+from ._lib import FitDesc, PredictDesc, SceneHeader, TrainsetDesc
 from .gp_model import GPModel
 
 
@@ -182,6 +183,50 @@ class PendingFit:
     h_state: object = None  # keep_models: pinned model states, their offsets (doubles) and size
     state_off: Optional[np.ndarray] = None
     state_bytes: int = 0
+    d_state: object = None  # keep_models: the states where the launch leaves them (device)
+
+
+def pack_point_problems(problems, n_points: int, npoint_nearest: int, spp_pool: bool):
+    """Descriptors and the int32 index array [b1 | b2 | intersect] of point-level problems.  Every ValueError of the
+    point-level API is raised here, on the host, before a device is touched."""
+    if not spp_pool and not (1 <= int(npoint_nearest) <= _lib.TRAINSET_MAX_NEAREST):
+        raise ValueError("npoint_nearest must be in [1, %d], got %r" % (_lib.TRAINSET_MAX_NEAREST, npoint_nearest))
+    n = len(problems)
+    if n == 0:
+        raise ValueError("no problem given")
+    descs = (TrainsetDesc * n)()
+    idx, io = [], 0
+    for i, prob in enumerate(problems):
+        b1, b2, it = (_to_np(x, np.int64).reshape(-1) for x in prob)
+        if len(b1) == 0 or len(b2) == 0:
+            raise ValueError("problem %d: fit_gp needs at least one point on each side" % i)
+        for a in (b1, b2, it):
+            if len(a) and (a.min() < 0 or a.max() >= n_points):
+                raise ValueError("problem %d: a point index lies outside the %d points" % (i, n_points))
+            if len(a) > _lib.TRAINSET_MAX_LIST_FACTOR * n_points:  # the exact int64 sums have room for 4 N terms
+                raise ValueError("problem %d: a list of %d entries is longer than %d times the %d points"
+                                 % (i, len(a), _lib.TRAINSET_MAX_LIST_FACTOR, n_points))
+        if not spp_pool and len(it) == 0 and max(len(b1), len(b2)) > npoint_nearest:
+            raise ValueError("problem %d: a side is longer than npoint_nearest and there is no intersection point to "
+                             "take the centroid of" % i)
+        d = descs[i]
+        d.idx_offset, d.n1, d.n2, d.t, d.reserved = io, len(b1), len(b2), len(it), 0
+        idx += [b1, b2, it]
+        io += len(b1) + len(b2) + len(it)
+    return descs, np.ascontiguousarray(np.concatenate(idx).astype(np.int32))
+
+
+@dataclass
+class TrainSets:
+    """What train_sets leaves on the device: the table a fit launch reads with identity indices."""
+    train: object  # f32[n_rows, D]
+    sel: object  # i64[n_rows]: superpoint id (pool) or point index (nearest) of every row
+    status: object  # i32[n problems]
+    descs: object  # TrainsetDesc per problem with m1 / m2 / row_offset
+    n_rows: int
+    d_idx: object  # i32: every problem's [b1 | b2 | intersect] point indices
+    feats: object  # f32[N, D]: the row table of the predictions
+    keep: Optional[tuple] = None
 
 
 class FitRunner:
@@ -242,6 +287,7 @@ class FitRunner:
         self.last_fit_m = None  # with profile_fit: M of every fit of the last launch
         self._pin_cache = {}
         self._ws = {}  # slot -> fit workspace (device, float64)
+        self.stage_events = None  # set to a list: fit_points appends (stage, HIP event) at its stage boundaries
 
     def _sh(self) -> C.c_void_p:
         """raw handle of the backend's current stream"""
@@ -324,13 +370,30 @@ class FitRunner:
             return self._ws[slot][:n_doubles]
 
     # ------------------------------------------------------------------ prediction from kept models
+    def _predict_launch(self, d_state, h_m: np.ndarray, descs, feats, d_rows, no: int):
+        """One gapro_svgp_predict_batch launch over states, features and rows that are on the device.  Enqueue only:
+        returns the device block of ``no`` ROW_FIELDS rows (nothing is written for a model that fails before its rows)
+        and the per-model status (device)."""
+        lib, ctx, be = self.lib, self.ctx, self.be
+        n, D, R = len(h_m), int(feats.shape[1]), int(feats.shape[0])
+        ws_bytes = int(lib.gapro_svgp_predict_workspace_bytes(n, D, _ptr(h_m)))
+        ws = be.empty(ws_bytes)
+        out = be.empty(block_bytes(ROW_FIELDS, no))
+        o = block_views(ROW_FIELDS, out, no, be)
+        stat = be.empty(n * 4)
+        ctx.check(lib.gapro_svgp_predict_batch(
+            ctx.handle, self._sh(), n, D, _ptr(d_state), _ptr(h_m), C.cast(descs, C.c_void_p), _ptr(feats), R,
+            _ptr(d_rows), C.byref(self.opt), _ptr(ws), ws_bytes, _ptr(o["probs"]), _ptr(o["probs_new"]),
+            _ptr(o["labels"]), _ptr(o["mu"]), _ptr(o["var"]), _ptr(stat)))
+        return out, stat
+
     def predict_models(self, models: Sequence[GPModel], feats, rows: Sequence, raise_on_failure: bool = True):
         """Posterior of every model at its own rows of ``feats`` (device f32[R, D]): one gapro_svgp_predict_batch
         launch.  ``rows[i]`` indexes ``feats`` (any order, repeats allowed).  Returns a dict like fit_collect's: probs,
         probs_new, mu, var f32 and labels u8 over all rows (model i at [offsets[i], offsets[i + 1])) and a per-model
         ``status``.  A model of a failed fit, or of another feature width, is refused: ValueError with
         ``raise_on_failure``, otherwise status BAD_ARG / the fit's own status for that model alone."""
-        lib, ctx, be = self.lib, self.ctx, self.be
+        be = self.be
         n = len(models)
         D, R = int(feats.shape[1]), int(feats.shape[0])
         rows = [np.ascontiguousarray(_to_np(r, np.int64).reshape(-1)) for r in rows]
@@ -370,15 +433,7 @@ class FitRunner:
         d_state = be.from_numpy(np.concatenate(states))
         h_rows = np.concatenate([rows[i] for i in live]).astype(np.int32) if ro else np.zeros(1, np.int32)
         d_rows = be.from_numpy(h_rows)
-        ws_bytes = int(lib.gapro_svgp_predict_workspace_bytes(nl, D, _ptr(h_m)))
-        ws = be.empty(ws_bytes)
-        out = be.empty(block_bytes(ROW_FIELDS, no))
-        o = block_views(ROW_FIELDS, out, no, be)
-        stat = be.empty(nl * 4)
-        ctx.check(lib.gapro_svgp_predict_batch(
-            ctx.handle, self._sh(), nl, D, _ptr(d_state), _ptr(h_m), C.cast(descs, C.c_void_p), _ptr(feats), R,
-            _ptr(d_rows), C.byref(self.opt), _ptr(ws), ws_bytes, _ptr(o["probs"]), _ptr(o["probs_new"]),
-            _ptr(o["labels"]), _ptr(o["mu"]), _ptr(o["var"]), _ptr(stat)))
+        out, stat = self._predict_launch(d_state, h_m, descs, feats, d_rows, no)
         flat = block_views(ROW_FIELDS, _host(out), no)
         st = _host(stat).view(np.int32)
         ro = 0
@@ -392,6 +447,145 @@ class FitRunner:
         if raise_on_failure and (res["status"] != 0).any():
             bad = int(np.nonzero(res["status"])[0][0])
             raise _lib.GaproError(int(res["status"][bad]), "prediction of model %d of %d failed" % (bad, n))
+        return res
+
+    # ------------------------------------------------------------------ point-level fits
+    def _stage(self, name: str):
+        """HIP event on the current stream at a stage boundary of fit_points (tools/bench_fit_gp.py sets stage_events)."""
+        ev = self.stage_events
+        if ev is not None:
+            e = self.be.event(enable_timing=True)
+            e.record(self.be.current_stream())
+            ev.append((name, e))
+
+    def _to_device(self, x, np_dtype, be_dtype):
+        if self.be.name == "torch" and hasattr(x, "is_cuda"):
+            return x.to(device=self.be.device, dtype=be_dtype).contiguous()
+        return self.be.from_numpy(_to_np(x, np_dtype))
+
+    def train_sets(self, coords, feats, spp, descs, h_idx: np.ndarray, npoint_nearest: int = 800,
+                   spp_pool: bool = True) -> TrainSets:
+        """Training sets of point-level problems (pack_point_problems) on the device: gapro_partition_prepare on the
+        whole input, then gapro_trainset_count / gapro_trainset_fill.  Pool mode reads the per-side row counts on the
+        host once (its only synchronisation beside prepare's); nearest mode enqueues only.  A superpoint id range beyond
+        the rank table raises (SPP_RANGE); non-finite input raises in pool mode and is a per-problem status in nearest
+        mode: prepare's NOT_FINITE verdict on the whole input is set aside there, the centroid's fixed-point scale is
+        taken from the finite coordinates by gapro_trainset_fill itself, and only the problems that meet the non-finite
+        value fail."""
+        lib, ctx, be = self.lib, self.ctx, self.be
+        P = len(descs)
+        d_coords = self._to_device(coords, np.float64, be.f64)
+        d_feats = self._to_device(feats, np.float32, be.f32)
+        d_spp = self._to_device(spp, np.int64, be.i64)
+        N, D = int(d_feats.shape[0]), int(d_feats.shape[1])
+        if tuple(d_coords.shape) != (N, 3) or int(d_spp.numel()) != N:
+            raise ValueError("coords_float must be [N, 3], feats [N, D] and spp [N] for one N")
+        self._stage("start")
+        cap = max(4 * N, 1 << 20)
+        pbytes = int(lib.gapro_partition_prepare_workspace_bytes(N, cap))
+        prep_ws = be.empty(pbytes)
+        spp_inv = be.empty(4 * N)
+        hdr = SceneHeader()
+        rc = lib.gapro_partition_prepare(ctx.handle, self._sh(), N, D, _ptr(d_coords), _ptr(d_feats), _ptr(d_spp), cap,
+                                         _ptr(prep_ws), pbytes, _ptr(spp_inv), C.byref(hdr))
+        if rc != 0 and not (rc == _lib.GAPRO_ERR_NOT_FINITE and not spp_pool):
+            ctx.check(rc)
+        self._stage("prepare")
+        mode = _lib.TRAINSET_POOL if spp_pool else _lib.TRAINSET_NEAREST
+        S = max(int(hdr.n_spps), 1)
+        d_idx = be.from_numpy(h_idx)
+        d_descs = be.empty(P * C.sizeof(TrainsetDesc))
+        ws_bytes = int(lib.gapro_trainset_workspace_bytes(mode, C.cast(descs, C.c_void_p), P, S, D))
+        ws = be.empty(ws_bytes)
+        status = be.empty(4 * P)
+        if spp_pool:
+            counts = be.empty(8 * P)
+            ctx.check(lib.gapro_trainset_count(ctx.handle, self._sh(), P, D, C.cast(descs, C.c_void_p), _ptr(d_descs), N,
+                                               S, _ptr(spp_inv), _ptr(d_idx), _ptr(ws), ws_bytes, _ptr(counts),
+                                               _ptr(status)))
+            h_counts = _host(counts).view(np.int32)  # the call's one synchronisation beside prepare's
+        rows = 0
+        for i in range(P):
+            d = descs[i]
+            d.m1 = int(h_counts[2 * i]) if spp_pool else min(int(d.n1), int(npoint_nearest))
+            d.m2 = int(h_counts[2 * i + 1]) if spp_pool else min(int(d.n2), int(npoint_nearest))
+            d.row_offset = rows
+            rows += d.m1 + d.m2
+        train = be.empty(4 * rows * D)
+        sel = be.empty(8 * rows)
+        ctx.check(lib.gapro_trainset_fill(ctx.handle, self._sh(), mode, P, D, C.cast(descs, C.c_void_p), _ptr(d_descs), N,
+                                          S, _ptr(d_coords), _ptr(d_feats), _ptr(d_spp), _ptr(spp_inv),
+                                          int(hdr.fixed_shift), int(npoint_nearest), _ptr(d_idx), _ptr(ws), ws_bytes,
+                                          rows, _ptr(train), _ptr(sel), _ptr(status)))
+        self._stage("assemble")
+        return TrainSets(train=train.view(be.f32).view(rows, D), sel=sel.view(be.i64), status=status.view(be.i32),
+                         descs=descs, n_rows=rows, d_idx=d_idx, feats=d_feats,
+                         keep=(d_coords, d_spp, spp_inv, prep_ws, ws, d_descs))
+
+    def fit_points(self, coords, feats, spp, descs, h_idx: np.ndarray, npoint_nearest: int = 800, spp_pool: bool = True,
+                   keep_models: bool = False, raise_on_failure: bool = True):
+        """Point-level fits, on the device from end to end: train_sets, one fit launch on the assembled table (identity
+        indices, zero initial variational mean), one predict launch that reads the trained states where the fit left
+        them, at every intersection point's own feature row.  Returns a dict: probs, probs_new, mu, var f32 and labels
+        u8 over all intersection points (problem i at [offsets[i], offsets[i + 1])), a per-problem ``status`` (the
+        assembly's, else the fit's, else the prediction's) and, with ``keep_models``, ``models``."""
+        ts = self.train_sets(coords, feats, spp, descs, h_idx, npoint_nearest, spp_pool)
+        P = len(descs)
+        # the fit launch's own test set is not wanted: every fit gets its first training row as a throw-away test row
+        fd = (FitDesc * P)()
+        pd = (PredictDesc * P)()
+        fidx, io, oo = [], 0, 0
+        offsets = np.zeros(P + 1, dtype=np.int64)
+        for i in range(P):
+            t, f = descs[i], fd[i]
+            m = int(t.m1 + t.m2)
+            f.m1, f.m2, f.t, f.b1, f.b2, f.scene = t.m1, t.m2, 1, 0, 1, i
+            f.idx_offset, f.out_offset, f.ws_offset = io, i, 0
+            fidx.append(np.arange(t.row_offset, t.row_offset + m + 1, dtype=np.int32))
+            fidx[-1][m] = t.row_offset
+            io += m + 1
+            q = pd[i]
+            q.row_offset, q.out_offset, q.t, q.reserved = t.idx_offset + t.n1 + t.n2, oo, t.t, 0
+            oo += int(t.t)
+            offsets[i + 1] = oo
+        fidx = np.concatenate(fidx)
+        h_m = np.array([descs[i].m1 + descs[i].m2 for i in range(P)], dtype=np.int32)
+        no = max(oo, 1)
+        flags0, prof = self.opt.reserved, self.profile_fit
+        try:
+            for attempt in range(2):
+                pend = self.fit_launch(ts.train, fd, P, fidx, P, keep_models=True, state_to_host=keep_models)
+                self._stage("fit")
+                for i in range(P):
+                    pd[i].state_offset = int(pend.state_off[i])
+                out, pstat = self._predict_launch(pend.d_state, h_m, pd, ts.feats, ts.d_idx, no)
+                self._stage("predict")
+                flat = block_views(ROW_FIELDS, _host(out), no)
+                st_pred = _host(pstat).view(np.int32)
+                st_asm = _host(ts.status).view(np.int32)
+                fit = self.fit_collect(pend, raise_on_failure=False)
+                timed_out = fit["status"] == _lib.GAPRO_ERR_TIMEOUT
+                if attempt or not timed_out.any() or not self.retry_timeouts:
+                    break
+                # a cluster member was not resident in time (transient): the launch once more on one workgroup per fit
+                print("[gapro_amd] %d GP fit(s) timed out at a cluster barrier; retrying on one workgroup each"
+                      % int(timed_out.sum()), file=sys.stderr)
+                self.timeout_retries += int(timed_out.sum())
+                self.opt.reserved = (int(flags0) | _lib.FIT_DBG_NO_CLUSTER) & ~_lib.FIT_DBG_CLUSTER_STALL
+                self.profile_fit = False
+        finally:
+            self.opt.reserved, self.profile_fit = flags0, prof
+        status = np.where(st_asm != 0, st_asm, np.where(fit["status"] != 0, fit["status"], st_pred)).astype(np.int32)
+        res = {k: flat[k][:oo].copy() for k in flat}
+        for i in np.nonzero(status)[0]:  # a failed problem's rows may not have been written at all
+            for k in flat:
+                res[k][offsets[i]:offsets[i + 1]] = 0
+        res.update(status=status, offsets=offsets, loss=fit["loss"], train_sets=ts)
+        if keep_models:
+            res["models"] = fit["models"]
+        if raise_on_failure and (status != 0).any():
+            bad = int(np.nonzero(status)[0][0])
+            raise _lib.GaproError(int(status[bad]), "point-level fit %d of %d failed" % (bad, P))
         return res
 
     # ------------------------------------------------------------------ stage D
@@ -483,7 +677,10 @@ class FitRunner:
 
     def fit_launch(self, feats_spp, descs, n_fits: int, h_idx: np.ndarray, n_out: int,
                    init_mean: Optional[np.ndarray] = None, keep_debug: bool = False, slot: str = "s0",
-                   scene_keys: Optional[Sequence[int]] = None, keep_models: bool = False) -> PendingFit:
+                   scene_keys: Optional[Sequence[int]] = None, keep_models: bool = False,
+                   state_to_host: bool = True) -> PendingFit:
+        """Enqueue one launch.  ``keep_models`` keeps the trained states (PendingFit.d_state, on the device);
+        ``state_to_host`` also brings them to the host, where fit_collect turns them into GPModels."""
         lib, ctx, be = self.lib, self.ctx, self.be
         D = int(feats_spp.shape[1])
         ws_bytes = int(lib.gapro_fit_plan_workspace(C.cast(descs, C.c_void_p), n_fits, D))
@@ -550,7 +747,7 @@ class FitRunner:
         h_out[:out.numel()].copy_(out, non_blocking=True)
         h_stat[:stat.numel()].copy_(stat, non_blocking=True)
         h_state = None
-        if d_state is not None:
+        if d_state is not None and state_to_host:
             h_state = self._pinned(slot + "fit_state", max(state_bytes, 8))
             h_state[:max(state_bytes, 8)].copy_(d_state, non_blocking=True)
         done = be.event()
@@ -564,7 +761,7 @@ class FitRunner:
         keep = (d_descs, d_idx, d_init, ws, out, stat, feats_spp, d_state)  # alive until the launch has finished
         return PendingFit(done=done, h_out=h_out, h_stat=h_stat, no=no, n_fits=n_fits, ws_bytes=ws_bytes, keep=keep,
                           ws=ws if keep_debug else None, descs=descs if keep_debug else None, h_state=h_state,
-                          state_off=state_off, state_bytes=state_bytes)
+                          state_off=state_off, state_bytes=state_bytes, d_state=d_state)
 
     def fit_collect(self, p: PendingFit, raise_on_failure: bool = True):
         """Results of a launch.  The library reports a gapro_status per fit and never fails the batch; with

@@ -1,7 +1,11 @@
-"""Same-name mirror of reference gapro/gaussian_process_utils.py for its only live fitter.
+"""Same-name mirror of reference gapro/gaussian_process_utils.py for its two single-model fitters.
 
-``fit_gp_spp`` keeps the reference signature (gaussian_process_utils.py:382) and return order (:445):
+``fit_gp_spp`` (the generator's fitter, on pooled superpoint features) keeps the reference signature
+(gaussian_process_utils.py:382) and return order (:445):
 (pred_probs f32[T], pred_probs_new f32[T], pred_labels bool[T], pred_mu f32[T], pred_variance f32[T]).
+``fit_gp`` (:28-116) is the point-level fitter: point index sets in, the training set assembled on the device, every
+intersection point predicted from its own feature row; it returns (pred_probs, pred_probs_new, pred_labels,
+pred_variance) with the Bernoulli variance p (1 - p).
 """
 from __future__ import annotations
 
@@ -10,7 +14,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import FitDesc
+from ._lib import FitDesc, GaproError
+from .fit_runner import _host, pack_point_problems
 from .gen_ps_utils import _pick_device, _pipeline
 from .gp_model import GPModel, load_models, save_models  # noqa: F401  (re-exported: the models of return_models=True)
 
@@ -120,5 +125,82 @@ def fit_gp_spp(coords_float_spp, feats_spp, b1_inds, b2_inds, intersect_inds, tr
     out = fit_gp_spp_batch(feats_spp, [(b1_inds, b2_inds, intersect_inds)], training_iter,
                            init_mean=None if init_mean is None else [init_mean], device=dev, **pipe_kw)[0]
     keep_cpu = isinstance(feats_spp, torch.Tensor) and not feats_spp.is_cuda
+    tens = tuple(torch.from_numpy(np.ascontiguousarray(o)) for o in out)
+    return tens if keep_cpu else tuple(t.to(dev) for t in tens)
+
+
+# ---------------------------------------------------------------------- point-level fits (reference :28-116)
+def _n_points(coords_float, feats, spp):
+    shp = tuple(getattr(feats, "shape", ()))
+    if len(shp) != 2:
+        raise ValueError("feats must be [N, D]")
+    if tuple(coords_float.shape) != (shp[0], 3) or len(spp) != shp[0]:
+        raise ValueError("coords_float must be [N, 3], feats [N, D] and spp [N] for one N")
+    return int(shp[0])
+
+
+def gp_train_sets(coords_float, feats, spp, problems, npoint_nearest=800, spp_pool=True, device=None, **pipe_kw):
+    """The training sets ``fit_gp_batch`` fits, assembled on the device (assembly only).
+
+    problems = list of (b1_inds, b2_inds, intersect_inds), POINT indices in any order (an index listed twice counts
+    twice).  Returns, per problem, ``(train_x f32[M, D], m1, m2, sel1, sel2)``: side 1's rows (label -1), then side
+    2's (+1).  ``spp_pool=True``: a side's rows are its distinct superpoints in ascending id order, each the exact
+    fixed-point mean of the side's points of that superpoint (``npoint_nearest`` is ignored); ``sel`` holds the ids.
+    ``spp_pool=False``: a side of at most ``npoint_nearest`` (1 .. 1024) points is kept as given, a longer one keeps the
+    points nearest to the centroid of the intersection's points, ordered by (distance, position in the list); ``sel``
+    holds the chosen point indices.  DESIGN.md 4.4 has the arithmetic.  A problem that meets a non-finite coordinate
+    or row raises GaproError (``fit_gp_batch(..., return_status=True)`` reports it per problem instead)."""
+    n = _n_points(coords_float, feats, spp)
+    descs, h_idx = pack_point_problems(problems, n, npoint_nearest, spp_pool)
+    dev = _pick_device(feats, device)
+    pipe = _pipeline(dev, 50, **pipe_kw)
+    ts = pipe.train_sets(coords_float, feats, spp, descs, h_idx, npoint_nearest, spp_pool)
+    status = _host(ts.status).copy()
+    if (status != 0).any():
+        bad = int(np.nonzero(status)[0][0])
+        raise GaproError(int(status[bad]), "training set of problem %d of %d" % (bad, len(descs)))
+    train, sel = _host(ts.train), _host(ts.sel)
+    outs = []
+    for d in descs:
+        a, b, c = int(d.row_offset), int(d.row_offset + d.m1), int(d.row_offset + d.m1 + d.m2)
+        outs.append((train[a:c].copy(), int(d.m1), int(d.m2), sel[a:b].copy(), sel[b:c].copy()))
+    return outs
+
+
+def fit_gp_batch(coords_float, feats, spp, problems, training_iter=50, npoint_nearest=800, spp_pool=True, device=None,
+                 return_latent=False, return_models=False, return_status=False, **pipe_kw):
+    """Point-level GP fits of many problems, on the device from the index sets to the predictions: the training sets
+    of ``gp_train_sets``, one fit launch on them (zero initial variational mean, the default options, as
+    ``fit_gp_spp``), one predict launch at ``feats[intersect_inds]`` from the trained states where the fit left them.
+
+    Returns a list of 4-tuples of NumPy arrays, one per problem: (pred_probs f32[T], pred_probs_new f32[T],
+    pred_labels bool[T], pred_variance f32[T]) with pred_variance = p (1 - p) in float32 (the Bernoulli variance,
+    reference :112); ``return_latent`` appends the latent mean and variance (6-tuples).  Then, as in
+    ``fit_gp_spp_batch``: with ``return_models`` the list of trained GPModel, with ``return_status`` the per-problem
+    gapro_status array (nothing is raised; a failed problem does not affect the others)."""
+    n = _n_points(coords_float, feats, spp)
+    descs, h_idx = pack_point_problems(problems, n, npoint_nearest, spp_pool)
+    dev = _pick_device(feats, device)
+    pipe = _pipeline(dev, training_iter, **pipe_kw)
+    res = pipe.fit_points(coords_float, feats, spp, descs, h_idx, npoint_nearest, spp_pool, keep_models=return_models,
+                          raise_on_failure=not return_status)
+    outs, off = [], res["offsets"]
+    for i in range(len(descs)):
+        a, b = int(off[i]), int(off[i + 1])
+        p = res["probs"][a:b]
+        tup = (p, res["probs_new"][a:b], res["labels"][a:b].astype(bool), p * (np.float32(1.0) - p))
+        outs.append(tup + ((res["mu"][a:b], res["var"][a:b]) if return_latent else ()))
+    ret = (outs,) + ((res["models"],) if return_models else ()) + ((res["status"],) if return_status else ())
+    return ret if len(ret) > 1 else outs
+
+
+def fit_gp(coords_float, feats, spp, b1_inds, b2_inds, intersect_inds, training_iter=50, npoint_nearest=800,
+           spp_pool=True, *, device=None, **pipe_kw):
+    """Reference gaussian_process_utils.py:28-116: (pred_probs f32[T], pred_probs_new f32[T], pred_labels bool[T],
+    pred_variance f32[T]) as torch tensors on the device of ``feats``."""
+    out = fit_gp_batch(coords_float, feats, spp, [(b1_inds, b2_inds, intersect_inds)], training_iter, npoint_nearest,
+                       spp_pool, device=device, **pipe_kw)[0]
+    dev = _pick_device(feats, device)
+    keep_cpu = isinstance(feats, torch.Tensor) and not feats.is_cuda
     tens = tuple(torch.from_numpy(np.ascontiguousarray(o)) for o in out)
     return tens if keep_cpu else tuple(t.to(dev) for t in tens)

@@ -524,6 +524,69 @@ int gapro_svgp_predict_batch(gapro_ctx* ctx, void* stream, int32_t n_models, int
                              void* d_workspace, size_t workspace_bytes, float* d_probs, float* d_probs_new,
                              uint8_t* d_labels, float* d_mu, float* d_var, int32_t* d_status);
 
+/* ------------------------------------------------------------------------------------------
+ * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
+ * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
+ * to superpoint means (:64-69) or by keeping the npoint_nearest points of each side nearest to the centroid of the
+ * intersection's points (:39, :49-62).  The rows go straight into a table a fit launch reads with identity indices
+ * (side 1's rows, then side 2's).  Exact and order-independent where the reference is not:
+ *   pool     side rows = its distinct superpoints in ascending id order; a row is the mean of the side's points of that
+ *            superpoint (an index listed twice counts twice): sum of rint(x 2^fixed_shift) in int64, then
+ *            ldexp(sum, -fixed_shift) / count in float64, rounded once to float32 -- gapro_partition_pool's expression;
+ *   nearest  centroid c = ldexp(sum of rint(x 2^coord_shift), -coord_shift) / t in float64 per axis; a side of
+ *            n <= npoint_nearest points is kept in its order; a longer one keeps its npoint_nearest smallest
+ *            (dx dx + dy dy) + dz dz (every operation rounded to float64 on its own), ordered by (distance, position in
+ *            the side's list); rows are those points' own features.
+ * d_spp_inv, n_spps and fixed_shift come from gapro_partition_prepare on the whole input; coord_shift is the same rule
+ * applied to the largest |coordinate| among the FINITE coordinates of the input and n_points, computed by the call on
+ * the device (a non-finite coordinate somewhere must not change the other problems' centroids).  Both scales leave room
+ * for 4 N terms per sum: a list may hold at most GAPRO_TRAINSET_MAX_LIST_FACTOR N entries.
+ * ---------------------------------------------------------------------------------------- */
+enum {
+  GAPRO_TRAINSET_POOL = 0,
+  GAPRO_TRAINSET_NEAREST = 1
+};
+#define GAPRO_TRAINSET_MAX_NEAREST 1024
+#define GAPRO_TRAINSET_MAX_LIST_FACTOR 2
+
+/* One problem: its lists lie back to back, [b1 (n1) | b2 (n2) | intersect (t)], at idx_offset of one int32 index array. */
+typedef struct {
+  int64_t idx_offset;
+  int32_t n1, n2, t;     /* n1, n2 >= 1; t >= 0 */
+  int32_t m1, m2;        /* in for gapro_trainset_fill: rows of the two sides -- pool: the counts gapro_trainset_count
+                          * wrote; nearest: min(n, npoint_nearest) */
+  int32_t reserved;      /* 0 */
+  int64_t row_offset;    /* in for gapro_trainset_fill: the problem's first row in d_train / d_sel */
+} gapro_trainset_desc;
+
+/* Bytes of the workspace both calls below use for these problems (the lists' lengths bound the rows of every outcome of
+ * the count; 0 on a bad argument).  n_spps is ignored in nearest mode. */
+size_t gapro_trainset_workspace_bytes(int32_t mode, const gapro_trainset_desc* h_descs, int32_t n_problems,
+                                      int32_t n_spps, int32_t feat_dim);
+/* Pool mode, pass 1: d_counts i32[2 n_problems] = distinct superpoints of side 1 and side 2 of every problem; their
+ * ranks stay in the workspace for the fill.  d_status i32[n_problems] is cleared, then GAPRO_ERR_BAD_ARG for a problem
+ * with a point index outside [0, n_points).  h_descs is copied to d_descs on the stream.  Enqueue only: the caller copies
+ * the counts to the host, plans m1 / m2 / row_offset from them and calls gapro_trainset_fill with the same workspace. */
+int gapro_trainset_count(gapro_ctx* ctx, void* stream, int32_t n_problems, int32_t feat_dim,
+                         const gapro_trainset_desc* h_descs, gapro_trainset_desc* d_descs, int64_t n_points,
+                         int32_t n_spps, const int32_t* d_spp_inv, const int32_t* d_idx, void* d_workspace,
+                         size_t workspace_bytes, int32_t* d_counts, int32_t* d_status);
+/* The rows.  in : d_coords f64[N,3] (nearest), d_feats f32[N,D], d_spp i64[N] and d_spp_inv i32[N] (pool), d_idx.
+ *   out: d_train f32[n_rows, D]; d_sel i64[n_rows]: the row's superpoint id (pool) or point index (nearest);
+ *        d_status i32[n_problems] (pool: carried on from the count; nearest: cleared first): GAPRO_ERR_BAD_ARG (an index
+ *        outside the points, row counts that are not the problem's), GAPRO_ERR_NOT_FINITE (nearest: a non-finite
+ *        coordinate among the problem's points or a non-finite feature in one of its rows; in pool mode
+ *        gapro_partition_prepare has refused such an input as a whole).  A problem never affects another.
+ * npoint_nearest in [1, GAPRO_TRAINSET_MAX_NEAREST]; a problem with t = 0 and a side longer than npoint_nearest has no
+ * centroid and is refused, and so is a list beyond the length bound (GAPRO_ERR_BAD_ARG, nothing is launched).
+ * Enqueue only. */
+int gapro_trainset_fill(gapro_ctx* ctx, void* stream, int32_t mode, int32_t n_problems, int32_t feat_dim,
+                        const gapro_trainset_desc* h_descs, gapro_trainset_desc* d_descs, int64_t n_points,
+                        int32_t n_spps, const double* d_coords, const float* d_feats, const int64_t* d_spp,
+                        const int32_t* d_spp_inv, int32_t fixed_shift, int32_t npoint_nearest, const int32_t* d_idx,
+                        void* d_workspace, size_t workspace_bytes, int64_t n_rows, float* d_train, int64_t* d_sel,
+                        int32_t* d_status);
+
 /* Which kernel gapro_svgp_fit_batch routes a fit of m = m1 + m2 inducing points to: 0 = strip-streaming
  * kernel (64 < M_p <= 128), 1 = LDS-staged kernel (128 < M_p < 512 while Z and X fit the LDS: M_p <= 192 at
  * feat_dim 32), 2 = generic kernel (feat_dim > 32), 3 = the small-fit strip kernel (M_p <= 64: 256 threads per fit,
