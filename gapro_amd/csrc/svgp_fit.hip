@@ -212,6 +212,10 @@ int gapro_svgp_fit_batch_state(gapro_ctx* ctx, void* stream_, int32_t n_fits, in
   if (opt->training_iter < 0 || !(opt->lr > 0.0) || !(opt->jitter >= 0.0) || opt->psd_retries < 0 ||
       opt->psd_retries > 8 || !(opt->psd_jitter >= 0.0))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch: bad options");
+  // (a NaN would switch the clamp off without a word: `vraw < NaN` is false in every kernel)
+  if (!(opt->min_variance >= 0.0 && opt->min_variance < INFINITY))
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch: min_variance %g is negative or not finite",
+                      opt->min_variance);
   const int route_flags = opt->reserved;
   if (route_flags & ~GAPRO_FIT_DBG_ALL)
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch: unknown or retired debug bits 0x%x in reserved",

@@ -410,6 +410,9 @@ int gapro_svgp_predict_batch(gapro_ctx* ctx, void* stream_, int32_t n_models, in
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_predict_batch: bad argument");
   if (opt->psd_retries < 0 || opt->psd_retries > 8 || !(opt->psd_jitter >= 0.0))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_predict_batch: bad options");
+  if (!(opt->min_variance >= 0.0 && opt->min_variance < INFINITY))
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_predict_batch: min_variance %g is negative or not finite",
+                      opt->min_variance);
   const size_t need = gapro_svgp_predict_workspace_bytes(n_models, feat_dim, h_m);
   if (need > workspace_bytes)
     return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_svgp_predict_batch: workspace too small (%zu > %zu)", need,

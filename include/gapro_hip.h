@@ -391,7 +391,7 @@ typedef struct {
   int32_t training_iter;     /* 50   gaussian_process_utils.py:382,416 */
   double lr;                 /* 0.1  gaussian_process_utils.py:410 */
   double jitter;             /* 1e-4 gpytorch variational_cholesky_jitter (float32 default) */
-  double min_variance;       /* 1e-6 gpytorch settings.min_variance */
+  double min_variance;       /* 1e-6 gpytorch settings.min_variance; negative or not finite is refused (BAD_ARG) */
   int32_t eval_stale_chol;   /* 0 = refactor K_ZZ with the trained parameters for prediction (default);
                                 1 = reuse the factor of the last training step */
   int32_t reserved;          /* 0; debug bits GAPRO_FIT_DBG_* (below); any other bit is refused */

@@ -74,10 +74,11 @@ def psd_safe_cholesky(A, jitter=PSD_JITTER, max_tries=PSD_MAX_TRIES):
 
 
 def svgp_fit_predict_autograd(train_x, train_y, test_x, training_iter=50, dtype="f64", init_mean=None,
-                              jitter=JITTER, eval_chol="fresh", lr=ADAM_LR, return_trace=False):
+                              jitter=JITTER, eval_chol="fresh", lr=ADAM_LR, return_trace=False, min_variance=None):
     """dtype: "f64" all float64 (ground truth); "mixed" the reference's split (float32 everywhere, float64 for the
     Cholesky factor and the triangular solve); tolerance-study modes of BASELINE configs[4]: "f32" float32 everywhere
-    including the factorisation, "bf16in" = "mixed" with the input features rounded to bfloat16 first."""
+    including the factorisation, "bf16in" = "mixed" with the input features rounded to bfloat16 first.
+    min_variance: the clamp on the predictive variance, None = the module's MIN_VARIANCE."""
     import torch
 
     if dtype == "bf16in":
@@ -85,6 +86,7 @@ def svgp_fit_predict_autograd(train_x, train_y, test_x, training_iter=50, dtype=
         test_x = torch.as_tensor(np.asarray(test_x), dtype=torch.float32).bfloat16().float().numpy()
     chol_dt = torch.float32 if dtype == "f32" else torch.float64
     T = torch.float64 if dtype == "f64" else torch.float32
+    min_variance = MIN_VARIANCE if min_variance is None else float(min_variance)
     X = torch.as_tensor(np.asarray(train_x), dtype=T)
     y = torch.as_tensor(np.asarray(train_y), dtype=T)
     Xt = torch.as_tensor(np.asarray(test_x), dtype=T)
@@ -118,7 +120,7 @@ def svgp_fit_predict_autograd(train_x, train_y, test_x, training_iter=50, dtype=
         mean = A.t() @ m + c
         B = torch.tril(LS).t() @ A
         var = s + jitter + ((B * B) - (A * A)).sum(0)
-        return mean, var.clamp_min(MIN_VARIANCE)
+        return mean, var.clamp_min(min_variance)
 
     trace = []
     L = None
@@ -185,8 +187,10 @@ def _triu_solve_T(L, Bm):
     return solve_triangular(L, Bm, lower=True, trans="T")
 
 
-def svgp_loss_and_grads(X, y, Z, m, LS, c, rho_s, rho_l, jitter=JITTER):
-    """One ELBO evaluation + hand-derived gradients (float64).  Returns (loss, grads dict)."""
+def svgp_loss_and_grads(X, y, Z, m, LS, c, rho_s, rho_l, jitter=JITTER, min_variance=None, aux=None):
+    """One ELBO evaluation + hand-derived gradients (float64).  Returns (loss, grads dict).  min_variance: None = the
+    module's MIN_VARIANCE; aux: a dict that receives the unclamped variances of this evaluation as "var_raw"."""
+    min_variance = MIN_VARIANCE if min_variance is None else float(min_variance)
     M, D = Z.shape
     N = X.shape[0]
     ell = _softplus(rho_l)
@@ -204,8 +208,10 @@ def svgp_loss_and_grads(X, y, Z, m, LS, c, rho_s, rho_l, jitter=JITTER):
     mean = A.T @ m + c
     Bm = LSt.T @ A
     var_raw = s + jitter + (Bm * Bm - A * A).sum(0)
-    clamped = var_raw < MIN_VARIANCE
-    var = np.where(clamped, MIN_VARIANCE, var_raw)
+    clamped = var_raw < min_variance
+    var = np.where(clamped, min_variance, var_raw)
+    if aux is not None:
+        aux["var_raw"] = var_raw
     sd = np.sqrt(2.0 * var)
     f = sd[None, :] * _GH_T[:, None] + mean[None, :]
     lp, r = log_ndtr_and_ratio(f * y[None, :])
@@ -240,7 +246,8 @@ def svgp_loss_and_grads(X, y, Z, m, LS, c, rho_s, rho_l, jitter=JITTER):
     return loss, grads
 
 
-def svgp_predict(Xt, Z, m, LS, c, rho_s, rho_l, jitter=JITTER, L=None):
+def svgp_predict(Xt, Z, m, LS, c, rho_s, rho_l, jitter=JITTER, L=None, min_variance=None):
+    min_variance = MIN_VARIANCE if min_variance is None else float(min_variance)
     ell = _softplus(rho_l)
     s = _softplus(rho_s)
     inv_l2 = 1.0 / (ell * ell)
@@ -252,14 +259,16 @@ def svgp_predict(Xt, Z, m, LS, c, rho_s, rho_l, jitter=JITTER, L=None):
     A = _tril_solve(L, s * np.exp(-0.5 * d2zx * inv_l2))
     mean = A.T @ m + c
     Bm = np.tril(LS).T @ A
-    var = np.maximum(s + jitter + (Bm * Bm - A * A).sum(0), MIN_VARIANCE)
+    var = np.maximum(s + jitter + (Bm * Bm - A * A).sum(0), min_variance)
     from scipy.special import ndtr
 
     return mean, var, ndtr(mean / np.sqrt(1.0 + var))
 
 
 def svgp_fit_predict_manual(train_x, train_y, test_x, training_iter=50, init_mean=None, jitter=JITTER,
-                            lr=ADAM_LR, return_trace=False):
+                            lr=ADAM_LR, return_trace=False, min_variance=None, step_aux=None):
+    """min_variance: None = the module's MIN_VARIANCE; step_aux: a list that receives one dict per Adam step with that
+    step's unclamped training variances ("var_raw")."""
     X = np.asarray(train_x, dtype=np.float64)
     y = np.asarray(train_y, dtype=np.float64)
     Xt = np.asarray(test_x, dtype=np.float64)
@@ -270,7 +279,11 @@ def svgp_fit_predict_manual(train_x, train_y, test_x, training_iter=50, init_mea
     m2 = {k: np.zeros_like(np.asarray(v, dtype=np.float64)) for k, v in P.items()}
     trace = []
     for t in range(1, training_iter + 1):
-        loss, G = svgp_loss_and_grads(X, y, P["Z"], P["m"], P["LS"], P["c"], P["rho_s"], P["rho_l"], jitter)
+        aux = {} if step_aux is not None else None
+        loss, G = svgp_loss_and_grads(X, y, P["Z"], P["m"], P["LS"], P["c"], P["rho_s"], P["rho_l"], jitter,
+                                      min_variance=min_variance, aux=aux)
+        if step_aux is not None:
+            step_aux.append(aux)
         trace.append(loss)
         bc1 = 1.0 - ADAM_B1 ** t
         bc2 = 1.0 - ADAM_B2 ** t
@@ -280,7 +293,8 @@ def svgp_fit_predict_manual(train_x, train_y, test_x, training_iter=50, init_mea
             m2[k] = ADAM_B2 * m2[k] + (1.0 - ADAM_B2) * g * g
             denom = np.sqrt(m2[k]) / math.sqrt(bc2) + ADAM_EPS
             P[k] = P[k] - (lr / bc1) * m1[k] / denom
-    out = svgp_predict(Xt, P["Z"], P["m"], P["LS"], float(P["c"]), float(P["rho_s"]), float(P["rho_l"]), jitter)
+    out = svgp_predict(Xt, P["Z"], P["m"], P["LS"], float(P["c"]), float(P["rho_s"]), float(P["rho_l"]), jitter,
+                       min_variance=min_variance)
     if return_trace:
         return out, dict(P, loss=trace)
     return out
