@@ -138,6 +138,7 @@ SIGNATURES = {
     "gapro_broadcast_labels": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "gapro_partition_prepare_batch": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "gapro_partition_pool_batch": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "gapro_partition_pool_plan": (C.c_int, [C.c_int32, C.c_int32]),
     "gapro_broadcast_labels_batch": (C.c_int, [_P, _P, C.c_int32, _P, _P]),
     "gapro_instance_info_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gapro_instance_info": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P, _P, _P,

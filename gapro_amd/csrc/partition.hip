@@ -561,6 +561,13 @@ inline int grid_for(long long n, int cap = 2048) {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// LDS of the pooling kernels: the box corners (both kernels), and k_pool_lds's table of 2^log2_slots slots of
+// {key, count, n_boxes occupancy counts, feat_dim 64-bit sums}
+inline size_t pool_box_bytes(int n_boxes) { return (size_t)n_boxes * 6 * sizeof(double); }
+inline size_t pool_table_bytes(int feat_dim, int n_boxes, int log2_slots) {
+  return ((size_t)8 + 4 * (size_t)n_boxes + 8 * (size_t)feat_dim) << log2_slots;
+}
+
 }  // namespace
 
 extern "C" {
@@ -619,6 +626,22 @@ int gapro_partition_prepare_batch(gapro_ctx* ctx, void* stream_, int32_t n_scene
   return GAPRO_OK;
 }
 
+// Which pooling kernel a batch of (feat_dim, largest box count) gets: 6 / 5 / 4 = k_pool_lds with a table of 2^that
+// slots (the largest of 64, 32, 16 that fits 60 KiB of LDS beside the box corners; 64 slots hold the ~10 .. 40
+// superpoints of a run several times over, a small table keeps 5+ workgroups per CU), 0 = k_pool (no table fits, or
+// GAPRO_POOL_GLOBAL_ATOMICS is set: round 1's kernel for A/B runs and tests), GAPRO_ERR_BAD_ARG = the box corners alone
+// exceed the LDS.  The launcher below asks this function and nothing else.
+int gapro_partition_pool_plan(int32_t feat_dim, int32_t n_boxes_max) {
+  if (feat_dim <= 0 || n_boxes_max <= 0) return GAPRO_ERR_BAD_ARG;
+  const size_t lds = pool_box_bytes(n_boxes_max);
+  if (lds > 64 * 1024) return GAPRO_ERR_BAD_ARG;
+  static const bool global_only = getenv("GAPRO_POOL_GLOBAL_ATOMICS") != nullptr;
+  if (global_only) return 0;
+  int log2_slots = 6;
+  while (log2_slots > 4 && lds + pool_table_bytes(feat_dim, n_boxes_max, log2_slots) > 60 * 1024) --log2_slots;
+  return lds + pool_table_bytes(feat_dim, n_boxes_max, log2_slots) <= 60 * 1024 ? log2_slots : 0;
+}
+
 int gapro_partition_pool_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, int32_t feat_dim,
                                const gapro_scene_task* h_tasks, gapro_scene_task* d_tasks) {
   int rc = check_tasks(ctx, "gapro_partition_pool_batch", n_scenes, h_tasks, d_tasks);
@@ -635,21 +658,19 @@ int gapro_partition_pool_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, 
     s_max = std::max(s_max, (int)t.n_spps);
     clear_max = std::max<long long>(clear_max, (long long)t.n_spps * (feat_dim + t.n_boxes + 1));
   }
-  const size_t lds = (size_t)nb_max * 6 * sizeof(double);
-  if (lds > 64 * 1024) return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_partition_pool: too many boxes (%d)", nb_max);
+  const int plan = gapro_partition_pool_plan(feat_dim, nb_max);
+  if (plan < 0) return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_partition_pool: too many boxes (%d)", nb_max);
+  const size_t lds = pool_box_bytes(nb_max);
   hipStream_t stream = (hipStream_t)stream_;
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_tasks, h_tasks, (size_t)n_scenes * sizeof(gapro_scene_task),
                                       hipMemcpyHostToDevice, stream));
   const unsigned ny = (unsigned)n_scenes;
   hipLaunchKernelGGL(k_pool_clear, dim3(grid_for(clear_max, 256), ny), dim3(kThreads), 0, stream, d_tasks, (int)feat_dim);
-  // LDS-privatised tallies (k_pool_lds): a table of 16 .. 64 slots beside the box corners; GAPRO_POOL_GLOBAL_ATOMICS=1 keeps round 1's kernel (A/B runs, tests)
-  static const bool global_only = getenv("GAPRO_POOL_GLOBAL_ATOMICS") != nullptr;
-  const int slot_bytes = 8 + 4 * nb_max + 8 * (int)feat_dim;
-  // 64 slots hold the ~10 .. 40 superpoints of a run several times over; a small table keeps 5+ workgroups per CU
-  int log2_slots = 6;
-  while (log2_slots > 4 && lds + ((size_t)slot_bytes << log2_slots) > 60 * 1024) --log2_slots;
-  const size_t lds2 = lds + ((size_t)slot_bytes << log2_slots);
-  if (!global_only && lds2 <= 60 * 1024) {
+  // LDS-privatised tallies (k_pool_lds): a table of 16 .. 64 slots beside the box corners, or round 1's kernel: the
+  // choice is gapro_partition_pool_plan's
+  if (plan > 0) {
+    const int log2_slots = plan;
+    const size_t lds2 = lds + pool_table_bytes(feat_dim, nb_max, log2_slots);
     if (lds2 > 48 * 1024)
       GAPRO_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)k_pool_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)lds2));

@@ -160,6 +160,10 @@ int gapro_partition_prepare_batch(gapro_ctx* ctx, void* stream, int32_t n_scenes
 /* gapro_partition_pool for n_scenes scenes (zeroes the tallies itself). */
 int gapro_partition_pool_batch(gapro_ctx* ctx, void* stream, int32_t n_scenes, int32_t feat_dim,
                                const gapro_scene_task* h_tasks, gapro_scene_task* d_tasks);
+/* Which pooling kernel gapro_partition_pool_batch runs for (feat_dim, the largest n_boxes of the batch): 6, 5 or 4 =
+ * the LDS-table kernel with 2^that slots, 0 = the global-atomics kernel (also whenever GAPRO_POOL_GLOBAL_ATOMICS is set),
+ * GAPRO_ERR_BAD_ARG = more boxes than the LDS holds corners of (1365), or a non-positive argument. */
+int gapro_partition_pool_plan(int32_t feat_dim, int32_t n_boxes_max);
 /* gapro_broadcast_labels for n_scenes scenes. */
 int gapro_broadcast_labels_batch(gapro_ctx* ctx, void* stream, int32_t n_scenes,
                                  const gapro_scene_task* h_tasks, gapro_scene_task* d_tasks);

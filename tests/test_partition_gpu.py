@@ -7,49 +7,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _run_partition(kw, thresh=0.999, spp_range_cap=None):
-    import torch
-    from gapro_amd.pipeline import Pipeline, make_job
-
-    pipe = Pipeline(device=0, training_iter=0, spp_range_cap=spp_range_cap)
-    job = make_job(kw["coords_float"], kw["mask_feats"], kw["spp"], kw["instance_cls"], kw["instance_box"],
-                   kw["instance_box_volume"], kw["wall_box"], kw["wall_box_volume"], 18, 0.1, thresh)
-    pipe._prepare(job)  # launches gapro_partition_prepare_async, one sync, checks the header status
-    feats_spp = torch.empty((job.n_spps, job.feats.shape[1]), dtype=torch.float32, device=pipe.device)
-    pipe._pool(job, feats_spp)
-    torch.cuda.synchronize()
-    return pipe, job
-
-
-def _check_against_oracle(kw, job, thresh=0.999):
-    from oracle import gen_ps_oracle as O
-
-    boxes, cls, vol = O.assemble_boxes(kw["coords_float"], kw["instance_cls"], kw["instance_box"],
-                                       kw["instance_box_volume"], kw["wall_box"], kw["wall_box_volume"])
-    part = O.partition(kw["coords_float"], kw["mask_feats"], kw["spp"], boxes, cls, vol, thresh)
-    h = job.header
-    coords = np.asarray(kw["coords_float"], dtype=np.float64)
-    np.testing.assert_array_equal(np.array(list(h.coord_min)), coords.min(0))
-    np.testing.assert_array_equal(np.array(list(h.coord_max)), coords.max(0))
-    assert (h.spp_min, h.spp_max) == (int(np.min(kw["spp"])), int(np.max(kw["spp"])))
-    assert job.n_spps == part.n_spps
-    np.testing.assert_array_equal(job.boxes, boxes)  # incl. the float64 floor box
-    np.testing.assert_array_equal(job.boxes_cls, cls)
-    np.testing.assert_array_equal(job.boxes_volume, vol)
-    np.testing.assert_array_equal(job.spp_inv.cpu().numpy(), part.spp_inv)
-    np.testing.assert_array_equal(job.dev["occ_count"].cpu().numpy(), part.occ_count)
-    np.testing.assert_array_equal(job.dev["point_count"].cpu().numpy(), part.point_count)
-    np.testing.assert_array_equal(job.dev["n_bbs"].cpu().numpy(), part.n_bbs_per_spp)
-    bits = job.dev["occ_bits"].cpu().numpy().view(np.uint64)
-    B = len(boxes)
-    got = np.zeros((part.n_spps, B), dtype=bool)
-    for b in range(B):
-        got[:, b] = (bits[:, b // 64] >> np.uint64(b % 64)) & np.uint64(1)
-    np.testing.assert_array_equal(got, part.occ_spp)
-    assert int(h.fixed_shift) == O.fixed_point_shift(float(np.max(np.abs(np.asarray(kw["mask_feats"], np.float32)))),
-                                                    len(coords))
-    np.testing.assert_array_equal(job.dev["feats_spp"].cpu().numpy(), part.feats_spp)  # bit-exact
-    return part
+from partition_cases import _check_against_oracle, _run_partition  # noqa: E402  (shared with the edge tests)
 
 
 def test_partition_matches_oracle_on_golden(golden):

@@ -307,3 +307,58 @@ def test_s3dis_sizes_size_independent_properties(n_points):
     lab = np.flatnonzero(ins >= 0)[:: max(1, n_points // 2000)]
     bx = box[ins[lab]].astype(np.float64)
     assert ((xyz[lab] >= bx[:, :3] - 0.0051) & (xyz[lab] <= bx[:, 3:] + 0.0051)).all()
+
+
+def _many_box_scene(seed=0, pts=20):
+    """72 instance boxes + the floor: eight regions, each with box r (word 0) and box 64 + r (word 1) overlapping on one
+    slab of 0.25-cell superpoints (27 + 36 training superpoints, 9 to label: one GP fit per region, across the word
+    boundary), and 56 isolated one-superpoint boxes 8 .. 63 between them in the box order."""
+    rng = np.random.default_rng(seed)
+    cell = 0.25
+    first, last, alone, coords, spp, feats = [], [], [], [], [], []
+
+    def fill(x0, nx, ny, nz, edge=1.0):
+        for ix in range(nx):
+            for iy in range(ny):
+                for iz in range(nz):
+                    lo = np.array([x0 + ix * cell, iy * cell, 0.5 + iz * cell])
+                    p = lo + rng.uniform(0.02, cell - 0.02, size=(pts, 3))
+                    coords.append(p)
+                    spp.append(np.full(pts, len(spp) * 3 + 11))
+                    f = np.concatenate([(p - [x0, 0, 0.5]) * 2.0, 0.3 * rng.standard_normal((pts, 3))], 1)
+                    f[:, 3] += np.where(p[:, 0] - x0 < edge, 1.0, -1.0)  # the shared slab looks like one of the two boxes
+                    feats.append(f)
+
+    for r in range(8):
+        x0 = 3.0 * r
+        first.append([x0, 0, 0.5, x0 + 1.0, 0.75, 1.25])
+        last.append([x0 + 0.75, 0, 0.5, x0 + 2.0, 0.75, 1.25])
+        fill(x0, 8, 3, 3, 1.0 if r % 2 == 0 else 0.75)
+    for j in range(56):
+        x0 = 30.0 + j
+        alone.append([x0, 0, 0.5, x0 + 0.25, 0.25, 0.75])
+        fill(x0, 1, 1, 1)
+    box = np.array(first + alone + last, np.float32)
+    perm = rng.permutation(sum(len(c) for c in coords))
+    return dict(coords_float=np.concatenate(coords)[perm], mask_feats=np.concatenate(feats).astype(np.float32)[perm],
+                spp=np.concatenate(spp).astype(np.int64)[perm], instance_cls=np.arange(len(box)) % 18,
+                instance_box=box, instance_box_volume=np.prod(box[:, 3:] - box[:, :3], axis=1).astype(np.float32),
+                wall_box=[], wall_box_volume=[], instance_classes=18, ground_h=0.1, training_iter=50,
+                thresh_spp_occu=0.8)
+
+
+def test_generator_past_64_boxes_matches_oracle():
+    """The whole generator on a scene whose occupancy rows have two words: pairs across the word boundary are enumerated,
+    fitted and merged, and instance ids >= 64 reach the output."""
+    from gapro_amd import gen_pseudo_label_gaussian_process
+
+    kw = _many_box_scene()
+    assert len(kw["instance_box"]) >= 66
+    ref, dbg = _oracle_outputs(kw)
+    fits = [e for e in dbg["events"] if e.kind == "fit"]
+    assert sum(max(e.b1, e.b2) >= 64 for e in fits) >= 5 and sum(e.b1 < 64 <= e.b2 for e in fits) >= 5
+    assert len(fits) <= 40 and max(len(e.b1_inds) + len(e.b2_inds) for e in fits) <= 64
+    assert (ref[1] >= 64).any()  # an instance id of the second word in the output
+    gp = dbg["state"]["mu"] != -100
+    assert (dbg["state"]["inst_spp"][gp] >= 64).any() and (dbg["state"]["inst_spp"][gp] < 64).any()
+    _check(gen_pseudo_label_gaussian_process(**kw), ref, dbg)
