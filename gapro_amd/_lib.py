@@ -53,6 +53,20 @@ class PredictDesc(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class PointRefineScene(C.Structure):
+    """gapro_point_refine_scene: one scene of gapro_point_refine_gather / gapro_point_refine_apply."""
+    _fields_ = [("n_points", C.c_int64), ("n_spps", C.c_int32), ("reserved", C.c_int32), ("spp_inv", C.c_void_p),
+                ("feats", C.c_void_p), ("sp_row", C.c_void_p), ("cursor", C.c_void_p), ("mu_spp", C.c_void_p),
+                ("var_spp", C.c_void_p), ("sem", C.c_void_p), ("inst", C.c_void_p), ("prob", C.c_void_p),
+                ("mu", C.c_void_p), ("var", C.c_void_p)]
+
+
+class PointRefineModel(C.Structure):
+    """gapro_point_refine_model: one predict model of a point-level launch, as gapro_point_refine_apply reads it."""
+    _fields_ = [("row_offset", C.c_int64), ("t", C.c_int32), ("scene", C.c_int32), ("sem1", C.c_int32),
+                ("inst1", C.c_int32), ("sem2", C.c_int32), ("inst2", C.c_int32)]
+
+
 class TrainsetDesc(C.Structure):
     """gapro_trainset_desc: one point-level problem of gapro_trainset_count / gapro_trainset_fill."""
     _fields_ = [("idx_offset", C.c_int64), ("n1", C.c_int32), ("n2", C.c_int32), ("t", C.c_int32), ("m1", C.c_int32),
@@ -167,6 +181,7 @@ SIGNATURES = {
     "gapro_schedule_export_fits": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
     "gapro_schedule_export_events": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "gapro_schedule_merge": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "gapro_schedule_merge_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "gapro_fit_options_default": (None, [C.POINTER(FitOptions)]),
     "gapro_fit_workspace_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "gapro_fit_plan_workspace": (C.c_int64, [_P, C.c_int32, C.c_int32]),
@@ -181,6 +196,9 @@ SIGNATURES = {
     "gapro_svgp_predict_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, _P]),
     "gapro_svgp_predict_batch": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P,
                                            C.POINTER(FitOptions), _P, C.c_size_t, _P, _P, _P, _P, _P, _P]),
+    "gapro_point_refine_gather": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P]),
+    "gapro_point_refine_apply": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, _P,
+                                           _P]),
     "gapro_trainset_workspace_bytes": (C.c_size_t, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32]),
     "gapro_trainset_count": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_size_t,
                                        _P, _P]),
@@ -324,7 +342,7 @@ def load() -> C.CDLL:
         except AttributeError:
             variant = os.path.abspath(LIB_PATH) != os.path.abspath(default)
             if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state",
-                                            "gapro_trainset_")):
+                                            "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

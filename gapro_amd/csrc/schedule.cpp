@@ -221,11 +221,11 @@ int gapro_schedule_export_events(const gapro_schedule* s, uint8_t* h_kind, int32
   return GAPRO_OK;
 }
 
-int gapro_schedule_merge(const gapro_schedule* s, const float* h_probs_new, const uint8_t* h_labels,
-                         const float* h_mu, const float* h_var, const int64_t* h_boxes_cls,
-                         const double* h_boxes_volume, int32_t n_fg_instances, int32_t instance_classes,
-                         int32_t* h_sem_spp, int32_t* h_inst_spp, float* h_prob_spp, float* h_mu_spp,
-                         float* h_var_spp) {
+int gapro_schedule_merge_ex(const gapro_schedule* s, const float* h_probs_new, const uint8_t* h_labels,
+                            const float* h_mu, const float* h_var, const int64_t* h_boxes_cls,
+                            const double* h_boxes_volume, int32_t n_fg_instances, int32_t instance_classes,
+                            int32_t* h_sem_spp, int32_t* h_inst_spp, float* h_prob_spp, float* h_mu_spp,
+                            float* h_var_spp, int32_t* h_winner_fit) {
   if (!s || !h_boxes_cls || !h_boxes_volume || !h_sem_spp || !h_inst_spp || !h_prob_spp || !h_mu_spp || !h_var_spp)
     return GAPRO_ERR_BAD_ARG;
   if (!s->fits.empty() && (!h_probs_new || !h_labels || !h_mu || !h_var)) return GAPRO_ERR_BAD_ARG;
@@ -236,6 +236,7 @@ int gapro_schedule_merge(const gapro_schedule* s, const float* h_probs_new, cons
     h_prob_spp[i] = 0.f;                     // :367
     h_mu_spp[i] = -100.f;                    // :368
     h_var_spp[i] = -100.f;                   // :369
+    if (h_winner_fit) h_winner_fit[i] = -1;  // the fit whose outputs the superpoint holds (no reference counterpart)
   }
   for (int b = 0; b < B; ++b)
     for (int32_t sp : s->single[b]) {        // :373-377
@@ -257,6 +258,7 @@ int gapro_schedule_merge(const gapro_schedule* s, const float* h_probs_new, cons
         inst[sp] = e.aux;
         determined[sp] = kMaxNum;
         h_prob_spp[sp] = 1.f;
+        if (h_winner_fit) h_winner_fit[sp] = -1;
       }
       continue;
     }
@@ -270,6 +272,7 @@ int gapro_schedule_merge(const gapro_schedule* s, const float* h_probs_new, cons
         h_mu_spp[sp] = h_mu[out_off + j];
         h_var_spp[sp] = h_var[out_off + j];
         determined[sp] = n;
+        if (h_winner_fit) h_winner_fit[sp] = e.aux;
       }
     }
     out_off += n;
@@ -311,6 +314,15 @@ int gapro_schedule_merge(const gapro_schedule* s, const float* h_probs_new, cons
     h_inst_spp[sp] = ins;
   }
   return GAPRO_OK;
+}
+
+int gapro_schedule_merge(const gapro_schedule* s, const float* h_probs_new, const uint8_t* h_labels,
+                         const float* h_mu, const float* h_var, const int64_t* h_boxes_cls,
+                         const double* h_boxes_volume, int32_t n_fg_instances, int32_t instance_classes,
+                         int32_t* h_sem_spp, int32_t* h_inst_spp, float* h_prob_spp, float* h_mu_spp,
+                         float* h_var_spp) {
+  return gapro_schedule_merge_ex(s, h_probs_new, h_labels, h_mu, h_var, h_boxes_cls, h_boxes_volume, n_fg_instances,
+                                 instance_classes, h_sem_spp, h_inst_spp, h_prob_spp, h_mu_spp, h_var_spp, nullptr);
 }
 
 }  // extern "C"

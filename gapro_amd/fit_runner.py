@@ -634,7 +634,8 @@ class FitRunner:
                 dp[k] = float(np.max(np.abs(res["probs"][a:b].astype(np.float64) - r2["probs"][a:b].astype(np.float64))))
         return dv, dp
 
-    def _retry_timeouts(self, res, feats_spp, descs, h_idx, n_out, init_mean=None, slot="s0", scene_keys=None):
+    def _retry_timeouts(self, res, feats_spp, descs, h_idx, n_out, init_mean=None, slot="s0", scene_keys=None,
+                        keep_state=False):
         """Fits whose status is GAPRO_ERR_TIMEOUT are launched once more with the cluster kernel switched off
         (FIT_DBG_NO_CLUSTER: the LDS-staged kernel up to M_p = 512, the generic kernel beyond -- one
         workgroup each, no cross-workgroup barrier that could time out) and their outputs, status and loss replace the
@@ -642,7 +643,9 @@ class FitRunner:
         GAPRO_CLUSTER_BARRIER_TIMEOUT_MS; the arithmetic never ran to an end, so there is nothing deterministic about
         the failure and the second attempt computes what the first one would have (the per-fit result does not
         depend on the kernel beyond float64 round-off: tests/test_fit_gpu.py).  Same descriptors, same index array,
-        same output offsets; only the workspace is the retry's own."""
+        same output offsets; only the workspace is the retry's own.  With ``keep_state`` the retry keeps its trained
+        states on the device: res["retry_state"] = (state buffer, offset in doubles of every retried fit, in the order of
+        res["retried"]), for a caller that predicts from the states where the launches left them."""
         bad = np.nonzero(res["status"] == _lib.GAPRO_ERR_TIMEOUT)[0]
         if not len(bad) or not self.retry_timeouts:
             return res
@@ -655,9 +658,10 @@ class FitRunner:
         self.opt.reserved = (int(old) | _lib.FIT_DBG_NO_CLUSTER) & ~_lib.FIT_DBG_CLUSTER_STALL
         self.profile_fit = False  # the retry is not a step of whoever is timing the launches
         try:
-            r2 = self.fit_collect(self.fit_launch(feats_spp, sub, len(bad), h_idx, n_out, init_mean, slot=slot + "retry",
-                                                  scene_keys=scene_keys, keep_models="models" in res),
-                                  raise_on_failure=False)
+            pend = self.fit_launch(feats_spp, sub, len(bad), h_idx, n_out, init_mean, slot=slot + "retry",
+                                   scene_keys=scene_keys, keep_models=keep_state or "models" in res,
+                                   state_to_host="models" in res)
+            r2 = self.fit_collect(pend, raise_on_failure=False)
         finally:
             self.opt.reserved, self.profile_fit = old, prof
             with self._ws_lock:
@@ -673,6 +677,8 @@ class FitRunner:
                 res["models"][int(i)] = r2["models"][k]
         self.timeout_retries += len(bad)
         res["retried"] = [int(i) for i in bad]
+        if keep_state:
+            res["retry_state"] = (pend.d_state, [int(pend.state_off[k]) for k in range(len(bad))])
         return res
 
     def fit_launch(self, feats_spp, descs, n_fits: int, h_idx: np.ndarray, n_out: int,

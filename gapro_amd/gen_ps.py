@@ -26,6 +26,10 @@ resume mechanism, gen_ps.py:39-41) and every scene is written as the same 5-tupl
     --init_mean_std S      std of the random initial variational mean (gpytorch: 1e-3 unseeded;
                            default 0 = deterministic), --seed seeds it
     --broadcast_mu_var     write mu/var at point length (what the released data loaders index)
+    --point_level          every point of a superpoint that a GP fit labelled is predicted from its own features by the
+                           model that won the superpoint (Pipeline(point_level=True)): the same 5-tuple
+                           files, all five arrays at point length; --eval_pslabel evaluates these labels.  Together with
+                           --broadcast_mu_var it is --point_level.  Stays on the torch-free backend
     --loader_threads T     threads of the library's batch feeder (csrc/feeder.hip) that read scenes from disk two
                            batches ahead, preprocess and upload them, and write the label files (default -1 =
                            min(16, usable CPUs / W - 1) per worker for W workers, at least 2; "usable" honours the
@@ -304,9 +308,12 @@ class Worker:
         # the process, and loaded the other way round torch.cuda.is_available() comes up False.
         self.pipe = None
         self.backend = None
+        self.broadcast = False
         if not dry:
             want = os.environ.get("GAPRO_BACKEND", "").strip().lower()
-            needs_torch = bool(args.eval_pslabel or args.broadcast_mu_var or os.environ.get("GAPRO_DRIVER_HOST_ONLY"))
+            # (with --point_level mu / var already are point-length: --broadcast_mu_var has nothing left to do)
+            self.broadcast = bool(args.broadcast_mu_var) and not getattr(args, "point_level", False)
+            needs_torch = bool(args.eval_pslabel or self.broadcast or os.environ.get("GAPRO_DRIVER_HOST_ONLY"))
             self.backend = "torch" if (needs_torch or want == "torch") else "native"
             if self.backend == "torch":
                 self._torch_threads = torch.get_num_threads()
@@ -315,7 +322,7 @@ class Worker:
 
             self.make_job = make_job
             self.pipe = Pipeline(device=device_index, training_iter=50, init_mean_std=args.init_mean_std, seed=args.seed,
-                                 backend=self.backend)
+                                 backend=self.backend, point_level=bool(getattr(args, "point_level", False)))
             self.pipe.strict = False  # a scene that cannot be processed is reported and skipped, the rest is written
             if os.environ.get("GAPRO_DRIVER_TIMES"):
                 self.pipe.trace = []  # host-side stage timeline of the pipeline (printed at the end)
@@ -550,14 +557,14 @@ class Worker:
             if sem.dtype != be.i32 or ins.dtype != be.i32:
                 sem, ins = sem.int(), ins.int()
                 alive += [sem, ins]
-            if a.broadcast_mu_var:
+            if self.broadcast:
                 inv = job.spp_inv.long()
                 mu, var = mu[inv], var[inv]
                 alive += [mu, var]
             items.append((osp.join(self.out_folder, s["scan_name"] + ".pth"), sem.data_ptr(), ins.data_ptr(),
                           prob.data_ptr(), mu.data_ptr(), var.data_ptr(), sem.numel(), mu.numel()))
             self.done += 1
-        if a.eval_pslabel or a.broadcast_mu_var:
+        if a.eval_pslabel or self.broadcast:
             ready = be.current_stream().record_event()
             alive.append(ready)
         self.feeder.export(items, ready.cuda_event)
@@ -759,6 +766,7 @@ def main(argv=None):
     parser.add_argument("--init_mean_std", type=float, default=0.0)
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--broadcast_mu_var", action="store_true")
+    parser.add_argument("--point_level", action="store_true")
     parser.add_argument("--raw_cache", type=str, default=None, help=argparse.SUPPRESS)  # ignored since round 5
     parser.add_argument("--loader_threads", type=int, default=-1)
     parser.add_argument("--loader_procs", type=int, default=-1, help=argparse.SUPPRESS)  # ignored since round 5

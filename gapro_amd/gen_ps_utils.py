@@ -46,6 +46,7 @@ def gen_pseudo_label_gaussian_process(
     *,
     broadcast_mu_var=False,
     return_models=False,
+    point_level=False,
     device=None,
     init_mean_std=0.0,
     seed=0,
@@ -59,7 +60,15 @@ def gen_pseudo_label_gaussian_process(
     return_models     one more value after the 5-tuple: an object with ``feats_spp`` f32[S, D] (the pooled features,
                       NumPy) and ``fits``, the scene's GP fits in schedule order as (b1, b2, train superpoint ranks,
                       test superpoint ranks, GPModel) -- gaussian_process_utils.predict_gp_batch evaluates the models
-                      at other inputs, e.g. every point's own features.  The 5-tuple is the same bits either way.
+                      at other inputs, e.g. every point's own features -- and ``winner`` i32[S] (NumPy): the index into
+                      ``fits`` of the fit that finally labelled each superpoint, -1 elsewhere.  The 5-tuple is the same
+                      bits either way.
+    point_level       every point of a superpoint that a GP fit labelled is predicted from its OWN feature row by the
+                      model that won the superpoint in the ordered merge, and gets its own (instance, semantic,
+                      probability, mu, sigma^2); every other point keeps the superpoint's values.  All five outputs are
+                      then point-length: (sem i32[N], inst i32[N], prob f32[N], mu f32[N], var f32[N]), and
+                      ``broadcast_mu_var`` changes nothing.  The competition between several fits over one superpoint
+                      is not re-run per point.
     init_mean_std     std of the random initial variational mean (gpytorch uses 1e-3 with an unseeded
                       RNG; 0 = deterministic zeros), ``seed`` seeds it.
     eval_stale_chol   predict with the Cholesky factor of the last training step.
@@ -68,32 +77,36 @@ def gen_pseudo_label_gaussian_process(
     was_cpu = not (isinstance(coords_float, torch.Tensor) and coords_float.is_cuda)
     job = make_job(coords_float, mask_feats, spp, instance_cls, instance_box, instance_box_volume, wall_box,
                    wall_box_volume, instance_classes, ground_h, thresh_spp_occu, device=dev)
-    pipe = _pipeline(dev, training_iter, init_mean_std=init_mean_std, seed=seed, eval_stale_chol=eval_stale_chol)
+    # (the keyword only when set: every other caller of _pipeline keeps sharing the default pipeline of its options)
+    extra = dict(point_level=True) if point_level else {}
+    pipe = _pipeline(dev, training_iter, init_mean_std=init_mean_std, seed=seed, eval_stale_chol=eval_stale_chol, **extra)
     sem, ins, prob, mu, var = pipe.run([job], keep_models=return_models)[0]
-    if broadcast_mu_var:
+    if broadcast_mu_var and not point_level:
         idx = job.spp_inv.long()
         mu, var = mu[idx], var[idx]
     outs = (sem, ins, prob, mu, var)
     if was_cpu:
         outs = tuple(o.cpu() for o in outs)
     if return_models:
-        outs = outs + (SceneModels(job.feats_spp, job.fits),)
+        outs = outs + (SceneModels(job.feats_spp, job.fits, job.winner),)
     return outs
 
 
 class SceneModels:
     """The trained GPs of one scene (gen_pseudo_label_gaussian_process(..., return_models=True))."""
 
-    def __init__(self, feats_spp, fits):
+    def __init__(self, feats_spp, fits, winner=None):
         self.feats_spp = feats_spp  # f32[S, D] pooled superpoint features
         self.fits = fits            # [(b1, b2, train ranks, test ranks, GPModel)] in schedule order
+        self.winner = winner        # i32[S]: index into fits of the fit that labelled the superpoint, -1 elsewhere
 
 
 def gen_pseudo_label_gaussian_process_batch(scenes, training_iter=50, device=None, **pipe_kw):
     """Several scenes through one pipeline pass (all their GP fits share one launch).
 
     ``scenes`` is a list of dicts holding the positional arguments of
-    ``gen_pseudo_label_gaussian_process`` by name.  Returns a list of 5-tuples of device tensors.
+    ``gen_pseudo_label_gaussian_process`` by name.  Returns a list of 5-tuples of device tensors.  ``pipe_kw`` are
+    Pipeline options; ``point_level=True`` returns the point-level labels (mu / var at point length).
     """
     dev = torch.device(device if device is not None else "cuda:0")
     jobs = [make_job(s["coords_float"], s["mask_feats"], s["spp"], s["instance_cls"], s["instance_box"],

@@ -9,6 +9,8 @@ number of scenes share each device launch:
   stage D  gapro_svgp_fit_batch      every GP fit of every scene in ONE launch    (device)
   stage E  gapro_schedule_merge      ordered merge, fallback, label tables        (host, C++)
   stage F  gapro_broadcast_labels    superpoint -> point                          (device)
+  stage G  gapro_point_refine_*      opt-in (point_level): every point of a GP-labelled superpoint predicted from its
+                                     own features by the model that won the superpoint (device; planned on the host)
 
 All arithmetic happens in libgapro_hip.so.  Device memory, streams and events come from a backend (devmem.py): torch's
 (default: the Python API shims take and return torch tensors) or the library's own arena ("native": the gen_ps workers,
@@ -24,9 +26,9 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import FitDesc, SceneHeader, SceneTask, ScheduleCounts
-from .fit_runner import FitRunner, PendingFit, _host, _ptr, _to_np
-from .gp_model import SceneFit
+from ._lib import FitDesc, PointRefineModel, PointRefineScene, PredictDesc, SceneHeader, SceneTask, ScheduleCounts
+from .fit_runner import ROW_FIELDS, FitRunner, PendingFit, _host, _ptr, _to_np, block_views
+from .gp_model import SceneFit, state_doubles
 
 
 class LazyViews(dict):
@@ -86,6 +88,7 @@ class SceneJob:
     # (b1, b2, train superpoint ranks [b1_inds | b2_inds], test superpoint ranks, GPModel)
     feats_spp: Optional[np.ndarray] = None
     fits: Optional[list] = None
+    winner: Optional[np.ndarray] = None  # keep_models: i32[S] index into fits of the fit that labelled the superpoint, or -1
     scene_key: int = 0  # stable id of the scene (e.g. crc32 of the scan name): seeds the optional initial-mean noise
 
     @property
@@ -163,10 +166,21 @@ class BatchState:
 
 class Pipeline(FitRunner):
     def __init__(self, device=0, training_iter=50, init_mean_std=0.0, seed=0, eval_stale_chol=False,
-                 spp_range_cap=None, force_staged=False, precision="f64", cluster_all=False, backend="torch"):
+                 spp_range_cap=None, force_staged=False, precision="f64", cluster_all=False, backend="torch",
+                 point_level=False):
         super().__init__(device, training_iter, init_mean_std, seed, eval_stale_chol, force_staged, precision,
                          cluster_all, backend)
         self.spp_range_cap = spp_range_cap
+        # point_level: after the ordered merge every point of a superpoint that a GP fit labelled is predicted from its
+        # own feature row by the model that won the superpoint (_refine_plan / _refine); all five outputs are then
+        # point-length.  Off (the default): nothing of it runs.
+        self.point_level = bool(point_level)
+        if self.point_level and not self.serialize_fits:
+            # the fit launches keep their states on the device, which the library allows on one stream per context at
+            # a time: the pipeline's three streams qualify only while launch i + 1 waits for launch i
+            raise ValueError("point_level needs serialised fit launches (GAPRO_OVERLAP_FITS is set)")
+        self.last_refine = {}  # point_level: refined superpoints, rows, models and host seconds of the last batch's plan
+        self._ident_rows = None
         # strict: a scene that cannot be processed (non-finite input, id range beyond the rank table, a GP fit that
         # fails after the jitter retries) raises, as the reference would.  The gen_ps driver clears it: the scene's
         # outputs come back as None with job.error set, and the other scenes of the batch are unaffected.
@@ -308,11 +322,13 @@ class Pipeline(FitRunner):
         d_boxes = be.empty(box_tot)
         d_boxes.copy_(h_boxes[:box_tot], non_blocking=True)
         # host-visible tables [occ_bits | n_bbs] per scene, laid out exactly like the pinned staging area
-        tab_sizes = [j.n_spps * (((j.n_boxes + 63) // 64) * 8 + 4) for j in jobs]
+        # (point_level: point_count rides along -- the host plans the row table of the predict launch from it)
+        pl = 4 if self.point_level else 0
+        tab_sizes = [j.n_spps * (((j.n_boxes + 63) // 64) * 8 + 4 + pl) for j in jobs]
         tab_off, tab_tot = self._carve(tab_sizes, 16)
         d_tables = be.empty(tab_tot)
         # integer tallies [feat_sum i64 | occ_count i32 | point_count i32] per scene
-        tal_sizes = [j.n_spps * (8 * D + 4 * j.n_boxes + 4) for j in jobs]
+        tal_sizes = [j.n_spps * (8 * D + 4 * j.n_boxes + 4 - pl) for j in jobs]
         tal_off, tal_tot = self._carve(tal_sizes, 16)
         d_tallies = be.empty(tal_tot)
         if stage is None:
@@ -325,7 +341,10 @@ class Pipeline(FitRunner):
             t.boxes = d.spec("boxes", d_boxes, bo, job.boxes.nbytes, be.f64, (B, 6))
             t.feat_sum = d.spec("feat_sum", d_tallies, ao, 8 * S * D, be.i64, (S, D))
             t.occ_count = d.spec("occ_count", d_tallies, ao + 8 * S * D, 4 * S * B, be.i32, (S, B))
-            t.point_count = d.spec("point_count", d_tallies, ao + 8 * S * D + 4 * S * B, 4 * S, be.i32, (S,))
+            if pl:
+                t.point_count = d.spec("point_count", d_tables, to + 8 * S * W + 4 * S, 4 * S, be.i32, (S,))
+            else:
+                t.point_count = d.spec("point_count", d_tallies, ao + 8 * S * D + 4 * S * B, 4 * S, be.i32, (S,))
             t.occ_bits = d.spec("occ_bits", d_tables, to, 8 * S * W, be.i64, (S, W))
             t.n_bbs = d.spec("n_bbs", d_tables, to + 8 * S * W, 4 * S, be.i32, (S,))
             t.feats_spp = fbase + job.feats_row_base * fstride
@@ -338,6 +357,8 @@ class Pipeline(FitRunner):
             h = job.host
             h.spec("occ_bits_pin", stage, to, 8 * S * W, be.i64, (S, W))
             h.spec("n_bbs_pin", stage, to + 8 * S * W, 4 * S, be.i32, (S,))
+            if pl:
+                h.spec("point_count_pin", stage, to + 8 * S * W + 4 * S, 4 * S, be.i32, (S,))
         ev = self._part_event(jobs, "pool")
         self.ctx.check(lib.gapro_partition_pool_batch(self.ctx.handle, self._sh(), len(jobs), D,
                                                       C.cast(tasks, C.c_void_p), _ptr(d_tasks)))
@@ -356,6 +377,8 @@ class Pipeline(FitRunner):
         h = job.host
         h["occ_bits"] = np.ascontiguousarray(h["occ_bits_pin"].numpy().view(np.uint64))
         h["n_bbs"] = np.ascontiguousarray(h["n_bbs_pin"].numpy())
+        if "point_count_pin" in h:
+            h["point_count"] = h["point_count_pin"].numpy().copy()  # read at the END of the batch: not a view of the stage
         sched = C.c_void_p()
         rc = self.lib.gapro_schedule_build(job.n_spps, job.n_boxes, _ptr(job.boxes), _ptr(h["occ_bits"]),
                                            _ptr(h["n_bbs"]), C.byref(sched))
@@ -370,8 +393,9 @@ class Pipeline(FitRunner):
     def run(self, jobs: Sequence[SceneJob], keep_debug: bool = False, keep_models: bool = False):
         """Process a batch of scenes; fills job.outputs = (sem i32[N], inst i32[N], prob f32[N], mu f32[S],
         var f32[S]) as device tensors (same lengths as the reference returns).  With ``keep_models`` every
-        job also gets ``feats_spp`` and ``fits`` (see SceneJob): the trained GP of every box pair, for predictions at
-        other inputs (predict_models).  The outputs are the same bits either way."""
+        job also gets ``feats_spp``, ``fits`` and ``winner`` (see SceneJob): the trained GP of every box pair, for
+        predictions at other inputs (predict_models), and which of them labelled each superpoint.  The outputs are the
+        same bits either way.  A ``point_level`` pipeline returns mu and var at point length, f32[N] (see __init__)."""
         return self._finish(self._start(jobs, keep_debug, keep_models))
 
     kSlots = 3  # pipeline streams = slots of per-batch buffers (see _stream_batches)
@@ -452,6 +476,13 @@ class Pipeline(FitRunner):
         prev_state = None
         while cur_state is not None:
             nxt_state = on(i + 1, self._partition, nxt, False) if nxt is not None else None
+            # point_level: finish(i-1) waits for its predict kernels (the predict entry synchronises its stream and the
+            # per-model status is read back), and those cannot be dispatched beside a fit that holds every CU: it runs
+            # BEFORE fit(i) is launched.  The merge of batch i-1 is then not hidden behind a fit; the pull and the
+            # schedule of the batches behind it still are.
+            early = None
+            if self.point_level and prev_state is not None:
+                early = on(i - 1, self._finish, prev_state, False)
             if i > 0:
                 on(i, self._launch, cur_state)
             # everything below is host work that runs while the fit just launched occupies the GPU: the merge of the
@@ -460,7 +491,7 @@ class Pipeline(FitRunner):
             # partition kernels above only ran once it had drained -- and the pull can block for a whole batch of
             # reads, which in a worker's first second kept finished labels waiting for 0.3 .. 0.5 s
             if prev_state is not None:
-                yield on(i - 1, self._finish, prev_state, False)
+                yield early if early is not None else on(i - 1, self._finish, prev_state, False)
             nxt = on(i + 2, next, it, None) if nxt is not None else None
             if nxt_state is not None:
                 on(i + 1, self._schedule_all, nxt_state)
@@ -512,7 +543,8 @@ class Pipeline(FitRunner):
             base += job.n_spps
         feats_spp_all = self.be.empty_typed((base, D), self.be.f32)
         # one pinned staging area for the tables the host scheduler needs from every scene
-        need = sum(job.n_spps * (((job.n_boxes + 63) // 64) * 8 + 4) + 16 for job in jobs)
+        need = sum(job.n_spps * (((job.n_boxes + 63) // 64) * 8 + 4 + (4 if self.point_level else 0)) + 16
+                   for job in jobs)
         stage = self._pinned(slot + "tables", need)
         self._pool_all(jobs, tasks, d_tasks, feats_spp_all, stage)
         stream.synchronize()  # one sync: pooled tables of every scene are on the host
@@ -559,7 +591,9 @@ class Pipeline(FitRunner):
         if state.n_fits:
             state.pending = self.fit_launch(state.feats_spp_all, state.descs, state.n_fits, state.h_idx, state.n_out,
                                             keep_debug=state.keep_debug, slot=state.slot,
-                                            scene_keys=[j.scene_key for j in state.jobs], keep_models=state.keep_models)
+                                            scene_keys=[j.scene_key for j in state.jobs],
+                                            keep_models=state.keep_models or self.point_level,
+                                            state_to_host=state.keep_models)
         state.mark("D launched")
 
     def _finish(self, state: BatchState, sync: bool = True):
@@ -574,7 +608,15 @@ class Pipeline(FitRunner):
         res = self.fit_collect(state.pending, raise_on_failure=False) if state.pending is not None else None
         if res is not None:
             res = self._retry_timeouts(res, state.feats_spp_all, state.descs, state.h_idx, state.n_out,
-                                       slot=state.slot, scene_keys=[j.scene_key for j in jobs])
+                                       slot=state.slot, scene_keys=[j.scene_key for j in jobs],
+                                       keep_state=self.point_level)
+            if "retry_state" in res:  # the retried fits are predicted from the retry's states: copied into place
+                d2, off2 = res["retry_state"]
+                D = int(state.feats_spp_all.shape[1])
+                for k, i in enumerate(res["retried"]):
+                    nb = 8 * state_doubles(int(state.descs[i].m1 + state.descs[i].m2), D)
+                    a, b = 8 * int(state.pending.state_off[i]), 8 * off2[k]
+                    state.pending.d_state[a:a + nb].copy_(d2[b:b + nb], non_blocking=True)
         _mark("D fit")
         if state.keep_models:
             feats_all = _host(state.feats_spp_all)
@@ -598,6 +640,7 @@ class Pipeline(FitRunner):
                                                 % (k, job.counts.n_fits, int((st != 0).sum())))
             if self.strict:
                 raise next(j.error for j in jobs if j.error is not None)
+        want_winner = self.point_level or state.keep_models
         tot_s = sum(job.n_spps for job in jobs)
         tables = self._pinned(state.slot + "labels", tot_s * 20)
         busy = self._pin_events.pop(state.slot + "labels", None)
@@ -623,13 +666,18 @@ class Pipeline(FitRunner):
                 pn, lb, mu, var = (res["probs_new"][a:b], res["labels"][a:b], res["mu"][a:b], res["var"][a:b])
             else:
                 pn = lb = mu = var = None
-            rc = lib.gapro_schedule_merge(job.schedule, _ptr(pn), _ptr(lb), _ptr(mu), _ptr(var),
-                                          _ptr(job.boxes_cls), _ptr(job.boxes_volume), len(job.instance_box),
-                                          job.instance_classes, _ptr(sem_spp), _ptr(inst_spp), _ptr(prob_spp),
-                                          _ptr(mu_spp), _ptr(var_spp))
+            winner = np.empty(S, dtype=np.int32) if want_winner else None
+            rc = lib.gapro_schedule_merge_ex(job.schedule, _ptr(pn), _ptr(lb), _ptr(mu), _ptr(var),
+                                             _ptr(job.boxes_cls), _ptr(job.boxes_volume), len(job.instance_box),
+                                             job.instance_classes, _ptr(sem_spp), _ptr(inst_spp), _ptr(prob_spp),
+                                             _ptr(mu_spp), _ptr(var_spp), _ptr(winner))
             if rc != 0:
-                raise _lib.GaproError(rc, "gapro_schedule_merge")
+                raise _lib.GaproError(rc, "gapro_schedule_merge_ex")
             job.host.update(sem_spp=sem_spp.copy(), inst_spp=inst_spp.copy(), prob_spp=prob_spp.copy())
+            if want_winner:
+                dict.__setitem__(job.host, "winner", winner)
+                if state.keep_models:
+                    job.winner = winner
 
         # the ordered merge of a scene is host C++ on that scene's own slices: one host thread per scene
         if len(jobs) >= 8:
@@ -637,11 +685,14 @@ class Pipeline(FitRunner):
         else:
             for arg in zip(jobs, offs):
                 merge_one(arg)
+        # point_level: the row table of the predict launch is planned here, on the host, before anything is enqueued
+        plan = self._refine_plan(state) if self.point_level else None
         d_tables.copy_(tables[:tot_s * 20], non_blocking=True)  # one H2D copy for the whole batch
         self._pin_events[state.slot + "labels"] = be.current_stream().record_event()
         tasks, d_tasks = state.tasks, state.d_tasks
-        out_off, out_tot = self._carve([12 * job.n_points for job in jobs], 16)
-        d_out = be.empty(out_tot)  # [sem | inst | prob] per scene
+        per_point = 20 if self.point_level else 12
+        out_off, out_tot = self._carve([per_point * job.n_points for job in jobs], 16)
+        d_out = be.empty(out_tot)  # [sem | inst | prob] per scene; point_level: [sem | inst | prob | mu | var]
         for t, job, off, oo in zip(tasks, jobs, offs, out_off):
             S, n = job.n_spps, job.n_points
             sem = d_out[oo:oo + 4 * n].view(be.i32)
@@ -651,8 +702,14 @@ class Pipeline(FitRunner):
             t.inst_spp = d_tables.data_ptr() + off + 4 * S
             t.prob_spp = d_tables.data_ptr() + off + 8 * S
             t.sem, t.inst, t.prob = sem.data_ptr(), ins.data_ptr(), prb.data_ptr()
-            job.outputs = (sem, ins, prb, d_tables[off + 12 * S:off + 16 * S].view(be.f32),
-                           d_tables[off + 16 * S:off + 20 * S].view(be.f32))
+            mu_spp = d_tables[off + 12 * S:off + 16 * S].view(be.f32)
+            var_spp = d_tables[off + 16 * S:off + 20 * S].view(be.f32)
+            if self.point_level:
+                job.outputs = (sem, ins, prb, d_out[oo + 12 * n:oo + 16 * n].view(be.f32),
+                               d_out[oo + 16 * n:oo + 20 * n].view(be.f32))
+                dict.__setitem__(job.dev, "mu_var_spp", (mu_spp, var_spp))
+            else:
+                job.outputs = (sem, ins, prb, mu_spp, var_spp)
             if not keep_debug:
                 lib.gapro_schedule_free(job.schedule)
                 job.schedule = None
@@ -661,7 +718,7 @@ class Pipeline(FitRunner):
                                                    C.cast(tasks, C.c_void_p), _ptr(d_tasks)))
         self._part_event_end(ev)
         # the task array must outlive the (possibly delayed) upload enqueued above
-        self._keep[state.slot] = (tasks, d_tasks)
+        self._keep[state.slot] = (tasks, d_tasks, self._refine(state, plan) if self.point_level else None)
         if sync:
             be.current_stream().synchronize()
         _mark("E+F merge/broadcast")
@@ -670,4 +727,120 @@ class Pipeline(FitRunner):
             if j.error is not None:  # merged from a failed fit's garbage: not a result
                 j.outputs = None
         return [j.outputs if j.error is None else None for j in state.all_jobs]
+
+    # ------------------------------------------------------------------ stage G (point_level)
+    def _refine_plan(self, state: BatchState):
+        """Host plan of the batch's point-level predict launch, from each scene's merge winners and point counts (no
+        device round trip).  A scene's refined superpoints (winner >= 0) are ordered by (winning fit, superpoint): the
+        superpoints of one fit are contiguous and ascending, the fits in batch order.  Every fit that won at least one
+        superpoint becomes a predict model whose rows are the points of its superpoints; sp_row[sp] is the first row of
+        the superpoint's block.  Scenes that already failed take no part."""
+        import time as _time
+
+        t0 = _time.perf_counter()
+        jobs, descs = state.jobs, state.descs
+        sp_row = np.full(sum(j.n_spps for j in jobs), -1, dtype=np.int64)
+        models, rows, n_ref, base = [], 0, 0, 0
+        for si, job in enumerate(jobs):
+            S = job.n_spps
+            w = job.host["winner"]
+            ref = np.nonzero(w >= 0)[0] if job.error is None else np.zeros(0, np.int64)
+            if len(ref):
+                order = ref[np.argsort(w[ref], kind="stable")]
+                cnt = job.host["point_count"][order].astype(np.int64)
+                start = rows + np.cumsum(cnt) - cnt
+                sp_row[base + order] = start
+                fit_ids, first = np.unique(w[order], return_index=True)
+                ends = np.r_[first[1:], len(order)]
+                n_fg = len(job.instance_box)
+                for k, a, b in zip(fit_ids, first, ends):
+                    d = descs[job.fit_base + int(k)]
+                    pair = []
+                    for box in (int(d.b1), int(d.b2)):  # the merge's last loop (schedule.cpp) for a box
+                        pair += [int(job.boxes_cls[box]), box if box < n_fg else -100]
+                    models.append((job.fit_base + int(k), si, int(start[a]), int(cnt[a:b].sum()), pair))
+                rows += int(cnt.sum())
+                n_ref += len(ref)
+            base += S
+        if rows > 2**31 - 1:  # row indices are int32 (the predict ABI): refused before anything is launched
+            raise _lib.GaproError(-1, "point_level: %d rows in one batch exceed the int32 row index" % rows)
+        self.last_refine = dict(refined_spps=n_ref, rows=rows, models=len(models), plan_s=_time.perf_counter() - t0)
+        return dict(sp_row=sp_row, models=models, rows=rows)
+
+    def _refine(self, state: BatchState, plan):
+        """Behind the broadcast, on the same stream: gather the rows, ONE gapro_svgp_predict_batch over them with identity
+        rows, apply.  A batch without a refined superpoint runs neither gather nor predict, only apply's mu / var
+        broadcast.  A model whose prediction fails (status != 0) fails its scene like a failed fit.  Returns what must
+        stay alive until the stream has run all of it."""
+        lib, ctx, be = self.lib, self.ctx, self.be
+        jobs = state.jobs
+        D = int(state.feats_spp_all.shape[1])
+        R, models = plan["rows"], plan["models"]
+        ns = len(jobs)
+        scenes = (PointRefineScene * ns)()
+        d_scenes = be.empty(ns * C.sizeof(PointRefineScene))
+        d_sp_row = be.from_numpy(plan["sp_row"])
+        d_cursor = be.empty(4 * len(plan["sp_row"]))
+        base = 0
+        for t, job in zip(scenes, jobs):
+            S = job.n_spps
+            sem, ins, prb, mu, var = job.outputs
+            mu_spp, var_spp = job.dev["mu_var_spp"]
+            t.n_points, t.n_spps, t.reserved = job.n_points, S, 0
+            t.spp_inv, t.feats = job.dev["spp_inv"].data_ptr(), job.feats.data_ptr()
+            t.sp_row, t.cursor = d_sp_row.data_ptr() + 8 * base, d_cursor.data_ptr() + 4 * base
+            t.mu_spp, t.var_spp = mu_spp.data_ptr(), var_spp.data_ptr()
+            t.sem, t.inst, t.prob, t.mu, t.var = (x.data_ptr() for x in (sem, ins, prb, mu, var))
+            base += S
+        self._stage("broadcast")
+        keep = [scenes, d_scenes, d_sp_row, d_cursor]
+        nm = len(models) if R else 0
+        if nm == 0:
+            ctx.check(lib.gapro_point_refine_apply(ctx.handle, self._sh(), ns, C.cast(scenes, C.c_void_p), _ptr(d_scenes),
+                                                   0, None, None, 0, None, None, None, None, None, None))
+            self._stage("apply")
+            return keep
+        row_feats = be.empty_typed((R, D), be.f32)
+        row_point = be.empty(4 * R)
+        ctx.check(lib.gapro_point_refine_gather(ctx.handle, self._sh(), ns, D, C.cast(scenes, C.c_void_p),
+                                                _ptr(d_scenes), R, _ptr(row_feats), _ptr(row_point)))
+        self._stage("gather")
+        pd = (PredictDesc * nm)()
+        rm = (PointRefineModel * nm)()
+        h_m = np.empty(nm, dtype=np.int32)
+        off = state.pending.state_off
+        for q, r, (f, si, row0, t, pair) in zip(pd, rm, models):
+            q.state_offset, q.row_offset, q.out_offset, q.t, q.reserved = int(off[f]), row0, row0, t, 0
+            r.row_offset, r.t, r.scene = row0, t, si
+            r.sem1, r.inst1, r.sem2, r.inst2 = pair
+        for k, m in enumerate(models):
+            d = state.descs[m[0]]
+            h_m[k] = int(d.m1 + d.m2)
+        out, pstat = self._predict_launch(state.pending.d_state, h_m, pd, row_feats, self._identity_rows(R), R)
+        self._stage("predict")
+        o = block_views(ROW_FIELDS, out, R, be)
+        d_models = be.empty(nm * C.sizeof(PointRefineModel))
+        ctx.check(lib.gapro_point_refine_apply(ctx.handle, self._sh(), ns, C.cast(scenes, C.c_void_p), _ptr(d_scenes), nm,
+                                               C.cast(rm, C.c_void_p), _ptr(d_models), R, _ptr(row_point),
+                                               _ptr(o["probs_new"]), _ptr(o["labels"]), _ptr(o["mu"]), _ptr(o["var"]),
+                                               _ptr(pstat)))
+        self._stage("apply")
+        st = _host(pstat).view(np.int32)[:nm]  # the batch waits here for its predict launch
+        if (st != 0).any():
+            for k in np.nonzero(st)[0]:
+                job = jobs[models[k][1]]
+                if job.error is None:
+                    job.error = _lib.GaproError(int(st[k]), "point-level prediction from GP fit %d of the scene failed"
+                                                % (models[k][0] - job.fit_base))
+            if self.strict:
+                raise next(j.error for j in jobs if j.error is not None)
+        return keep + [rm, d_models, pd, row_feats, row_point, out, pstat]
+
+    def _identity_rows(self, n: int):
+        """i32[>= n] = 0, 1, 2, .. on the device (grow-only): the predict launch reads the gathered table in order."""
+        cur = self._ident_rows
+        if cur is None or cur.numel() < n:
+            cur = self._ident_rows = self.be.from_numpy(np.arange(max(n, 1 << 16) * 5 // 4, dtype=np.int32))
+            self.be.current_stream().synchronize()  # every pipeline stream reads it from now on
+        return cur
 

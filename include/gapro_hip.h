@@ -384,9 +384,22 @@ int gapro_schedule_merge(const gapro_schedule* s, const float* h_probs_new, cons
                          const double* h_boxes_volume, int32_t n_fg_instances, int32_t instance_classes,
                          int32_t* h_sem_spp, int32_t* h_inst_spp, float* h_prob_spp, float* h_mu_spp,
                          float* h_var_spp);
+/* gapro_schedule_merge plus one more output: h_winner_fit i32[S] (NULL = not wanted, which is gapro_schedule_merge; the
+ * other outputs are the same bits either way).  winner[sp] is the index, in gapro_schedule_export_fits order, of the fit
+ * whose outputs superpoint sp ends up with, -1 where no fit labels it:
+ *   - it starts at -1;
+ *   - a fit event that overwrites sp (the strict float32 `<` on probs_new) sets it to that fit;
+ *   - a containment event that writes sp sets it back to -1 (probability 1; the superpoint keeps the stale mu / var
+ *     of the fit it had, as gapro_schedule_merge always did);
+ *   - the smallest-volume fallback only touches superpoints no event determined, which have no winner. */
+int gapro_schedule_merge_ex(const gapro_schedule* s, const float* h_probs_new, const uint8_t* h_labels,
+                            const float* h_mu, const float* h_var, const int64_t* h_boxes_cls,
+                            const double* h_boxes_volume, int32_t n_fg_instances, int32_t instance_classes,
+                            int32_t* h_sem_spp, int32_t* h_inst_spp, float* h_prob_spp, float* h_mu_spp,
+                            float* h_var_spp, int32_t* h_winner_fit);
 
 /* ------------------------------------------------------------------------------------------
- * Batched variational-GP fit (device).  Replaces gaussian_process_utils.py:382-445 and the
+ * Batched variational-GP fit (device). Replaces gaussian_process_utils.py:382-445 and the
  * gpytorch objects it builds (GPClassificationModel :11-25, BernoulliLikelihood, VariationalELBO,
  * Adam lr 0.1, 50 steps).  One workgroup trains one fit for all `training_iter` steps inside a
  * single launch; every fit of every scene in the batch runs concurrently.
@@ -527,6 +540,76 @@ int gapro_svgp_predict_batch(gapro_ctx* ctx, void* stream, int32_t n_models, int
                              int64_t n_feat_rows, const int32_t* d_rows, const gapro_fit_options* opt,
                              void* d_workspace, size_t workspace_bytes, float* d_probs, float* d_probs_new,
                              uint8_t* d_labels, float* d_mu, float* d_var, int32_t* d_status);
+
+/* ------------------------------------------------------------------------------------------
+ * Point-level labels inside GP-labelled superpoints (csrc/point_refine.hip; no reference counterpart: the reference
+ * labels whole superpoints, gen_ps_utils.py:438-480).  After the ordered merge a superpoint is REFINED iff a fit won it
+ * (gapro_schedule_merge_ex: winner >= 0).  Every point of a refined superpoint is predicted from its own feature row by
+ * the model that won the superpoint, and its own five values replace the broadcast ones:
+ *   (p, p_new, label, mu, var) = gapro_svgp_predict_batch's result for that model at feats[i]   (float32 row, width D)
+ *   box = label ? b2 : b1;  sem[i] = boxes_cls[box];  inst[i] = box, or -100 when box >= n_fg_instances;
+ *   prob[i] = p_new;  mu[i] = mu;  var[i] = var.
+ * Every other point keeps the broadcast values, mu[i] = mu_spp[spp_inv[i]], var[i] = var_spp[spp_inv[i]]: all five
+ * outputs are point-length.  The competition between several fits that tested one superpoint is NOT re-run per point:
+ * the superpoint-level merge picks the model, and that model alone labels the points, between its own two boxes.
+ *
+ * The chain of a batch, on one stream: gapro_broadcast_labels_batch -> gapro_point_refine_gather -> ONE
+ * gapro_svgp_predict_batch over the gathered rows (identity d_rows, out_offset == row_offset) -> gapro_point_refine_apply.
+ * The launch's ROW TABLE holds the points of every refined superpoint of every scene: a superpoint's points form one
+ * block of point_count[sp] rows, the blocks of one model's superpoints are contiguous, and the host plans the block
+ * starts (sp_row) from the point counts gapro_partition_pool left.  Row indices are int32 (the predict ABI).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t n_points;
+  int32_t n_spps;
+  int32_t reserved;          /* 0 */
+  const int32_t* spp_inv;    /* i32[N] */
+  const float* feats;        /* f32[N,D]                                                   gather */
+  const int64_t* sp_row;     /* i64[S] first row of the superpoint's block, -1 = not refined gather */
+  int32_t* cursor;           /* i32[S] tmp: next free position of each block (zeroed by the call) gather */
+  const float* mu_spp;       /* f32[S]                                                     apply */
+  const float* var_spp;      /* f32[S]                                                     apply */
+  int32_t* sem;              /* i32[N] in/out: the broadcast labels, refined in place       apply */
+  int32_t* inst;             /* i32[N] in/out                                              apply */
+  float* prob;               /* f32[N] in/out                                              apply */
+  float* mu;                 /* f32[N] out                                                 apply */
+  float* var;                /* f32[N] out                                                 apply */
+} gapro_point_refine_scene;
+
+/* One predict model of the launch as gapro_point_refine_apply needs it: its rows are [row_offset, row_offset + t) of the
+ * row table and of the five predict outputs; (sem, inst) of a point labelled 0 (box b1) and 1 (box b2), prepared on the
+ * host with the rule above. */
+typedef struct {
+  int64_t row_offset;
+  int32_t t;
+  int32_t scene;             /* index into the scenes of the call */
+  int32_t sem1, inst1;
+  int32_t sem2, inst2;
+} gapro_point_refine_model;
+
+/* One pass over the points of every scene (grid.y = scene): a point of a refined superpoint takes the next free position
+ * of its superpoint's block, copies its feat_dim floats to d_row_feats f32[n_rows, feat_dim] and writes its scene-local
+ * index to d_row_point i32[n_rows].  The ORDER of the points inside a block is not part of the contract (it follows the
+ * order in which the atomics land); a predict row's result is its own, so the per-point outputs do not depend on it.
+ * sp_row must give every refined superpoint a block of exactly its number of points inside [0, n_rows), blocks disjoint;
+ * a position that would fall outside the table is dropped, never written.  h_scenes is copied to d_scenes (device,
+ * n_scenes entries) on the stream and must stay valid until the stream has executed that copy.  n_scenes == 0 or
+ * n_rows == 0: nothing is launched.  GAPRO_ERR_BAD_ARG: a null or negative argument, n_rows beyond 2^31 - 1 (refused
+ * before anything is launched).  Enqueue only. */
+int gapro_point_refine_gather(gapro_ctx* ctx, void* stream, int32_t n_scenes, int32_t feat_dim,
+                              const gapro_point_refine_scene* h_scenes, gapro_point_refine_scene* d_scenes,
+                              int64_t n_rows, float* d_row_feats, int32_t* d_row_point);
+/* mu[i] = mu_spp[spp_inv[i]], var[i] = var_spp[spp_inv[i]] for every point of every scene; then, for every row r of every
+ * model whose d_model_status is 0 (NULL = all), the five values of point d_row_point[r] of the model's scene from the
+ * predict outputs at r.  sem / inst / prob must already hold the broadcast labels (same stream).  h_models is copied to
+ * d_models on the stream like the scenes.  n_models == 0 (then the model and row arguments may be NULL) leaves the
+ * broadcast; n_scenes == 0 is a no-op.  A row whose point index lies outside its scene is skipped.  Enqueue only. */
+int gapro_point_refine_apply(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro_point_refine_scene* h_scenes,
+                             gapro_point_refine_scene* d_scenes, int32_t n_models,
+                             const gapro_point_refine_model* h_models, gapro_point_refine_model* d_models,
+                             int64_t n_rows, const int32_t* d_row_point, const float* d_probs_new,
+                             const uint8_t* d_labels, const float* d_mu, const float* d_var,
+                             const int32_t* d_model_status);
 
 /* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
