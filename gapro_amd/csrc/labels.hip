@@ -288,6 +288,17 @@ __global__ __launch_bounds__(kThreads) void k_lab_chunk_scan(int n_chunks, LabWs
   }
   t.chunk[n_chunks] = run;
 }
+// torch.sum((p - c) ** 2, -1) (:526): every square and every sum rounded on its own, in x, y, z order.  Contraction into
+// FMAs is switched off for the function (as in trainset.hip's dist_key): a fused square is rounded together with the sum
+// it joins, and two boxes at the same distance in the reference's arithmetic (centres mirrored about a coordinate plane,
+// the point on it) would no longer tie -- the later box could win where the reference keeps the first.
+__device__ inline double lab_sqdist(double x, double y, double z, const double* __restrict__ c) {
+#pragma clang fp contract(off)
+  const double dx = x - c[0], dy = y - c[1], dz = z - c[2];
+  const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+  return (xx + yy) + zz;
+}
+
 // "dist" (:523-531), reproducing the reference's indexing: the k-th multi-box point (k = its rank among the
 // multi-box points) is measured from the coordinates of SCENE POINT k, not from its own
 __global__ __launch_bounds__(kThreads) void k_lab_dist(long long n, const double* __restrict__ coords, int B,
@@ -323,8 +334,7 @@ __global__ __launch_bounds__(kThreads) void k_lab_dist(long long n, const double
       double best_d = 0.0;
       for (int b = 0; b < B; ++b) {
         if (!((t.bits[i * W + (b >> 6)] >> (b & 63)) & 1ull)) continue;
-        const double dx = x - sh_center[3 * b], dy = y - sh_center[3 * b + 1], dz = z - sh_center[3 * b + 2];
-        const double d = dx * dx + dy * dy + dz * dz;
+        const double d = lab_sqdist(x, y, z, sh_center + 3 * b);
         if (best < 0 || d < best_d) {
           best_d = d;
           best = b;
