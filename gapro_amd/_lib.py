@@ -67,6 +67,17 @@ class PointRefineModel(C.Structure):
                 ("inst1", C.c_int32), ("sem2", C.c_int32), ("inst2", C.c_int32)]
 
 
+class PointRefineBlock(C.Structure):
+    """gapro_point_refine_block: the gathered rows of one refined superpoint and its segments (point_level="compete")."""
+    _fields_ = [("row_start", C.c_int64), ("n_rows", C.c_int32), ("scene", C.c_int32), ("seg_start", C.c_int32),
+                ("n_seg", C.c_int32)]
+
+
+class PointRefineSegment(C.Structure):
+    """gapro_point_refine_segment: one (tester fit, refined superpoint) pair of the expanded predict launch."""
+    _fields_ = [("out_start", C.c_int64), ("model", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TrainsetDesc(C.Structure):
     """gapro_trainset_desc: one point-level problem of gapro_trainset_count / gapro_trainset_fill."""
     _fields_ = [("idx_offset", C.c_int64), ("n1", C.c_int32), ("n2", C.c_int32), ("t", C.c_int32), ("m1", C.c_int32),
@@ -180,6 +191,7 @@ SIGNATURES = {
     "gapro_schedule_get_counts": (C.c_int, [_P, C.POINTER(ScheduleCounts)]),
     "gapro_schedule_export_fits": (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
     "gapro_schedule_export_events": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "gapro_schedule_export_testers": (C.c_int, [_P, _P, _P, _P]),
     "gapro_schedule_merge": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "gapro_schedule_merge_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "gapro_fit_options_default": (None, [C.POINTER(FitOptions)]),
@@ -199,6 +211,9 @@ SIGNATURES = {
     "gapro_point_refine_gather": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P]),
     "gapro_point_refine_apply": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, _P,
                                            _P]),
+    "gapro_point_refine_expand": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P]),
+    "gapro_point_refine_compete": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32,
+                                             _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "gapro_trainset_workspace_bytes": (C.c_size_t, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32]),
     "gapro_trainset_count": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_size_t,
                                        _P, _P]),
@@ -342,7 +357,8 @@ def load() -> C.CDLL:
         except AttributeError:
             variant = os.path.abspath(LIB_PATH) != os.path.abspath(default)
             if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state",
-                                            "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex")):
+                                            "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex",
+                                            "gapro_schedule_export_testers")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

@@ -2,6 +2,8 @@
 // passes on either side of the batch's one gapro_svgp_predict_batch launch.
 //   gather  every point of a refined superpoint -> a row of the launch's row table (its features, its point index)
 //   apply   mu / var broadcast for every point, then the predict outputs of every row -> the row's point
+//   expand  ("compete") the row list of the predict launch: a gathered row once per fit that tested its superpoint
+//   compete ("compete") the ordered merge replayed per point over those fits' outputs -> the row's point
 // No reference counterpart: the reference labels whole superpoints (gen_ps_utils.py:438-480).  Batched over the scenes of
 // a batch like gapro_broadcast_labels_batch (grid.y = scene), with a per-scene struct of its own.
 #include "common.h"
@@ -120,6 +122,109 @@ __global__ __launch_bounds__(kThreads) void k_refine_apply(const gapro_point_ref
   }
 }
 
+// "compete": the block that holds gathered row r, by bisection over the blocks' first rows (ascending, disjoint: checked
+// on the host), or -1 for a row between two blocks.  A block has 1 to a few hundred rows, so rows, not blocks, are
+// dealt to the lanes: consecutive lanes take consecutive rows and the reads of a segment are contiguous.
+__device__ __forceinline__ int block_of_row(const gapro_point_refine_block* __restrict__ blocks, int n_blocks,
+                                            long long r) {
+  int lo = 0, hi = n_blocks;  // the last block with row_start <= r lies in [lo, hi)
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (blocks[mid].row_start <= r) lo = mid; else hi = mid;
+  }
+  const long long first = blocks[lo].row_start;
+  return (r >= first && r - first < blocks[lo].n_rows) ? lo : -1;
+}
+
+__global__ __launch_bounds__(kThreads) void k_refine_expand(const gapro_point_refine_block* __restrict__ blocks,
+                                                            int n_blocks,
+                                                            const gapro_point_refine_segment* __restrict__ segs,
+                                                            long long n_rows, long long n_rows2,
+                                                            int* __restrict__ rows) {
+  const long long stride = (long long)gridDim.x * kThreads;
+  for (long long r = (long long)blockIdx.x * kThreads + threadIdx.x; r < n_rows; r += stride) {
+    const int b = block_of_row(blocks, n_blocks, r);
+    if (b < 0) continue;
+    const gapro_point_refine_block blk = blocks[b];
+    const long long j = r - blk.row_start;
+    for (int s = 0; s < blk.n_seg; ++s) {
+      const long long o = segs[blk.seg_start + s].out_start + j;
+      if (o >= 0 && o < n_rows2) rows[o] = (int)r;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_refine_compete(
+    const gapro_point_refine_scene* __restrict__ scenes, const gapro_point_refine_model* __restrict__ models,
+    const gapro_point_refine_block* __restrict__ blocks, int n_blocks,
+    const gapro_point_refine_segment* __restrict__ segs, long long n_rows, long long n_rows2,
+    const int* __restrict__ row_point, const float* __restrict__ probs_new, const unsigned char* __restrict__ labels,
+    const float* __restrict__ mu_r, const float* __restrict__ var_r, const int* __restrict__ status,
+    int* __restrict__ row_model) {
+  const long long stride = (long long)gridDim.x * kThreads;
+  for (long long r = (long long)blockIdx.x * kThreads + threadIdx.x; r < n_rows; r += stride) {
+    const int b = block_of_row(blocks, n_blocks, r);
+    int took = -1;
+    long long at = -1;
+    long long i = -1;
+    if (b >= 0) {
+      const gapro_point_refine_block blk = blocks[b];
+      const long long j = r - blk.row_start;
+      float best = 0.0f;  // the merge's start for a superpoint in several boxes (gen_ps_utils.py:367)
+      for (int s = 0; s < blk.n_seg; ++s) {
+        const gapro_point_refine_segment sg = segs[blk.seg_start + s];
+        if (status && status[sg.model] != 0) continue;  // its rows may hold nothing
+        const long long o = sg.out_start + j;
+        if (o < 0 || o >= n_rows2) continue;
+        const float p = probs_new[o];
+        if (best < p) {  // strict, float32: the first maximum; a NaN never wins
+          best = p;
+          took = sg.model;
+          at = o;
+        }
+      }
+      if (took >= 0) {
+        const gapro_point_refine_scene& t = scenes[blk.scene];
+        i = row_point[r];
+        if (i < 0 || i >= t.n_points) {
+          took = -1;
+        } else {
+          const gapro_point_refine_model m = models[took];
+          const bool second = labels[at] != 0;
+          t.sem[i] = second ? m.sem2 : m.sem1;
+          t.inst[i] = second ? m.inst2 : m.inst1;
+          t.prob[i] = best;
+          t.mu[i] = mu_r[at];
+          t.var[i] = var_r[at];
+        }
+      }
+    }
+    if (row_model) row_model[r] = took;
+  }
+}
+
+// the checks expand and compete share: blocks ascending and disjoint inside [0, n_rows), segments inside [0, n_rows2)
+const char* check_blocks(int n_blocks, const gapro_point_refine_block* h_blocks, int n_segs,
+                         const gapro_point_refine_segment* h_segs, long long n_rows, long long n_rows2, int n_scenes,
+                         int n_models) {
+  long long end = 0;
+  for (int b = 0; b < n_blocks; ++b) {
+    const gapro_point_refine_block& k = h_blocks[b];
+    if (k.n_rows <= 0 || k.row_start < end || k.row_start > n_rows - k.n_rows)
+      return "a block outside the rows or out of order";
+    end = k.row_start + k.n_rows;
+    if (k.n_seg < 0 || k.seg_start < 0 || k.seg_start > n_segs - k.n_seg)
+      return "a block's segments outside the segments";
+    if (n_scenes >= 0 && (k.scene < 0 || k.scene >= n_scenes)) return "a block of no scene";
+    for (int s = 0; s < k.n_seg; ++s) {
+      const gapro_point_refine_segment& g = h_segs[k.seg_start + s];
+      if (g.out_start < 0 || g.out_start > n_rows2 - k.n_rows) return "a segment outside the expanded rows";
+      if (n_models >= 0 && (g.model < 0 || g.model >= n_models)) return "a segment of no model";
+    }
+  }
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -201,6 +306,81 @@ int gapro_point_refine_apply(gapro_ctx* ctx, void* stream_, int32_t n_scenes, co
                          d_model_status ? d_model_status + lo : nullptr);
     }
   }
+  GAPRO_LAUNCH_CHECK(ctx);
+  return GAPRO_OK;
+}
+
+int gapro_point_refine_expand(gapro_ctx* ctx, void* stream_, int32_t n_blocks, const gapro_point_refine_block* h_blocks,
+                              gapro_point_refine_block* d_blocks, int32_t n_segs,
+                              const gapro_point_refine_segment* h_segs, gapro_point_refine_segment* d_segs,
+                              int64_t n_rows, int64_t n_rows2, int32_t* d_rows) {
+  if (!ctx) return GAPRO_ERR_BAD_ARG;
+  if (n_blocks < 0 || n_segs < 0 || n_rows < 0 || n_rows > kMaxRows || n_rows2 < 0 || n_rows2 > kMaxRows)
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG,
+                      "gapro_point_refine_expand: bad argument (%d blocks, %d segments, %lld -> %lld rows)", (int)n_blocks, (int)n_segs, (long long)n_rows, (long long)n_rows2);
+  if (n_blocks == 0 || n_segs == 0) return GAPRO_OK;
+  if (!h_blocks || !d_blocks || !h_segs || !d_segs || !d_rows)
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_expand: null argument");
+  if (const char* why = check_blocks(n_blocks, h_blocks, n_segs, h_segs, n_rows, n_rows2, -1, -1))
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_expand: %s", why);
+  hipStream_t stream = (hipStream_t)stream_;
+  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_blocks, h_blocks, (size_t)n_blocks * sizeof(gapro_point_refine_block),
+                                      hipMemcpyHostToDevice, stream));
+  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_segs, h_segs, (size_t)n_segs * sizeof(gapro_point_refine_segment),
+                                      hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL(k_refine_expand, dim3(grid_for(n_rows, 2048)), dim3(kThreads), 0, stream, d_blocks, (int)n_blocks,
+                     d_segs, (long long)n_rows, (long long)n_rows2, d_rows);
+  GAPRO_LAUNCH_CHECK(ctx);
+  return GAPRO_OK;
+}
+
+int gapro_point_refine_compete(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapro_point_refine_scene* h_scenes,
+                               gapro_point_refine_scene* d_scenes, int32_t n_models,
+                               const gapro_point_refine_model* h_models, gapro_point_refine_model* d_models,
+                               int32_t n_blocks, const gapro_point_refine_block* h_blocks,
+                               gapro_point_refine_block* d_blocks, int32_t n_segs,
+                               const gapro_point_refine_segment* h_segs, gapro_point_refine_segment* d_segs,
+                               int64_t n_rows, int64_t n_rows2, const int32_t* d_row_point, const float* d_probs_new,
+                               const uint8_t* d_labels, const float* d_mu, const float* d_var,
+                               const int32_t* d_model_status, int32_t* d_row_model) {
+  if (!ctx) return GAPRO_ERR_BAD_ARG;
+  if (n_scenes < 0 || n_models < 0 || n_blocks < 0 || n_segs < 0 || n_rows < 0 || n_rows > kMaxRows || n_rows2 < 0 ||
+      n_rows2 > kMaxRows)
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG,
+                      "gapro_point_refine_compete: bad argument (%d scenes, %d models, %d blocks, %d segments, "
+                      "%lld -> %lld rows)",
+                      (int)n_scenes, (int)n_models, (int)n_blocks, (int)n_segs, (long long)n_rows, (long long)n_rows2);
+  if (n_scenes == 0 || n_blocks == 0) return GAPRO_OK;
+  if (!h_scenes || !d_scenes || !h_blocks || !d_blocks || !d_row_point)
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_compete: null argument");
+  if (n_segs > 0 && (!h_segs || !d_segs || !h_models || !d_models || n_models == 0 || !d_probs_new || !d_labels ||
+                     !d_mu || !d_var))
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_compete: null argument");
+  for (int i = 0; i < n_scenes; ++i) {
+    const gapro_point_refine_scene& t = h_scenes[i];
+    if (t.n_points <= 0 || !t.sem || !t.inst || !t.prob || !t.mu || !t.var)
+      return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_compete: scene %d: bad argument", i);
+  }
+  for (int k = 0; k < n_models; ++k)
+    if (h_models[k].scene < 0 || h_models[k].scene >= n_scenes)
+      return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_compete: model %d: scene %d", k,
+                        (int)h_models[k].scene);
+  if (const char* why = check_blocks(n_blocks, h_blocks, n_segs, h_segs, n_rows, n_rows2, n_scenes, n_models))
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_compete: %s", why);
+  hipStream_t stream = (hipStream_t)stream_;
+  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_scenes, h_scenes, (size_t)n_scenes * sizeof(gapro_point_refine_scene),
+                                      hipMemcpyHostToDevice, stream));
+  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_blocks, h_blocks, (size_t)n_blocks * sizeof(gapro_point_refine_block),
+                                      hipMemcpyHostToDevice, stream));
+  if (n_segs > 0) {
+    GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_models, h_models, (size_t)n_models * sizeof(gapro_point_refine_model),
+                                        hipMemcpyHostToDevice, stream));
+    GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_segs, h_segs, (size_t)n_segs * sizeof(gapro_point_refine_segment),
+                                        hipMemcpyHostToDevice, stream));
+  }
+  hipLaunchKernelGGL(k_refine_compete, dim3(grid_for(n_rows, 2048)), dim3(kThreads), 0, stream, d_scenes, d_models,
+                     d_blocks, (int)n_blocks, d_segs, (long long)n_rows, (long long)n_rows2, d_row_point, d_probs_new,
+                     d_labels, d_mu, d_var, d_model_status, d_row_model);
   GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;
 }

@@ -221,6 +221,31 @@ int gapro_schedule_export_events(const gapro_schedule* s, uint8_t* h_kind, int32
   return GAPRO_OK;
 }
 
+int gapro_schedule_export_testers(const gapro_schedule* s, int64_t* h_offsets, int32_t* h_fit, int32_t* h_pos) {
+  if (!s || !h_offsets) return GAPRO_ERR_BAD_ARG;
+  const int S = s->n_spps;
+  std::fill(h_offsets, h_offsets + S + 1, (int64_t)0);
+  int64_t n = 0;
+  for (const Fit& f : s->fits)
+    for (int32_t sp : s->events[f.event].inter) {
+      ++h_offsets[sp + 1];
+      ++n;
+    }
+  for (int sp = 0; sp < S; ++sp) h_offsets[sp + 1] += h_offsets[sp];
+  if (n == 0) return GAPRO_OK;
+  if (!h_fit || !h_pos) return GAPRO_ERR_BAD_ARG;
+  std::vector<int64_t> next(h_offsets, h_offsets + S);
+  for (size_t i = 0; i < s->fits.size(); ++i) {  // the fits are numbered in event order: the order the merge meets them
+    const std::vector<int32_t>& in = s->events[s->fits[i].event].inter;
+    for (size_t j = 0; j < in.size(); ++j) {
+      const int64_t o = next[in[j]]++;
+      h_fit[o] = (int32_t)i;
+      h_pos[o] = (int32_t)j;
+    }
+  }
+  return GAPRO_OK;
+}
+
 int gapro_schedule_merge_ex(const gapro_schedule* s, const float* h_probs_new, const uint8_t* h_labels,
                             const float* h_mu, const float* h_var, const int64_t* h_boxes_cls,
                             const double* h_boxes_volume, int32_t n_fg_instances, int32_t instance_classes,

@@ -30,6 +30,9 @@ resume mechanism, gen_ps.py:39-41) and every scene is written as the same 5-tupl
                            model that won the superpoint (Pipeline(point_level=True)): the same 5-tuple
                            files, all five arrays at point length; --eval_pslabel evaluates these labels.  Together with
                            --broadcast_mu_var it is --point_level.  Stays on the torch-free backend
+    --point_compete        --point_level with the fit competition re-run per point (Pipeline(point_level="compete")):
+                           every fit that tested the superpoint is evaluated at every point of it and the point goes to
+                           the first fit with the largest probability.  Implies --point_level; same files, same backend
     --loader_threads T     threads of the library's batch feeder (csrc/feeder.hip) that read scenes from disk two
                            batches ahead, preprocess and upload them, and write the label files (default -1 =
                            min(16, usable CPUs / W - 1) per worker for W workers, at least 2; "usable" honours the
@@ -312,7 +315,9 @@ class Worker:
         if not dry:
             want = os.environ.get("GAPRO_BACKEND", "").strip().lower()
             # (with --point_level mu / var already are point-length: --broadcast_mu_var has nothing left to do)
-            self.broadcast = bool(args.broadcast_mu_var) and not getattr(args, "point_level", False)
+            compete = bool(getattr(args, "point_compete", False))
+            point_level = "compete" if compete else bool(getattr(args, "point_level", False))
+            self.broadcast = bool(args.broadcast_mu_var) and not point_level
             needs_torch = bool(args.eval_pslabel or self.broadcast or os.environ.get("GAPRO_DRIVER_HOST_ONLY"))
             self.backend = "torch" if (needs_torch or want == "torch") else "native"
             if self.backend == "torch":
@@ -322,7 +327,7 @@ class Worker:
 
             self.make_job = make_job
             self.pipe = Pipeline(device=device_index, training_iter=50, init_mean_std=args.init_mean_std, seed=args.seed,
-                                 backend=self.backend, point_level=bool(getattr(args, "point_level", False)))
+                                 backend=self.backend, point_level=point_level)
             self.pipe.strict = False  # a scene that cannot be processed is reported and skipped, the rest is written
             if os.environ.get("GAPRO_DRIVER_TIMES"):
                 self.pipe.trace = []  # host-side stage timeline of the pipeline (printed at the end)
@@ -767,6 +772,7 @@ def main(argv=None):
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--broadcast_mu_var", action="store_true")
     parser.add_argument("--point_level", action="store_true")
+    parser.add_argument("--point_compete", action="store_true")
     parser.add_argument("--raw_cache", type=str, default=None, help=argparse.SUPPRESS)  # ignored since round 5
     parser.add_argument("--loader_threads", type=int, default=-1)
     parser.add_argument("--loader_procs", type=int, default=-1, help=argparse.SUPPRESS)  # ignored since round 5
@@ -776,6 +782,8 @@ def main(argv=None):
     parser.add_argument("--job_dir", type=str, default=None, help=argparse.SUPPRESS)
     parser.add_argument("--dry_run", action="store_true", help=argparse.SUPPRESS)
     args = parser.parse_args(argv)
+    if args.point_compete:
+        args.point_level = True
 
     os.makedirs(args.save_folder, exist_ok=True)
     filenames = sorted(glob(osp.join(args.data_root, args.split, "*_inst_nostuff.pth")))  # :27-32

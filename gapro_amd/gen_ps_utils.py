@@ -8,7 +8,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .pipeline import Pipeline, make_job
+from .pipeline import Pipeline, make_job, point_mode
 
 _PIPELINES = {}
 
@@ -67,8 +67,13 @@ def gen_pseudo_label_gaussian_process(
                       model that won the superpoint in the ordered merge, and gets its own (instance, semantic,
                       probability, mu, sigma^2); every other point keeps the superpoint's values.  All five outputs are
                       then point-length: (sem i32[N], inst i32[N], prob f32[N], mu f32[N], var f32[N]), and
-                      ``broadcast_mu_var`` changes nothing.  The competition between several fits over one superpoint
-                      is not re-run per point.
+                      ``broadcast_mu_var`` changes nothing.  True or "winner": the competition between several fits over
+                      one superpoint is not re-run per point.  "compete": it is -- every fit that tested the superpoint
+                      is evaluated at every point of it and the point goes to the first fit with the largest
+                      probability (strict float32 <, in schedule order), which may give it to a box that is neither of
+                      the superpoint's winner's two; with ``return_models`` the models object then has ``point_fit``
+                      i32[N], the index into ``fits`` of the fit that labelled each point, -1 elsewhere.  Superpoints
+                      labelled by a containment verdict or the fallback are not refined in either mode.
     init_mean_std     std of the random initial variational mean (gpytorch uses 1e-3 with an unseeded
                       RNG; 0 = deterministic zeros), ``seed`` seeds it.
     eval_stale_chol   predict with the Cholesky factor of the last training step.
@@ -78,27 +83,29 @@ def gen_pseudo_label_gaussian_process(
     job = make_job(coords_float, mask_feats, spp, instance_cls, instance_box, instance_box_volume, wall_box,
                    wall_box_volume, instance_classes, ground_h, thresh_spp_occu, device=dev)
     # (the keyword only when set: every other caller of _pipeline keeps sharing the default pipeline of its options)
-    extra = dict(point_level=True) if point_level else {}
+    mode = point_mode(point_level)
+    extra = dict(point_level=True if mode == "winner" else mode) if mode else {}
     pipe = _pipeline(dev, training_iter, init_mean_std=init_mean_std, seed=seed, eval_stale_chol=eval_stale_chol, **extra)
     sem, ins, prob, mu, var = pipe.run([job], keep_models=return_models)[0]
-    if broadcast_mu_var and not point_level:
+    if broadcast_mu_var and not mode:
         idx = job.spp_inv.long()
         mu, var = mu[idx], var[idx]
     outs = (sem, ins, prob, mu, var)
     if was_cpu:
         outs = tuple(o.cpu() for o in outs)
     if return_models:
-        outs = outs + (SceneModels(job.feats_spp, job.fits, job.winner),)
+        outs = outs + (SceneModels(job.feats_spp, job.fits, job.winner, job.point_fit),)
     return outs
 
 
 class SceneModels:
     """The trained GPs of one scene (gen_pseudo_label_gaussian_process(..., return_models=True))."""
 
-    def __init__(self, feats_spp, fits, winner=None):
+    def __init__(self, feats_spp, fits, winner=None, point_fit=None):
         self.feats_spp = feats_spp  # f32[S, D] pooled superpoint features
         self.fits = fits            # [(b1, b2, train ranks, test ranks, GPModel)] in schedule order
         self.winner = winner        # i32[S]: index into fits of the fit that labelled the superpoint, -1 elsewhere
+        self.point_fit = point_fit  # point_level="compete" only: i32[N] index into fits of the fit that labelled the point
 
 
 def gen_pseudo_label_gaussian_process_batch(scenes, training_iter=50, device=None, **pipe_kw):
@@ -106,8 +113,13 @@ def gen_pseudo_label_gaussian_process_batch(scenes, training_iter=50, device=Non
 
     ``scenes`` is a list of dicts holding the positional arguments of
     ``gen_pseudo_label_gaussian_process`` by name.  Returns a list of 5-tuples of device tensors.  ``pipe_kw`` are
-    Pipeline options; ``point_level=True`` returns the point-level labels (mu / var at point length).
+    Pipeline options; ``point_level=True`` (or "winner", "compete") returns the point-level labels (mu / var at point
+    length).
     """
+    if "point_level" in pipe_kw:  # True and "winner" share one pipeline
+        mode = point_mode(pipe_kw.pop("point_level"))
+        if mode:
+            pipe_kw["point_level"] = True if mode == "winner" else mode
     dev = torch.device(device if device is not None else "cuda:0")
     jobs = [make_job(s["coords_float"], s["mask_feats"], s["spp"], s["instance_cls"], s["instance_box"],
                      s["instance_box_volume"], s["wall_box"], s["wall_box_volume"],

@@ -373,6 +373,12 @@ int gapro_schedule_export_fits(const gapro_schedule* s, int32_t feats_row_base, 
  * fit id (fit), offsets[n_events+1] into h_event_idx (superpoint indices of the intersection). */
 int gapro_schedule_export_events(const gapro_schedule* s, uint8_t* h_kind, int32_t* h_b1, int32_t* h_b2,
                                  int32_t* h_aux, int64_t* h_offsets, int32_t* h_event_idx);
+/* The fit events that tested each superpoint, as a CSR over the superpoints: entries [h_offsets[sp], h_offsets[sp + 1])
+ * of h_fit / h_pos, in event order (the order in which the merge meets them).  h_fit is the fit's index in
+ * gapro_schedule_export_fits order, h_pos the superpoint's position inside that fit's intersection, i.e. its row in the
+ * fit's output slice.  h_offsets i64[n_spps + 1]; h_fit, h_pos i32[gapro_schedule_counts.n_fit_out] (may be NULL when
+ * that is 0).  Containment events are not listed. */
+int gapro_schedule_export_testers(const gapro_schedule* s, int64_t* h_offsets, int32_t* h_fit, int32_t* h_pos);
 
 /* Merge + fallback + label tables (gen_ps_utils.py:365-383, :411-423, :438-476).
  * Fit outputs are this schedule's slices (out_offset relative to 0): probs_new f32, labels u8,
@@ -550,14 +556,27 @@ int gapro_svgp_predict_batch(gapro_ctx* ctx, void* stream, int32_t n_models, int
  *   box = label ? b2 : b1;  sem[i] = boxes_cls[box];  inst[i] = box, or -100 when box >= n_fg_instances;
  *   prob[i] = p_new;  mu[i] = mu;  var[i] = var.
  * Every other point keeps the broadcast values, mu[i] = mu_spp[spp_inv[i]], var[i] = var_spp[spp_inv[i]]: all five
- * outputs are point-length.  The competition between several fits that tested one superpoint is NOT re-run per point:
- * the superpoint-level merge picks the model, and that model alone labels the points, between its own two boxes.
+ * outputs are point-length.  In this mode ("winner") the competition between several fits that tested one superpoint is
+ * not re-run per point: the superpoint-level merge picks the model, and that model alone labels the points, between its
+ * own two boxes.
+ *
+ * The "compete" mode re-runs it.  The refined set is the same (a superpoint with winner >= 0 is listed by no containment
+ * event: a containment write sets probability 1, which no p_new <= 1 passes under the strict `<`, and a later one resets
+ * the winner; so its history is fit events only and its probability starts at 0).  Every fit that TESTED the superpoint
+ * (gapro_schedule_export_testers, event order) is evaluated at every point of it, and the merge is replayed for the
+ * point alone: best = 0.0f; for k in order: if (best < p_new_k) take k   (strict, float32: the first maximum; a NaN never
+ * wins).  The point's five values come from the fit that took it, by the rule above.  Containment- and fallback-labelled
+ * superpoints are not refined in either mode, and the schedule stays static.
  *
  * The chain of a batch, on one stream: gapro_broadcast_labels_batch -> gapro_point_refine_gather -> ONE
  * gapro_svgp_predict_batch over the gathered rows (identity d_rows, out_offset == row_offset) -> gapro_point_refine_apply.
  * The launch's ROW TABLE holds the points of every refined superpoint of every scene: a superpoint's points form one
  * block of point_count[sp] rows, the blocks of one model's superpoints are contiguous, and the host plans the block
  * starts (sp_row) from the point counts gapro_partition_pool left.  Row indices are int32 (the predict ABI).
+ * The chain of "compete": gapro_broadcast_labels_batch -> gapro_point_refine_gather (blocks in (scene, superpoint)
+ * order) -> gapro_point_refine_expand -> ONE gapro_svgp_predict_batch over the gathered rows with the expanded d_rows
+ * (a row is listed once per tester of its superpoint: R rows become R2 >= R) -> gapro_point_refine_apply with
+ * n_models = 0 (the mu / var broadcast) -> gapro_point_refine_compete.
  * ---------------------------------------------------------------------------------------- */
 typedef struct {
   int64_t n_points;
@@ -610,6 +629,52 @@ int gapro_point_refine_apply(gapro_ctx* ctx, void* stream, int32_t n_scenes, con
                              int64_t n_rows, const int32_t* d_row_point, const float* d_probs_new,
                              const uint8_t* d_labels, const float* d_mu, const float* d_var,
                              const int32_t* d_model_status);
+
+/* "compete": one refined superpoint = one BLOCK of gathered rows, tested by n_seg fits; one (tester, block) pair = one
+ * SEGMENT of block.n_rows consecutive entries of the predict launch's d_rows and of its outputs. */
+typedef struct {
+  int64_t row_start;         /*  0  first gathered row of the block (sp_row of its superpoint) */
+  int32_t n_rows;            /*  8  its number of points, > 0 */
+  int32_t scene;             /* 12  index into the scenes of the call */
+  int32_t seg_start;         /* 16  its segments are [seg_start, seg_start + n_seg), in tester (event) order */
+  int32_t n_seg;             /* 20  >= 0 */
+} gapro_point_refine_block;  /* 24 bytes */
+
+typedef struct {
+  int64_t out_start;         /*  0  entry j of the segment is d_rows[out_start + j] and output row out_start + j */
+  int32_t model;             /*  8  index into the predict models of the launch */
+  int32_t reserved;          /* 12  0 */
+} gapro_point_refine_segment; /* 16 bytes */
+
+/* d_rows[seg.out_start + j] = block.row_start + j for every segment of every block and j < block.n_rows: the row list of
+ * the predict launch (d_rows i32[n_rows2]).  The segments of one model must be contiguous there for the model's
+ * row_offset / out_offset / t to describe them; that is the planner's business, the call only checks bounds.  h_blocks
+ * must be ascending in row_start and disjoint inside [0, n_rows); every segment must lie inside [0, n_rows2).  The host
+ * arrays are copied to d_blocks / d_segs on the stream and must stay valid until the stream has executed the copies.
+ * n_blocks == 0 or n_segs == 0: nothing is launched.  GAPRO_ERR_BAD_ARG: a null or negative argument, a block or
+ * segment out of bounds, n_rows or n_rows2 beyond 2^31 - 1 (refused before anything is launched).  Enqueue only. */
+int gapro_point_refine_expand(gapro_ctx* ctx, void* stream, int32_t n_blocks, const gapro_point_refine_block* h_blocks,
+                              gapro_point_refine_block* d_blocks, int32_t n_segs,
+                              const gapro_point_refine_segment* h_segs, gapro_point_refine_segment* d_segs,
+                              int64_t n_rows, int64_t n_rows2, int32_t* d_rows);
+/* The per-point merge.  For gathered row r = block.row_start + j of every block: best = 0.0f; the block's segments in
+ * order, those of a model with non-zero d_model_status (NULL = all 0) skipped: p = d_probs_new[seg.out_start + j];
+ * if (best < p) the segment takes the row.  The five values of point d_row_point[r] of the block's scene are then
+ * written from the taking segment's output row and its model's (sem, inst) pair, as gapro_point_refine_apply does; a row
+ * that no segment took, or whose point index lies outside its scene, is skipped (its point keeps what it holds: run
+ * gapro_point_refine_apply with n_models = 0 before, on the same stream).  d_row_model i32[n_rows] (NULL = not wanted)
+ * receives the model that took row r, -1 for a skipped row.  Of a gapro_point_refine_model only scene and the two pairs
+ * are read.  Block and segment rules, copies and refusals as for gapro_point_refine_expand; every row is written by
+ * exactly one lane (no atomics).  n_blocks == 0 or n_scenes == 0 is a no-op.  Enqueue only. */
+int gapro_point_refine_compete(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro_point_refine_scene* h_scenes,
+                               gapro_point_refine_scene* d_scenes, int32_t n_models,
+                               const gapro_point_refine_model* h_models, gapro_point_refine_model* d_models,
+                               int32_t n_blocks, const gapro_point_refine_block* h_blocks,
+                               gapro_point_refine_block* d_blocks, int32_t n_segs,
+                               const gapro_point_refine_segment* h_segs, gapro_point_refine_segment* d_segs,
+                               int64_t n_rows, int64_t n_rows2, const int32_t* d_row_point, const float* d_probs_new,
+                               const uint8_t* d_labels, const float* d_mu, const float* d_var,
+                               const int32_t* d_model_status, int32_t* d_row_model);
 
 /* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem

@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
 """Point-level label benchmark (run on the GPU box): one synth.make_scene scene of --points points (the scene of
-tools/bench_fit_gp.py) through Pipeline(point_level=True).
+tools/bench_fit_gp.py) through Pipeline(point_level=True) (--mode winner) or Pipeline(point_level="compete").
 
-python tools/bench_point_refine.py [--points 150000] [--seed 0] [--reps 3]
+python tools/bench_point_refine.py [--points 150000] [--seed 0] [--reps 3] [--mode winner|compete]
 
 Reports the point-level stages behind the label broadcast -- gather (row table of the refined superpoints' points),
-predict (one gapro_svgp_predict_batch over it, which synchronises the stream once) and apply -- as spans between HIP
+predict (one gapro_svgp_predict_batch over it, which synchronises the stream once) and apply; with --mode compete also
+expand (the row list: a gathered row once per fit that tested its superpoint, R rows -> R2 entries) in front of the
+predict and compete (the per-point merge) behind the apply, which is then the mu / var broadcast alone -- as spans between HIP
 events recorded on the stream at the stage boundaries (a span contains the host's work between the launches of the
 stage, it is not a kernel time), and the host's wall clock for the plan: the median over --reps runs after one warm-up
-run, inputs resident on the device.  Also: refined superpoints, rows and predict models, how many refined points end
-with another instance than their superpoint's, and the scene's mean instance IoU (get_miou_scene) with and without the
-refinement.  One JSON line at the end.
+run, inputs resident on the device.  Also: refined superpoints, rows R, expanded rows R2 and predict models, how many
+refined points end with another instance than their superpoint's, how many points end with another instance in the two
+modes (the other mode is run once for that), and the scene's mean instance IoU (get_miou_scene) without the refinement and
+in both modes.  One JSON line at the end.
 """
 import argparse
 import json
@@ -28,7 +31,7 @@ from gapro_amd.gen_ps_utils import _pipeline, getInstanceInfo  # noqa: E402
 from gapro_amd.pipeline import make_job  # noqa: E402
 from gapro_amd.synth import make_scene  # noqa: E402
 
-STAGES = ("gather", "predict", "apply")
+STAGES = {"winner": ("gather", "predict", "apply"), "compete": ("gather", "expand", "predict", "apply", "compete")}
 
 
 def main():
@@ -36,7 +39,9 @@ def main():
     ap.add_argument("--points", type=int, default=150000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--mode", choices=("winner", "compete"), default="winner")
     args = ap.parse_args()
+    stages = STAGES[args.mode]
     if not torch.cuda.is_available():
         raise SystemExit("bench_point_refine.py needs the GPU: there is nothing to time without it")
     dev = torch.device("cuda", 0)
@@ -52,8 +57,9 @@ def main():
     plain_pipe = _pipeline(dev, 50)
     plain_job = make_job(*dev_in, *rest, **opts)
     plain = plain_pipe.run([plain_job])[0]
-    pipe = _pipeline(dev, 50, point_level=True)
-    times = {s: [] for s in STAGES}
+    modes = {"winner": True, "compete": "compete"}
+    pipe = _pipeline(dev, 50, point_level=modes[args.mode])
+    times = {s: [] for s in stages}
     plan, total = [], []
     out = None
     for rep in range(args.reps + 1):  # the first run warms every kernel and buffer up
@@ -68,7 +74,7 @@ def main():
         pipe.stage_events = None
         if rep:
             prev = ev["broadcast"]
-            for s in STAGES:
+            for s in stages:
                 times[s].append(prev.elapsed_time(ev[s]))
                 prev = ev[s]
             plan.append(1e3 * pipe.last_refine["plan_s"])
@@ -86,20 +92,28 @@ def main():
     ins_gt = torch.from_numpy(np.asarray(sc.inst)).to(dev).int()
     sem_gt[sem_gt != -100] -= 2  # reference gen_ps.py:119-120
     sem_gt[(sem_gt == -1) | (sem_gt == -2)] = 18
+    other_mode = "compete" if args.mode == "winner" else "winner"
+    other = _pipeline(dev, 50, point_level=modes[other_mode]).run([make_job(*dev_in, *rest, **opts)])[0]
+    by_mode = {args.mode: out, other_mode: other}
     miou = [float(get_miou_scene(sem_gt.long(), ins_gt.long(), o[0].long(), o[1].long()).float().mean())
-            for o in (plain, out)]
-    res = dict(points=args.points, seed=args.seed, reps=args.reps, refined_spps=pipe.last_refine["refined_spps"],
-               refined_points=int(refined.sum()), rows=pipe.last_refine["rows"], models=pipe.last_refine["models"],
-               changed_instance=changed, miou_spp_level=round(miou[0], 6), miou_point_level=round(miou[1], 6),
+            for o in (plain, by_mode["winner"], by_mode["compete"])]
+    res = dict(mode=args.mode, points=args.points, seed=args.seed, reps=args.reps,
+               refined_spps=pipe.last_refine["refined_spps"], refined_points=int(refined.sum()),
+               rows=pipe.last_refine["rows"], expanded_rows=pipe.last_refine["expanded_rows"],
+               multi_spps=pipe.last_refine.get("multi_spps"), models=pipe.last_refine["models"],
+               changed_instance=changed, differs_between_modes=int((out[1] != other[1]).sum()),
+               miou_spp_level=round(miou[0], 6), miou_point_level=round(miou[1 if args.mode == "winner" else 2], 6),
+               miou_winner=round(miou[1], 6), miou_compete=round(miou[2], 6),
                plan_host_ms=round(float(np.median(plan)), 3), run_ms=round(float(np.median(total)), 3),
                run_ms_plain_once=round(plain_ms, 3))
-    for s in STAGES:
+    for s in stages:
         res[s + "_ms"] = round(float(np.median(times[s])), 3)
         res[s + "_ms_min_max"] = [round(float(min(times[s])), 3), round(float(max(times[s])), 3)]
-    print("%(points)d points: %(refined_spps)d refined superpoints, %(rows)d rows, %(models)d models; "
-          "%(changed_instance)d refined points end with another instance; mean instance IoU %(miou_spp_level).4f -> "
-          "%(miou_point_level).4f" % res)
-    for s in STAGES:
+    print("%(mode)s, %(points)d points: %(refined_spps)d refined superpoints, %(rows)d rows -> %(expanded_rows)d, "
+          "%(models)d models; %(changed_instance)d refined points end with another instance, %(differs_between_modes)d "
+          "points differ between the modes; mean instance IoU %(miou_spp_level).4f -> %(miou_winner).4f (winner) / "
+          "%(miou_compete).4f (compete)" % res)
+    for s in stages:
         print("  %-8s %8.3f ms  (min %.3f, max %.3f over %d runs)" % ((s, res[s + "_ms"]) + tuple(res[s + "_ms_min_max"])
                                                                      + (args.reps,)))
     print("  plan     %8.3f ms  (host wall clock)" % res["plan_host_ms"])
