@@ -78,6 +78,12 @@ class PointRefineSegment(C.Structure):
     _fields_ = [("out_start", C.c_int64), ("model", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PointRefineVoteScene(C.Structure):
+    """gapro_point_refine_vote_scene: the superpoint-level label tables of one scene (point_level="vote")."""
+    _fields_ = [("sem_spp", C.c_void_p), ("inst_spp", C.c_void_p), ("prob_spp", C.c_void_p), ("mu_spp", C.c_void_p),
+                ("var_spp", C.c_void_p), ("n_spps", C.c_int32), ("reserved", C.c_int32)]
+
+
 class TrainsetDesc(C.Structure):
     """gapro_trainset_desc: one point-level problem of gapro_trainset_count / gapro_trainset_fill."""
     _fields_ = [("idx_offset", C.c_int64), ("n1", C.c_int32), ("n2", C.c_int32), ("t", C.c_int32), ("m1", C.c_int32),
@@ -214,6 +220,11 @@ SIGNATURES = {
     "gapro_point_refine_expand": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int64, _P]),
     "gapro_point_refine_compete": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32,
                                              _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    "gapro_point_refine_vote": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P,
+                                          C.c_int32, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "gapro_spp_vote_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gapro_spp_vote": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P,
+                                 C.c_size_t, _P, _P, _P]),
     "gapro_trainset_workspace_bytes": (C.c_size_t, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32]),
     "gapro_trainset_count": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_size_t,
                                        _P, _P]),
@@ -358,7 +369,7 @@ def load() -> C.CDLL:
             variant = os.path.abspath(LIB_PATH) != os.path.abspath(default)
             if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state",
                                             "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex",
-                                            "gapro_schedule_export_testers")):
+                                            "gapro_schedule_export_testers", "gapro_spp_vote")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

@@ -154,6 +154,34 @@ __global__ __launch_bounds__(kThreads) void k_refine_expand(const gapro_point_re
   }
 }
 
+// The merge replayed for gathered row j of a block ("compete" and "vote"): best = 0.0f (the merge's start for a superpoint
+// in several boxes, gen_ps_utils.py:367); the block's segments in tester order, those of a model with non-zero status
+// skipped (its rows may hold nothing); strict float32 <: the first maximum, a NaN never wins.  Returns the position of
+// the taking segment inside the block (-1: none took the row), its output row in *at and its probability in *best.
+__device__ __forceinline__ int take_row(const gapro_point_refine_block& blk, long long j,
+                                        const gapro_point_refine_segment* __restrict__ segs, long long n_rows2,
+                                        const float* __restrict__ probs_new, const int* __restrict__ status,
+                                        float* best_out, long long* at_out) {
+  float best = 0.0f;
+  int took = -1;
+  long long at = -1;
+  for (int s = 0; s < blk.n_seg; ++s) {
+    const gapro_point_refine_segment sg = segs[blk.seg_start + s];
+    if (status && status[sg.model] != 0) continue;
+    const long long o = sg.out_start + j;
+    if (o < 0 || o >= n_rows2) continue;
+    const float p = probs_new[o];
+    if (best < p) {
+      best = p;
+      took = s;
+      at = o;
+    }
+  }
+  *best_out = best;
+  *at_out = at;
+  return took;
+}
+
 __global__ __launch_bounds__(kThreads) void k_refine_compete(
     const gapro_point_refine_scene* __restrict__ scenes, const gapro_point_refine_model* __restrict__ models,
     const gapro_point_refine_block* __restrict__ blocks, int n_blocks,
@@ -165,25 +193,14 @@ __global__ __launch_bounds__(kThreads) void k_refine_compete(
   for (long long r = (long long)blockIdx.x * kThreads + threadIdx.x; r < n_rows; r += stride) {
     const int b = block_of_row(blocks, n_blocks, r);
     int took = -1;
-    long long at = -1;
     long long i = -1;
     if (b >= 0) {
       const gapro_point_refine_block blk = blocks[b];
-      const long long j = r - blk.row_start;
-      float best = 0.0f;  // the merge's start for a superpoint in several boxes (gen_ps_utils.py:367)
-      for (int s = 0; s < blk.n_seg; ++s) {
-        const gapro_point_refine_segment sg = segs[blk.seg_start + s];
-        if (status && status[sg.model] != 0) continue;  // its rows may hold nothing
-        const long long o = sg.out_start + j;
-        if (o < 0 || o >= n_rows2) continue;
-        const float p = probs_new[o];
-        if (best < p) {  // strict, float32: the first maximum; a NaN never wins
-          best = p;
-          took = sg.model;
-          at = o;
-        }
-      }
-      if (took >= 0) {
+      float best;
+      long long at;
+      const int s = take_row(blk, r - blk.row_start, segs, n_rows2, probs_new, status, &best, &at);
+      if (s >= 0) {
+        took = segs[blk.seg_start + s].model;
         const gapro_point_refine_scene& t = scenes[blk.scene];
         i = row_point[r];
         if (i < 0 || i >= t.n_points) {
@@ -200,6 +217,163 @@ __global__ __launch_bounds__(kThreads) void k_refine_compete(
       }
     }
     if (row_model) row_model[r] = took;
+  }
+}
+
+// "vote": one workgroup per block (= refined superpoint), its rows dealt to the lanes in strides.  A CANDIDATE is a
+// (segment, label) pair, 2 n_seg per block: s_cnt[2 s + label] counts the rows that segment s took with that label and
+// s_box holds the box it argues for.  Integer LDS atomics only; the three sums are int64 fixed point, so neither the
+// gather order nor the order of the lanes reaches a result bit.
+constexpr int kVoteMaxSeg = 2048;  // 2 * 2 * kVoteMaxSeg ints of dynamic LDS = 32 KiB at most
+
+__device__ __forceinline__ int vote_shift(unsigned absmax_bits, int n) {  // oracle/gen_ps_oracle.py:fixed_point_shift
+  const float a = __uint_as_float(absmax_bits);
+  int k = 0;
+  if (a > 0.f && isfinite(a)) {
+    int e; (void)frexpf(a, &e);
+    const int lg = n > 1 ? 32 - __clz((unsigned)(n - 1)) : 0;
+    k = 61 - e - lg;
+    k = k < -1000 ? -1000 : (k > 1000 ? 1000 : k);
+  }
+  return k;
+}
+
+// wave-level reductions in front of the LDS atomics: one atomic per wave and quantity instead of one per lane
+__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
+  for (int o = 32; o > 0; o >>= 1) { const unsigned w = (unsigned)__shfl_xor((int)v, o); v = w > v ? w : v; }
+  return v;
+}
+__device__ __forceinline__ long long wave_sum_ll(long long v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(unsigned long long)v, o);
+    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)((unsigned long long)v >> 32), o);
+    v = (long long)((unsigned long long)v + (((unsigned long long)hi << 32) | lo));  // wraps like the atomic would
+  }
+  return v;
+}
+__device__ __forceinline__ int wave_or_i(int v) {
+  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
+  return v;
+}
+
+__device__ __forceinline__ float vote_mean(long long sum, int k, int count, bool poisoned) {
+  if (poisoned) return __uint_as_float(0x7fc00000u);
+  return (float)(ldexp((double)sum, -k) / (double)count);
+}
+
+__global__ __launch_bounds__(kThreads) void k_refine_vote(
+    const gapro_point_refine_vote_scene* __restrict__ scenes, const gapro_point_refine_model* __restrict__ models,
+    const int* __restrict__ model_boxes, const gapro_point_refine_block* __restrict__ blocks, int n_blocks,
+    const int* __restrict__ block_spp, const gapro_point_refine_segment* __restrict__ segs, int max_seg,
+    long long n_rows2, const float* __restrict__ probs_new, const unsigned char* __restrict__ labels,
+    const float* __restrict__ mu_r, const float* __restrict__ var_r, const int* __restrict__ status,
+    int* __restrict__ block_out) {
+  extern __shared__ int s_dyn[];
+  int* s_cnt = s_dyn;
+  int* s_box = s_dyn + 2 * max_seg;
+  __shared__ unsigned s_amax[3];             // bits of the largest finite |p_new|, |mu|, |var| among the voting rows
+  __shared__ unsigned long long s_key[2];    // (votes, ~box) of the winner box; (voters, ~segment) of its representative
+  __shared__ unsigned long long s_sum[3];
+  __shared__ int s_poison;
+  const int tid = threadIdx.x;
+  for (int b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+    const gapro_point_refine_block blk = blocks[b];
+    const int nc = 2 * blk.n_seg;
+    for (int c = tid; c < nc; c += kThreads) {
+      s_cnt[c] = 0;
+      s_box[c] = model_boxes[2 * segs[blk.seg_start + (c >> 1)].model + (c & 1)];
+    }
+    if (tid < 3) { s_amax[tid] = 0u; s_sum[tid] = 0ull; }
+    if (tid < 2) s_key[tid] = 0ull;
+    if (tid == 0) s_poison = 0;
+    __syncthreads();
+    // 1. take: every row votes for the box of the segment that took it
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int j = tid; j < blk.n_rows; j += kThreads) {
+      float best;
+      long long at;
+      const int s = take_row(blk, j, segs, n_rows2, probs_new, status, &best, &at);
+      if (s < 0) continue;
+      atomicAdd(&s_cnt[2 * s + (labels[at] != 0 ? 1 : 0)], 1);
+      const float m = mu_r[at], v = var_r[at];
+      if (isfinite(best)) a0 = fmaxf(a0, best);
+      if (isfinite(m)) a1 = fmaxf(a1, fabsf(m));
+      if (isfinite(v)) a2 = fmaxf(a2, fabsf(v));
+    }
+    {  // every lane is here (the row loop has ended): non-negative floats order like their bits
+      const unsigned m0 = wave_max_u(__float_as_uint(a0)), m1 = wave_max_u(__float_as_uint(a1)),
+                     m2 = wave_max_u(__float_as_uint(a2));
+      if ((tid & 63) == 0) {
+        if (m0) atomicMax(&s_amax[0], m0);
+        if (m1) atomicMax(&s_amax[1], m1);
+        if (m2) atomicMax(&s_amax[2], m2);
+      }
+    }
+    __syncthreads();
+    // 2. the box with the most votes, the lowest index among equals
+    for (int c = tid; c < nc; c += kThreads) {
+      if (s_cnt[c] == 0) continue;
+      const int box = s_box[c];
+      unsigned votes = 0;
+      for (int e = 0; e < nc; ++e) votes += s_box[e] == box ? (unsigned)s_cnt[e] : 0u;
+      atomicMax(&s_key[0], ((unsigned long long)votes << 32) | (0xffffffffu - (unsigned)box));
+    }
+    __syncthreads();
+    const unsigned long long key_x = s_key[0];
+    if (key_x == 0ull) {  // 5. nobody voted: the merge's values stay (uniform over the workgroup)
+      if (tid == 0 && block_out) { block_out[3 * b] = -1; block_out[3 * b + 1] = -1; block_out[3 * b + 2] = 0; }
+      __syncthreads();
+      continue;
+    }
+    const int X = (int)(0xffffffffu - (unsigned)(key_x & 0xffffffffull));
+    // 3. the fit that took the most voters for X, the earliest tester among equals
+    for (int c = tid; c < nc; c += kThreads)
+      if (s_cnt[c] > 0 && s_box[c] == X)
+        atomicMax(&s_key[1], ((unsigned long long)(unsigned)s_cnt[c] << 32) | (0xffffffffu - (unsigned)(c >> 1)));
+    __syncthreads();
+    const unsigned long long key_f = s_key[1];
+    const int sf = (int)(0xffffffffu - (unsigned)(key_f & 0xffffffffull));
+    const int nf = (int)(key_f >> 32);
+    const int k0 = vote_shift(s_amax[0], blk.n_rows), k1 = vote_shift(s_amax[1], blk.n_rows),
+              k2 = vote_shift(s_amax[2], blk.n_rows);
+    // 4. exact sums: p_new over every voter for X, mu and var over those the representative took.  take_row runs a
+    // second time per row (n_seg reads) instead of keeping every row's verdict: a block has no bound on its rows
+    long long q0 = 0, q1 = 0, q2 = 0;
+    int poison = 0;
+    for (int j = tid; j < blk.n_rows; j += kThreads) {
+      float best;
+      long long at;
+      const int s = take_row(blk, j, segs, n_rows2, probs_new, status, &best, &at);
+      if (s < 0 || s_box[2 * s + (labels[at] != 0 ? 1 : 0)] != X) continue;
+      if (isfinite(best)) q0 += (long long)rint(ldexp((double)best, k0)); else poison |= 1;
+      if (s != sf) continue;
+      const float m = mu_r[at], v = var_r[at];
+      if (isfinite(m)) q1 += (long long)rint(ldexp((double)m, k1)); else poison |= 2;
+      if (isfinite(v)) q2 += (long long)rint(ldexp((double)v, k2)); else poison |= 4;
+    }
+    q0 = wave_sum_ll(q0); q1 = wave_sum_ll(q1); q2 = wave_sum_ll(q2);
+    poison = wave_or_i(poison);
+    if ((tid & 63) == 0) {
+      if (q0) atomicAdd(&s_sum[0], (unsigned long long)q0);
+      if (q1) atomicAdd(&s_sum[1], (unsigned long long)q1);
+      if (q2) atomicAdd(&s_sum[2], (unsigned long long)q2);
+      if (poison) atomicOr(&s_poison, poison);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const gapro_point_refine_vote_scene& t = scenes[blk.scene];
+      const int sp = block_spp[b];
+      const int model = segs[blk.seg_start + sf].model;
+      const gapro_point_refine_model m = models[model];
+      const bool second = s_box[2 * sf] != X;
+      t.sem_spp[sp] = second ? m.sem2 : m.sem1;
+      t.inst_spp[sp] = second ? m.inst2 : m.inst1;
+      t.prob_spp[sp] = vote_mean((long long)s_sum[0], k0, blk.n_rows, s_poison & 1);
+      t.mu_spp[sp] = vote_mean((long long)s_sum[1], k1, nf, s_poison & 2);
+      t.var_spp[sp] = vote_mean((long long)s_sum[2], k2, nf, s_poison & 4);
+      if (block_out) { block_out[3 * b] = model; block_out[3 * b + 1] = X; block_out[3 * b + 2] = (int)(key_x >> 32); }
+    }
+    __syncthreads();
   }
 }
 
@@ -381,6 +555,74 @@ int gapro_point_refine_compete(gapro_ctx* ctx, void* stream_, int32_t n_scenes, 
   hipLaunchKernelGGL(k_refine_compete, dim3(grid_for(n_rows, 2048)), dim3(kThreads), 0, stream, d_scenes, d_models,
                      d_blocks, (int)n_blocks, d_segs, (long long)n_rows, (long long)n_rows2, d_row_point, d_probs_new,
                      d_labels, d_mu, d_var, d_model_status, d_row_model);
+  GAPRO_LAUNCH_CHECK(ctx);
+  return GAPRO_OK;
+}
+
+int gapro_point_refine_vote(gapro_ctx* ctx, void* stream_, int32_t n_scenes,
+                            const gapro_point_refine_vote_scene* h_scenes, gapro_point_refine_vote_scene* d_scenes,
+                            int32_t n_models, const gapro_point_refine_model* h_models,
+                            gapro_point_refine_model* d_models, const int32_t* h_model_boxes, int32_t* d_model_boxes,
+                            int32_t n_blocks, const gapro_point_refine_block* h_blocks,
+                            gapro_point_refine_block* d_blocks, const int32_t* h_block_spp, int32_t* d_block_spp,
+                            int32_t n_segs, const gapro_point_refine_segment* h_segs,
+                            gapro_point_refine_segment* d_segs, int64_t n_rows, int64_t n_rows2,
+                            const float* d_probs_new, const uint8_t* d_labels, const float* d_mu, const float* d_var,
+                            const int32_t* d_model_status, int32_t* d_block_out) {
+  if (!ctx) return GAPRO_ERR_BAD_ARG;
+  if (n_scenes < 0 || n_models < 0 || n_blocks < 0 || n_segs < 0 || n_rows < 0 || n_rows > kMaxRows || n_rows2 < 0 ||
+      n_rows2 > kMaxRows)
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG,
+                      "gapro_point_refine_vote: bad argument (%d scenes, %d models, %d blocks, %d segments, "
+                      "%lld -> %lld rows)",
+                      (int)n_scenes, (int)n_models, (int)n_blocks, (int)n_segs, (long long)n_rows, (long long)n_rows2);
+  if (n_scenes == 0 || n_blocks == 0) return GAPRO_OK;
+  if (!h_scenes || !d_scenes || !h_blocks || !d_blocks || !h_block_spp || !d_block_spp)
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_vote: null argument");
+  if (n_segs > 0 && (!h_segs || !d_segs || !h_models || !d_models || !h_model_boxes || !d_model_boxes ||
+                     n_models == 0 || !d_probs_new || !d_labels || !d_mu || !d_var))
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_vote: null argument");
+  for (int i = 0; i < n_scenes; ++i) {
+    const gapro_point_refine_vote_scene& t = h_scenes[i];
+    if (t.n_spps <= 0 || !t.sem_spp || !t.inst_spp || !t.prob_spp || !t.mu_spp || !t.var_spp)
+      return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_vote: scene %d: bad argument", i);
+  }
+  for (int k = 0; k < n_models; ++k)
+    if (h_models[k].scene < 0 || h_models[k].scene >= n_scenes || h_model_boxes[2 * k] < 0 ||
+        h_model_boxes[2 * k + 1] < 0)
+      return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_vote: model %d: scene %d, boxes %d, %d", k,
+                        (int)h_models[k].scene, (int)h_model_boxes[2 * k], (int)h_model_boxes[2 * k + 1]);
+  if (const char* why = check_blocks(n_blocks, h_blocks, n_segs, h_segs, n_rows, n_rows2, n_scenes, n_models))
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_vote: %s", why);
+  int max_seg = 1;
+  for (int b = 0; b < n_blocks; ++b) {
+    if (h_block_spp[b] < 0 || h_block_spp[b] >= h_scenes[h_blocks[b].scene].n_spps)
+      return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_vote: block %d: superpoint %d of scene %d", b,
+                        (int)h_block_spp[b], (int)h_blocks[b].scene);
+    max_seg = std::max(max_seg, (int)h_blocks[b].n_seg);
+  }
+  if (max_seg > kVoteMaxSeg)
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_vote: a block of %d segments, %d at most", max_seg,
+                      kVoteMaxSeg);
+  hipStream_t stream = (hipStream_t)stream_;
+  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_scenes, h_scenes, (size_t)n_scenes * sizeof(gapro_point_refine_vote_scene),
+                                      hipMemcpyHostToDevice, stream));
+  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_blocks, h_blocks, (size_t)n_blocks * sizeof(gapro_point_refine_block),
+                                      hipMemcpyHostToDevice, stream));
+  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_block_spp, h_block_spp, (size_t)n_blocks * sizeof(int32_t),
+                                      hipMemcpyHostToDevice, stream));
+  if (n_segs > 0) {
+    GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_models, h_models, (size_t)n_models * sizeof(gapro_point_refine_model),
+                                        hipMemcpyHostToDevice, stream));
+    GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_model_boxes, h_model_boxes, (size_t)n_models * 2 * sizeof(int32_t),
+                                        hipMemcpyHostToDevice, stream));
+    GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_segs, h_segs, (size_t)n_segs * sizeof(gapro_point_refine_segment),
+                                        hipMemcpyHostToDevice, stream));
+  }
+  const size_t lds = (size_t)4 * max_seg * sizeof(int);
+  hipLaunchKernelGGL(k_refine_vote, dim3((unsigned)std::min(n_blocks, 1 << 18)), dim3(kThreads), lds, stream, d_scenes,
+                     d_models, d_model_boxes, d_blocks, (int)n_blocks, d_block_spp, d_segs, max_seg,
+                     (long long)n_rows2, d_probs_new, d_labels, d_mu, d_var, d_model_status, d_block_out);
   GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;
 }

@@ -33,6 +33,10 @@ resume mechanism, gen_ps.py:39-41) and every scene is written as the same 5-tupl
     --point_compete        --point_level with the fit competition re-run per point (Pipeline(point_level="compete")):
                            every fit that tested the superpoint is evaluated at every point of it and the point goes to
                            the first fit with the largest probability.  Implies --point_level; same files, same backend
+    --point_vote           the points predicted and competing as with --point_compete, then every superpoint takes the box
+                           most of its points chose (Pipeline(point_level="vote")): the files keep the default shapes
+                           (mu / var at superpoint length, or point length with --broadcast_mu_var).  Not together with
+                           --point_level / --point_compete; same backend
     --loader_threads T     threads of the library's batch feeder (csrc/feeder.hip) that read scenes from disk two
                            batches ahead, preprocess and upload them, and write the label files (default -1 =
                            min(16, usable CPUs / W - 1) per worker for W workers, at least 2; "usable" honours the
@@ -317,7 +321,9 @@ class Worker:
             # (with --point_level mu / var already are point-length: --broadcast_mu_var has nothing left to do)
             compete = bool(getattr(args, "point_compete", False))
             point_level = "compete" if compete else bool(getattr(args, "point_level", False))
-            self.broadcast = bool(args.broadcast_mu_var) and not point_level
+            if getattr(args, "point_vote", False):
+                point_level = "vote"  # the default path's lengths: --broadcast_mu_var still has its work to do
+            self.broadcast = bool(args.broadcast_mu_var) and point_level in (False, "vote")
             needs_torch = bool(args.eval_pslabel or self.broadcast or os.environ.get("GAPRO_DRIVER_HOST_ONLY"))
             self.backend = "torch" if (needs_torch or want == "torch") else "native"
             if self.backend == "torch":
@@ -773,6 +779,7 @@ def main(argv=None):
     parser.add_argument("--broadcast_mu_var", action="store_true")
     parser.add_argument("--point_level", action="store_true")
     parser.add_argument("--point_compete", action="store_true")
+    parser.add_argument("--point_vote", action="store_true")
     parser.add_argument("--raw_cache", type=str, default=None, help=argparse.SUPPRESS)  # ignored since round 5
     parser.add_argument("--loader_threads", type=int, default=-1)
     parser.add_argument("--loader_procs", type=int, default=-1, help=argparse.SUPPRESS)  # ignored since round 5
@@ -782,6 +789,8 @@ def main(argv=None):
     parser.add_argument("--job_dir", type=str, default=None, help=argparse.SUPPRESS)
     parser.add_argument("--dry_run", action="store_true", help=argparse.SUPPRESS)
     args = parser.parse_args(argv)
+    if args.point_vote and (args.point_level or args.point_compete):
+        parser.error("--point_vote cannot be combined with --point_level or --point_compete")
     if args.point_compete:
         args.point_level = True
 

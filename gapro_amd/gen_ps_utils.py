@@ -74,6 +74,12 @@ def gen_pseudo_label_gaussian_process(
                       the superpoint's winner's two; with ``return_models`` the models object then has ``point_fit``
                       i32[N], the index into ``fits`` of the fit that labelled each point, -1 elsewhere.  Superpoints
                       labelled by a containment verdict or the fallback are not refined in either mode.
+                      "vote": the points are predicted and compete as in "compete", then the superpoint takes the box
+                      most of its points chose (the lowest box index among equals); prob = mean confidence of that box's
+                      voters x their share of the superpoint, mu / var = the means over the voters of the box's
+                      representative fit.  The outputs keep the default lengths (mu / var f32[S]; ``broadcast_mu_var``
+                      applies); with ``return_models``, ``winner`` is the representative fit and ``vote_box`` /
+                      ``vote_count`` i32[S] say what won and by how many points.
     init_mean_std     std of the random initial variational mean (gpytorch uses 1e-3 with an unseeded
                       RNG; 0 = deterministic zeros), ``seed`` seeds it.
     eval_stale_chol   predict with the Cholesky factor of the last training step.
@@ -87,25 +93,29 @@ def gen_pseudo_label_gaussian_process(
     extra = dict(point_level=True if mode == "winner" else mode) if mode else {}
     pipe = _pipeline(dev, training_iter, init_mean_std=init_mean_std, seed=seed, eval_stale_chol=eval_stale_chol, **extra)
     sem, ins, prob, mu, var = pipe.run([job], keep_models=return_models)[0]
-    if broadcast_mu_var and not mode:
+    if broadcast_mu_var and mode in (None, "vote"):  # "vote" keeps the default path's lengths
         idx = job.spp_inv.long()
         mu, var = mu[idx], var[idx]
     outs = (sem, ins, prob, mu, var)
     if was_cpu:
         outs = tuple(o.cpu() for o in outs)
     if return_models:
-        outs = outs + (SceneModels(job.feats_spp, job.fits, job.winner, job.point_fit),)
+        outs = outs + (SceneModels(job.feats_spp, job.fits, job.winner, job.point_fit, job.vote_box, job.vote_count),)
     return outs
 
 
 class SceneModels:
     """The trained GPs of one scene (gen_pseudo_label_gaussian_process(..., return_models=True))."""
 
-    def __init__(self, feats_spp, fits, winner=None, point_fit=None):
+    def __init__(self, feats_spp, fits, winner=None, point_fit=None, vote_box=None, vote_count=None):
         self.feats_spp = feats_spp  # f32[S, D] pooled superpoint features
         self.fits = fits            # [(b1, b2, train ranks, test ranks, GPModel)] in schedule order
         self.winner = winner        # i32[S]: index into fits of the fit that labelled the superpoint, -1 elsewhere
         self.point_fit = point_fit  # point_level="compete" only: i32[N] index into fits of the fit that labelled the point
+        # point_level="vote" only: i32[S] the box the superpoint's points voted for and its votes (-1 / 0 where the
+        # superpoint was not refined or nobody voted); winner then is the representative fit of that box
+        self.vote_box = vote_box
+        self.vote_count = vote_count
 
 
 def gen_pseudo_label_gaussian_process_batch(scenes, training_iter=50, device=None, **pipe_kw):
@@ -114,7 +124,7 @@ def gen_pseudo_label_gaussian_process_batch(scenes, training_iter=50, device=Non
     ``scenes`` is a list of dicts holding the positional arguments of
     ``gen_pseudo_label_gaussian_process`` by name.  Returns a list of 5-tuples of device tensors.  ``pipe_kw`` are
     Pipeline options; ``point_level=True`` (or "winner", "compete") returns the point-level labels (mu / var at point
-    length).
+    length), ``point_level="vote"`` the superpoint vote of them (default lengths).
     """
     if "point_level" in pipe_kw:  # True and "winner" share one pipeline
         mode = point_mode(pipe_kw.pop("point_level"))
@@ -126,6 +136,92 @@ def gen_pseudo_label_gaussian_process_batch(scenes, training_iter=50, device=Non
                      s.get("instance_classes", 18), s.get("ground_h", 0.1), s.get("thresh_spp_occu", 0.8),
                      device=dev) for s in scenes]
     return _pipeline(dev, training_iter, **pipe_kw).run(jobs)
+
+
+def _spp_vote(mode, spp, label, n_classes, gate, prob_label):
+    """gapro_spp_vote behind spp_align_label / spp_major_voting: inputs as arrays or tensors, as in gen_pseudo_label."""
+    import ctypes as C
+
+    from ._lib import Context, GaproError
+
+    if not torch.cuda.is_available():
+        raise RuntimeError("the superpoint vote runs on a HIP device; there is no CPU fallback")
+    device = next((x.device for x in (spp, label, prob_label, gate) if isinstance(x, torch.Tensor) and x.is_cuda),
+                  torch.device("cuda", torch.cuda.current_device()))
+
+    def dev(a, dtype=None):
+        a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        return a.to(device=device, dtype=dtype).contiguous()
+
+    spp_d = dev(spp, torch.int64).view(-1)
+    n = int(spp_d.shape[0])
+    label_d = dev(label).view(-1)
+    if label_d.dtype not in (torch.int32, torch.int64):
+        if label_d.dtype.is_floating_point or label_d.dtype == torch.bool:
+            raise ValueError("spp vote: label must be an integer array, not %s" % label_d.dtype)
+        label_d = label_d.to(torch.int64)
+    if n == 0 or int(label_d.shape[0]) != n:
+        raise ValueError("spp vote: %d superpoint ids, %d labels" % (n, int(label_d.shape[0])))
+    prob_d = None
+    if prob_label is not None:
+        prob_d = dev(prob_label, torch.float32).view(-1)
+        if int(prob_d.shape[0]) != n:
+            raise ValueError("spp vote: %d points, %d probabilities" % (n, int(prob_d.shape[0])))
+    if n_classes == -1:
+        n_classes = int(label_d.max()) + 1
+    n_classes = int(n_classes)
+    if n_classes < 1:
+        raise ValueError("spp vote: n_classes = %d" % n_classes)
+    ctx = Context.get(device.index or 0)
+    lib = ctx.lib
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        # torch.unique(spp, return_inverse=True) as at :107 / :139: the inverse of the sorted unique ids IS the dense rank
+        # in ascending id order, for ids of any range.  (The partition's rank kernels keep a flag table over the id
+        # range and refuse ranges beyond it, GAPRO_ERR_SPP_RANGE; ranking is index plumbing, the vote is gapro_spp_vote.)
+        uniq, ids = torch.unique(spp_d, return_inverse=True)
+        ids = ids.to(torch.int32).contiguous()
+        S = int(uniq.shape[0])
+        gate_d = None
+        if gate is not None:
+            gate_d = dev(gate)
+            want = (n_classes - 1, S) if mode == 0 else (n, n_classes - 1)
+            if tuple(gate_d.shape) != want:
+                raise ValueError("spp vote: occupancy of shape %s, %s expected" % (tuple(gate_d.shape), want))
+            gate_d = (gate_d != 0).to(torch.uint8).contiguous() if mode == 1 else (gate_d == 1).to(torch.uint8).contiguous()
+        vbytes = int(lib.gapro_spp_vote_workspace_bytes(n, S, n_classes))
+        vws = torch.empty(max(vbytes, 16), dtype=torch.uint8, device=device)
+        out_label = torch.empty(n, dtype=torch.int64, device=device)
+        out_prob = torch.empty(n, dtype=torch.float32, device=device) if prob_d is not None else None
+        status = torch.zeros(1, dtype=torch.int32, device=device)
+        ctx.check(lib.gapro_spp_vote(ctx.handle, stream, mode, n, S, n_classes, ids.data_ptr(), label_d.data_ptr(),
+                                     1 if label_d.dtype == torch.int64 else 0,
+                                     prob_d.data_ptr() if prob_d is not None else None,
+                                     gate_d.data_ptr() if gate_d is not None and gate_d.numel() else None,
+                                     vws.data_ptr(), vbytes, out_label.data_ptr(),
+                                     out_prob.data_ptr() if out_prob is not None else None, status.data_ptr()))
+        st = int(status.item())
+    if st != 0:
+        raise GaproError(st, "spp vote: a label outside [0, %d), or a probability that is not finite%s"
+                         % (n_classes, " or outside [0, 1]" if mode == 1 else ""))
+    return out_label, out_prob
+
+
+def spp_align_label(spp, label, n_classes=-1, bb_occupancy_spp=None, prob_label=None):
+    """Reference gen_ps_utils.py:99-129 on the GPU behind ``gapro_spp_vote``: every point takes the label most points of
+    its superpoint carry (the first maximum over ascending label), the votes of label c >= 1 counted only where
+    ``bb_occupancy_spp[c - 1, s]`` is 1.  Returns the labels (int64 device tensor) and, with ``prob_label``, the
+    superpoint mean of it gathered back to the points (float32; an exact fixed-point sum)."""
+    lab, prob = _spp_vote(0, spp, label, n_classes, bb_occupancy_spp, prob_label)
+    return lab if prob_label is None else (lab, prob)
+
+
+def spp_major_voting(spp, label, prob_label, bb_occupancy, n_classes):
+    """Reference gen_ps_utils.py:132-166 on the GPU behind ``gapro_spp_vote``: the vote of spp_align_label with box
+    c - 1 counted only in superpoints whose every point lies inside it (``bb_occupancy`` bool[N, n_classes - 1]), and
+    the superpoint's probability sum_c mean(prob | label c) * masked share of c.  Takes any superpoint ids (the
+    reference only runs on dense ones).  Returns (labels int64, probabilities float32) device tensors."""
+    return _spp_vote(1, spp, label, n_classes, bb_occupancy, prob_label)
 
 
 def getInstanceInfo(xyz, instance_label, semantic_label, dataset_name="scannetv2"):

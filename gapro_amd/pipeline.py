@@ -11,7 +11,9 @@ number of scenes share each device launch:
   stage F  gapro_broadcast_labels    superpoint -> point                          (device)
   stage G  gapro_point_refine_*      opt-in (point_level): every point of a GP-labelled superpoint predicted from its
                                      own features by the model that won the superpoint (device; planned on the host)
-                                     ("compete": by every fit that tested the superpoint, the merge replayed per point)
+                                     ("compete": by every fit that tested the superpoint, the merge replayed per point;
+                                      "vote": that, then the superpoint takes the box most of its points chose -- in
+                                      front of stage F, which broadcasts the voted tables)
 
 All arithmetic happens in libgapro_hip.so.  Device memory, streams and events come from a backend (devmem.py): torch's
 (default: the Python API shims take and return torch tensors) or the library's own arena ("native": the gen_ps workers,
@@ -27,8 +29,8 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (FitDesc, PointRefineBlock, PointRefineModel, PointRefineScene, PointRefineSegment, PredictDesc,
-                   SceneHeader, SceneTask, ScheduleCounts)
+from ._lib import (FitDesc, PointRefineBlock, PointRefineModel, PointRefineScene, PointRefineSegment,
+                   PointRefineVoteScene, PredictDesc, SceneHeader, SceneTask, ScheduleCounts)
 from .fit_runner import ROW_FIELDS, FitRunner, PendingFit, _host, _ptr, _to_np, block_views
 from .gp_model import SceneFit, state_doubles
 
@@ -92,6 +94,8 @@ class SceneJob:
     fits: Optional[list] = None
     winner: Optional[np.ndarray] = None  # keep_models: i32[S] index into fits of the fit that labelled the superpoint, or -1
     point_fit: Optional[np.ndarray] = None  # keep_models + point_level="compete": i32[N] fit that labelled the point, or -1
+    vote_box: Optional[np.ndarray] = None  # keep_models + point_level="vote": i32[S] the box the points chose, or -1
+    vote_count: Optional[np.ndarray] = None  # ... and its votes, 0 where the superpoint was not voted on
     scene_key: int = 0  # stable id of the scene (e.g. crc32 of the scan name): seeds the optional initial-mean noise
 
     @property
@@ -167,7 +171,7 @@ class BatchState:
     pending: Optional[PendingFit] = None  # stage D: the launch in flight
 
 
-POINT_MODES = {False: None, True: "winner", "winner": "winner", "compete": "compete"}
+POINT_MODES = {False: None, True: "winner", "winner": "winner", "compete": "compete", "vote": "vote"}
 
 # the host images of gapro_point_refine_block / gapro_point_refine_segment (include/gapro_hip.h)
 BLOCK_DTYPE = np.dtype([("row_start", np.int64), ("n_rows", np.int32), ("scene", np.int32), ("seg_start", np.int32),
@@ -176,12 +180,12 @@ SEGMENT_DTYPE = np.dtype([("out_start", np.int64), ("model", np.int32), ("reserv
 
 
 def point_mode(point_level):
-    """None (off), "winner" or "compete" for a ``point_level`` argument; ValueError for anything else."""
+    """None (off), "winner", "compete" or "vote" for a ``point_level`` argument; ValueError for anything else."""
     if isinstance(point_level, (bool, np.bool_)):
         return "winner" if point_level else None
-    if isinstance(point_level, str) and point_level in ("winner", "compete"):
+    if isinstance(point_level, str) and point_level in ("winner", "compete", "vote"):
         return point_level
-    raise ValueError("point_level must be False, True, 'winner' or 'compete', not %r" % (point_level,))
+    raise ValueError("point_level must be False, True, 'winner', 'compete' or 'vote', not %r" % (point_level,))
 
 
 def plan_point_compete(winners, point_counts, testers, fit_bases, descs=None):
@@ -259,8 +263,11 @@ class Pipeline(FitRunner):
         # point-length.  Off (the default): nothing of it runs.  True / "winner": that model alone.  "compete": every fit
         # that TESTED the superpoint is evaluated at every point of it and the merge's rule is replayed per point
         # (plan_point_compete / _refine_compete).
+        # "vote": the chain of "compete" up to its predict launch, then every refined superpoint takes the box most of its
+        # points chose (_refine_vote, in FRONT of the label broadcast): the outputs keep the default path's lengths.
         self.point_level = mode is not None
         self.point_mode = mode
+        self.point_outputs = mode in ("winner", "compete")  # all five outputs at point length
         if self.point_level and not self.serialize_fits:
             # the fit launches keep their states on the device, which the library allows on one stream per context at
             # a time: the pipeline's three streams qualify only while launch i + 1 waits for launch i
@@ -776,7 +783,7 @@ class Pipeline(FitRunner):
         d_tables.copy_(tables[:tot_s * 20], non_blocking=True)  # one H2D copy for the whole batch
         self._pin_events[state.slot + "labels"] = be.current_stream().record_event()
         tasks, d_tasks = state.tasks, state.d_tasks
-        per_point = 20 if self.point_level else 12
+        per_point = 20 if self.point_outputs else 12
         out_off, out_tot = self._carve([per_point * job.n_points for job in jobs], 16)
         d_out = be.empty(out_tot)  # [sem | inst | prob] per scene; point_level: [sem | inst | prob | mu | var]
         for t, job, off, oo in zip(tasks, jobs, offs, out_off):
@@ -790,7 +797,7 @@ class Pipeline(FitRunner):
             t.sem, t.inst, t.prob = sem.data_ptr(), ins.data_ptr(), prb.data_ptr()
             mu_spp = d_tables[off + 12 * S:off + 16 * S].view(be.f32)
             var_spp = d_tables[off + 16 * S:off + 20 * S].view(be.f32)
-            if self.point_level:
+            if self.point_outputs:
                 job.outputs = (sem, ins, prb, d_out[oo + 12 * n:oo + 16 * n].view(be.f32),
                                d_out[oo + 16 * n:oo + 20 * n].view(be.f32))
                 dict.__setitem__(job.dev, "mu_var_spp", (mu_spp, var_spp))
@@ -799,12 +806,16 @@ class Pipeline(FitRunner):
             if not keep_debug:
                 lib.gapro_schedule_free(job.schedule)
                 job.schedule = None
+        # "vote" works on the superpoint tables, in front of the broadcast that reads them
+        voted = self._refine_vote(state, plan, offs, d_tables) if self.point_mode == "vote" else None
         ev = self._part_event(jobs, "broadcast")
         ctx.check(lib.gapro_broadcast_labels_batch(ctx.handle, self._sh(), len(jobs),
                                                    C.cast(tasks, C.c_void_p), _ptr(d_tasks)))
         self._part_event_end(ev)
+        if voted is not None:
+            self._stage("labels")
         # the task array must outlive the (possibly delayed) upload enqueued above
-        self._keep[state.slot] = (tasks, d_tasks, self._refine(state, plan) if self.point_level else None)
+        self._keep[state.slot] = (tasks, d_tasks, self._refine(state, plan) if self.point_outputs else voted)
         if sync:
             be.current_stream().synchronize()
         _mark("E+F merge/broadcast")
@@ -825,7 +836,7 @@ class Pipeline(FitRunner):
 
         t0 = _time.perf_counter()
         jobs, descs = state.jobs, state.descs
-        if self.point_mode == "compete":
+        if self.point_mode in ("compete", "vote"):
             testers = []
             for job in jobs:
                 off = np.zeros(job.n_spps + 1, dtype=np.int64)
@@ -1022,6 +1033,100 @@ class Pipeline(FitRunner):
                 job.point_fit[h_point[a:a + n][ok]] = (fit_of[took[ok]] - job.fit_base).astype(np.int32)
         return keep + [rm, d_models, pd, row_feats, row_point, out, pstat, blocks, segs, d_blocks, d_segs, d_rows,
                        row_model]
+
+    def _refine_vote(self, state: BatchState, plan, offs, d_tables):
+        """point_level="vote", between the upload of the merge's tables and the label broadcast: gather -> expand -> ONE
+        gapro_svgp_predict_batch over the expanded rows (the chain of "compete") -> gapro_point_refine_vote, which writes
+        the five superpoint values of every refined superpoint into ``d_tables`` (``offs``: each scene's first byte).
+        Failures as in _refine.  With keep_models every job gets ``vote_box`` / ``vote_count`` i32[S], and ``winner``
+        becomes the representative fit where a vote took place."""
+        lib, ctx, be = self.lib, self.ctx, self.be
+        jobs = state.jobs
+        D = int(state.feats_spp_all.shape[1])
+        R, R2, models = plan["rows"], plan["expanded_rows"], plan["models"]
+        ns, nm = len(jobs), len(models)
+        if state.keep_models:
+            for job in jobs:
+                if job.winner is not None:  # f* goes into a copy: job.host["winner"] stays the merge's
+                    job.winner = job.winner.copy()
+                job.vote_box = np.full(job.n_spps, -1, dtype=np.int32)
+                job.vote_count = np.zeros(job.n_spps, dtype=np.int32)
+        self._stage("broadcast")  # (the name of the chain's start in every mode; here nothing has been broadcast yet)
+        if R == 0:
+            return []
+        scenes = (PointRefineScene * ns)()
+        vscenes = (PointRefineVoteScene * ns)()
+        d_scenes = be.empty(ns * C.sizeof(PointRefineScene))
+        d_vscenes = be.empty(ns * C.sizeof(PointRefineVoteScene))
+        d_sp_row = be.from_numpy(plan["sp_row"])
+        d_cursor = be.empty(4 * len(plan["sp_row"]))
+        base, tab = 0, d_tables.data_ptr()
+        for t, v, job, off in zip(scenes, vscenes, jobs, offs):
+            S = job.n_spps
+            t.n_points, t.n_spps, t.reserved = job.n_points, S, 0
+            t.spp_inv, t.feats = job.dev["spp_inv"].data_ptr(), job.feats.data_ptr()
+            t.sp_row, t.cursor = d_sp_row.data_ptr() + 8 * base, d_cursor.data_ptr() + 4 * base
+            v.sem_spp, v.inst_spp, v.prob_spp = tab + off, tab + off + 4 * S, tab + off + 8 * S
+            v.mu_spp, v.var_spp, v.n_spps, v.reserved = tab + off + 12 * S, tab + off + 16 * S, S, 0
+            base += S
+        sp = C.cast(scenes, C.c_void_p)
+        row_feats = be.empty_typed((R, D), be.f32)
+        row_point = be.empty(4 * R)
+        ctx.check(lib.gapro_point_refine_gather(ctx.handle, self._sh(), ns, D, sp, _ptr(d_scenes), R, _ptr(row_feats),
+                                                _ptr(row_point)))
+        self._stage("gather")
+        blocks, segs = plan["blocks"], plan["segments"]
+        nb, nsg = len(blocks), len(segs)
+        d_blocks, d_segs = be.empty(nb * BLOCK_DTYPE.itemsize), be.empty(nsg * SEGMENT_DTYPE.itemsize)
+        d_rows = be.empty(4 * R2)
+        ctx.check(lib.gapro_point_refine_expand(ctx.handle, self._sh(), nb, _ptr(blocks), _ptr(d_blocks), nsg, _ptr(segs),
+                                                _ptr(d_segs), R, R2, _ptr(d_rows)))
+        self._stage("expand")
+        pd = (PredictDesc * nm)()
+        rm = (PointRefineModel * nm)()
+        h_m = np.empty(nm, dtype=np.int32)
+        boxes = np.empty((nm, 2), dtype=np.int32)
+        off = state.pending.state_off
+        for k, (q, r, (f, si, row0, t, b1, b2)) in enumerate(zip(pd, rm, models)):
+            q.state_offset, q.row_offset, q.out_offset, q.t, q.reserved = int(off[f]), row0, row0, t, 0
+            r.row_offset, r.t, r.scene = row0, t, si
+            r.sem1, r.inst1, r.sem2, r.inst2 = self._pair(jobs[si], b1, b2)
+            h_m[k] = int(state.descs[f].m1 + state.descs[f].m2)
+            boxes[k] = b1, b2
+        out, pstat = self._predict_launch(state.pending.d_state, h_m, pd, row_feats, d_rows, R2)
+        self._stage("predict")
+        o = block_views(ROW_FIELDS, out, R2, be)
+        # the blocks are in (scene, superpoint) order (plan_point_compete): their scene-local superpoints
+        block_spp = np.concatenate([np.nonzero(np.asarray(j.host["winner"]) >= 0)[0] for j in jobs
+                                    if j.error is None] or [np.zeros(0, np.int64)]).astype(np.int32)
+        assert len(block_spp) == nb
+        d_models, d_boxes = be.empty(nm * C.sizeof(PointRefineModel)), be.empty(8 * nm)
+        d_block_spp = be.empty(4 * nb)
+        block_out = be.empty(12 * nb) if state.keep_models else None
+        ctx.check(lib.gapro_point_refine_vote(
+            ctx.handle, self._sh(), ns, C.cast(vscenes, C.c_void_p), _ptr(d_vscenes), nm, C.cast(rm, C.c_void_p),
+            _ptr(d_models), _ptr(boxes), _ptr(d_boxes), nb, _ptr(blocks), _ptr(d_blocks), _ptr(block_spp),
+            _ptr(d_block_spp), nsg, _ptr(segs), _ptr(d_segs), R, R2, _ptr(o["probs_new"]), _ptr(o["labels"]),
+            _ptr(o["mu"]), _ptr(o["var"]), _ptr(pstat), _ptr(block_out)))
+        self._stage("vote")
+        st = _host(pstat).view(np.int32)[:nm]  # the batch waits here for its predict launch
+        if (st != 0).any():
+            for k in np.nonzero(st)[0]:
+                job = jobs[models[k][1]]
+                if job.error is None:
+                    job.error = _lib.GaproError(int(st[k]), "point-level prediction from GP fit %d of the scene failed"
+                                                % (models[k][0] - job.fit_base))
+            if self.strict:
+                raise next(j.error for j in jobs if j.error is not None)
+        if state.keep_models:
+            h_out = _host(block_out).view(np.int32)[:3 * nb].reshape(nb, 3)
+            fit_of = np.array([m[0] for m in models], dtype=np.int64)
+            for b in np.nonzero(h_out[:, 0] >= 0)[0]:
+                job, s = jobs[int(blocks["scene"][b])], int(block_spp[b])
+                job.winner[s] = int(fit_of[h_out[b, 0]]) - job.fit_base
+                job.vote_box[s], job.vote_count[s] = h_out[b, 1], h_out[b, 2]
+        return [scenes, vscenes, d_scenes, d_vscenes, d_sp_row, d_cursor, rm, d_models, pd, row_feats, row_point, out,
+                pstat, blocks, segs, d_blocks, d_segs, d_rows, boxes, d_boxes, block_spp, d_block_spp, block_out]
 
     def _identity_rows(self, n: int):
         """i32[>= n] = 0, 1, 2, .. on the device (grow-only): the predict launch reads the gathered table in order."""

@@ -676,6 +676,88 @@ int gapro_point_refine_compete(gapro_ctx* ctx, void* stream, int32_t n_scenes, c
                                const uint8_t* d_labels, const float* d_mu, const float* d_var,
                                const int32_t* d_model_status, int32_t* d_row_model);
 
+/* "vote": the chain of "compete" up to and including the predict launch, then a majority vote inside every block; the
+ * result is written to the block's SUPERPOINT, and the ordinary gapro_broadcast_labels_batch runs behind it, so the
+ * outputs keep the default path's lengths.  One workgroup per block:
+ *   1. take   every gathered row of the block is taken by a segment exactly as in gapro_point_refine_compete (one device
+ *             function).  A taken row VOTES for the box `label ? b2 : b1` of the taking model (h_model_boxes i32[2 *
+ *             n_models] = b1, b2 of every model, >= 0); a row that no segment took votes for nobody.
+ *   2. box    X = the box with the most votes, the lowest box index among equals (spp_align_label's first maximum over
+ *             class = box + 1).  spp_major_voting's occupancy gate is vacuous here: a box whose fit tests a superpoint
+ *             occupies it, so every candidate's gate is open.
+ *   3. fit    f* = the segment that took the most voters for X, the earliest in tester order among equals.  Its voters
+ *             for X carry one label, hence one sign convention for mu.
+ *   4. values (sem, inst) = f*'s pair for that label (of a gapro_point_refine_model only scene and the pairs are read);
+ *             prob = (sum of p_new over ALL voters for X) / block.n_rows (the winning class's term of spp_major_voting's
+ *             sum: mean confidence x vote share); mu, var = the means over the voters for X that f* took.  Each of the
+ *             three is an exact sum: k = fixed_point_shift(largest finite |value| of that quantity among the block's
+ *             voting rows, each read at the output row that took it; block.n_rows), sum of rint(x 2^k) in int64,
+ *             ldexp(sum, -k) / count in float64, rounded once to float32.  k is per block: a scene's result does not
+ *             depend on what shares its batch, nor on the gather order.  A non-finite summand makes that one value the
+ *             quiet NaN 0x7fc00000.
+ *   5. none   a block in which nobody voted keeps what the five tables hold (the merge's values).
+ * h_block_spp i32[n_blocks]: the scene-local superpoint of every block, inside [0, scene.n_spps); no two blocks may
+ * share one.  d_block_out i32[3 * n_blocks] (NULL = not wanted): the model of f*, X and the votes for X; -1, -1, 0 for
+ * rule 5.  Block and segment rules, copies and refusals as for gapro_point_refine_expand; also refused: a negative box,
+ * a block of more than 2048 segments (the candidates' counters live in LDS).  Only thread 0 of a workgroup writes, to
+ * its own block's entries.  n_blocks == 0 or n_scenes == 0 is a no-op.  Enqueue only. */
+typedef struct {
+  int32_t* sem_spp;          /* i32[S] in/out: the merge's tables, voted in place */
+  int32_t* inst_spp;         /* i32[S] */
+  float* prob_spp;           /* f32[S] */
+  float* mu_spp;             /* f32[S] */
+  float* var_spp;            /* f32[S] */
+  int32_t n_spps;            /* S */
+  int32_t reserved;          /* 0 */
+} gapro_point_refine_vote_scene; /* 48 bytes */
+
+int gapro_point_refine_vote(gapro_ctx* ctx, void* stream, int32_t n_scenes,
+                            const gapro_point_refine_vote_scene* h_scenes, gapro_point_refine_vote_scene* d_scenes,
+                            int32_t n_models, const gapro_point_refine_model* h_models,
+                            gapro_point_refine_model* d_models, const int32_t* h_model_boxes, int32_t* d_model_boxes,
+                            int32_t n_blocks, const gapro_point_refine_block* h_blocks,
+                            gapro_point_refine_block* d_blocks, const int32_t* h_block_spp, int32_t* d_block_spp,
+                            int32_t n_segs, const gapro_point_refine_segment* h_segs,
+                            gapro_point_refine_segment* d_segs, int64_t n_rows, int64_t n_rows2,
+                            const float* d_probs_new, const uint8_t* d_labels, const float* d_mu, const float* d_var,
+                            const int32_t* d_model_status, int32_t* d_block_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Superpoint vote of per-point labels (csrc/spp_vote.hip).  Replaces gen_ps_utils.py:99-129 spp_align_label
+ * (GAPRO_VOTE_ALIGN) and :132-166 spp_major_voting (GAPRO_VOTE_MAJOR).
+ *   d_ids i32[N] dense rank of each point's superpoint (gapro_partition_prepare's spp_inv, or the inverse of a sorted
+ *   unique), S = the exact number of ranks: every s in [0, S) must own a point (a superpoint without one gets label 0
+ *   and probability 0, which nothing gathers);
+ *   d_label i32[N] or i64[N] (label_is_i64) in [0, C): 0 = background, c >= 1 = box c - 1;  d_prob f32[N].
+ * cnt[s, c] = points of s labelled c (int32 atomics), n[s] = sum_c cnt[s, c].  Masked count m[s, 0] = cnt[s, 0] and, for
+ * c >= 1, m[s, c] = cnt[s, c] where the gate of (s, c - 1) is open, else 0.  The gate:
+ *   ALIGN  d_gate u8[C - 1, S] (the reference's bb_occupancy_spp, non-zero = open); NULL = every gate open;
+ *   MAJOR  d_gate u8[N, C - 1] (bb_occupancy): open when every point of s lies in box c - 1, i.e. the integer count of
+ *          non-zero entries over s equals n[s] (the reference's scatter(mean) == 1 for 0 / 1 inputs).
+ * label_spp[s] = the first maximum of m[s, .] over ascending c (torch.argmax; an all-masked row gives 0);
+ * d_label_out i64[N] = label_spp[ids].  With d_prob (ALIGN: optional, d_prob_out NULL with it; MAJOR: required),
+ * P[s, c] = the exact sum of prob over the points of s labelled c: rint(x 2^k) in int64, k = fixed_point_shift(max
+ * |prob|, N).  d_prob_out f32[N] = prob_spp[ids] with
+ *   ALIGN  prob_spp[s] = ldexp(sum_c P[s, c], -k) / n[s] in float64, rounded once to float32;
+ *   MAJOR  prob_spp[s] = sum_c (P[s, c] / (cnt[s, c] + 1e-4)) * (m[s, c] / n[s]), float64, c ascending, every operation
+ *          rounded on its own (no contraction), the result rounded once to float32.
+ * The reference sums probabilities in float32 in scatter order, and its :141-143 indexes the occupancy scatter with the
+ * raw superpoint ids (it only runs on dense ids); the exact sums and the ranks replace both.  The entry point takes
+ * ranks; the Python functions rank ids of ANY range (sorted unique on the device), not only those the partition's
+ * flag table holds.
+ * d_status i32[1]: GAPRO_OK; GAPRO_ERR_BAD_ARG (an id outside [0, S), a label outside [0, C), MAJOR: a probability
+ * outside [0, 1], which the reference asserts against at :154); GAPRO_ERR_NOT_FINITE (a non-finite probability; it wins
+ * over BAD_ARG).  With a non-zero status nothing is written to the outputs.  Refused before anything is launched
+ * (GAPRO_ERR_BAD_ARG): a null or non-positive argument, S > N, S * C > 2^31 - 1; GAPRO_ERR_WORKSPACE: d_ws smaller
+ * than gapro_spp_vote_workspace_bytes (0 for sizes the call would refuse).  Enqueue only.
+ * ---------------------------------------------------------------------------------------- */
+enum { GAPRO_VOTE_ALIGN = 0, GAPRO_VOTE_MAJOR = 1 };
+size_t gapro_spp_vote_workspace_bytes(int64_t n_points, int32_t n_spps, int32_t n_classes);
+int gapro_spp_vote(gapro_ctx* ctx, void* stream, int32_t mode, int64_t n_points, int32_t n_spps, int32_t n_classes,
+                   const int32_t* d_ids, const void* d_label, int32_t label_is_i64, const float* d_prob,
+                   const uint8_t* d_gate, void* d_ws, size_t ws_bytes, int64_t* d_label_out, float* d_prob_out,
+                   int32_t* d_status);
+
 /* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
  * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
