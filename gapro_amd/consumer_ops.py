@@ -21,14 +21,18 @@ def _ctx_stream(t):
 
 def pool_labels_to_superpoints(prob_labels, mu_labels, var_labels, spps, n_out=None):
     """``custom_scatter_mean`` (ISBNet/isbnet/model/model_utils.py:600-613) of the three label channels in one
-    pass (isbnet.py:387-389): float32 means per superpoint index, output length ``max(spps) + 1`` unless given."""
+    pass (isbnet.py:387-389): float32 means per superpoint index, output length ``max(spps) + 1`` unless given.
+    An index below 0 or at or above the output length is a ``ValueError``."""
     ctx, stream = _ctx_stream(prob_labels)
     dev = prob_labels.device
     idx = spps.to(device=dev, dtype=torch.int64).contiguous()
     chans = [t.to(device=dev, dtype=torch.float32).contiguous() for t in (prob_labels, mu_labels, var_labels)]
     n = int(idx.numel())
+    lo, hi = (int(v) for v in torch.aminmax(idx)) if n else (0, -1)
     if n_out is None:
-        n_out = int(idx.max()) + 1 if n else 0
+        n_out = hi + 1
+    if n and (lo < 0 or hi >= n_out):
+        raise ValueError("pool_labels_to_superpoints: superpoint indices span [%d, %d], outside [0, %d)" % (lo, hi, n_out))
     outs = [torch.zeros(n_out, dtype=torch.float32, device=dev) for _ in range(3)]
     if n == 0 or n_out == 0:
         return tuple(outs)

@@ -43,13 +43,16 @@ __device__ inline void block_accumulate(double (&v)[K], double* out) {
 }
 
 // ---- custom_scatter_mean of three label channels ------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void k_pool3_sum(long long n, const long long* __restrict__ idx,
+// An index outside [0, n_out) is skipped (one unsigned compare covers both sides): nothing is added outside sums / counts.
+// The Python wrapper refuses such indices before the launch.
+__global__ __launch_bounds__(kThreads) void k_pool3_sum(long long n, int n_out, const long long* __restrict__ idx,
                                                         const float* __restrict__ a, const float* __restrict__ b,
                                                         const float* __restrict__ c, double* __restrict__ sums,
                                                         int* __restrict__ counts) {
   const long long stride = (long long)gridDim.x * kThreads;
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
     const long long s = idx[i];
+    if ((unsigned long long)s >= (unsigned long long)n_out) continue;
     atomicAdd(&sums[3 * s], (double)a[i]);
     atomicAdd(&sums[3 * s + 1], (double)b[i]);
     atomicAdd(&sums[3 * s + 2], (double)c[i]);
@@ -94,9 +97,13 @@ __global__ __launch_bounds__(kThreads) void k_wbce_grad(int G, long long P, cons
   if (!gx) return;
   const long long n = (long long)G * P, stride = (long long)gridDim.x * kThreads;
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
-    const double xi = (double)x[i];
-    const double sg = 1.0 / (1.0 + exp(-xi));  // float64: sigmoid(x) - y cancels for confident predictions
-    gx[i] = (float)((double)grad_out * (sg - (double)y[i]) * (double)w[i % P] / denom);
+    // sigmoid(x) - y without the cancellation of 1 / (1 + exp(-x)) - y at confident predictions (in float64 that form
+    // loses digits from |x| = 24 on and is 0 from 37 on): with t = exp(-|x|), s = t / (1 + t) the difference is
+    // (1 - y) - s for x >= 0 and s - y for x < 0, exact for y in {0, 1}
+    const double xi = (double)x[i], yi = (double)y[i];
+    const double t = exp(-fabs(xi)), s = t / (1.0 + t);
+    const double dx = xi >= 0.0 ? (1.0 - yi) - s : s - yi;
+    gx[i] = (float)((double)grad_out * dx * (double)w[i % P] / denom);
   }
 }
 
@@ -174,7 +181,7 @@ int gapro_label_pool_mean(gapro_ctx* ctx, void* stream_, int64_t n_points, int32
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_sums_ws, 0, (size_t)n_out * 3 * sizeof(double), stream));
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_counts_ws, 0, (size_t)n_out * sizeof(int32_t), stream));
   hipLaunchKernelGGL(k_pool3_sum, dim3(grid_for(n_points, 2048)), dim3(kThreads), 0, stream, (long long)n_points,
-                     (const long long*)d_index, d_prob, d_mu, d_var, d_sums_ws, d_counts_ws);
+                     (int)n_out, (const long long*)d_index, d_prob, d_mu, d_var, d_sums_ws, d_counts_ws);
   hipLaunchKernelGGL(k_pool3_mean, dim3((n_out + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, (int)n_out,
                      d_sums_ws, d_counts_ws, d_out_prob, d_out_mu, d_out_var);
   GAPRO_LAUNCH_CHECK(ctx);

@@ -312,7 +312,8 @@ int gapro_label_heuristic(gapro_ctx* ctx, void* stream, int64_t n_points, const 
  * ---------------------------------------------------------------------------------------- */
 /* custom_scatter_mean (ISBNet/isbnet/model/model_utils.py:600-613) of the three label channels at once
  * (isbnet.py:387-389): out[s] = mean of the points with index s (count clamped at 1, as torch_scatter does).
- *   d_index i64[N] in [0, n_out), d_sums_ws f64[3 n_out] and d_counts_ws i32[n_out] are scratch. */
+ *   d_index i64[N] in [0, n_out) (a point whose index is outside is skipped), d_sums_ws f64[3 n_out] and
+ *   d_counts_ws i32[n_out] are scratch. */
 int gapro_label_pool_mean(gapro_ctx* ctx, void* stream, int64_t n_points, int32_t n_out, const int64_t* d_index,
                           const float* d_prob, const float* d_mu, const float* d_var, double* d_sums_ws,
                           int32_t* d_counts_ws, float* d_out_prob, float* d_out_mu, float* d_out_var);
