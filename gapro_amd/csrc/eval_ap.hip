@@ -3,8 +3,8 @@
 // back in the label arrays (blockIdx.y = scene).  The matching and the AP (evaluate_matches) run on the host.
 //
 // A GT point's key is the reference's code g = (sem + 1) * 1000 + (inst + 1) after the script's remap (:59-60):
-// class c = sem + 1 in 1..18 and inst + 1 in [0, 999) make a GT instance; any other class, or inst + 1 < 0, is void.
-// An inst >= 999 would carry into the class digit: it sets the scene's status.
+// class c = sem + 1 in 1..18 and inst + 1 in [0, 1000) make a GT instance; any other class, or inst + 1 < 0, is void.
+// An inst >= 999 (inst + 1 >= 1000) would carry into the class digit: it sets the scene's status.
 //   gapro_eval_ap_keys   : pass 1 marks the present keys in a per-scene bitmap (LDS-privatised), and a per-scene
 //                          exclusive scan of the word popcounts turns it into dense ranks in ascending code order.
 //   gapro_eval_ap_tables : pass 2 tallies per point the (key rank + 1, pseudo id + 1) pair count (row 0 = void,
@@ -22,7 +22,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kApClasses = 18;                        // ScanNet's valid class ids 1..18
-constexpr int kApInst = 999;                          // inst + 1 in [0, 999): the instance digits of a code
+constexpr int kApInst = 1000;                         // inst + 1 in [0, 1000): the instance digits of a code
 constexpr int kApCodes = kApClasses * kApInst;        // (class, inst + 1) keys, ranked in ascending code order
 constexpr int kApWords = (kApCodes + 31) / 32;        // presence bitmap words per scene
 constexpr int kPairLds = 8192;                        // pair cells kept in LDS ((keys + 1) x (ids + 1))
@@ -54,11 +54,12 @@ __device__ inline SceneWs scene_ws(void* ws, const gapro_eval_ap_scene& s) {
   return w;
 }
 
-// the key index of a GT point ((class - 1) * 999 + inst + 1, ascending in the code), -1 = void, -2 = inst >= 999
+// the key index of a GT point ((class - 1) * 1000 + inst + 1 = code - 1000, ascending in the code), -1 = void,
+// -2 = inst >= 999
 template <class TGS, class TGI>
 __device__ inline int gt_key(const TGS* sem_gt, const TGI* inst_gt, long long i, int remap) {
   const long long sg = remap_gt(label_at(sem_gt, i), remap), g = label_at(inst_gt, i);
-  if (g >= kApInst) return -2;
+  if (g >= kApInst - 1) return -2;  // inst + 1 = 1000 is the next class's inst + 1 = 0
   if (g < -1 || sg < 0 || sg >= kApClasses) return -1;  // code 0, class 0 (wall / floor after the remap) or > 18
   return (int)sg * kApInst + (int)g + 1;
 }

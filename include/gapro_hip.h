@@ -245,8 +245,9 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro
  * ScanNetEval.assign_instances_for_scan): the integer tables of a batch of scenes laid out back to back, in two
  * calls with one host read of the key counts in between.  A GT point's key is the code
  * (sem + 1) * 1000 + (inst + 1) after the optional remap; it is a GT instance when sem + 1 is in 1..18 and
- * inst + 1 in [0, 999), else the point is void.  The matching and the AP run on the host.  Integer atomics
- * only: every table is bit-identical to a plain tally of the scene alone, whatever the batch composition. */
+ * inst + 1 in [0, 1000), i.e. inst in -1..998, else the point is void.  The matching and the AP run on the host.
+ * Integer atomics only: every table is bit-identical to a plain tally of the scene alone, whatever the batch
+ * composition. */
 typedef struct {
   int64_t point_offset;  /* in : first point of the scene in the label arrays                                 */
   int64_t n_points;      /* in : may be 0                                                                     */

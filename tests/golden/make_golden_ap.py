@@ -13,6 +13,8 @@ Cases (confidence "one" = the reference's 1.0; "mean_prob" = float64(S) / (float
 S = sum of rint(float64(prob) * 2**32) over the instance's points):
   golden_*: the six golden scenes tests/golden/s0..s5 (sem_gt, inst_gt, out_sem, out_inst, out_prob);
   synth_*:  seeded synthetic scenes built to reach every branch of the matching (see _branch_scene).
+A second file, ap_eval_edges.npz, holds the case ``edges``: two scenes that put a value ON every comparison of
+evaluate_matches (see _edge_scene), so that ap_from_tables' strict and non-strict comparisons are pinned by the reference.
 """
 import importlib
 import os
@@ -173,6 +175,50 @@ def _random_scene(seed, n_gt, gt_dtype):
     return b.build(rng, gt_dtype)
 
 
+def _edge_scene(seed, gt_dtype):
+    """Values on the comparisons of evaluate_matches (iou > th, prop_ignore <= th, >= min_region_size):"""
+    rng = np.random.default_rng(seed)
+    b = _Builder()
+    # an IoU of exactly 0.5 (class 3): GT 0 of 300 points, pseudo 0 on 200 of them and 100 void points
+    b.add(200, 4, 0, 2, 0, 0.75)
+    b.add(100, 4, 0, 2, -100, 0.5)
+    b.add(100, 0, -100, 2, 0, 0.75)
+    # an IoU of exactly 0.25 with a prediction of exactly 100 points, all inside GT 1 of 400 points (class 4)
+    b.add(100, 5, 1, 3, 1, 0.75)
+    b.add(300, 5, 1, -100, -100, 0.5)
+    # instances of 99 and of 100 points, GT and prediction alike (class 5): either side of min_region_size
+    b.add(99, 6, 2, 4, 2, 0.5)
+    b.add(100, 6, 3, 4, 3, 1.0)
+    # prop_ignore exactly 0.5 (150 void + 150 on a 1000-point GT) and exactly 0.25 (100 void + 300 on a 2000-point GT)
+    b.add(150, 0, -100, 5, 4, 0.75)
+    b.add(150, 7, 4, 5, 4, 0.75)
+    b.add(850, 7, 4, -100, -100, 0.5)
+    b.add(100, 1, -100, 5, 5, 0.5)
+    b.add(300, 7, 5, 5, 5, 0.5)
+    b.add(1700, 7, 5, -100, -100, 0.5)
+    # a prediction ignored through a same-class GT of 60 points (class 7): pseudo 6 = all of GT 6 + 60 of GT 7 (500 points)
+    b.add(60, 8, 6, 6, 6, 0.75)
+    b.add(60, 8, 7, 6, 6, 0.75)
+    b.add(440, 8, 7, 6, 7, 1.0)
+    # one prediction over two GTs at IoU 0.5 each (class 8): GT 8 and GT 9 of 200 points, pseudo 8 covers both
+    b.add(200, 9, 8, 7, 8, 0.75)
+    b.add(200, 9, 9, 7, 8, 0.75)
+    # two predictions of equal IoU (0.5) and equal confidence on one GT of 600 points (class 9)
+    b.add(300, 10, 10, 8, 9, 0.75)
+    b.add(300, 10, 10, 8, 10, 0.75)
+    # class 18 with inst 998, and with inst -1
+    b.add(150, 19, 998, 17, 11, 1.0)
+    b.add(150, 19, -1, 17, 12, 0.25)
+    # wall / floor and unlabelled GT under no prediction
+    b.add(600, 0, -100, -100, -100, 0.5)
+    b.add(291, -100, -100, -100, -100, 0.5)
+    return b.build(rng, gt_dtype)
+
+
+def edge_scenes():
+    return [_edge_scene(11, np.float64), _edge_scene(12, np.int64)]
+
+
 def synthetic_scenes():
     return [_branch_scene(1), _random_scene(2, 25, np.int64), _random_scene(3, 40, np.float64),
             _random_scene(4, 12, np.int32)]
@@ -200,6 +246,19 @@ def main():
             out[key + "_ap"], out[key + "_rc"], out[key + "_avg"], out[key + "_cls"] = ap, rc, avg, cls
             print("%-16s AP %.4f AP50 %.4f AP25 %.4f" % (key, avg[0], avg[1], avg[2]))
     path = os.path.join(HERE, "ap_eval.npz")
+    np.savez_compressed(path, **out)
+    print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
+    edges = edge_scenes()
+    out = dict(n_edges=np.int64(len(edges)))
+    for i, sc in enumerate(edges):
+        for k, a in zip(("sem_gt", "inst_gt", "ps_sem", "ps_inst", "prob"), sc):
+            out["edges%d_%s" % (i, k)] = a
+    for conf in ("one", "mean_prob"):
+        ap, rc, avg, cls = reference_ap(ScanNetEval, edges, conf)
+        key = "edges_%s" % conf
+        out[key + "_ap"], out[key + "_rc"], out[key + "_avg"], out[key + "_cls"] = ap, rc, avg, cls
+        print("%-16s AP %.4f AP50 %.4f AP25 %.4f" % (key, avg[0], avg[1], avg[2]))
+    path = os.path.join(HERE, "ap_eval_edges.npz")
     np.savez_compressed(path, **out)
     print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
 

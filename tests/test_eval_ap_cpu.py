@@ -36,7 +36,7 @@ def test_ap_workspace_and_pair_layout():
     d = (_lib.EvalApScene * 3)()
     for i, (n, p) in enumerate([(10, 4), (0, 1), (5, 900)]):
         d[i].point_offset, d[i].n_points, d[i].max_ps = 0, n, p
-    words = (18 * 999 + 31) // 32
+    words = (18 * 1000 + 31) // 32  # inst + 1 in [0, 1000) per class
     sizes = [-(-(words * 8 + p * 8) // 256) * 256 for p in (4, 1, 900)]
     assert lib.gapro_eval_ap_workspace_bytes(d, 3) == sum(sizes)
     assert [x.ws_offset for x in d] == [0, sizes[0], sizes[0] + sizes[1]]
@@ -49,7 +49,7 @@ def test_ap_workspace_and_pair_layout():
     # bad arguments: 0
     assert lib.gapro_eval_ap_workspace_bytes(d, 0) == 0
     assert lib.gapro_eval_ap_workspace_bytes(None, 3) == 0
-    d[2].n_keys = 18 * 999 + 1
+    d[2].n_keys = 18 * 1000 + 1
     assert lib.gapro_eval_ap_pair_cells(d, 3) == 0
     d[1].max_ps = 0
     assert lib.gapro_eval_ap_workspace_bytes(d, 3) == 0
@@ -144,3 +144,29 @@ def test_results_table_and_argument_errors():
         A.ap_tables([], device="cuda:0")
     with pytest.raises(SystemExit):
         A.main(["--confidence", "max"])
+
+
+def _edge_fixture():
+    """tests/golden/ap_eval_edges.npz: two scenes with a value ON every comparison of evaluate_matches, and the reference
+    ScanNetEval's numbers on them."""
+    z = np.load(os.path.join(ROOT, "tests", "golden", "ap_eval_edges.npz"))
+    return z, [[z["edges%d_%s" % (i, k)] for k in ("sem_gt", "inst_gt", "ps_sem", "ps_inst", "prob")]
+               for i in range(int(z["n_edges"]))]
+
+
+@pytest.mark.parametrize("conf", ["one", "mean_prob"])
+def test_ap_from_tables_reproduces_the_reference_on_the_threshold_edges(conf):
+    """iou > th, prop_ignore <= th and >= min_region_size with values on the comparison: IoUs of exactly 0.5 and 0.25,
+    instances of 99 and 100 points, ignored shares of exactly 0.5 and 0.25."""
+    z, scenes = _edge_fixture()
+    tables = [tally(*sc, confidence=conf) for sc in scenes]
+    _check(A.ap_from_tables(tables), z, "edges_%s" % conf)
+    for t in tables:  # the fixture holds what it was built for
+        iou = t.pair_inter / (t.gt_n[t.pair_gt] + t.pred_n[t.pair_pred] - t.pair_inter)
+        assert (iou == 0.5).sum() >= 5 and (iou == 0.25).sum() >= 1 and 100 in t.pred_n[t.pair_pred[iou == 0.25]]
+        assert {99, 100} <= set(t.gt_n.tolist()) and {99, 100} <= set(t.pred_n.tolist())
+        small = np.bincount(t.pair_pred[t.gt_n[t.pair_gt] < 100], t.pair_inter[t.gt_n[t.pair_gt] < 100], len(t.pred_n))
+        share = (t.pred_void + small) / t.pred_n
+        assert (share[t.pred_void > 0] == 0.5).any() and (share[t.pred_void > 0] == 0.25).any()
+        assert (share[(t.pred_void == 0) & (t.pred_n >= 100)] == 0.5).any()   # ignored through a 60-point GT alone
+        assert 18999 in t.gt_code and 18000 in t.gt_code

@@ -179,3 +179,21 @@ def test_cli_end_to_end(tmp_path):
     p = _run_cli(["--ps_folder", str(two), "--data_root", root, "--confidence", "mean_prob", "--json", out])
     assert p.returncode == 2, p.stdout + p.stderr
     assert "Traceback" not in p.stderr and sorted(json.load(open(out))["failed"]) == ["scene0001_00", "scene0004_00"]
+
+
+@pytest.mark.parametrize("conf", ["one", "mean_prob"])
+def test_evaluate_ap_reproduces_the_reference_on_the_threshold_edges(conf):
+    """tests/golden/ap_eval_edges.npz: values on every comparison of evaluate_matches (IoU exactly 0.5 and 0.25, 99 and
+    100 points, ignored shares of exactly 0.5 and 0.25), the device tables included."""
+    from gapro_amd.eval_ap_ps_labels import ap_tables, evaluate_ap
+
+    z = np.load(os.path.join(ROOT, "tests", "golden", "ap_eval_edges.npz"))
+    scenes = [[z["edges%d_%s" % (i, k)] for k in ("sem_gt", "inst_gt", "ps_sem", "ps_inst", "prob")]
+              for i in range(int(z["n_edges"]))]
+    for got, sc in zip(ap_tables(scenes, conf), scenes):
+        assert_tables_equal(got, tally(*sc, confidence=conf))
+    res = evaluate_ap(scenes, confidence=conf)
+    key = "edges_%s" % conf
+    np.testing.assert_allclose(res.ap, z[key + "_ap"], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(res.rc, z[key + "_rc"], rtol=0, atol=1e-12)
+    np.testing.assert_allclose([res.avgs[k] for k in AVG_KEYS], z[key + "_avg"], rtol=0, atol=1e-12)
