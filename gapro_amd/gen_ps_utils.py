@@ -8,7 +8,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .pipeline import Pipeline, make_job, point_mode
+from .pipeline import Pipeline, make_job, point_level_kw, point_mode
 
 _PIPELINES = {}
 
@@ -90,8 +90,8 @@ def gen_pseudo_label_gaussian_process(
                    wall_box_volume, instance_classes, ground_h, thresh_spp_occu, device=dev)
     # (the keyword only when set: every other caller of _pipeline keeps sharing the default pipeline of its options)
     mode = point_mode(point_level)
-    extra = dict(point_level=True if mode == "winner" else mode) if mode else {}
-    pipe = _pipeline(dev, training_iter, init_mean_std=init_mean_std, seed=seed, eval_stale_chol=eval_stale_chol, **extra)
+    pipe = _pipeline(dev, training_iter, init_mean_std=init_mean_std, seed=seed, eval_stale_chol=eval_stale_chol,
+                     **point_level_kw(point_level))
     sem, ins, prob, mu, var = pipe.run([job], keep_models=return_models)[0]
     if broadcast_mu_var and mode in (None, "vote"):  # "vote" keeps the default path's lengths
         idx = job.spp_inv.long()
@@ -127,9 +127,7 @@ def gen_pseudo_label_gaussian_process_batch(scenes, training_iter=50, device=Non
     length), ``point_level="vote"`` the superpoint vote of them (default lengths).
     """
     if "point_level" in pipe_kw:  # True and "winner" share one pipeline
-        mode = point_mode(pipe_kw.pop("point_level"))
-        if mode:
-            pipe_kw["point_level"] = True if mode == "winner" else mode
+        pipe_kw.update(point_level_kw(pipe_kw.pop("point_level")))
     dev = torch.device(device if device is not None else "cuda:0")
     jobs = [make_job(s["coords_float"], s["mask_feats"], s["spp"], s["instance_cls"], s["instance_box"],
                      s["instance_box_volume"], s["wall_box"], s["wall_box_volume"],

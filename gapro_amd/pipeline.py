@@ -9,8 +9,9 @@ number of scenes share each device launch:
   stage D  gapro_svgp_fit_batch      every GP fit of every scene in ONE launch    (device)
   stage E  gapro_schedule_merge      ordered merge, fallback, label tables        (host, C++)
   stage F  gapro_broadcast_labels    superpoint -> point                          (device)
-  stage G  gapro_point_refine_*      opt-in (point_level): every point of a GP-labelled superpoint predicted from its
-                                     own features by the model that won the superpoint (device; planned on the host)
+  stage G  gapro_point_refine_*      opt-in (point_level), in point_level.py: every point of a GP-labelled superpoint
+                                     predicted from its own features by the model that won the superpoint (device;
+                                     planned on the host: refine_plan, then refine_chain for every mode)
                                      ("compete": by every fit that tested the superpoint, the merge replayed per point;
                                       "vote": that, then the superpoint takes the box most of its points chose -- in
                                       front of stage F, which broadcasts the voted tables)
@@ -29,10 +30,11 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (FitDesc, PointRefineBlock, PointRefineModel, PointRefineScene, PointRefineSegment,
-                   PointRefineVoteScene, PredictDesc, SceneHeader, SceneTask, ScheduleCounts)
-from .fit_runner import ROW_FIELDS, FitRunner, PendingFit, _host, _ptr, _to_np, block_views
+from ._lib import FitDesc, SceneHeader, SceneTask, ScheduleCounts
+from .fit_runner import FitRunner, PendingFit, _host, _ptr, _to_np
 from .gp_model import SceneFit, state_doubles
+from .point_level import (BLOCK_DTYPE, SEGMENT_DTYPE, plan_point_compete, plan_point_winner,  # noqa: F401 (re-exported)
+                          point_level_kw, point_mode, refine_chain, refine_plan)
 
 
 class LazyViews(dict):
@@ -171,85 +173,6 @@ class BatchState:
     pending: Optional[PendingFit] = None  # stage D: the launch in flight
 
 
-POINT_MODES = {False: None, True: "winner", "winner": "winner", "compete": "compete", "vote": "vote"}
-
-# the host images of gapro_point_refine_block / gapro_point_refine_segment (include/gapro_hip.h)
-BLOCK_DTYPE = np.dtype([("row_start", np.int64), ("n_rows", np.int32), ("scene", np.int32), ("seg_start", np.int32),
-                        ("n_seg", np.int32)], align=True)
-SEGMENT_DTYPE = np.dtype([("out_start", np.int64), ("model", np.int32), ("reserved", np.int32)], align=True)
-
-
-def point_mode(point_level):
-    """None (off), "winner", "compete" or "vote" for a ``point_level`` argument; ValueError for anything else."""
-    if isinstance(point_level, (bool, np.bool_)):
-        return "winner" if point_level else None
-    if isinstance(point_level, str) and point_level in ("winner", "compete", "vote"):
-        return point_level
-    raise ValueError("point_level must be False, True, 'winner', 'compete' or 'vote', not %r" % (point_level,))
-
-
-def plan_point_compete(winners, point_counts, testers, fit_bases, descs=None):
-    """Host plan of a batch's point_level="compete" predict launch: pure NumPy, no device.
-
-    Per scene: ``winners[i]`` i32[S] (gapro_schedule_merge_ex; None = the scene takes no part), ``point_counts[i]``
-    i32[S], ``testers[i]`` = (offsets i64[S + 1], fit i32[n], pos i32[n]) from gapro_schedule_export_testers,
-    ``fit_bases[i]`` = index of the scene's first fit among the batch's fit descriptors ``descs`` (optional; with them
-    every model carries its b1, b2).
-
-    A superpoint is refined iff winner >= 0.  Its points form one BLOCK of the gathered row table, the blocks ordered by
-    (scene, superpoint): sp_row[sp] = first row, R rows in all.  Every fit that tested a refined superpoint is a predict
-    MODEL (scene order, then fit order); a (tester, block) pair is a SEGMENT of the block's n_rows entries in the predict
-    launch's row list, R2 entries in all.  The segments of a block are stored in tester order (the order in which the
-    merge meets the fits); in the row list the segments of one model are contiguous, ascending in superpoint.
-
-    Returns dict(sp_row i64[sum S], blocks BLOCK_DTYPE[], segments SEGMENT_DTYPE[], models [(batch fit index, scene,
-    first entry, entries, b1, b2)], rows R, expanded_rows R2, refined_spps, multi_spps, scene_rows [(first row, rows)])."""
-    i64 = np.int64
-    sp_row = np.full(int(sum(len(pc) for pc in point_counts)), -1, dtype=i64)
-    blocks, segs, models, scene_rows = [], [], [], []
-    R = R2 = n_seg_tot = multi = n_ref = base = 0
-    for si, (w, pc, (t_off, t_fit, _), fb) in enumerate(zip(winners, point_counts, testers, fit_bases)):
-        S = len(pc)
-        ref = np.nonzero(np.asarray(w) >= 0)[0] if w is not None else np.zeros(0, i64)
-        scene_rows.append((R, 0))
-        if len(ref):
-            t_off = np.asarray(t_off, dtype=i64)
-            cnt = np.asarray(pc)[ref].astype(i64)
-            start = R + np.cumsum(cnt) - cnt
-            sp_row[base + ref] = start
-            ns = t_off[ref + 1] - t_off[ref]
-            first_seg = np.cumsum(ns) - ns
-            tot = int(ns.sum())
-            blk = np.zeros(len(ref), dtype=BLOCK_DTYPE)
-            blk["row_start"], blk["n_rows"], blk["scene"] = start, cnt, si
-            blk["seg_start"], blk["n_seg"] = n_seg_tot + first_seg, ns
-            blocks.append(blk)
-            blk_of_seg = np.repeat(np.arange(len(ref)), ns)
-            fit = np.asarray(t_fit)[np.repeat(t_off[ref] - first_seg, ns) + np.arange(tot)]
-            order = np.argsort(fit, kind="stable")  # the row list: by (fit, superpoint)
-            rows_o = cnt[blk_of_seg[order]]
-            out_o = R2 + np.cumsum(rows_o) - rows_o
-            sg = np.zeros(tot, dtype=SEGMENT_DTYPE)
-            sg["out_start"][order] = out_o
-            fits_u, first = np.unique(fit[order], return_index=True)
-            sg["model"] = len(models) + np.searchsorted(fits_u, fit)
-            segs.append(sg)
-            for k, a, b in zip(fits_u, first, np.r_[first[1:], tot]):
-                d = descs[fb + int(k)] if descs is not None else None
-                models.append((fb + int(k), si, int(out_o[a]), int(rows_o[a:b].sum()),
-                               int(d.b1) if d is not None else -1, int(d.b2) if d is not None else -1))
-            scene_rows[-1] = (R, int(cnt.sum()))
-            R += int(cnt.sum())
-            R2 += int(rows_o.sum())
-            n_seg_tot += tot
-            multi += int((ns >= 2).sum())
-            n_ref += len(ref)
-        base += S
-    return dict(sp_row=sp_row, blocks=np.concatenate(blocks) if blocks else np.zeros(0, BLOCK_DTYPE),
-                segments=np.concatenate(segs) if segs else np.zeros(0, SEGMENT_DTYPE), models=models, rows=R,
-                expanded_rows=R2, refined_spps=n_ref, multi_spps=multi, scene_rows=scene_rows)
-
-
 class Pipeline(FitRunner):
     def __init__(self, device=0, training_iter=50, init_mean_std=0.0, seed=0, eval_stale_chol=False,
                  spp_range_cap=None, force_staged=False, precision="f64", cluster_all=False, backend="torch",
@@ -259,12 +182,12 @@ class Pipeline(FitRunner):
                          cluster_all, backend)
         self.spp_range_cap = spp_range_cap
         # point_level: after the ordered merge every point of a superpoint that a GP fit labelled is predicted from its
-        # own feature row by the model that won the superpoint (_refine_plan / _refine); all five outputs are then
-        # point-length.  Off (the default): nothing of it runs.  True / "winner": that model alone.  "compete": every fit
-        # that TESTED the superpoint is evaluated at every point of it and the merge's rule is replayed per point
-        # (plan_point_compete / _refine_compete).
+        # own feature row by the model that won the superpoint (point_level.py: refine_plan / refine_chain, one chain
+        # for every mode); all five outputs are then point-length.  Off (the default): nothing of it runs.  True /
+        # "winner": that model alone (plan_point_winner).  "compete": every fit that TESTED the superpoint is evaluated at
+        # every point of it and the merge's rule is replayed per point (plan_point_compete).
         # "vote": the chain of "compete" up to its predict launch, then every refined superpoint takes the box most of its
-        # points chose (_refine_vote, in FRONT of the label broadcast): the outputs keep the default path's lengths.
+        # points chose (the chain runs in FRONT of the label broadcast): the outputs keep the default path's lengths.
         self.point_level = mode is not None
         self.point_mode = mode
         self.point_outputs = mode in ("winner", "compete")  # all five outputs at point length
@@ -779,7 +702,7 @@ class Pipeline(FitRunner):
             for arg in zip(jobs, offs):
                 merge_one(arg)
         # point_level: the row table of the predict launch is planned here, on the host, before anything is enqueued
-        plan = self._refine_plan(state) if self.point_level else None
+        plan = refine_plan(self, state) if self.point_level else None
         d_tables.copy_(tables[:tot_s * 20], non_blocking=True)  # one H2D copy for the whole batch
         self._pin_events[state.slot + "labels"] = be.current_stream().record_event()
         tasks, d_tasks = state.tasks, state.d_tasks
@@ -806,16 +729,20 @@ class Pipeline(FitRunner):
             if not keep_debug:
                 lib.gapro_schedule_free(job.schedule)
                 job.schedule = None
-        # "vote" works on the superpoint tables, in front of the broadcast that reads them
-        voted = self._refine_vote(state, plan, offs, d_tables) if self.point_mode == "vote" else None
+        # point_level at superpoint length works on the superpoint tables, in front of the broadcast that reads them
+        refined = None
+        if self.point_level and not self.point_outputs:
+            refined = refine_chain(self, state, plan, offs, d_tables)
         ev = self._part_event(jobs, "broadcast")
         ctx.check(lib.gapro_broadcast_labels_batch(ctx.handle, self._sh(), len(jobs),
                                                    C.cast(tasks, C.c_void_p), _ptr(d_tasks)))
         self._part_event_end(ev)
-        if voted is not None:
+        if refined is not None:
             self._stage("labels")
+        if self.point_outputs:  # ... and at point length on the broadcast's outputs, behind it
+            refined = refine_chain(self, state, plan, offs, d_tables)
         # the task array must outlive the (possibly delayed) upload enqueued above
-        self._keep[state.slot] = (tasks, d_tasks, self._refine(state, plan) if self.point_outputs else voted)
+        self._keep[state.slot] = (tasks, d_tasks, refined)
         if sync:
             be.current_stream().synchronize()
         _mark("E+F merge/broadcast")
@@ -824,315 +751,3 @@ class Pipeline(FitRunner):
             if j.error is not None:  # merged from a failed fit's garbage: not a result
                 j.outputs = None
         return [j.outputs if j.error is None else None for j in state.all_jobs]
-
-    # ------------------------------------------------------------------ stage G (point_level)
-    def _refine_plan(self, state: BatchState):
-        """Host plan of the batch's point-level predict launch, from each scene's merge winners and point counts (no
-        device round trip).  A scene's refined superpoints (winner >= 0) are ordered by (winning fit, superpoint): the
-        superpoints of one fit are contiguous and ascending, the fits in batch order.  Every fit that won at least one
-        superpoint becomes a predict model whose rows are the points of its superpoints; sp_row[sp] is the first row of
-        the superpoint's block.  Scenes that already failed take no part."""
-        import time as _time
-
-        t0 = _time.perf_counter()
-        jobs, descs = state.jobs, state.descs
-        if self.point_mode in ("compete", "vote"):
-            testers = []
-            for job in jobs:
-                off = np.zeros(job.n_spps + 1, dtype=np.int64)
-                fit = np.zeros(max(int(job.counts.n_fit_out), 1), dtype=np.int32)
-                pos = np.zeros_like(fit)
-                rc = self.lib.gapro_schedule_export_testers(job.schedule, _ptr(off), _ptr(fit), _ptr(pos))
-                if rc != 0:
-                    raise _lib.GaproError(rc, "gapro_schedule_export_testers")
-                testers.append((off, fit, pos))
-            plan = plan_point_compete([j.host["winner"] if j.error is None else None for j in jobs],
-                                      [j.host["point_count"] for j in jobs], testers, [j.fit_base for j in jobs], descs)
-            if plan["expanded_rows"] > 2**31 - 1:  # refused before anything is launched
-                raise _lib.GaproError(-1, "point_level: %d expanded rows in one batch exceed the int32 row index"
-                                      % plan["expanded_rows"])
-            self.last_refine = dict(refined_spps=plan["refined_spps"], rows=plan["rows"], models=len(plan["models"]),
-                                    expanded_rows=plan["expanded_rows"], multi_spps=plan["multi_spps"],
-                                    plan_s=_time.perf_counter() - t0)
-            return plan
-        sp_row = np.full(sum(j.n_spps for j in jobs), -1, dtype=np.int64)
-        models, rows, n_ref, base = [], 0, 0, 0
-        for si, job in enumerate(jobs):
-            S = job.n_spps
-            w = job.host["winner"]
-            ref = np.nonzero(w >= 0)[0] if job.error is None else np.zeros(0, np.int64)
-            if len(ref):
-                order = ref[np.argsort(w[ref], kind="stable")]
-                cnt = job.host["point_count"][order].astype(np.int64)
-                start = rows + np.cumsum(cnt) - cnt
-                sp_row[base + order] = start
-                fit_ids, first = np.unique(w[order], return_index=True)
-                ends = np.r_[first[1:], len(order)]
-                n_fg = len(job.instance_box)
-                for k, a, b in zip(fit_ids, first, ends):
-                    d = descs[job.fit_base + int(k)]
-                    pair = []
-                    for box in (int(d.b1), int(d.b2)):  # the merge's last loop (schedule.cpp) for a box
-                        pair += [int(job.boxes_cls[box]), box if box < n_fg else -100]
-                    models.append((job.fit_base + int(k), si, int(start[a]), int(cnt[a:b].sum()), pair))
-                rows += int(cnt.sum())
-                n_ref += len(ref)
-            base += S
-        if rows > 2**31 - 1:  # row indices are int32 (the predict ABI): refused before anything is launched
-            raise _lib.GaproError(-1, "point_level: %d rows in one batch exceed the int32 row index" % rows)
-        self.last_refine = dict(refined_spps=n_ref, rows=rows, models=len(models), expanded_rows=rows,
-                                plan_s=_time.perf_counter() - t0)
-        return dict(sp_row=sp_row, models=models, rows=rows)
-
-    def _refine(self, state: BatchState, plan):
-        """Behind the broadcast, on the same stream: gather the rows, ONE gapro_svgp_predict_batch over them with identity
-        rows, apply.  A batch without a refined superpoint runs neither gather nor predict, only apply's mu / var
-        broadcast.  A model whose prediction fails (status != 0) fails its scene like a failed fit.  Returns what must
-        stay alive until the stream has run all of it."""
-        lib, ctx, be = self.lib, self.ctx, self.be
-        jobs = state.jobs
-        D = int(state.feats_spp_all.shape[1])
-        R, models = plan["rows"], plan["models"]
-        ns = len(jobs)
-        scenes = (PointRefineScene * ns)()
-        d_scenes = be.empty(ns * C.sizeof(PointRefineScene))
-        d_sp_row = be.from_numpy(plan["sp_row"])
-        d_cursor = be.empty(4 * len(plan["sp_row"]))
-        base = 0
-        for t, job in zip(scenes, jobs):
-            S = job.n_spps
-            sem, ins, prb, mu, var = job.outputs
-            mu_spp, var_spp = job.dev["mu_var_spp"]
-            t.n_points, t.n_spps, t.reserved = job.n_points, S, 0
-            t.spp_inv, t.feats = job.dev["spp_inv"].data_ptr(), job.feats.data_ptr()
-            t.sp_row, t.cursor = d_sp_row.data_ptr() + 8 * base, d_cursor.data_ptr() + 4 * base
-            t.mu_spp, t.var_spp = mu_spp.data_ptr(), var_spp.data_ptr()
-            t.sem, t.inst, t.prob, t.mu, t.var = (x.data_ptr() for x in (sem, ins, prb, mu, var))
-            base += S
-        self._stage("broadcast")
-        keep = [scenes, d_scenes, d_sp_row, d_cursor]
-        if self.point_mode == "compete":
-            return self._refine_compete(state, plan, scenes, d_scenes, keep)
-        nm = len(models) if R else 0
-        if nm == 0:
-            ctx.check(lib.gapro_point_refine_apply(ctx.handle, self._sh(), ns, C.cast(scenes, C.c_void_p), _ptr(d_scenes),
-                                                   0, None, None, 0, None, None, None, None, None, None))
-            self._stage("apply")
-            return keep
-        row_feats = be.empty_typed((R, D), be.f32)
-        row_point = be.empty(4 * R)
-        ctx.check(lib.gapro_point_refine_gather(ctx.handle, self._sh(), ns, D, C.cast(scenes, C.c_void_p),
-                                                _ptr(d_scenes), R, _ptr(row_feats), _ptr(row_point)))
-        self._stage("gather")
-        pd = (PredictDesc * nm)()
-        rm = (PointRefineModel * nm)()
-        h_m = np.empty(nm, dtype=np.int32)
-        off = state.pending.state_off
-        for q, r, (f, si, row0, t, pair) in zip(pd, rm, models):
-            q.state_offset, q.row_offset, q.out_offset, q.t, q.reserved = int(off[f]), row0, row0, t, 0
-            r.row_offset, r.t, r.scene = row0, t, si
-            r.sem1, r.inst1, r.sem2, r.inst2 = pair
-        for k, m in enumerate(models):
-            d = state.descs[m[0]]
-            h_m[k] = int(d.m1 + d.m2)
-        out, pstat = self._predict_launch(state.pending.d_state, h_m, pd, row_feats, self._identity_rows(R), R)
-        self._stage("predict")
-        o = block_views(ROW_FIELDS, out, R, be)
-        d_models = be.empty(nm * C.sizeof(PointRefineModel))
-        ctx.check(lib.gapro_point_refine_apply(ctx.handle, self._sh(), ns, C.cast(scenes, C.c_void_p), _ptr(d_scenes), nm,
-                                               C.cast(rm, C.c_void_p), _ptr(d_models), R, _ptr(row_point),
-                                               _ptr(o["probs_new"]), _ptr(o["labels"]), _ptr(o["mu"]), _ptr(o["var"]),
-                                               _ptr(pstat)))
-        self._stage("apply")
-        st = _host(pstat).view(np.int32)[:nm]  # the batch waits here for its predict launch
-        if (st != 0).any():
-            for k in np.nonzero(st)[0]:
-                job = jobs[models[k][1]]
-                if job.error is None:
-                    job.error = _lib.GaproError(int(st[k]), "point-level prediction from GP fit %d of the scene failed"
-                                                % (models[k][0] - job.fit_base))
-            if self.strict:
-                raise next(j.error for j in jobs if j.error is not None)
-        return keep + [rm, d_models, pd, row_feats, row_point, out, pstat]
-
-    def _pair(self, job: SceneJob, b1: int, b2: int):
-        """(sem, inst) of a point labelled 0 (box b1) and 1 (box b2): the merge's last loop (schedule.cpp) for a box."""
-        n_fg, pair = len(job.instance_box), []
-        for box in (b1, b2):
-            pair += [int(job.boxes_cls[box]), box if box < n_fg else -100]
-        return pair
-
-    def _refine_compete(self, state: BatchState, plan, scenes, d_scenes, keep):
-        """point_level="compete" behind the broadcast: gather -> expand -> ONE gapro_svgp_predict_batch over the gathered
-        rows with the expanded row list -> apply (mu / var broadcast only) -> compete.  Failures as in _refine.  With
-        keep_models every job gets ``point_fit`` i32[N]: the scene-local fit that labelled each point, -1 elsewhere."""
-        lib, ctx, be = self.lib, self.ctx, self.be
-        jobs = state.jobs
-        D = int(state.feats_spp_all.shape[1])
-        R, R2, models = plan["rows"], plan["expanded_rows"], plan["models"]
-        ns, nm = len(jobs), len(models)
-        sp = C.cast(scenes, C.c_void_p)
-        if state.keep_models:
-            for job in jobs:
-                job.point_fit = np.full(job.n_points, -1, dtype=np.int32)
-        if R == 0:
-            ctx.check(lib.gapro_point_refine_apply(ctx.handle, self._sh(), ns, sp, _ptr(d_scenes), 0, None, None, 0, None,
-                                                   None, None, None, None, None))
-            self._stage("apply")
-            return keep
-        row_feats = be.empty_typed((R, D), be.f32)
-        row_point = be.empty(4 * R)
-        ctx.check(lib.gapro_point_refine_gather(ctx.handle, self._sh(), ns, D, sp, _ptr(d_scenes), R, _ptr(row_feats),
-                                                _ptr(row_point)))
-        self._stage("gather")
-        blocks, segs = plan["blocks"], plan["segments"]
-        nb, nsg = len(blocks), len(segs)
-        d_blocks, d_segs = be.empty(nb * BLOCK_DTYPE.itemsize), be.empty(nsg * SEGMENT_DTYPE.itemsize)
-        d_rows = be.empty(4 * R2)
-        ctx.check(lib.gapro_point_refine_expand(ctx.handle, self._sh(), nb, _ptr(blocks), _ptr(d_blocks), nsg, _ptr(segs),
-                                                _ptr(d_segs), R, R2, _ptr(d_rows)))
-        self._stage("expand")
-        pd = (PredictDesc * nm)()
-        rm = (PointRefineModel * nm)()
-        h_m = np.empty(nm, dtype=np.int32)
-        off = state.pending.state_off
-        for k, (q, r, (f, si, row0, t, b1, b2)) in enumerate(zip(pd, rm, models)):
-            q.state_offset, q.row_offset, q.out_offset, q.t, q.reserved = int(off[f]), row0, row0, t, 0
-            r.row_offset, r.t, r.scene = row0, t, si
-            r.sem1, r.inst1, r.sem2, r.inst2 = self._pair(jobs[si], b1, b2)
-            h_m[k] = int(state.descs[f].m1 + state.descs[f].m2)
-        out, pstat = self._predict_launch(state.pending.d_state, h_m, pd, row_feats, d_rows, R2)
-        self._stage("predict")
-        o = block_views(ROW_FIELDS, out, R2, be)
-        ctx.check(lib.gapro_point_refine_apply(ctx.handle, self._sh(), ns, sp, _ptr(d_scenes), 0, None, None, 0, None,
-                                               None, None, None, None, None))
-        self._stage("apply")
-        d_models = be.empty(nm * C.sizeof(PointRefineModel))
-        row_model = be.empty(4 * R) if state.keep_models else None
-        ctx.check(lib.gapro_point_refine_compete(
-            ctx.handle, self._sh(), ns, sp, _ptr(d_scenes), nm, C.cast(rm, C.c_void_p), _ptr(d_models), nb, _ptr(blocks),
-            _ptr(d_blocks), nsg, _ptr(segs), _ptr(d_segs), R, R2, _ptr(row_point), _ptr(o["probs_new"]), _ptr(o["labels"]),
-            _ptr(o["mu"]), _ptr(o["var"]), _ptr(pstat), _ptr(row_model)))
-        self._stage("compete")
-        st = _host(pstat).view(np.int32)[:nm]  # the batch waits here for its predict launch
-        if (st != 0).any():
-            for k in np.nonzero(st)[0]:
-                job = jobs[models[k][1]]
-                if job.error is None:
-                    job.error = _lib.GaproError(int(st[k]), "point-level prediction from GP fit %d of the scene failed"
-                                                % (models[k][0] - job.fit_base))
-            if self.strict:
-                raise next(j.error for j in jobs if j.error is not None)
-        if state.keep_models:
-            h_model = _host(row_model).view(np.int32)[:R]
-            h_point = _host(row_point).view(np.int32)[:R]
-            fit_of = np.array([m[0] for m in models], dtype=np.int64)
-            for job, (a, n) in zip(jobs, plan["scene_rows"]):
-                took = h_model[a:a + n]
-                ok = took >= 0
-                job.point_fit[h_point[a:a + n][ok]] = (fit_of[took[ok]] - job.fit_base).astype(np.int32)
-        return keep + [rm, d_models, pd, row_feats, row_point, out, pstat, blocks, segs, d_blocks, d_segs, d_rows,
-                       row_model]
-
-    def _refine_vote(self, state: BatchState, plan, offs, d_tables):
-        """point_level="vote", between the upload of the merge's tables and the label broadcast: gather -> expand -> ONE
-        gapro_svgp_predict_batch over the expanded rows (the chain of "compete") -> gapro_point_refine_vote, which writes
-        the five superpoint values of every refined superpoint into ``d_tables`` (``offs``: each scene's first byte).
-        Failures as in _refine.  With keep_models every job gets ``vote_box`` / ``vote_count`` i32[S], and ``winner``
-        becomes the representative fit where a vote took place."""
-        lib, ctx, be = self.lib, self.ctx, self.be
-        jobs = state.jobs
-        D = int(state.feats_spp_all.shape[1])
-        R, R2, models = plan["rows"], plan["expanded_rows"], plan["models"]
-        ns, nm = len(jobs), len(models)
-        if state.keep_models:
-            for job in jobs:
-                if job.winner is not None:  # f* goes into a copy: job.host["winner"] stays the merge's
-                    job.winner = job.winner.copy()
-                job.vote_box = np.full(job.n_spps, -1, dtype=np.int32)
-                job.vote_count = np.zeros(job.n_spps, dtype=np.int32)
-        self._stage("broadcast")  # (the name of the chain's start in every mode; here nothing has been broadcast yet)
-        if R == 0:
-            return []
-        scenes = (PointRefineScene * ns)()
-        vscenes = (PointRefineVoteScene * ns)()
-        d_scenes = be.empty(ns * C.sizeof(PointRefineScene))
-        d_vscenes = be.empty(ns * C.sizeof(PointRefineVoteScene))
-        d_sp_row = be.from_numpy(plan["sp_row"])
-        d_cursor = be.empty(4 * len(plan["sp_row"]))
-        base, tab = 0, d_tables.data_ptr()
-        for t, v, job, off in zip(scenes, vscenes, jobs, offs):
-            S = job.n_spps
-            t.n_points, t.n_spps, t.reserved = job.n_points, S, 0
-            t.spp_inv, t.feats = job.dev["spp_inv"].data_ptr(), job.feats.data_ptr()
-            t.sp_row, t.cursor = d_sp_row.data_ptr() + 8 * base, d_cursor.data_ptr() + 4 * base
-            v.sem_spp, v.inst_spp, v.prob_spp = tab + off, tab + off + 4 * S, tab + off + 8 * S
-            v.mu_spp, v.var_spp, v.n_spps, v.reserved = tab + off + 12 * S, tab + off + 16 * S, S, 0
-            base += S
-        sp = C.cast(scenes, C.c_void_p)
-        row_feats = be.empty_typed((R, D), be.f32)
-        row_point = be.empty(4 * R)
-        ctx.check(lib.gapro_point_refine_gather(ctx.handle, self._sh(), ns, D, sp, _ptr(d_scenes), R, _ptr(row_feats),
-                                                _ptr(row_point)))
-        self._stage("gather")
-        blocks, segs = plan["blocks"], plan["segments"]
-        nb, nsg = len(blocks), len(segs)
-        d_blocks, d_segs = be.empty(nb * BLOCK_DTYPE.itemsize), be.empty(nsg * SEGMENT_DTYPE.itemsize)
-        d_rows = be.empty(4 * R2)
-        ctx.check(lib.gapro_point_refine_expand(ctx.handle, self._sh(), nb, _ptr(blocks), _ptr(d_blocks), nsg, _ptr(segs),
-                                                _ptr(d_segs), R, R2, _ptr(d_rows)))
-        self._stage("expand")
-        pd = (PredictDesc * nm)()
-        rm = (PointRefineModel * nm)()
-        h_m = np.empty(nm, dtype=np.int32)
-        boxes = np.empty((nm, 2), dtype=np.int32)
-        off = state.pending.state_off
-        for k, (q, r, (f, si, row0, t, b1, b2)) in enumerate(zip(pd, rm, models)):
-            q.state_offset, q.row_offset, q.out_offset, q.t, q.reserved = int(off[f]), row0, row0, t, 0
-            r.row_offset, r.t, r.scene = row0, t, si
-            r.sem1, r.inst1, r.sem2, r.inst2 = self._pair(jobs[si], b1, b2)
-            h_m[k] = int(state.descs[f].m1 + state.descs[f].m2)
-            boxes[k] = b1, b2
-        out, pstat = self._predict_launch(state.pending.d_state, h_m, pd, row_feats, d_rows, R2)
-        self._stage("predict")
-        o = block_views(ROW_FIELDS, out, R2, be)
-        # the blocks are in (scene, superpoint) order (plan_point_compete): their scene-local superpoints
-        block_spp = np.concatenate([np.nonzero(np.asarray(j.host["winner"]) >= 0)[0] for j in jobs
-                                    if j.error is None] or [np.zeros(0, np.int64)]).astype(np.int32)
-        assert len(block_spp) == nb
-        d_models, d_boxes = be.empty(nm * C.sizeof(PointRefineModel)), be.empty(8 * nm)
-        d_block_spp = be.empty(4 * nb)
-        block_out = be.empty(12 * nb) if state.keep_models else None
-        ctx.check(lib.gapro_point_refine_vote(
-            ctx.handle, self._sh(), ns, C.cast(vscenes, C.c_void_p), _ptr(d_vscenes), nm, C.cast(rm, C.c_void_p),
-            _ptr(d_models), _ptr(boxes), _ptr(d_boxes), nb, _ptr(blocks), _ptr(d_blocks), _ptr(block_spp),
-            _ptr(d_block_spp), nsg, _ptr(segs), _ptr(d_segs), R, R2, _ptr(o["probs_new"]), _ptr(o["labels"]),
-            _ptr(o["mu"]), _ptr(o["var"]), _ptr(pstat), _ptr(block_out)))
-        self._stage("vote")
-        st = _host(pstat).view(np.int32)[:nm]  # the batch waits here for its predict launch
-        if (st != 0).any():
-            for k in np.nonzero(st)[0]:
-                job = jobs[models[k][1]]
-                if job.error is None:
-                    job.error = _lib.GaproError(int(st[k]), "point-level prediction from GP fit %d of the scene failed"
-                                                % (models[k][0] - job.fit_base))
-            if self.strict:
-                raise next(j.error for j in jobs if j.error is not None)
-        if state.keep_models:
-            h_out = _host(block_out).view(np.int32)[:3 * nb].reshape(nb, 3)
-            fit_of = np.array([m[0] for m in models], dtype=np.int64)
-            for b in np.nonzero(h_out[:, 0] >= 0)[0]:
-                job, s = jobs[int(blocks["scene"][b])], int(block_spp[b])
-                job.winner[s] = int(fit_of[h_out[b, 0]]) - job.fit_base
-                job.vote_box[s], job.vote_count[s] = h_out[b, 1], h_out[b, 2]
-        return [scenes, vscenes, d_scenes, d_vscenes, d_sp_row, d_cursor, rm, d_models, pd, row_feats, row_point, out,
-                pstat, blocks, segs, d_blocks, d_segs, d_rows, boxes, d_boxes, block_spp, d_block_spp, block_out]
-
-    def _identity_rows(self, n: int):
-        """i32[>= n] = 0, 1, 2, .. on the device (grow-only): the predict launch reads the gathered table in order."""
-        cur = self._ident_rows
-        if cur is None or cur.numel() < n:
-            cur = self._ident_rows = self.be.from_numpy(np.arange(max(n, 1 << 16) * 5 // 4, dtype=np.int32))
-            self.be.current_stream().synchronize()  # every pipeline stream reads it from now on
-        return cur
-
