@@ -47,6 +47,17 @@ class FitDesc(C.Structure):
                 ("ws_offset", C.c_int64)]
 
 
+class FitLaunchStep(C.Structure):
+    """gapro_fit_launch_step: one kernel launch of a fit batch, as gapro_fit_launch_plan reports it."""
+    _fields_ = [("kernel", C.c_int32), ("variant", C.c_int32), ("first", C.c_int32), ("count", C.c_int32),
+                ("grid", C.c_int32), ("stream", C.c_int32), ("ticket", C.c_int32), ("timing", C.c_int32),
+                ("wait_gate", C.c_int32), ("reserved", C.c_int32), ("lds_bytes", C.c_int64)]
+
+
+FIT_STEP_COPY_FREE = 8
+FIT_MAX_STEPS = 10
+
+
 class PredictDesc(C.Structure):
     """gapro_predict_desc: one model of a gapro_svgp_predict_batch launch."""
     _fields_ = [("state_offset", C.c_int64), ("row_offset", C.c_int64), ("out_offset", C.c_int64), ("t", C.c_int32),
@@ -233,6 +244,8 @@ SIGNATURES = {
     "gapro_fit_workspace_layout": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P]),
     "gapro_fit_route": (C.c_int, [C.c_int32, C.c_int32]),
     "gapro_fit_route_flags": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "gapro_fit_launch_plan": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(FitLaunchStep),
+                                        C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gapro_fit_padded_m": (C.c_int, [C.c_int32, C.c_int32]),
     "gapro_fit_timing_create": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "gapro_fit_timing_destroy": (None, [_P]),
@@ -369,7 +382,8 @@ def load() -> C.CDLL:
             variant = os.path.abspath(LIB_PATH) != os.path.abspath(default)
             if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state",
                                             "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex",
-                                            "gapro_schedule_export_testers", "gapro_spp_vote")):
+                                            "gapro_schedule_export_testers", "gapro_spp_vote",
+                                            "gapro_fit_launch_plan")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

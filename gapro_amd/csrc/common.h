@@ -65,11 +65,30 @@ struct gapro_fit_timing {
   unsigned* tickets = nullptr;  // the launch's counter set (gapro_ctx::d_tickets): [5..7] = cluster kernel diagnostics
 };
 
+// What every fit kernel of a launch is started with; the launch functions below unpack it at their hipLaunchKernelGGL.
+struct FitArgs {
+  int feat_dim;
+  const float* d_feats_spp;
+  const int* d_idx;
+  const gapro_fit_desc* d_descs;  // the whole uploaded array: a step's fits are [first, first + count) of it
+  const double* d_init_mean;
+  const gapro_fit_options* opt;
+  double* d_workspace;
+  float *d_probs, *d_probs_new;
+  unsigned char* d_labels;
+  float *d_mu, *d_var;
+  int* d_fit_status;
+  double* d_fit_loss;
+  unsigned* d_tickets;  // the launch's counter set (gapro_ctx::d_tickets); a step's counter is [step.ticket] of it
+};
+using FitLaunchStep = gapro_fit_launch_step;  // include/gapro_hip.h; planned by plan_fit_launch (svgp_fit.hip)
+inline unsigned* gapro_fit_ticket(const FitLaunchStep& s, const FitArgs& a) {
+  return s.ticket >= 0 ? a.d_tickets + s.ticket : nullptr;
+}
+
+// The launch functions: step.count fits from step.first on, step.grid workgroups, on `stream`.
 // svgp_fit_large.hip: the generic kernel (one workgroup per fit, working set in global memory)
-void gapro_launch_fit_large(hipStream_t stream, int n_fits, int feat_dim, const float* d_feats_spp, const int* d_idx,
-                            const gapro_fit_desc* d_descs, const double* d_init_mean, const gapro_fit_options& opt,
-                            double* d_workspace, float* d_probs, float* d_probs_new, unsigned char* d_labels,
-                            float* d_mu, float* d_var, int* d_fit_status, double* d_fit_loss);
+int gapro_launch_fit_large(hipStream_t stream, const FitLaunchStep& step, const FitArgs& args);
 
 // svgp_fit_wg.hip: the single-workgroup kernels with 512 threads per fit -- LDS-staged k_svgp_fit<WPS, KMIN>
 // (128 < M_p <= 512) and strip-streaming k_svgp_fit_strip (M_p <= 128)
@@ -79,26 +98,13 @@ long long gapro_fit_staged_lds_bytes(int m, int feat_dim);  // dynamic LDS of on
 bool gapro_fit_staged_ok(int m, int feat_dim);              // the staged kernel takes the fit
 long long gapro_fit_strip_lds_bytes(int m, int feat_dim);
 bool gapro_fit_strip_ok(int m, int feat_dim);
-// k_svgp_fit<wps, kmin>: <2, false>, <2, true> or <kWavesPerSimd, true>
-int gapro_launch_fit_staged(hipStream_t stream, int wps, bool kmin, int n_fits, int n_wg, unsigned* d_ticket,
-                            int feat_dim, size_t lds_bytes, const float* d_feats_spp, const int* d_idx,
-                            const gapro_fit_desc* d_descs, const double* d_init_mean, const gapro_fit_options& opt,
-                            double* d_workspace, float* d_probs, float* d_probs_new, unsigned char* d_labels,
-                            float* d_mu, float* d_var, int* d_fit_status, double* d_fit_loss);
-int gapro_launch_fit_strip(hipStream_t stream, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim,
-                           size_t lds_bytes, const float* d_feats_spp, const int* d_idx, const gapro_fit_desc* d_descs,
-                           const double* d_init_mean, const gapro_fit_options& opt, double* d_workspace,
-                           float* d_probs, float* d_probs_new, unsigned char* d_labels, float* d_mu, float* d_var,
-                           int* d_fit_status, double* d_fit_loss);
+// k_svgp_fit<wps, kmin> by step.variant: <2, false>, <2, true> or <kWavesPerSimd, true>
+int gapro_launch_fit_staged(hipStream_t stream, const FitLaunchStep& step, const FitArgs& args);
+int gapro_launch_fit_strip(hipStream_t stream, const FitLaunchStep& step, const FitArgs& args);
 
 // svgp_fit_small.hip: the strip kernel built with 256 threads per fit (M_p <= 64, two fits per CU)
 long long gapro_fit_strip_small_lds_bytes(int m, int feat_dim);
-int gapro_launch_fit_strip_small(hipStream_t stream, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim,
-                                 size_t lds_bytes, const float* d_feats_spp, const int* d_idx,
-                                 const gapro_fit_desc* d_descs, const double* d_init_mean,
-                                 const gapro_fit_options& opt, double* d_workspace, float* d_probs, float* d_probs_new,
-                                 unsigned char* d_labels, float* d_mu, float* d_var, int* d_fit_status,
-                                 double* d_fit_loss);
+int gapro_launch_fit_strip_small(hipStream_t stream, const FitLaunchStep& step, const FitArgs& args);
 
 // svgp_fit_cluster.hip
 int gapro_cluster_size(int Mp, bool all);
@@ -108,22 +114,17 @@ size_t gapro_cluster_stage_bytes(int n_fits);
 // (*out_blocks: grid size; *out_members: workgroups that run a fit, the others are padding and exit at once);
 int gapro_prepare_fit_cluster(hipStream_t prep_stream, int n, const int* fit_index, const int* fit_mp, const int* fit_g,
                               void* h_stage, void* d_stage, unsigned* d_ctl, int* out_blocks, int* out_members);
-// d_info (may be null): [0] member workgroups started, [1] clusters whose members do NOT share an XCD, [2] clusters
-int gapro_launch_fit_cluster(hipStream_t stream, int n_blocks, int feat_dim, void* d_stage, unsigned* d_ctl,
-                             unsigned* d_info, const float* d_feats_spp,
-                             const int* d_idx, const gapro_fit_desc* d_descs, const double* d_init_mean,
-                             const gapro_fit_options& opt, double* d_workspace, float* d_probs, float* d_probs_new,
-                             unsigned char* d_labels, float* d_mu, float* d_var, int* d_fit_status, double* d_fit_loss);
+// step.grid: *out_blocks (the block table names its fits by their place in args.d_descs); the step's ticket is the
+// first of three diagnostic counters: member workgroups started, clusters whose members do NOT share an XCD, clusters
+int gapro_launch_fit_cluster(hipStream_t stream, const FitLaunchStep& step, const FitArgs& args, void* d_stage,
+                             unsigned* d_ctl);
 
 // svgp_fit_wave.hip: one wave per fit (M_p <= 48 at feat_dim 6)
 int gapro_fit_wave_max_mp(int feat_dim);            // largest padded size it takes at this feature width (0: none)
 size_t gapro_fit_wave_lds_bytes(int nb, int feat_dim);
 int gapro_fit_wave_per_cu(int nb, int feat_dim);    // fits (waves) per CU of the instantiation for M_p = 16 nb
-int gapro_launch_fit_wave(hipStream_t stream, int nb, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim,
-                          const float* d_feats_spp, const int* d_idx, const gapro_fit_desc* d_descs,
-                          const double* d_init_mean, const gapro_fit_options& opt, double* d_workspace, float* d_probs,
-                          float* d_probs_new, unsigned char* d_labels, float* d_mu, float* d_var, int* d_fit_status,
-                          double* d_fit_loss);
+// step.variant: nb
+int gapro_launch_fit_wave(hipStream_t stream, const FitLaunchStep& step, const FitArgs& args);
 
 // Padded size of a fit's M x M matrices: MFMA tiles are 16 wide, so M is rounded up to a multiple of 16 (everything
 // scales with M_p^2 M: rounding M = 80 to 96 instead of 80 costs 1.4x the work).  The staged kernel's 32 x 32 wave tiles

@@ -872,20 +872,21 @@ __global__ __launch_bounds__(NT, 2) void k_svgp_fit_strip(int n_fits, int D, con
   fit_epilogue(desc, opt, o_status, o_loss);
 }
 
-// host side: launch of this translation unit's build of the kernel (gapro_launch_fit_strip / _strip_small)
-int launch_fit_strip(hipStream_t stream, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim, size_t lds_bytes,
-                     const float* d_feats_spp, const int* d_idx, const gapro_fit_desc* d_descs,
-                     const double* d_init_mean, const gapro_fit_options& opt, double* d_workspace, float* d_probs,
-                     float* d_probs_new, unsigned char* d_labels, float* d_mu, float* d_var, int* d_fit_status,
-                     double* d_fit_loss) {
-  auto kern = feat_dim == 6 ? k_svgp_fit_strip<6, 6> : feat_dim == 32 ? k_svgp_fit_strip<32, 32> : k_svgp_fit_strip<32, 0>;
+}  // namespace
+
+// host side: launch of this translation unit's build of the kernel -- gapro_launch_fit_strip (common.h), or the name
+// that the including file gives it (svgp_fit_small.hip)
+#ifndef GAPRO_LAUNCH_FIT_STRIP
+#define GAPRO_LAUNCH_FIT_STRIP gapro_launch_fit_strip
+#endif
+int GAPRO_LAUNCH_FIT_STRIP(hipStream_t stream, const FitLaunchStep& s, const FitArgs& a) {
+  auto kern = a.feat_dim == 6 ? k_svgp_fit_strip<6, 6> : a.feat_dim == 32 ? k_svgp_fit_strip<32, 32> : k_svgp_fit_strip<32, 0>;
+  const size_t lds_bytes = (size_t)s.lds_bytes;
   if (lds_bytes > 48 * 1024 &&
       hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
     return GAPRO_ERR_HIP;
-  hipLaunchKernelGGL(kern, dim3(n_wg), dim3(NT), lds_bytes, stream, n_fits, feat_dim, d_feats_spp, d_idx, d_descs,
-                     d_init_mean, opt, d_workspace, d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status,
-                     d_fit_loss, d_ticket);
+  hipLaunchKernelGGL(kern, dim3(s.grid), dim3(NT), lds_bytes, stream, s.count, a.feat_dim, a.d_feats_spp, a.d_idx,
+                     a.d_descs + s.first, a.d_init_mean, *a.opt, a.d_workspace, a.d_probs, a.d_probs_new, a.d_labels,
+                     a.d_mu, a.d_var, a.d_fit_status, a.d_fit_loss, gapro_fit_ticket(s, a));
   return hipGetLastError() == hipSuccess ? GAPRO_OK : GAPRO_ERR_HIP;
 }
-
-}  // namespace

@@ -1,6 +1,7 @@
-// Host entry of the batched whitened-SVGP classifier fit: gapro_svgp_fit_batch[_ex] routes every fit of a launch to
-// one of the fit kernels (fit_route) and starts them side by side through their launch functions (common.h);
-// workspace planning, the fit timing API and k_fit_cond, the conditioning figure of every fit.
+// Host entry of the batched whitened-SVGP classifier fit: gapro_svgp_fit_batch[_ex, _state] routes every fit of a launch
+// to one of the fit kernels (fit_route), plans the launches on the host as data (plan_fit_launch) and issues them side
+// by side from one loop through their launch functions (common.h); workspace planning, the fit timing API and
+// k_fit_cond, the conditioning figure of every fit.
 #include <math.h>
 
 #include <algorithm>
@@ -110,33 +111,226 @@ static int fit_route(int m, int feat_dim, int flags) {
 // The launch groups of gapro_svgp_fit_batch, in the order of the descriptor array it uploads.  Kernels are launched
 // in another order: cluster, large, staged, strip, small, wave 3 / 2 / 1 (LABNOTES R4.4).
 enum FitGroupId { G_LARGE, G_STAGED, G_STRIP, G_SMALL, G_CLUSTER, G_WAVE3, G_WAVE2, G_WAVE1, kFitGroups };
-struct FitGroup {
-  int stream;  // ctx->fit_stream index
-  int ticket;  // counter of the launch's ticket set (-1: none)
-  int timing;  // gapro_fit_timing kernel k: events ev[2 k] (start), ev[2 k + 1] (end)
-  int join;    // ctx->ev_join index that joins `stream` back into the caller's stream
-  std::vector<gapro_fit_desc> descs;  // longest first
-  size_t base = 0;                    // offset of descs in the uploaded array
-  long long max_lds = 0;              // largest dynamic LDS need of a fit
+static int fit_group(int route, int m, int feat_dim) {  // (a wave fit's by its block count: M_p = 16 nb)
+  static const int of_route[6] = {G_STRIP, G_STAGED, G_LARGE, G_SMALL, G_CLUSTER, G_WAVE1};
+  return route == GAPRO_FIT_KERNEL_WAVE ? G_WAVE1 + 1 - gapro_pad_m(m, feat_dim) / 16 : of_route[route];
+}
+// kernel (GAPRO_FIT_KERNEL_*), fit stream (gapro_ctx::fit_stream), first counter of the launch's ticket set and timing
+// class (gapro_fit_timing) of every group
+static const struct { int kernel, stream, ticket, timing; } kFitGroupLaunch[kFitGroups] = {
+    {2, 0, -1, 0},  // large: the generic kernel, ahead of the staged fits on their stream
+    {1, 0, 0, 0},   // staged: tickets 0 .. 2 for its three launches; the third may go to fit stream 4 (below)
+    {0, 1, 3, 1},   // strip
+    {3, 2, 4, 2},   // small
+    {4, 3, 5, 3},   // cluster: tickets 5 .. 7 are its diagnostics (gapro_fit_timing_cluster_info)
+    {5, 5, 10, 4},  // wave, M_p = 48
+    {5, 6, 9, 4},   // wave, M_p = 32
+    {5, 7, 8, 4},   // wave, M_p = 16
 };
-static int fit_group(int route, int m, int feat_dim) {
-  switch (route) {
-    case 0: return G_STRIP;
-    case 1: return G_STAGED;
-    case 3: return G_SMALL;
-    case 4: return G_CLUSTER;
-    case 5: return G_WAVE1 + 1 - gapro_pad_m(m, feat_dim) / 16;  // M_p = 16 nb
-    default: return G_LARGE;
+constexpr int kStaged2 = 4;  // fit stream and join event of the two-per-CU staged launch beside the others
+
+// Everything gapro_svgp_fit_batch decides from the sizes of its fits and its debug flags, before it touches the device:
+// plan_fit_launch is a pure function (gapro_fit_launch_plan hands it out; tests/test_fit_plan_cpu.py holds it to the
+// decisions of rounds 4 to 6 that the comments below record).
+struct FitLaunchPlan {
+  std::vector<gapro_fit_desc> descs;        // in upload order: the groups of FitGroupId, each longest first
+  long long ws_bytes = 0;                   // workspace the fits' ws_offset need
+  std::vector<int> cl_index, cl_mp, cl_g;   // cluster fits: place in descs, padded size, workgroups per cluster
+  FitLaunchStep steps[GAPRO_FIT_MAX_STEPS]; // in the order of issue
+  int n_steps = 0;
+  int bad_fit = -1;                         // first fit with an empty side (nothing else is valid then)
+  int slow_m = 0;                           // M of the first fit beyond the cluster kernel's cap, on the generic kernel
+};
+
+static FitLaunchPlan plan_fit_launch(const gapro_fit_desc* h_descs, int n_fits, int feat_dim, int flags, int n_cu) {
+  FitLaunchPlan p;
+  // Routing (gapro_fit_route).  Every group is sorted longest processing time first (cost ~ M^3): workgroups are
+  // dispatched in block order, so the expensive fits start first and the tail of a launch stays short.  One sort by
+  // (group, M descending, input index) does it.
+  struct Key { int group, m, i; };
+  std::vector<Key> keys(n_fits);
+  size_t count[kFitGroups] = {}, base[kFitGroups];
+  for (int i = 0; i < n_fits; ++i) {
+    const gapro_fit_desc& d = h_descs[i];
+    const int m = d.m1 + d.m2;
+    if (d.m1 <= 0 || d.m2 <= 0 || d.t < 0) {
+      p.bad_fit = i;
+      return p;
+    }
+    p.ws_bytes = std::max<long long>(p.ws_bytes, (d.ws_offset + gapro_fit_workspace_doubles(m, d.t, feat_dim)) * 8LL);
+    const int g = fit_group(fit_route(m, feat_dim, flags), m, feat_dim);
+    keys[i] = {g, m, i};
+    ++count[g];
+    // beyond the cluster kernel's cap (kClusterMaxMp: its merge inverse keeps one LDS record per pair of panels) a
+    // fit runs on ONE workgroup of the generic kernel: correct, but minutes per fit -- never silently (ADVICE r03)
+    if (g == G_LARGE && feat_dim <= 32 && gapro_pad_m(m, feat_dim) > kClusterMaxMp && !p.slow_m) p.slow_m = m;
   }
-}
-static long long fit_lds_bytes(int group, int m, int feat_dim) {
-  switch (group) {
-    case G_STRIP: return gapro_fit_strip_lds_bytes(m, feat_dim);
-    case G_SMALL: return gapro_fit_strip_small_lds_bytes(m, feat_dim);
-    case G_STAGED: return gapro_fit_staged_lds_bytes(m, feat_dim);
-    default: return 0;
+  std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
+    return a.group != b.group ? a.group < b.group : a.m != b.m ? a.m > b.m : a.i < b.i;
+  });
+  p.descs.resize(n_fits);
+  for (int k = 0; k < n_fits; ++k) {
+    p.descs[k] = h_descs[keys[k].i];
+    p.descs[k].slot = keys[k].i;
   }
+  for (int g = 0; g < kFitGroups; ++g) base[g] = g ? base[g - 1] + count[g - 1] : 0;
+  const gapro_fit_desc* staged = p.descs.data() + base[G_STAGED];
+  // the staged fits whose LDS fits a CU twice and the larger ones are two launches (see below)
+  const long long kTwice = 72 * 1024;
+  size_t nbig = 0, nkmaj = 0;  // sorted by M, the LDS need grows with M: [0, nkmaj) M_p > kKminMaxMp, [0, nbig) "big"
+  long long lds_big = 0, lds_rest = 0, lds_kmaj = 0;
+  for (size_t k = 0; k < count[G_STAGED]; ++k) {
+    const int m = staged[k].m1 + staged[k].m2;
+    const long long b = gapro_fit_staged_lds_bytes(m, feat_dim);
+    // (the product forms of a fit are a function of its M_p, k_svgp_fit's KMIN: fits beyond kKminMaxMp are a launch of
+    // their own -- with D = 6 exactly the fits that need more than kTwice)
+    const bool kmaj = gapro_pad_m(m, feat_dim) > kKminMaxMp;
+    if (kmaj) {
+      ++nkmaj;
+      lds_kmaj = std::max(lds_kmaj, b);
+    }
+    if (kmaj || b > kTwice) {
+      ++nbig;
+      if (!kmaj) lds_big = std::max(lds_big, b);
+    } else {
+      lds_rest = std::max(lds_rest, b);
+    }
+  }
+  // Default since round 4: ticket counters (claim_fit) -- the fits stay in plain longest-first order and are taken by
+  // the workgroups in the order in which they start; GAPRO_FIT_DBG_STATIC_MAP restores the mapping fit = blockIdx.x
+  const bool tickets = !(flags & GAPRO_FIT_DBG_STATIC_MAP);
+  if (!tickets) {
+    // Workgroup b of a launch runs on XCD b % 8 (one slice of 32 CUs; the cluster kernel's same-XCD barrier relies on
+    // the same fact and checks it), so in longest-first order XCD 0 would get the largest fit of every group of eight
+    // and XCD 7 the smallest, in every kernel: at the end of a launch four XCDs sat idle for ~50 ms while the others
+    // still had their share of strip fits (tools/fit_timeline.py).  Every second group of eight is reversed.
+    auto serpentine = [&](size_t lo, size_t hi) {
+      for (size_t g0 = lo + 8; g0 + 8 <= hi; g0 += 16) std::reverse(p.descs.begin() + g0, p.descs.begin() + g0 + 8);
+    };
+    serpentine(base[G_STRIP], base[G_STRIP] + count[G_STRIP]);
+    serpentine(base[G_SMALL], base[G_SMALL] + count[G_SMALL]);
+    serpentine(base[G_STAGED], base[G_STAGED] + nbig);
+    serpentine(base[G_STAGED] + nbig, base[G_STAGED] + count[G_STAGED]);
+  }
+  p.cl_index.resize(count[G_CLUSTER]);
+  p.cl_mp.resize(count[G_CLUSTER]);
+  p.cl_g.resize(count[G_CLUSTER]);
+  for (size_t k = 0; k < count[G_CLUSTER]; ++k) {
+    const gapro_fit_desc& d = p.descs[base[G_CLUSTER] + k];
+    p.cl_index[k] = (int)(base[G_CLUSTER] + k);
+    p.cl_mp[k] = gapro_pad_m(d.m1 + d.m2, feat_dim);
+    p.cl_g[k] = gapro_cluster_size(p.cl_mp[k], true);
+  }
+  // The kernels go to the context's fit streams so that the staged kernel (a few large fits, which leave most CUs
+  // idle), the strip kernels and the others run side by side; GAPRO_FIT_DBG_CALLER_STREAM keeps them on the caller's
+  const bool own = !(flags & GAPRO_FIT_DBG_CALLER_STREAM);
+  // a step of group g: fits [first, first + n) of the group, counter `part` of the group's
+  auto step = [&](int g, size_t first, size_t n, int variant, size_t grid, long long lds,
+                  int part = 0) -> FitLaunchStep& {
+    const auto& L = kFitGroupLaunch[g];
+    FitLaunchStep& s = p.steps[p.n_steps++];
+    s = FitLaunchStep{L.kernel, variant, (int)(base[g] + first), (int)n, (int)grid, own ? L.stream : -1,
+                      tickets && L.ticket >= 0 ? L.ticket + part : -1, L.timing, 0, 0, lds};
+    return s;
+  };
+  // grid of a ticketed kernel: twice its fits, so that an XCD (a fixed eighth of the grid) can run up to twice its share
+  auto grid_of = [&](size_t n) { return tickets ? 2 * n : n; };
+  auto max_lds = [&](int g, long long (*bytes)(int, int)) {  // largest dynamic LDS need of a fit of the group
+    long long b = 0;
+    for (size_t k = 0; k < count[g]; ++k)
+      b = std::max(b, bytes(p.descs[base[g] + k].m1 + p.descs[base[g] + k].m2, feat_dim));
+    return b;
+  };
+  // First the largest fits of the launch, each over several CUs.
+  // (Round 4, tried: holding the other kernels back until the cluster's members are resident.  They are within 1 .. 15
+  // us anyway, and every cluster sits on one XCD (gapro_fit_timing_cluster_info); what makes the same cluster kernel
+  // take 240 ms in one run of a step and 500 ms in the next is what runs beside it -- LABNOTES R4.4.)
+  if (count[G_CLUSTER]) step(G_CLUSTER, 0, count[G_CLUSTER], 0, 0, 0);
+  // gate of the two-per-CU staged launch and of the small fits (below): behind the cluster kernel
+  const bool gate = count[G_CLUSTER] && own;
+  if (count[G_LARGE]) step(G_LARGE, 0, count[G_LARGE], 0, count[G_LARGE], 0);
+  // The dynamic LDS of a launch is its largest fit's, and beyond ~72 KiB (M_p > 256 at D = 6) a CU holds ONE
+  // workgroup whatever the registers allow: a launch with one such fit ran every staged fit one per CU.  So the
+  // staged fits go out as two launches side by side: those whose LDS fits a CU twice in the `<4>` build (128 VGPRs,
+  // two workgroups per CU: 17 % more fits/s at M <= 256 than one per CU), the larger ones in the `<2>` build (the
+  // whole register file, no spills).  Either part with fewer fits than CUs takes `<2>` as well.
+  auto staged_step = [&](size_t first, size_t n, long long lds, bool kmaj, int part) -> FitLaunchStep& {
+    const bool one_per_cu = (int)n <= n_cu || lds > kTwice;
+    return step(G_STAGED, first, n, kmaj ? 2 : (one_per_cu ? 2 : kWavesPerSimd) | GAPRO_FIT_STEP_COPY_FREE, grid_of(n),
+                lds, part);
+  };
+  if (nkmaj > 0) staged_step(0, nkmaj, lds_kmaj, true, 0);
+  // M_p <= kKminMaxMp with an LDS need beyond kTwice (wide features): behind the former
+  if (nbig > nkmaj) staged_step(nkmaj, nbig - nkmaj, lds_big, false, 1);
+  if (nbig < count[G_STAGED]) {
+    FitLaunchStep& s = staged_step(nbig, count[G_STAGED] - nbig, lds_rest, false, 2);
+    if (nbig > 0 && own) s.stream = kStaged2;  // beside the larger ones
+    // The two-per-CU staged fits are the launch's memory-bound class (3.8 FLOP/B: with the chip to themselves they
+    // sit on the HBM roof), the cluster fits its latency-bound one (a chain of cluster barriers and small products
+    // per Adam step).  Side by side from the start, the same cluster kernel took 230 .. 270 ms or 500 .. 800 ms
+    // depending on which kernels the runtime happened to put on one hardware queue (LABNOTES R4.4); so the order is
+    // explicit: this launch starts when the cluster kernel has ended -- small and strip fits, light on memory, take
+    // the CUs beside the clusters meanwhile.  Same box, 2 x 8 steps: 361 .. 372 scenes/s with 4 or 8 hardware queues
+    // (GPU_MAX_HW_QUEUES), the cluster kernel at its undisturbed time in every step; without the gate 368 / 372 with
+    // the default 4 queues (the lucky mapping) and 351 .. 362 with 8.
+    s.wait_gate = gate;
+  }
+  if (count[G_STRIP])
+    step(G_STRIP, 0, count[G_STRIP], 0, grid_of(count[G_STRIP]), max_lds(G_STRIP, gapro_fit_strip_lds_bytes));
+  // the small fits start behind the cluster kernel as well: beside the clusters run the whole-CU strip fits and the
+  // one-per-CU staged fits, and every CU half the two-per-CU staged fits leave later goes to a small fit, light on
+  // memory, instead of a second memory-bound one -- 367.8 / 367.4 / 362.6 scenes/s against 364.0 / 363.2 / 356.1
+  // without this gate, alternating on one box
+  if (count[G_SMALL])
+    step(G_SMALL, 0, count[G_SMALL], 0, grid_of(count[G_SMALL]), max_lds(G_SMALL, gapro_fit_strip_small_lds_bytes))
+        .wait_gate = gate;
+  // One wave per fit (svgp_fit_wave.hip), one kernel per block count, side by side on their own streams; the waves of a
+  // kernel take its fits by ticket until none is left.  They touch no memory between their first and last step, so
+  // nothing holds them back: they take whatever wave slots and LDS the other kernels leave.
+  for (int g = G_WAVE3; g <= G_WAVE1; ++g) {
+    if (!count[g]) continue;
+    const int nb = G_WAVE1 + 1 - g;
+    const int slots = n_cu * gapro_fit_wave_per_cu(nb, feat_dim);
+    step(g, 0, count[g], nb, std::min<size_t>(count[g], (size_t)std::max(slots, 1)), 0);
+  }
+  return p;
 }
+
+// Grows the context's buffers to the launch: the state offsets by fit slot (n_state fits: 0 without a state export) and
+// the cluster kernel's staging (n_clus fits): block table and one barrier counter line per fit, two halves of each.
+static int grow_fit_buffers(gapro_ctx* ctx, size_t n_state, size_t n_clus) {
+  if (n_state > ctx->state_off_cap) {
+    if (ctx->d_state_off) (void)hipFree(ctx->d_state_off);
+    ctx->d_state_off = nullptr;
+    ctx->state_off_cap = 0;
+    const size_t cap = std::max<size_t>(1024, 2 * n_state);
+    GAPRO_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_state_off, cap * sizeof(long long)));
+    ctx->state_off_cap = cap;
+  }
+  const size_t need_stage = n_clus ? gapro_cluster_stage_bytes((int)n_clus) : 0;
+  if (2 * need_stage > ctx->cl_stage_bytes) {  // cl_stage_bytes counts BOTH halves; a launch uses one of them
+    if (ctx->h_cl_stage) (void)hipHostFree(ctx->h_cl_stage);
+    if (ctx->d_cl_stage) (void)hipFree(ctx->d_cl_stage);
+    ctx->h_cl_stage = ctx->d_cl_stage = nullptr;
+    ctx->cl_stage_bytes = 0;
+    GAPRO_HIP_CHECK(ctx, hipHostMalloc(&ctx->h_cl_stage, 2 * need_stage, hipHostMallocDefault));
+    GAPRO_HIP_CHECK(ctx, hipMalloc(&ctx->d_cl_stage, 2 * need_stage));
+    ctx->cl_stage_bytes = 2 * need_stage;
+  }
+  if (n_clus > ctx->cl_ctl_fits) {
+    if (ctx->d_cl_ctl) (void)hipFree(ctx->d_cl_ctl);
+    ctx->d_cl_ctl = nullptr;
+    ctx->cl_ctl_fits = 0;
+    GAPRO_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_cl_ctl, 2 * 2 * n_clus * 128));  // two halves
+    ctx->cl_ctl_fits = 2 * n_clus;
+  }
+  return GAPRO_OK;
+}
+
+// launch function and name of a step's kernel, by GAPRO_FIT_KERNEL_* (the cluster kernel's takes its staging as well)
+static const struct { int (*launch)(hipStream_t, const FitLaunchStep&, const FitArgs&); const char* name; } kFitKernel[6] = {
+    {gapro_launch_fit_strip, "strip"}, {gapro_launch_fit_staged, "staged"},   {gapro_launch_fit_large, "generic"},
+    {gapro_launch_fit_strip_small, "small-fit"}, {nullptr, "cluster"}, {gapro_launch_fit_wave, "wave"}};
 
 extern "C" {
 
@@ -221,133 +415,36 @@ int gapro_svgp_fit_batch_state(gapro_ctx* ctx, void* stream_, int32_t n_fits, in
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch: unknown or retired debug bits 0x%x in reserved",
                       (unsigned)(route_flags & ~GAPRO_FIT_DBG_ALL));
   hipStream_t stream = (hipStream_t)stream_;
-  FitGroup grp[kFitGroups] = {
-      // stream, ticket, timing, join
-      {0, -1, 0, 0},  // large: the generic kernel, ahead of the staged fits on their stream
-      {0, 0, 0, 0},   // staged: tickets 0 .. 2 for its three launches; the third may go to fit stream 4 (below)
-      {1, 3, 1, 1},   // strip
-      {2, 4, 2, 2},   // small
-      {3, 5, 3, 3},   // cluster: tickets 5 .. 7 are its diagnostics (gapro_fit_timing_cluster_info)
-      {5, 10, 4, 7},  // wave, M_p = 48
-      {6, 9, 4, 6},   // wave, M_p = 32
-      {7, 8, 4, 5},   // wave, M_p = 16
-  };
-  FitGroup &large = grp[G_LARGE], &staged = grp[G_STAGED], &strip = grp[G_STRIP], &small = grp[G_SMALL],
-           &clus = grp[G_CLUSTER];
-  strip.descs.reserve(n_fits);
-  small.descs.reserve(n_fits);
-  // Routing (gapro_fit_route).  Every group is sorted longest processing time first (cost ~ M^3): workgroups are
-  // dispatched in block order, so the expensive fits start first and the tail of a launch stays short.
-  long long need = 0;
-  for (int i = 0; i < n_fits; ++i) {
-    gapro_fit_desc d = h_descs[i];
-    const int m = d.m1 + d.m2;
-    if (d.m1 <= 0 || d.m2 <= 0 || d.t < 0)
-      return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch: fit %d has an empty side", i);
-    d.slot = i;
-    need = std::max<long long>(need, (d.ws_offset + gapro_fit_workspace_doubles(m, d.t, feat_dim)) * 8LL);
-    const int g = fit_group(fit_route(m, feat_dim, route_flags), m, feat_dim);
-    grp[g].descs.push_back(d);
-    grp[g].max_lds = std::max(grp[g].max_lds, fit_lds_bytes(g, m, feat_dim));
-    // beyond the cluster kernel's cap (kClusterMaxMp: its merge inverse keeps one LDS record per pair of panels) a
-    // fit runs on ONE workgroup of the generic kernel: correct, but minutes per fit -- never silently (ADVICE r03)
-    if (g == G_LARGE && feat_dim <= 32 && gapro_pad_m(m, feat_dim) > gapro_fit::kClusterMaxMp) {
-      static bool warned = false;
-      if (!warned) {
-        warned = true;
-        fprintf(stderr, "libgapro_hip: a GP fit with M = %d inducing points exceeds the multi-workgroup kernel's cap "
-                        "(M_p <= %d): it runs on one workgroup of the generic kernel (minutes per fit)\n", m,
-                gapro_fit::kClusterMaxMp);
-      }
+  const FitLaunchPlan plan = plan_fit_launch(h_descs, n_fits, feat_dim, route_flags, ctx->n_cu);
+  if (plan.bad_fit >= 0)
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch: fit %d has an empty side", plan.bad_fit);
+  if (plan.slow_m) {
+    static bool warned = false;
+    if (!warned) {
+      warned = true;
+      fprintf(stderr, "libgapro_hip: a GP fit with M = %d inducing points exceeds the multi-workgroup kernel's cap "
+                      "(M_p <= %d): it runs on one workgroup of the generic kernel (minutes per fit)\n", plan.slow_m,
+              gapro_fit::kClusterMaxMp);
     }
   }
-  if ((size_t)need > workspace_bytes)
-    return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_svgp_fit_batch: workspace too small (%lld > %zu)", need,
+  if ((size_t)plan.ws_bytes > workspace_bytes)
+    return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_svgp_fit_batch: workspace too small (%lld > %zu)", plan.ws_bytes,
                       workspace_bytes);
   if (d_state) {  // every fit's state inside the caller's buffer; the offsets go up with the descriptors (below)
     if (!h_state_offsets) return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_svgp_fit_batch_state: no state offsets");
     for (int i = 0; i < n_fits; ++i) {
       const long long end = h_state_offsets[i] + state_doubles(h_descs[i].m1 + h_descs[i].m2, feat_dim);
       if (h_state_offsets[i] < 0 || (unsigned long long)end * 8ULL > state_bytes)
-        return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_svgp_fit_batch_state: state of fit %d ends at %lld bytes of %zu",
-                          i, end * 8LL, state_bytes);
-    }
-    if ((size_t)n_fits > ctx->state_off_cap) {
-      if (ctx->d_state_off) (void)hipFree(ctx->d_state_off);
-      ctx->d_state_off = nullptr;
-      ctx->state_off_cap = 0;
-      const size_t cap = std::max<size_t>(1024, 2 * (size_t)n_fits);
-      GAPRO_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_state_off, cap * sizeof(long long)));
-      ctx->state_off_cap = cap;
+        return gapro_fail(ctx, GAPRO_ERR_WORKSPACE,
+                          "gapro_svgp_fit_batch_state: state of fit %d ends at %lld bytes of %zu", i, end * 8LL, state_bytes);
     }
   }
-  auto by_cost = [](const gapro_fit_desc& a, const gapro_fit_desc& b) { return a.m1 + a.m2 > b.m1 + b.m2; };
-  for (FitGroup& g : grp) std::stable_sort(g.descs.begin(), g.descs.end(), by_cost);
-  // the staged fits whose LDS fits a CU twice and the larger ones are two launches (see below)
-  const long long kTwice = 72 * 1024;
-  size_t nbig = 0, nkmaj = 0;  // sorted by M, the LDS need grows with M: [0, nkmaj) M_p > kKminMaxMp, [0, nbig) "big"
-  long long lds_big = 0, lds_rest = 0, lds_kmaj = 0;
-  for (const gapro_fit_desc& d : staged.descs) {
-    const long long b = gapro_fit_staged_lds_bytes(d.m1 + d.m2, feat_dim);
-    // (the product forms of a fit are a function of its M_p, k_svgp_fit's KMIN: fits beyond kKminMaxMp are a launch of
-    // their own -- with D = 6 exactly the fits that need more than kTwice)
-    const bool kmaj = gapro_pad_m(d.m1 + d.m2, feat_dim) > kKminMaxMp;
-    if (kmaj) {
-      ++nkmaj;
-      lds_kmaj = std::max(lds_kmaj, b);
-    }
-    if (kmaj || b > kTwice) {
-      ++nbig;
-      if (!kmaj) lds_big = std::max(lds_big, b);
-    } else {
-      lds_rest = std::max(lds_rest, b);
-    }
-  }
-  // Workgroup b of a launch runs on XCD b % 8 (one slice of 32 CUs; the cluster kernel's same-XCD barrier relies on the
-  // same fact and checks it), so in longest-first order XCD 0 would get the largest fit of every group of eight and XCD
-  // 7 the smallest, in every kernel: at the end of a launch four XCDs sat idle for ~50 ms while the others still had
-  // their share of strip fits (tools/fit_timeline.py).  Every second group of eight is reversed.
-  auto serpentine = [](std::vector<gapro_fit_desc>& v, size_t lo, size_t hi) {
-    for (size_t g0 = lo + 8; g0 + 8 <= hi; g0 += 16) std::reverse(v.begin() + g0, v.begin() + g0 + 8);
-  };
-  // Default since round 4: ticket counters (claim_fit) -- the fits stay in plain longest-first order and are taken by
-  // the workgroups in the order in which they start; GAPRO_FIT_DBG_STATIC_MAP restores the mapping fit = blockIdx.x
-  const bool tickets = !(route_flags & GAPRO_FIT_DBG_STATIC_MAP) && ctx->d_tickets;
-  if (!tickets) {
-    serpentine(strip.descs, 0, strip.descs.size());
-    serpentine(small.descs, 0, small.descs.size());
-    serpentine(staged.descs, 0, nbig);
-    serpentine(staged.descs, nbig, staged.descs.size());
-  }
-  std::vector<gapro_fit_desc> all;
-  all.reserve(n_fits);
-  for (FitGroup& g : grp) {
-    g.base = all.size();
-    all.insert(all.end(), g.descs.begin(), g.descs.end());
-  }
-  if (!clus.descs.empty()) {  // staging of the cluster kernel: block table + one barrier counter line per fit
-    const size_t need_stage = gapro_cluster_stage_bytes((int)clus.descs.size());
-    if (2 * need_stage > ctx->cl_stage_bytes) {  // cl_stage_bytes counts BOTH halves; a launch uses one of them
-      if (ctx->h_cl_stage) (void)hipHostFree(ctx->h_cl_stage);
-      if (ctx->d_cl_stage) (void)hipFree(ctx->d_cl_stage);
-      ctx->h_cl_stage = ctx->d_cl_stage = nullptr;
-      ctx->cl_stage_bytes = 0;
-      GAPRO_HIP_CHECK(ctx, hipHostMalloc(&ctx->h_cl_stage, 2 * need_stage, hipHostMallocDefault));
-      GAPRO_HIP_CHECK(ctx, hipMalloc(&ctx->d_cl_stage, 2 * need_stage));
-      ctx->cl_stage_bytes = 2 * need_stage;
-    }
-    if (clus.descs.size() > ctx->cl_ctl_fits) {
-      if (ctx->d_cl_ctl) (void)hipFree(ctx->d_cl_ctl);
-      ctx->d_cl_ctl = nullptr;
-      ctx->cl_ctl_fits = 0;
-      GAPRO_HIP_CHECK(ctx, hipMalloc((void**)&ctx->d_cl_ctl, 2 * 2 * clus.descs.size() * 128));  // two halves
-      ctx->cl_ctl_fits = 2 * clus.descs.size();
-    }
-  }
-  // ticket counters of this launch (FitGroup::ticket; kTicketsPerSet of them).  The sets rotate, so that a set is zeroed
-  // again only kTicketSets launches later
+  const size_t n_clus = plan.cl_index.size();
+  if (const int rc = grow_fit_buffers(ctx, d_state ? (size_t)n_fits : 0, n_clus)) return rc;
+  // ticket counters of this launch (FitLaunchStep::ticket; kTicketsPerSet of them).  The sets rotate, so that a set is
+  // zeroed again only kTicketSets launches later
   unsigned* tk = nullptr;
-  if (tickets) {
+  if (!(route_flags & GAPRO_FIT_DBG_STATIC_MAP)) {
     tk = ctx->d_tickets + (size_t)(ctx->ticket_seq++ % gapro_ctx::kTicketSets) * gapro_ctx::kTicketsPerSet;
     GAPRO_HIP_CHECK(ctx, hipMemsetAsync(tk, 0, gapro_ctx::kTicketsPerSet * sizeof(unsigned), stream));
   }
@@ -356,14 +453,7 @@ int gapro_svgp_fit_batch_state(gapro_ctx* ctx, void* stream_, int32_t n_fits, in
   int cl_blocks = 0, cl_members = 0, cl_par = 0;
   char* cl_d_half = nullptr;
   unsigned* cl_ctl_half = nullptr;
-  if (!clus.descs.empty()) {
-    const size_t n = clus.descs.size();
-    std::vector<int> fi(n), fmp(n), fg(n);
-    for (size_t k = 0; k < n; ++k) {
-      fi[k] = (int)(clus.base + k);
-      fmp[k] = gapro_pad_m(clus.descs[k].m1 + clus.descs[k].m2, feat_dim);
-      fg[k] = gapro_cluster_size(fmp[k], true);
-    }
+  if (n_clus) {
     // the block table is built in one half of the context's pinned buffer, the halves alternating per launch: the
     // copy of launch i - 2 has long been consumed (callers collect a launch before they issue the one after next),
     // so the host never waits for the previous cluster kernel here
@@ -379,177 +469,86 @@ int gapro_svgp_fit_batch_state(gapro_ctx* ctx, void* stream_, int32_t n_fits, in
     cl_d_half = (char*)ctx->d_cl_stage + par * (ctx->cl_stage_bytes / 2);
     cl_ctl_half = ctx->d_cl_ctl + par * ctx->cl_ctl_fits * 32;
     ctx->cl_parity++;
-    const int rc = gapro_prepare_fit_cluster(stream, (int)n, fi.data(), fmp.data(), fg.data(), h_half, cl_d_half,
-                                             cl_ctl_half, &cl_blocks, &cl_members);
+    const int rc = gapro_prepare_fit_cluster(stream, (int)n_clus, plan.cl_index.data(), plan.cl_mp.data(),
+                                             plan.cl_g.data(), h_half, cl_d_half, cl_ctl_half, &cl_blocks, &cl_members);
     if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: cluster block table upload failed");
   }
-  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_descs, all.data(), all.size() * sizeof(gapro_fit_desc), hipMemcpyHostToDevice,
-                                      stream));
+  GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_descs, plan.descs.data(), plan.descs.size() * sizeof(gapro_fit_desc),
+                                      hipMemcpyHostToDevice, stream));
   if (d_state)
     GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(ctx->d_state_off, h_state_offsets, (size_t)n_fits * sizeof(long long),
                                         hipMemcpyHostToDevice, stream));
-  GAPRO_HIP_CHECK(ctx, hipStreamSynchronize(stream));  // `all` is pageable host memory that dies with this call
-  // The kernels go to the context's fit streams so that the staged kernel (a few large fits, which leave most CUs
-  // idle), the strip kernels and the others run side by side.  No fork event is needed: `stream` has just been
-  // synchronised, so everything the kernels read is complete (and an event recorded here completes together with the
-  // NEXT dispatch of `stream` under this runtime, which would serialise the kernels again).  All are joined back into
-  // `stream` with events.
-  bool own = !(route_flags & GAPRO_FIT_DBG_CALLER_STREAM);
-  for (int k = 0; k < gapro_ctx::kFitStreams; ++k) own = own && ctx->fit_stream[k];
+  GAPRO_HIP_CHECK(ctx, hipStreamSynchronize(stream));  // plan.descs is pageable host memory that dies with this call
+  // No fork event is needed for the fit streams: `stream` has just been synchronised, so everything the kernels read is
+  // complete (and an event recorded here completes together with the NEXT dispatch of `stream` under this runtime,
+  // which would serialise the kernels again).  All are joined back into `stream` with events.
+  // A timing class (FitLaunchStep::timing) is the steps that share a pair of timing marks: its stream is its first
+  // step's, [first, last] are its steps in the order of issue.
+  constexpr int NK = gapro_fit_timing::kKernels;
+  int first[NK], last[NK];
+  for (int c = 0; c < NK; ++c) first[c] = last[c] = -1;
+  for (int k = 0; k < plan.n_steps; ++k) {
+    const int c = plan.steps[k].timing;
+    if (first[c] < 0) first[c] = k;
+    last[c] = k;
+  }
   gapro_fit_timing* tm = ctx->armed_timing;
   ctx->armed_timing = nullptr;
   if (tm) {
     tm->tickets = tk;
-    for (bool& u : tm->used) u = false;
-    for (const FitGroup& g : grp) tm->used[g.timing] = tm->used[g.timing] || !g.descs.empty();
+    for (int c = 0; c < NK; ++c) tm->used[c] = first[c] >= 0;
   }
-  auto on = [&](const FitGroup& g) { return own ? ctx->fit_stream[g.stream] : stream; };
-  auto ticket = [&](const FitGroup& g, int k = 0) { return tk && g.ticket >= 0 ? tk + g.ticket + k : nullptr; };
-  auto mark = [&](const FitGroup& g, int end) {  // timing event: start (0) or end (1) of the group's kernels
-    return tm ? hipEventRecord(tm->ev[2 * g.timing + end], on(g)) : hipSuccess;
+  auto on = [&](const FitLaunchStep& s) { return s.stream >= 0 ? ctx->fit_stream[s.stream] : stream; };
+  auto mark = [&](const FitLaunchStep& s, int end) {  // timing event of the step's class on its stream: start, end
+    return tm ? hipEventRecord(tm->ev[2 * s.timing + end], on(s)) : hipSuccess;
   };
-  // grid of a ticketed kernel: twice its fits, so that an XCD (a fixed eighth of the grid) can run up to twice its share
-  auto grid_of = [&](size_t n) { return (int)(tickets ? 2 * n : n); };
-  bool gate = false;
-  if (!clus.descs.empty()) {  // first: the largest fits of the launch, each over several CUs
-    GAPRO_HIP_CHECK(ctx, mark(clus, 0));
-    // (Round 4, tried: holding the other kernels back until the cluster's members are resident.  They are within 1 .. 15
-    // us anyway, and every cluster sits on one XCD (gapro_fit_timing_cluster_info); what makes the same cluster kernel
-    // take 240 ms in one run of a step and 500 ms in the next is what runs beside it -- LABNOTES R4.4.)
-    const int rc = gapro_launch_fit_cluster(on(clus), cl_blocks, feat_dim, cl_d_half, cl_ctl_half, ticket(clus),
-                                            d_feats_spp, d_idx, d_descs, d_init_mean, *opt, d_workspace, d_probs,
-                                            d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
-    if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: cluster kernel launch failed");
-    GAPRO_HIP_CHECK(ctx, mark(clus, 1));
-    GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_clus_half[cl_par], on(clus)));
-    ctx->clus_half_used[cl_par] = true;
-    // gate of the two-per-CU staged launch and of the small fits (below): behind the cluster kernel
-    gate = own;
-    if (gate) GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_gate, on(clus)));
-  }
-  const bool staged_class = !large.descs.empty() || !staged.descs.empty();  // one stream, timing pair and join
-  if (staged_class) GAPRO_HIP_CHECK(ctx, mark(staged, 0));
-  if (!large.descs.empty())
-    gapro_launch_fit_large(on(large), (int)large.descs.size(), feat_dim, d_feats_spp, d_idx, d_descs + large.base,
-                           d_init_mean, *opt, d_workspace, d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status,
-                           d_fit_loss);
-  if (!staged.descs.empty()) {
-    // The dynamic LDS of a launch is its largest fit's, and beyond ~72 KiB (M_p > 256 at D = 6) a CU holds ONE
-    // workgroup whatever the registers allow: a launch with one such fit ran every staged fit one per CU.  So the
-    // staged fits go out as two launches side by side: those whose LDS fits a CU twice in the `<4>` build (128 VGPRs,
-    // two workgroups per CU: 17 % more fits/s at M <= 256 than one per CU), the larger ones in the `<2>` build (the
-    // whole register file, no spills).  Either part with fewer fits than CUs takes `<2>` as well.
-    auto launch = [&](hipStream_t st, size_t first, size_t count, long long lds, bool kmaj, int part) -> int {
-      const bool one_per_cu = (int)count <= ctx->n_cu || lds > kTwice;
-      const int rc = gapro_launch_fit_staged(st, kmaj || one_per_cu ? 2 : kWavesPerSimd, !kmaj, (int)count,
-                                             grid_of(count), ticket(staged, part), feat_dim, (size_t)lds, d_feats_spp,
-                                             d_idx, d_descs + staged.base + first, d_init_mean, *opt, d_workspace,
-                                             d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
-      return rc == GAPRO_OK ? rc : gapro_fail(ctx, rc, "gapro_svgp_fit_batch: staged kernel launch failed");
-    };
-    const size_t n = staged.descs.size();
-    if (nkmaj > 0) {
-      const int rc = launch(on(staged), 0, nkmaj, lds_kmaj, true, 0);
-      if (rc != GAPRO_OK) return rc;
-    }
-    if (nbig > nkmaj) {  // M_p <= kKminMaxMp with an LDS need beyond kTwice (wide features): behind the former
-      const int rc = launch(on(staged), nkmaj, nbig - nkmaj, lds_big, false, 1);
-      if (rc != GAPRO_OK) return rc;
-    }
-    if (nbig < n) {
-      constexpr int kStaged2 = 4;  // fit stream and join event of the two-per-CU launch beside the others
-      hipStream_t st = nbig > 0 && own ? ctx->fit_stream[kStaged2] : on(staged);
-      // The two-per-CU staged fits are the launch's memory-bound class (3.8 FLOP/B: with the chip to themselves they
-      // sit on the HBM roof), the cluster fits its latency-bound one (a chain of cluster barriers and small products
-      // per Adam step).  Side by side from the start, the same cluster kernel took 230 .. 270 ms or 500 .. 800 ms
-      // depending on which kernels the runtime happened to put on one hardware queue (LABNOTES R4.4); so the order is
-      // explicit: this launch starts when the cluster kernel has ended -- small and strip fits, light on memory, take
-      // the CUs beside the clusters meanwhile.  Same box, 2 x 8 steps: 361 .. 372 scenes/s with 4 or 8 hardware queues
-      // (GPU_MAX_HW_QUEUES), the cluster kernel at its undisturbed time in every step; without the gate 368 / 372 with
-      // the default 4 queues (the lucky mapping) and 351 .. 362 with 8.
-      if (gate) GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(st, ctx->ev_gate, 0));
-      const int rc = launch(st, nbig, n - nbig, lds_rest, false, 2);
-      if (rc != GAPRO_OK) return rc;
-      if (st != on(staged)) {  // everything staged is finished once the staged stream has passed this point
-        GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[kStaged2], st));
-        GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(on(staged), ctx->ev_join[kStaged2], 0));
-      }
-    }
-  }
-  if (staged_class) GAPRO_HIP_CHECK(ctx, mark(staged, 1));
-  if (!strip.descs.empty()) {
-    GAPRO_HIP_CHECK(ctx, mark(strip, 0));
-    const int rc = gapro_launch_fit_strip(on(strip), (int)strip.descs.size(), grid_of(strip.descs.size()),
-                                          ticket(strip), feat_dim, (size_t)strip.max_lds, d_feats_spp, d_idx,
-                                          d_descs + strip.base, d_init_mean, *opt, d_workspace, d_probs, d_probs_new,
-                                          d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
-    if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: strip kernel launch failed");
-    GAPRO_HIP_CHECK(ctx, mark(strip, 1));
-  }
-  if (!small.descs.empty()) {
-    // the small fits start behind the cluster kernel as well: beside the clusters run the whole-CU strip fits and the
-    // one-per-CU staged fits, and every CU half the two-per-CU staged fits leave later goes to a small fit, light on
-    // memory, instead of a second memory-bound one -- 367.8 / 367.4 / 362.6 scenes/s against 364.0 / 363.2 / 356.1
-    // without this gate, alternating on one box
-    if (gate) GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(on(small), ctx->ev_gate, 0));
-    GAPRO_HIP_CHECK(ctx, mark(small, 0));
-    const int rc = gapro_launch_fit_strip_small(on(small), (int)small.descs.size(), grid_of(small.descs.size()),
-                                                ticket(small), feat_dim, (size_t)small.max_lds, d_feats_spp, d_idx,
-                                                d_descs + small.base, d_init_mean, *opt, d_workspace, d_probs,
-                                                d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
-    if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: small-fit kernel launch failed");
-    GAPRO_HIP_CHECK(ctx, mark(small, 1));
-  }
-  // One wave per fit (svgp_fit_wave.hip), one kernel per block count, side by side on their own streams; the waves of a
-  // kernel take its fits by ticket until none is left.  They touch no memory between their first and last step, so
-  // nothing holds them back: they take whatever wave slots and LDS the other kernels leave.  The stream of the first
-  // (largest) one collects the others.
-  int first = -1;
-  for (int g = G_WAVE3; g <= G_WAVE1 && first < 0; ++g)
-    if (!grp[g].descs.empty()) first = g;
+  // the event that joins a step's stream into another: ev_join[stream]; a wave stream's is ev_join[4 + nb]
+  auto join = [&](const FitLaunchStep& s, hipStream_t into) {
+    hipEvent_t ev = ctx->ev_join[s.kernel == GAPRO_FIT_KERNEL_WAVE ? 4 + s.variant : s.stream];
+    const hipError_t e = hipEventRecord(ev, on(s));
+    return e != hipSuccess ? e : hipStreamWaitEvent(into, ev, 0);
+  };
   gapro_fit_options wave_opt = *opt;  // the wave kernel keeps its model on chip: it writes it out only when asked
   if (d_state) wave_opt.reserved |= kFitOptKeepState;
-  if (first >= 0) {
-    const FitGroup& wf = grp[first];
-    GAPRO_HIP_CHECK(ctx, mark(wf, 0));
-    for (int g = G_WAVE3; g <= G_WAVE1; ++g) {
-      const FitGroup& w = grp[g];
-      if (w.descs.empty()) continue;
-      const int nb = G_WAVE1 + 1 - g;
-      const int slots = ctx->n_cu * gapro_fit_wave_per_cu(nb, feat_dim);
-      const int n_wg = (int)std::min<size_t>(w.descs.size(), (size_t)std::max(slots, 1));
-      const int rc = gapro_launch_fit_wave(on(w), nb, (int)w.descs.size(), n_wg, ticket(w), feat_dim, d_feats_spp,
-                                           d_idx, d_descs + w.base, d_init_mean, wave_opt, d_workspace, d_probs,
-                                           d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss);
-      if (rc != GAPRO_OK) return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: wave kernel launch failed");
-      if (own && g != first) {
-        GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[w.join], on(w)));
-        GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(on(wf), ctx->ev_join[w.join], 0));
-      }
-    }
-    GAPRO_HIP_CHECK(ctx, mark(wf, 1));
-    if (own) {
-      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[wf.join], on(wf)));
-      GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_join[wf.join], 0));
-    }
-  }
-  if (own) {  // the other streams, each once
-    bool joined[gapro_ctx::kFitStreams] = {};
-    for (int g = G_LARGE; g <= G_CLUSTER; ++g) {
-      const FitGroup& x = grp[g];
-      if (x.descs.empty() || joined[x.join]) continue;
-      joined[x.join] = true;
-      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_join[x.join], on(x)));
-      GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(stream, ctx->ev_join[x.join], 0));
+  const FitArgs args = {feat_dim, d_feats_spp, d_idx, d_descs, d_init_mean, opt, d_workspace, d_probs, d_probs_new,
+                        d_labels, d_mu, d_var, d_fit_status, d_fit_loss, tk};
+  FitArgs wave_args = args;
+  wave_args.opt = &wave_opt;
+  for (int k = 0; k < plan.n_steps; ++k) {
+    FitLaunchStep s = plan.steps[k];
+    const FitLaunchStep& cls = plan.steps[first[s.timing]];
+    // the small fits' span starts behind the gate; the staged class's mark is in front of its gated launch
+    const bool opens = first[s.timing] == k, mark_behind_gate = s.kernel == GAPRO_FIT_KERNEL_SMALL;
+    if (opens && !mark_behind_gate) GAPRO_HIP_CHECK(ctx, mark(cls, 0));
+    if (s.wait_gate) GAPRO_HIP_CHECK(ctx, hipStreamWaitEvent(on(s), ctx->ev_gate, 0));
+    if (opens && mark_behind_gate) GAPRO_HIP_CHECK(ctx, mark(cls, 0));
+    const bool cluster = s.kernel == GAPRO_FIT_KERNEL_CLUSTER;
+    if (cluster) s.grid = cl_blocks;
+    const int rc = cluster ? gapro_launch_fit_cluster(on(s), s, args, cl_d_half, cl_ctl_half)
+                           : kFitKernel[s.kernel].launch(on(s), s, s.kernel == GAPRO_FIT_KERNEL_WAVE ? wave_args : args);
+    if (rc != GAPRO_OK)
+      return gapro_fail(ctx, rc, "gapro_svgp_fit_batch: %s kernel launch failed", kFitKernel[s.kernel].name);
+    // a step beside its class's stream (the two-per-CU staged launch on stream 4, the later wave kernels): the class
+    // is finished once its stream has passed this point
+    if (s.stream != cls.stream) GAPRO_HIP_CHECK(ctx, join(s, on(cls)));
+    if (last[s.timing] == k) GAPRO_HIP_CHECK(ctx, mark(cls, 1));
+    if (cluster) {
+      GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_clus_half[cl_par], on(s)));
+      ctx->clus_half_used[cl_par] = true;
+      // gate of the two-per-CU staged launch and of the small fits: behind the cluster kernel
+      if (s.stream >= 0) GAPRO_HIP_CHECK(ctx, hipEventRecord(ctx->ev_gate, on(s)));
     }
   }
+  // every class's stream joins the caller's once: the wave kernels' first (their stream has collected the others)
+  for (int c : {4, 0, 1, 2, 3})
+    if (first[c] >= 0 && plan.steps[first[c]].stream >= 0) GAPRO_HIP_CHECK(ctx, join(plan.steps[first[c]], stream));
   // conditioning figures, behind every kernel of the launch (they have been joined into `stream` above)
   if (d_fit_cond)
     hipLaunchKernelGGL(k_fit_cond, dim3((n_fits + 3) / 4), dim3(256), 0, stream, (int)n_fits, (int)feat_dim, d_descs,
                        d_workspace, d_fit_cond);
   if (d_state) {
-    const bool f32 = opt->precision == GAPRO_PRECISION_MIXED;
-    const int lo = f32 ? (int)clus.base : 0, hi = f32 ? (int)(clus.base + clus.descs.size()) : 0;
+    const bool f32 = opt->precision == GAPRO_PRECISION_MIXED && n_clus;
+    const int lo = f32 ? plan.cl_index[0] : 0, hi = f32 ? lo + (int)n_clus : 0;
     hipLaunchKernelGGL(k_gp_state_export, dim3(n_fits), dim3(256), 0, stream, (int)feat_dim, d_descs, d_workspace,
                        d_state, ctx->d_state_off, opt->jitter, lo, hi);
   }
@@ -561,6 +560,20 @@ int gapro_fit_route(int32_t m, int32_t feat_dim) { return fit_route(m, feat_dim,
 
 int gapro_fit_route_flags(int32_t m, int32_t feat_dim, int32_t flags) {
   return (flags & ~GAPRO_FIT_DBG_ALL) ? (int)GAPRO_ERR_BAD_ARG : fit_route(m, feat_dim, flags);
+}
+
+int gapro_fit_launch_plan(const gapro_fit_desc* h_descs, int32_t n_fits, int32_t feat_dim, int32_t flags, int32_t n_cu,
+                          gapro_fit_launch_step* steps_out, int32_t max_steps, int32_t* n_steps_out,
+                          int32_t* order_out) {
+  if (!h_descs || !steps_out || !n_steps_out || !order_out || n_fits <= 0 || feat_dim <= 0 || n_cu <= 0 ||
+      (flags & ~GAPRO_FIT_DBG_ALL))
+    return GAPRO_ERR_BAD_ARG;
+  const FitLaunchPlan plan = plan_fit_launch(h_descs, n_fits, feat_dim, flags, n_cu);
+  if (plan.bad_fit >= 0 || plan.n_steps > max_steps) return GAPRO_ERR_BAD_ARG;
+  std::copy(plan.steps, plan.steps + plan.n_steps, steps_out);
+  *n_steps_out = plan.n_steps;
+  for (int k = 0; k < n_fits; ++k) order_out[k] = plan.descs[k].slot;
+  return GAPRO_OK;
 }
 
 int gapro_fit_padded_m(int32_t m, int32_t feat_dim) { return gapro_pad_m(m, feat_dim); }

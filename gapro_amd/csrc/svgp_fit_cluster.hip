@@ -1846,12 +1846,9 @@ int gapro_prepare_fit_cluster(hipStream_t stream, int n, const int* fit_index, c
   return GAPRO_OK;
 }
 
-int gapro_launch_fit_cluster(hipStream_t stream, int nb, int feat_dim, void* d_stage, unsigned* d_ctl, unsigned* d_info,
-                             const float* d_feats_spp, const int* d_idx, const gapro_fit_desc* d_descs,
-                             const double* d_init_mean, const gapro_fit_options& opt, double* d_workspace, float* d_probs,
-                             float* d_probs_new, unsigned char* d_labels, float* d_mu, float* d_var, int* d_fit_status,
-                             double* d_fit_loss) {
-  if (nb <= 0) return GAPRO_OK;
+int gapro_launch_fit_cluster(hipStream_t stream, const FitLaunchStep& s, const FitArgs& a, void* d_stage,
+                             unsigned* d_ctl) {
+  if (s.grid <= 0) return GAPRO_OK;
   // longest wait at one cluster barrier before the cluster gives up (cbar): 5 s unless the environment says otherwise
   static long long timeout_ms = -1;
   if (timeout_ms < 0) {
@@ -1859,8 +1856,9 @@ int gapro_launch_fit_cluster(hipStream_t stream, int nb, int feat_dim, void* d_s
     timeout_ms = e && atoll(e) >= 0 ? atoll(e) : 5000;
   }
   const unsigned long long bar_ticks = (unsigned long long)timeout_ms * 100000ull;  // wall_clock64: 100 MHz
-  hipLaunchKernelGGL(k_svgp_fit_cluster, dim3(nb), dim3(NT), 0, stream, (const ClBlock*)d_stage, feat_dim, d_feats_spp,
-                     d_idx, d_descs, d_init_mean, opt, d_workspace, d_ctl, d_probs, d_probs_new, d_labels, d_mu, d_var,
-                     d_fit_status, d_fit_loss, bar_ticks, d_info);
+  hipLaunchKernelGGL(k_svgp_fit_cluster, dim3(s.grid), dim3(NT), 0, stream, (const ClBlock*)d_stage, a.feat_dim,
+                     a.d_feats_spp, a.d_idx, a.d_descs, a.d_init_mean, *a.opt, a.d_workspace, d_ctl, a.d_probs,
+                     a.d_probs_new, a.d_labels, a.d_mu, a.d_var, a.d_fit_status, a.d_fit_loss, bar_ticks,
+                     gapro_fit_ticket(s, a));
   return hipGetLastError() == hipSuccess ? GAPRO_OK : GAPRO_ERR_HIP;
 }

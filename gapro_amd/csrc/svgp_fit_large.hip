@@ -795,11 +795,9 @@ __global__ __launch_bounds__(NT) void k_svgp_fit_large(int n_fits, int D, const 
 }  // namespace
 
 // Internal launcher used by gapro_svgp_fit_batch (svgp_fit.hip) for fits that exceed the LDS-staged kernel.
-void gapro_launch_fit_large(hipStream_t stream, int n_fits, int feat_dim, const float* d_feats_spp, const int* d_idx,
-                            const gapro_fit_desc* d_descs, const double* d_init_mean, const gapro_fit_options& opt,
-                            double* d_workspace, float* d_probs, float* d_probs_new, unsigned char* d_labels,
-                            float* d_mu, float* d_var, int* d_fit_status, double* d_fit_loss) {
-  hipLaunchKernelGGL(k_svgp_fit_large, dim3(n_fits), dim3(NT), 0, stream, n_fits, feat_dim, d_feats_spp, d_idx, d_descs,
-                     d_init_mean, opt, d_workspace, d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status,
-                     d_fit_loss);
+int gapro_launch_fit_large(hipStream_t stream, const FitLaunchStep& s, const FitArgs& a) {
+  hipLaunchKernelGGL(k_svgp_fit_large, dim3(s.grid), dim3(NT), 0, stream, s.count, a.feat_dim, a.d_feats_spp, a.d_idx,
+                     a.d_descs + s.first, a.d_init_mean, *a.opt, a.d_workspace, a.d_probs, a.d_probs_new, a.d_labels,
+                     a.d_mu, a.d_var, a.d_fit_status, a.d_fit_loss);
+  return GAPRO_OK;  // (a failed launch shows at the end of the call: GAPRO_LAUNCH_CHECK)
 }

@@ -1077,12 +1077,10 @@ int gapro_fit_wave_per_cu(int nb, int feat_dim) {
   return by_lds < by_reg ? by_lds : by_reg;
 }
 
-// n_fits descriptors of one block count NB (descs sorted longest first by the caller); n_wg waves are launched
-int gapro_launch_fit_wave(hipStream_t stream, int nb, int n_fits, int n_wg, unsigned* d_ticket, int feat_dim,
-                          const float* d_feats_spp, const int* d_idx, const gapro_fit_desc* d_descs,
-                          const double* d_init_mean, const gapro_fit_options& opt, double* d_workspace, float* d_probs,
-                          float* d_probs_new, unsigned char* d_labels, float* d_mu, float* d_var, int* d_fit_status,
-                          double* d_fit_loss) {
+// the step's descriptors have one block count NB = step.variant (sorted longest first by the caller); step.grid waves
+// are launched
+int gapro_launch_fit_wave(hipStream_t stream, const FitLaunchStep& s, const FitArgs& a) {
+  const int nb = s.variant, feat_dim = a.feat_dim;
   if ((feat_dim != 6 && feat_dim != 32) || nb < 1 || nb > (feat_dim == 6 ? 3 : 2)) return GAPRO_ERR_BAD_ARG;
   const size_t lds = gapro_fit_wave_lds_bytes(nb, feat_dim);
 #define GAPRO_WAVE_LAUNCH(NBV, DV, WPEV)                                                                          \
@@ -1091,8 +1089,9 @@ int gapro_launch_fit_wave(hipStream_t stream, int nb, int n_fits, int n_wg, unsi
     if (lds > 48 * 1024 &&                                                                                        \
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
       return GAPRO_ERR_HIP;                                                                                       \
-    hipLaunchKernelGGL(kern, dim3(n_wg), dim3(64), lds, stream, n_fits, d_feats_spp, d_idx, d_descs, d_init_mean, opt, \
-                       d_workspace, d_probs, d_probs_new, d_labels, d_mu, d_var, d_fit_status, d_fit_loss, d_ticket); \
+    hipLaunchKernelGGL(kern, dim3(s.grid), dim3(64), lds, stream, s.count, a.d_feats_spp, a.d_idx,                \
+                       a.d_descs + s.first, a.d_init_mean, *a.opt, a.d_workspace, a.d_probs, a.d_probs_new,       \
+                       a.d_labels, a.d_mu, a.d_var, a.d_fit_status, a.d_fit_loss, gapro_fit_ticket(s, a));        \
   } while (0)
   if (feat_dim == 32) {
     if (nb == 1) GAPRO_WAVE_LAUNCH(1, 32, 1);

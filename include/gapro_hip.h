@@ -834,6 +834,41 @@ int gapro_fit_route(int32_t m, int32_t feat_dim);
 /* The same for a launch whose gapro_fit_options.reserved holds `flags` (GAPRO_FIT_DBG_* bits; gapro_fit_route is
  * flags = 0).  A bit outside GAPRO_FIT_DBG_ALL returns GAPRO_ERR_BAD_ARG, as the launch refuses it. */
 int gapro_fit_route_flags(int32_t m, int32_t feat_dim, int32_t flags);
+
+/* One kernel launch of a gapro_svgp_fit_batch call, as the library plans it on the host before it issues anything. */
+enum {
+  GAPRO_FIT_KERNEL_STRIP = 0, GAPRO_FIT_KERNEL_STAGED = 1, GAPRO_FIT_KERNEL_GENERIC = 2, GAPRO_FIT_KERNEL_SMALL = 3,
+  GAPRO_FIT_KERNEL_CLUSTER = 4, GAPRO_FIT_KERNEL_WAVE = 5, /* the codes of gapro_fit_route */
+  GAPRO_FIT_STEP_COPY_FREE = 8, GAPRO_FIT_MAX_STEPS = 10
+};
+typedef struct {
+  int32_t kernel;     /* GAPRO_FIT_KERNEL_* */
+  int32_t variant;    /* staged: waves per SIMD of the build (2 or 4: one or two workgroups per CU), plus
+                       * GAPRO_FIT_STEP_COPY_FREE where it uses the copy-free product forms (M_p <= 256);
+                       * wave: M_p / 16; else 0 */
+  int32_t first;      /* the step's fits: [first, first + count) of the uploaded descriptor array */
+  int32_t count;
+  int32_t grid;       /* workgroups; 0 for the cluster kernel, whose block table is built when it is issued */
+  int32_t stream;     /* index of the library's fit stream, or -1: the caller's stream */
+  int32_t ticket;     /* counter of the launch's ticket set from which the workgroups take their fits, or -1: workgroup
+                       * b runs fit b (for the cluster kernel the first of its three diagnostic counters) */
+  int32_t timing;     /* timing class of gapro_fit_timing: 0 staged and generic, 1 strip, 2 small, 3 cluster, 4 wave */
+  int32_t wait_gate;  /* 1: the step starts when the launch's cluster kernel has ended */
+  int32_t reserved;
+  int64_t lds_bytes;  /* dynamic LDS of the launch (its largest fit's); 0 where the kernel's launcher computes it */
+} gapro_fit_launch_step;
+/* The launches that gapro_svgp_fit_batch makes of the n_fits fits h_descs (only m1, m2 and t are read) at feature
+ * width feat_dim with gapro_fit_options.reserved = flags on a device of n_cu compute units: the launch calls the same
+ * planner, so this IS its launch structure.  Needs no context and no device.  steps_out receives *n_steps_out <=
+ * GAPRO_FIT_MAX_STEPS records in the order of issue (cluster, generic, staged M_p > 256, staged beyond 72 KiB of LDS,
+ * staged two per CU, strip, small, wave M_p = 48 / 32 / 16; a kernel without fits has no step); order_out[k]
+ * (n_fits entries) is the index in h_descs of the k-th uploaded descriptor -- the groups in the order generic, staged,
+ * strip, small, cluster, wave 48 / 32 / 16, each longest first and equal sizes in input order.  A bit of flags
+ * outside GAPRO_FIT_DBG_ALL, a fit with an empty side, n_fits, feat_dim or n_cu <= 0, a null pointer or max_steps
+ * below the number of steps return GAPRO_ERR_BAD_ARG. */
+int gapro_fit_launch_plan(const gapro_fit_desc* h_descs, int32_t n_fits, int32_t feat_dim, int32_t flags, int32_t n_cu,
+                          gapro_fit_launch_step* steps_out, int32_t max_steps, int32_t* n_steps_out,
+                          int32_t* order_out);
 /* Padded size M_p of a fit's M x M matrices (a multiple of 16; of 32 where the kernel that takes the fit needs it):
  * a function of (M, D) only, never of the routing options.  The workspace layout is built on it. */
 int gapro_fit_padded_m(int32_t m, int32_t feat_dim);

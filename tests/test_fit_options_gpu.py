@@ -316,3 +316,39 @@ def test_predict_refuses_a_bad_min_variance(bad, trained):
     assert e.value.code == -1 and "min_variance" in str(e.value)
     again = predict_gp_batch([model], feats, [it])[0]
     _check(again, (out[3].astype(np.float64), out[4].astype(np.float64), out[0].astype(np.float64)), "after a refusal")
+
+
+# ------------------------------------------------------------------ 7. the launch structure the library plans is issued
+def test_every_timing_class_of_the_plan_is_issued_and_no_other():
+    """One fit per route in one launch (test_fit_plan_cpu.ROUTE_M, two Adam steps): the timing marks the launch loop
+    records are those of the classes in gapro_fit_launch_plan's steps for the same batch -- FitTiming.read() is positive
+    for exactly these -- and every fit ends with status 0."""
+    import torch
+    from gapro_amd import _lib
+    from gapro_amd.gaussian_process_utils import fit_gp_spp_batch
+    from gapro_amd.synth import make_gp_problem
+    from test_fit_plan_cpu import ROUTE_M, plan
+
+    rc, steps, _ = plan(ROUTE_M, n_cu=torch.cuda.get_device_properties(0).multi_processor_count)
+    assert rc == 0
+    planned = {s[7] for s in steps}
+    assert planned == {0, 1, 2, 3, 4}
+    parts, probs, base = [], [], 0
+    for i, m in enumerate(ROUTE_M):
+        f, b1, b2, it = make_gp_problem(700 + i, m // 2, m - m // 2, 3 + i, 6)
+        parts.append(f)
+        probs.append((b1 + base, b2 + base, it + base))
+        base += len(f)
+    pipe = _pipe(2)
+    pipe.profile_fit, pipe.fit_events = True, []
+    try:
+        _, status = fit_gp_spp_batch(np.concatenate(parts), probs, training_iter=2, return_status=True)
+        assert len(pipe.fit_events) == 1
+        ms = pipe.fit_events[0].read()
+    finally:
+        pipe.profile_fit, pipe.fit_events = False, []
+    assert (np.asarray(status) == 0).all()
+    by_class = {0: ms[0], 1: ms[1], 2: ms[3], 3: ms[4], 4: ms[5]}  # staged, strip, small, cluster, wave
+    print("timing classes: %s" % by_class)
+    assert {c for c, v in by_class.items() if v > 0} == planned
+    assert ms[2] > 0
