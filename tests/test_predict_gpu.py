@@ -12,6 +12,8 @@ import time
 import numpy as np
 import pytest
 
+from predict_edge_cases import _as_ref, _check, _oracle
+
 pytestmark = pytest.mark.gpu
 
 ULP = 2.0 ** -23
@@ -28,44 +30,6 @@ def _problem(m1, m2, d, t=T_FIT):
     from gapro_amd.synth import make_gp_problem
 
     return make_gp_problem(7 + m1, m1, m2, t, d, std=_std(d))
-
-
-def _check(out, ref, what="", untrained=False):
-    """out: the 5-tuple of the library; ref: (mu, var, p) in float64.  untrained: a model at zero Adam steps predicts
-    the prior, p = 0.5 exactly at every row; there the labels must agree on ALL rows (no row is left out as a tie)."""
-    probs, probs_new, labels, mu, var = out
-    mu_r, var_r, p_r = ref
-    assert probs.dtype == np.float32 and mu.dtype == np.float32 and var.dtype == np.float32 and labels.dtype == bool
-    dv = np.max(np.abs(var.astype(np.float64) - var_r.astype(np.float32)) / var_r) if len(var) else 0.0
-    dm = np.max(np.abs(mu.astype(np.float64) - mu_r.astype(np.float32))) if len(mu) else 0.0
-    dp = np.max(np.abs(probs.astype(np.float64) - p_r.astype(np.float32))) if len(mu) else 0.0
-    print("%s rows %d: var rel %.3e  mu abs %.3e  p abs %.3e" % (what, len(mu), dv, dm, dp))
-    np.testing.assert_allclose(var, var_r.astype(np.float32), rtol=ULP, atol=0, err_msg=what)
-    np.testing.assert_allclose(mu, mu_r.astype(np.float32), rtol=ULP, atol=1e-10, err_msg=what)
-    np.testing.assert_allclose(probs, p_r.astype(np.float32), rtol=0, atol=1.2e-7, err_msg=what)
-    safe = np.abs(p_r - 0.5) > 1e-6
-    if untrained:
-        assert (p_r == 0.5).all() and (probs == np.float32(0.5)).all()
-        safe[:] = True
-    assert (~safe).mean() <= 1e-3 if len(safe) else True
-    np.testing.assert_array_equal(labels[safe], (p_r.astype(np.float32) >= np.float32(0.5))[safe])
-    np.testing.assert_array_equal(probs_new, np.where(labels, probs, np.float32(1) - probs))
-
-
-def _as_ref(out):
-    """A fit's own five outputs as a (mu, var, p) reference (float32 values held in float64)."""
-    return out[3].astype(np.float64), out[4].astype(np.float64), out[0].astype(np.float64)
-
-
-def _oracle(model, X, chunk=2000):
-    from oracle import svgp_oracle as so
-
-    s, ell = model.outputscale, model.lengthscale
-    d2 = ((model.Z[:, None, :] - model.Z[None, :, :]) ** 2).sum(-1)
-    L = np.linalg.cholesky(s * np.exp(-0.5 * d2 / (ell * ell)) + model.jitter * np.eye(model.m))
-    outs = [so.svgp_predict(X[a:a + chunk].astype(np.float64), model.Z, model.mean, model.LS, model.c, model.rho_s,
-                            model.rho_l, jitter=model.jitter, L=L) for a in range(0, len(X), chunk)]
-    return tuple(np.concatenate([o[k] for o in outs]) for k in range(3))
 
 
 @pytest.fixture(scope="module")
