@@ -196,6 +196,10 @@ SIGNATURES = {
     "gapro_eval_ap_tables": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_int32,
                                        _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P, _P, _P, _P, _P, _P,
                                        _P]),
+    "gapro_eval_ap_workspace_bytes_rows": (C.c_size_t, [_P, C.c_int32, C.c_int32]),
+    "gapro_eval_ap_tables_rows": (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P,
+                                            C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, _P, C.c_size_t,
+                                            _P, _P, _P, _P, _P, _P, _P, _P]),
     "gapro_label_heuristic_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "gapro_label_heuristic": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32,
                                         C.c_int32, _P, C.c_size_t, _P, _P]),

@@ -11,6 +11,12 @@
 //                          column 0 = pseudo id -100), per pseudo id its first point (packed with the label of that
 //                          point) and the sum of rint(prob * 2^32); the finalize derives the key codes and counts
 //                          and the per-id counts from the pair table.
+//   gapro_eval_ap_tables_rows : the same pass with T probability thresholds.  A point tallies into the tables of its
+//                          bin b = #{j : prob >= thresholds[j]} (one pair cell, one first point, one probability sum,
+//                          as without thresholds); row t keeps the points of the bins t..T, so a suffix sum (pair
+//                          cells, probability sums) / suffix min (first points) over the bins turns the bin tables
+//                          into the row tables, and the finalize derives every row's counts and labels from them.
+//                          Key ranks are over the whole scene: a key without a kept point has count 0 in that row.
 // Integer atomics only: every table is bit-identical to a plain tally of the scene, whatever the batch.
 #include "common.h"
 #include "eval_labels.h"
@@ -38,6 +44,7 @@ inline int blocks_for(long long items, int per_thread, int cap) {
 }
 
 // one scene in the workspace: bitmap u32[kApWords] | exclusive rank of each word i32[kApWords] | first u64[max_ps]
+// (bin / row 0); the first points of the bins / rows 1..T follow the last scene's block as u64[T][ids of the batch]
 __host__ __device__ inline size_t scene_bytes(int max_ps) {
   return align_up((size_t)kApWords * 8 + (size_t)max_ps * sizeof(unsigned long long), 256);
 }
@@ -52,6 +59,17 @@ __device__ inline SceneWs scene_ws(void* ws, const gapro_eval_ap_scene& s) {
   w.rank = (int*)(w.bits + kApWords);
   w.first = (unsigned long long*)(w.rank + kApWords);
   return w;
+}
+
+// the row dimension of a launch: B = K + 1 bins / rows, each output's row stride, the first points of the rows 1..K
+struct Rows {
+  Thresholds thr;
+  int K;
+  long long n_keys, n_ids, n_cells;  // entries of the whole batch per key / per id / pair output: the row strides
+  unsigned long long* first;         // [K][n_ids]
+};
+__device__ inline unsigned long long* first_of(const SceneWs& w, const Rows& r, const gapro_eval_ap_scene& s, int b) {
+  return b == 0 ? w.first : r.first + (long long)(b - 1) * r.n_ids + s.id_offset;
 }
 
 // the key index of a GT point ((class - 1) * 1000 + inst + 1 = code - 1000, ascending in the code), -1 = void,
@@ -124,22 +142,22 @@ __global__ __launch_bounds__(kThreads) void k_ap_rank(const gapro_eval_ap_scene*
   if (threadIdx.x == kThreads - 1) n_keys[blockIdx.y] = s_sum[kThreads - 1];
 }
 
-// pass 2: pair counts, first points and probability sums; tables in LDS while they fit
+// pass 2: pair counts, first points and probability sums per bin; tables in LDS while all bins of them fit
 template <class TGS, class TGI, class TPS, class TPI>
 __global__ __launch_bounds__(kThreads) void k_ap_tally(const gapro_eval_ap_scene* __restrict__ scenes,
                                                        const TGS* __restrict__ sem_gt, const TGI* __restrict__ inst_gt,
                                                        const TPS* __restrict__ sem_ps, const TPI* __restrict__ inst_ps,
-                                                       const float* __restrict__ prob, int remap, void* ws,
-                                                       int* __restrict__ pair, long long* __restrict__ ps_sum,
-                                                       int* __restrict__ status) {
+                                                       const float* __restrict__ prob, Rows rows, int remap,
+                                                       void* ws, int* __restrict__ pair,
+                                                       long long* __restrict__ ps_sum, int* __restrict__ status) {
   const int scene = blockIdx.y;
   const gapro_eval_ap_scene s = scenes[scene];
   const long long n = s.n_points, off = s.point_offset;
   if ((long long)blockIdx.x * kThreads >= n) return;
   SceneWs w = scene_ws(ws, s);
-  const int P = s.max_ps, W = P + 1;
+  const int P = s.max_ps, W = P + 1, K = rows.K, B = K + 1;
   const long long cells = (long long)(s.n_keys + 1) * W;
-  const bool lds_pair = cells <= kPairLds, lds_id = P <= kIdLds;
+  const bool lds_pair = cells * B <= kPairLds, lds_id = (long long)P * B <= kIdLds;
   __shared__ unsigned s_bits[kApWords];
   __shared__ int s_rank[kApWords];
   __shared__ int s_pair[kPairLds];
@@ -149,9 +167,9 @@ __global__ __launch_bounds__(kThreads) void k_ap_tally(const gapro_eval_ap_scene
     s_rank[j] = w.rank[j];
   }
   if (lds_pair)
-    for (int j = threadIdx.x; j < (int)cells; j += kThreads) s_pair[j] = 0;
+    for (int j = threadIdx.x; j < (int)cells * B; j += kThreads) s_pair[j] = 0;
   if (lds_id)
-    for (int j = threadIdx.x; j < P; j += kThreads) {
+    for (int j = threadIdx.x; j < P * B; j += kThreads) {
       s_first[j] = kFirstNone;
       s_sum[j] = 0ull;
     }
@@ -185,44 +203,78 @@ __global__ __launch_bounds__(kThreads) void k_ap_tally(const gapro_eval_ap_scene
       continue;
     }
     const int col = p == -100 ? 0 : (int)p + 1;
+    const int b = K ? prob_bin(rows.thr, K, pr) : 0;
     const long long cell = (long long)row * W + col;
-    if (lds_pair) atomicAdd(&s_pair[(int)cell], 1);
-    else atomicAdd(&g_pair[cell], 1);
+    if (lds_pair) atomicAdd(&s_pair[b * (int)cells + (int)cell], 1);
+    else atomicAdd(&g_pair[b * rows.n_cells + cell], 1);
     if (col) {
       const long long sp = label_at(sem_ps, gi_);
       const unsigned long long first =
           ((unsigned long long)i << 8) | (unsigned long long)(sp >= 0 && sp < kApClasses ? sp + 1 : 0);
-      if (lds_id) atomicMin(&s_first[p], first);
-      else atomicMin(&w.first[p], first);
+      if (lds_id) atomicMin(&s_first[b * P + p], first);
+      else atomicMin(&first_of(w, rows, s, b)[p], first);
       if (prob) {
         const unsigned long long q = (unsigned long long)(long long)rint((double)pr * kProbScale);
-        if (lds_id) atomicAdd(&s_sum[p], q);
-        else atomicAdd(&g_sum[p], q);
+        if (lds_id) atomicAdd(&s_sum[b * P + p], q);
+        else atomicAdd(&g_sum[b * rows.n_ids + p], q);
       }
     }
   }
   if (bad) atomicExch(&status[scene], GAPRO_ERR_BAD_ARG);
   __syncthreads();
   if (lds_pair)
-    for (int j = threadIdx.x; j < (int)cells; j += kThreads)
-      if (s_pair[j]) atomicAdd(&g_pair[j], s_pair[j]);
+    for (int j = threadIdx.x; j < (int)cells * B; j += kThreads)
+      if (s_pair[j]) atomicAdd(&g_pair[j / (int)cells * rows.n_cells + j % (int)cells], s_pair[j]);
   if (lds_id)
-    for (int j = threadIdx.x; j < P; j += kThreads) {
-      if (s_first[j] != kFirstNone) atomicMin(&w.first[j], s_first[j]);
-      if (s_sum[j]) atomicAdd(&g_sum[j], s_sum[j]);
+    for (int j = threadIdx.x; j < P * B; j += kThreads) {
+      const int b = j / P, p = j % P;
+      if (s_first[j] != kFirstNone) atomicMin(&first_of(w, rows, s, b)[p], s_first[j]);
+      if (s_sum[j]) atomicAdd(&g_sum[b * rows.n_ids + p], s_sum[j]);
     }
 }
 
-// per scene: the key codes (class * 1000 + inst + 1) and point counts, and per pseudo id the point count, the void
-// points (row 0) and the label id of the first point, from the pair table
-__global__ __launch_bounds__(kThreads) void k_ap_finalize(const gapro_eval_ap_scene* __restrict__ scenes, void* ws,
-                                                          const int* __restrict__ pair, int* __restrict__ key_code,
-                                                          int* __restrict__ key_n, int* __restrict__ ps_n,
-                                                          int* __restrict__ ps_label, int* __restrict__ ps_void) {
+// bins -> rows: row t = bins t..K (suffix sum of the pair cells and the probability sums, suffix min of the first points)
+__global__ __launch_bounds__(kThreads) void k_ap_suffix(const gapro_eval_ap_scene* __restrict__ scenes, void* ws, Rows rows,
+                                                        int* __restrict__ pair, long long* __restrict__ ps_sum) {
   const gapro_eval_ap_scene s = scenes[blockIdx.y];
   SceneWs w = scene_ws(ws, s);
-  const int P = s.max_ps, W = P + 1, K = s.n_keys;
-  const int* t = pair + s.pair_offset;
+  const long long P = s.max_ps, cells = (long long)(s.n_keys + 1) * (P + 1), items = cells + 2 * P;
+  for (long long it = (long long)blockIdx.x * kThreads + threadIdx.x; it < items; it += (long long)gridDim.x * kThreads) {
+    if (it < cells) {
+      int* a = pair + s.pair_offset + it;
+      for (int b = rows.K - 1; b >= 0; --b) a[b * rows.n_cells] += a[(b + 1) * rows.n_cells];
+    } else if (it < cells + P) {
+      long long* a = ps_sum + s.id_offset + (it - cells);
+      for (int b = rows.K - 1; b >= 0; --b) a[b * rows.n_ids] += a[(b + 1) * rows.n_ids];
+    } else {
+      const long long p = it - cells - P;
+      unsigned long long f = first_of(w, rows, s, rows.K)[p];
+      for (int b = rows.K - 1; b >= 0; --b) {
+        unsigned long long* a = first_of(w, rows, s, b) + p;
+        f = *a < f ? *a : f;
+        *a = f;
+      }
+    }
+  }
+}
+
+// per scene and row (blockIdx.z): the key codes (class * 1000 + inst + 1) and point counts, and per pseudo id the
+// point count, the void points (pair row 0) and the label id of the first point, from the row's pair table
+__global__ __launch_bounds__(kThreads) void k_ap_finalize(const gapro_eval_ap_scene* __restrict__ scenes, void* ws,
+                                                          Rows rows, const int* __restrict__ pair,
+                                                          int* __restrict__ key_code, int* __restrict__ key_n,
+                                                          int* __restrict__ ps_n, int* __restrict__ ps_label,
+                                                          int* __restrict__ ps_void) {
+  const gapro_eval_ap_scene s = scenes[blockIdx.y];
+  SceneWs w = scene_ws(ws, s);
+  const int P = s.max_ps, W = P + 1, K = s.n_keys, z = blockIdx.z;
+  const int* t = pair + z * rows.n_cells + s.pair_offset;
+  const unsigned long long* first = first_of(w, rows, s, z);
+  key_code += z * rows.n_keys;
+  key_n += z * rows.n_keys;
+  ps_n += z * rows.n_ids;
+  ps_label += z * rows.n_ids;
+  ps_void += z * rows.n_ids;
   const long long items = (long long)kApWords + K + P;
   for (long long it = (long long)blockIdx.x * kThreads + threadIdx.x; it < items; it += (long long)gridDim.x * kThreads) {
     if (it < kApWords) {
@@ -247,7 +299,7 @@ __global__ __launch_bounds__(kThreads) void k_ap_finalize(const gapro_eval_ap_sc
       for (int k = 0; k <= K; ++k) c += t[(long long)k * W + p + 1];
       ps_n[s.id_offset + p] = c;
       ps_void[s.id_offset + p] = t[p + 1];
-      const unsigned long long f = w.first[p];
+      const unsigned long long f = first[p];
       ps_label[s.id_offset + p] = f == kFirstNone ? 0 : (int)(f & 0xffull);
     }
   }
@@ -276,6 +328,14 @@ size_t gapro_eval_ap_workspace_bytes(gapro_eval_ap_scene* h_scenes, int32_t n_sc
   return bytes;
 }
 
+size_t gapro_eval_ap_workspace_bytes_rows(gapro_eval_ap_scene* h_scenes, int32_t n_scenes, int32_t n_thresholds) {
+  if (n_thresholds < 0 || n_thresholds > GAPRO_EVAL_MAX_THRESHOLDS) return 0;
+  const size_t bytes = gapro_eval_ap_workspace_bytes(h_scenes, n_scenes);
+  if (!bytes) return 0;
+  const gapro_eval_ap_scene& last = h_scenes[n_scenes - 1];
+  return bytes + (size_t)n_thresholds * (size_t)(last.id_offset + last.max_ps) * sizeof(unsigned long long);
+}
+
 int64_t gapro_eval_ap_pair_cells(gapro_eval_ap_scene* h_scenes, int32_t n_scenes) {
   if (!h_scenes || n_scenes < 1 || n_scenes > 65535) return 0;
   long long keys = 0, cells = 0;
@@ -290,10 +350,11 @@ int64_t gapro_eval_ap_pair_cells(gapro_eval_ap_scene* h_scenes, int32_t n_scenes
   return cells;
 }
 
-// the descriptors as the two sizing functions laid them out, inside the arrays and the workspace: GAPRO_OK or the error
+// the descriptors as the two sizing functions laid them out, inside the arrays and the workspace (the scenes' blocks and
+// more_rows first-point rows behind them, at *rows_at): GAPRO_OK or the error
 static int check_layout(gapro_ctx* ctx, const char* fn, int32_t n_scenes, const gapro_eval_ap_scene* h_scenes,
-                         int64_t n_total_points, size_t workspace_bytes, bool with_keys, long long* n_max,
-                         long long* ps_max, long long* fin_max) {
+                         int64_t n_total_points, size_t workspace_bytes, bool with_keys, int more_rows, long long* n_max,
+                         long long* ps_max, long long* fin_max, size_t* rows_at) {
   size_t bytes = 0;
   long long ids = 0, keys = 0, cells = 0;
   *n_max = *ps_max = *fin_max = 0;
@@ -314,7 +375,9 @@ static int check_layout(gapro_ctx* ctx, const char* fn, int32_t n_scenes, const 
     *ps_max = std::max<long long>(*ps_max, s.max_ps);
     *fin_max = std::max<long long>(*fin_max, (long long)kApWords + (with_keys ? s.n_keys : 0) + s.max_ps);
   }
-  if (workspace_bytes < bytes) return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "%s: workspace too small", fn);
+  *rows_at = bytes;
+  if (workspace_bytes < bytes + (size_t)more_rows * (size_t)ids * sizeof(unsigned long long))
+    return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "%s: workspace too small", fn);
   return GAPRO_OK;
 }
 
@@ -329,8 +392,9 @@ int gapro_eval_ap_keys(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const ga
   if (!with_gt_type(sem_gt_dtype, [](auto) {}) || !with_gt_type(inst_gt_dtype, [](auto) {}))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_ap_keys: unsupported label dtype code");
   long long n_max, ps_max, fin_max;
-  const int rc = check_layout(ctx, "gapro_eval_ap_keys", n_scenes, h_scenes, n_total_points, workspace_bytes, false,
-                              &n_max, &ps_max, &fin_max);
+  size_t rows_at;
+  const int rc = check_layout(ctx, "gapro_eval_ap_keys", n_scenes, h_scenes, n_total_points, workspace_bytes, false, 0,
+                              &n_max, &ps_max, &fin_max, &rows_at);
   if (rc != GAPRO_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_scenes, h_scenes, (size_t)n_scenes * sizeof(gapro_eval_ap_scene),
@@ -353,34 +417,53 @@ int gapro_eval_ap_keys(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const ga
   return GAPRO_OK;
 }
 
-int gapro_eval_ap_tables(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapro_eval_ap_scene* h_scenes,
-                         gapro_eval_ap_scene* d_scenes, int64_t n_total_points, int32_t sem_gt_dtype,
-                         const void* d_sem_gt, int32_t inst_gt_dtype, const void* d_inst_gt, int32_t sem_ps_dtype,
-                         const void* d_sem_ps, int32_t inst_ps_dtype, const void* d_inst_ps, const float* d_prob,
-                         int32_t scannet_remap, void* d_workspace, size_t workspace_bytes, int32_t* d_key_code,
-                         int32_t* d_key_n, int32_t* d_ps_n, int32_t* d_ps_label, int32_t* d_ps_void,
-                         int64_t* d_ps_sum, int32_t* d_pair, int32_t* d_status) {
+// gapro_eval_ap_tables_rows, named fn in the errors
+static int ap_tables_rows(const char* fn, gapro_ctx* ctx, void* stream_, int32_t n_scenes,
+                          const gapro_eval_ap_scene* h_scenes, gapro_eval_ap_scene* d_scenes, int64_t n_total_points,
+                          int32_t sem_gt_dtype, const void* d_sem_gt, int32_t inst_gt_dtype, const void* d_inst_gt,
+                          int32_t sem_ps_dtype, const void* d_sem_ps, int32_t inst_ps_dtype, const void* d_inst_ps,
+                          const float* d_prob, int32_t n_thresholds, const float* h_thresholds, int32_t scannet_remap,
+                          void* d_workspace, size_t workspace_bytes, int32_t* d_key_code, int32_t* d_key_n,
+                          int32_t* d_ps_n, int32_t* d_ps_label, int32_t* d_ps_void, int64_t* d_ps_sum, int32_t* d_pair,
+                          int32_t* d_status) {
   if (!ctx) return GAPRO_ERR_BAD_ARG;
-  if (n_scenes < 1 || n_scenes > 65535 || !h_scenes || !d_scenes || n_total_points < 0 || !d_workspace ||
+  const int K = n_thresholds, B = K + 1;
+  if (n_scenes < 1 || n_scenes > 65535 || !h_scenes || !d_scenes || n_total_points < 0 || K < 0 ||
+      K > GAPRO_EVAL_MAX_THRESHOLDS || (K > 0 && (!h_thresholds || (n_total_points > 0 && !d_prob))) || !d_workspace ||
       !d_key_code || !d_key_n || !d_ps_n || !d_ps_label || !d_ps_void || !d_ps_sum || !d_pair || !d_status ||
       (n_total_points > 0 && (!d_sem_gt || !d_inst_gt || !d_sem_ps || !d_inst_ps)))
-    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_ap_tables: bad argument");
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "%s: bad argument", fn);
   if (!with_gt_type(sem_gt_dtype, [](auto) {}) || !with_gt_type(inst_gt_dtype, [](auto) {}) ||
       !with_ps_type(sem_ps_dtype, [](auto) {}) || !with_ps_type(inst_ps_dtype, [](auto) {}))
-    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_ap_tables: unsupported label dtype code");
-  long long n_max, ps_max, fin_max;
-  const int rc = check_layout(ctx, "gapro_eval_ap_tables", n_scenes, h_scenes, n_total_points, workspace_bytes, true,
-                              &n_max, &ps_max, &fin_max);
+    return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "%s: unsupported label dtype code", fn);
+  Rows rows = {};
+  rows.K = K;
+  for (int j = 0; j < K; ++j) {
+    rows.thr.t[j] = h_thresholds[j];
+    if (!(rows.thr.t[j] == rows.thr.t[j]) || (j > 0 && !(rows.thr.t[j] >= rows.thr.t[j - 1])))
+      return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "%s: thresholds must be ascending and not NaN", fn);
+  }
+  long long n_max, ps_max, fin_max, suffix_max = 0;
+  size_t rows_at;
+  const int rc = check_layout(ctx, fn, n_scenes, h_scenes, n_total_points, workspace_bytes, true, K, &n_max, &ps_max,
+                              &fin_max, &rows_at);
   if (rc != GAPRO_OK) return rc;
+  for (int i = 0; i < n_scenes; ++i)
+    suffix_max = std::max<long long>(
+        suffix_max, (long long)(h_scenes[i].n_keys + 1) * (h_scenes[i].max_ps + 1) + 2ll * h_scenes[i].max_ps);
   const gapro_eval_ap_scene& last = h_scenes[n_scenes - 1];
-  const long long n_ids = last.id_offset + last.max_ps;
-  const long long n_cells = last.pair_offset + (long long)(last.n_keys + 1) * (last.max_ps + 1);
+  rows.n_keys = last.key_offset + last.n_keys;
+  rows.n_ids = last.id_offset + last.max_ps;
+  rows.n_cells = last.pair_offset + (long long)(last.n_keys + 1) * (last.max_ps + 1);
+  rows.first = (unsigned long long*)((char*)d_workspace + rows_at);
   hipStream_t stream = (hipStream_t)stream_;
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_scenes, h_scenes, (size_t)n_scenes * sizeof(gapro_eval_ap_scene),
                                       hipMemcpyHostToDevice, stream));
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_status, 0, (size_t)n_scenes * sizeof(int32_t), stream));
-  GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_pair, 0, (size_t)n_cells * sizeof(int32_t), stream));
-  GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_ps_sum, 0, (size_t)n_ids * sizeof(int64_t), stream));
+  GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_pair, 0, (size_t)B * rows.n_cells * sizeof(int32_t), stream));
+  GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_ps_sum, 0, (size_t)B * rows.n_ids * sizeof(int64_t), stream));
+  if (K > 0)  // kFirstNone in every byte; row 0's first points are gapro_eval_ap_keys'
+    GAPRO_HIP_CHECK(ctx, hipMemsetAsync(rows.first, 0xff, (size_t)K * rows.n_ids * sizeof(unsigned long long), stream));
   if (n_max > 0)
     with_gt_type(sem_gt_dtype, [&](auto sgt) {
       with_gt_type(inst_gt_dtype, [&](auto igt) {
@@ -392,17 +475,47 @@ int gapro_eval_ap_tables(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const 
             using TPI = std::remove_const_t<std::remove_pointer_t<decltype(ips)>>;
             hipLaunchKernelGGL((k_ap_tally<TGS, TGI, TPS, TPI>), dim3(blocks_for(n_max, 8, 128), n_scenes),
                                dim3(kThreads), 0, stream, d_scenes, (const TGS*)d_sem_gt, (const TGI*)d_inst_gt,
-                               (const TPS*)d_sem_ps, (const TPI*)d_inst_ps, d_prob, (int)(scannet_remap != 0),
+                               (const TPS*)d_sem_ps, (const TPI*)d_inst_ps, d_prob, rows, (int)(scannet_remap != 0),
                                d_workspace, (int*)d_pair, (long long*)d_ps_sum, (int*)d_status);
           });
         });
       });
     });
-  hipLaunchKernelGGL(k_ap_finalize, dim3(blocks_for(fin_max, 1, 64), n_scenes), dim3(kThreads), 0, stream, d_scenes,
-                     d_workspace, (const int*)d_pair, (int*)d_key_code, (int*)d_key_n, (int*)d_ps_n, (int*)d_ps_label,
-                     (int*)d_ps_void);
+  if (K > 0 && n_max > 0)
+    hipLaunchKernelGGL(k_ap_suffix, dim3(blocks_for(suffix_max, 4, 256), n_scenes), dim3(kThreads), 0, stream, d_scenes,
+                       d_workspace, rows, (int*)d_pair, (long long*)d_ps_sum);
+  hipLaunchKernelGGL(k_ap_finalize, dim3(blocks_for(fin_max, 1, 64), n_scenes, B), dim3(kThreads), 0, stream, d_scenes,
+                     d_workspace, rows, (const int*)d_pair, (int*)d_key_code, (int*)d_key_n, (int*)d_ps_n,
+                     (int*)d_ps_label, (int*)d_ps_void);
   GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;
+}
+
+int gapro_eval_ap_tables_rows(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro_eval_ap_scene* h_scenes,
+                              gapro_eval_ap_scene* d_scenes, int64_t n_total_points, int32_t sem_gt_dtype,
+                              const void* d_sem_gt, int32_t inst_gt_dtype, const void* d_inst_gt, int32_t sem_ps_dtype,
+                              const void* d_sem_ps, int32_t inst_ps_dtype, const void* d_inst_ps, const float* d_prob,
+                              int32_t n_thresholds, const float* h_thresholds, int32_t scannet_remap, void* d_workspace,
+                              size_t workspace_bytes, int32_t* d_key_code, int32_t* d_key_n, int32_t* d_ps_n,
+                              int32_t* d_ps_label, int32_t* d_ps_void, int64_t* d_ps_sum, int32_t* d_pair,
+                              int32_t* d_status) {
+  return ap_tables_rows("gapro_eval_ap_tables_rows", ctx, stream, n_scenes, h_scenes, d_scenes, n_total_points,
+                        sem_gt_dtype, d_sem_gt, inst_gt_dtype, d_inst_gt, sem_ps_dtype, d_sem_ps, inst_ps_dtype, d_inst_ps,
+                        d_prob, n_thresholds, h_thresholds, scannet_remap, d_workspace, workspace_bytes, d_key_code,
+                        d_key_n, d_ps_n, d_ps_label, d_ps_void, d_ps_sum, d_pair, d_status);
+}
+
+int gapro_eval_ap_tables(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro_eval_ap_scene* h_scenes,
+                         gapro_eval_ap_scene* d_scenes, int64_t n_total_points, int32_t sem_gt_dtype,
+                         const void* d_sem_gt, int32_t inst_gt_dtype, const void* d_inst_gt, int32_t sem_ps_dtype,
+                         const void* d_sem_ps, int32_t inst_ps_dtype, const void* d_inst_ps, const float* d_prob,
+                         int32_t scannet_remap, void* d_workspace, size_t workspace_bytes, int32_t* d_key_code,
+                         int32_t* d_key_n, int32_t* d_ps_n, int32_t* d_ps_label, int32_t* d_ps_void,
+                         int64_t* d_ps_sum, int32_t* d_pair, int32_t* d_status) {
+  return ap_tables_rows("gapro_eval_ap_tables", ctx, stream, n_scenes, h_scenes, d_scenes, n_total_points, sem_gt_dtype,
+                        d_sem_gt, inst_gt_dtype, d_inst_gt, sem_ps_dtype, d_sem_ps, inst_ps_dtype, d_inst_ps, d_prob, 0,
+                        nullptr, scannet_remap, d_workspace, workspace_bytes, d_key_code, d_key_n, d_ps_n, d_ps_label,
+                        d_ps_void, d_ps_sum, d_pair, d_status);
 }
 
 }  // extern "C"

@@ -31,10 +31,6 @@ inline int blocks_for(long long items, int per_thread, int cap) {
   return (int)(g > cap ? cap : g);
 }
 
-struct Thresholds {
-  float t[GAPRO_EVAL_MAX_THRESHOLDS];
-};
-
 // one scene's tables in the workspace: B bins (rows after the suffix pass) of each
 struct SceneTables {
   unsigned long long* first_gt;  // [B][cap_gt] first point (scene-local index) of a gt id
@@ -111,11 +107,7 @@ __global__ __launch_bounds__(kThreads) void k_evb_points(const gapro_eval_scene*
   const long long stride = (long long)gridDim.x * kThreads;
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
     const long long gi_ = off + i;
-    int b = 0;
-    if (K) {
-      const float pr = prob[gi_];
-      for (int j = 0; j < K; ++j) b += pr >= thr.t[j] ? 1 : 0;
-    }
+    const int b = K ? prob_bin(thr, K, prob[gi_]) : 0;
     atomicAdd(&s_kept[b], 1);
     // get_scene_sem_conf (eval_ps_labels.py:150-172): unlabeled pseudo points count as a wrong class (:157-161)
     const long long sg = remap_gt(label_at(sem_gt, gi_), remap);

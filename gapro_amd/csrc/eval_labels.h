@@ -19,6 +19,17 @@ __device__ inline long long remap_gt(long long s, int remap) {
   return (s == -1 || s == -2) ? 18 : s;
 }
 
+// the probability thresholds of a launch (ascending) and the bin of a point: b = #{j : prob >= thresholds[j]}, so
+// row t of a result (the points with prob >= thresholds[t - 1]) is the bins t..K
+struct Thresholds {
+  float t[GAPRO_EVAL_MAX_THRESHOLDS];
+};
+__device__ inline int prob_bin(const Thresholds& thr, int K, float pr) {
+  int b = 0;
+  for (int j = 0; j < K; ++j) b += pr >= thr.t[j] ? 1 : 0;
+  return b;
+}
+
 // dtype code -> template instance
 template <class F>
 bool with_gt_type(int code, F&& f) {

@@ -14,6 +14,12 @@ and the intersections of the same-class pairs.  ``ap_from_tables`` is evaluate_m
 number of such tables: AP does not decompose per batch, so the tables of all batches are reduced once, on the host.
 ``evaluate_ap`` is the two together.  There is no CPU path for the tables.
 
+Probability thresholds: ``ap_tables_rows`` / ``evaluate_ap_rows`` return, beside the unfiltered row 0, one row per
+threshold tau: the tables / the AP of the scene restricted, in all four label arrays, to the points with
+ps_prob >= float32(tau) (the reference's certain_cond, eval_ps_labels.py:214-220, as eval_ps_labels applies it), and
+the share of the points that are kept.  All rows come from the same pass over the points; ``table_from_raw`` (host
+only) turns a row of the device arrays into its ApTable.
+
 Confidence: the reference scores every pseudo-instance 1.0 (``"one"``), which makes the precision/recall curve a
 single point.  ``"mean_prob"`` scores an instance by the mean per-point probability of gen_ps's label file, computed as
 float64(S) / (float64(n) * 2**32) from the kernel's S = sum of rint(float64(prob) * 2**32): exact and independent of
@@ -27,9 +33,10 @@ evaluator used here is that ScanNetEval, with its fixed IoU thresholds 0.50, 0.5
 
     python -m gapro_amd.eval_ap_ps_labels [--ps_folder DIR] [--data_root dataset/scannetv2] [--split train|val]
         [--stride 1] [--confidence one|mean_prob] [--min_region_size 100] [--batch_scenes 64] [--device cuda:0]
-        [--json PATH]
+        [--prob_thresholds 0.6,0.8] [--json PATH]
 
-prints print_results' table and the script's ``AP: x.xxx. AP_50: x.xxx. AP_25: x.xxx`` line.  The scene list,
+prints print_results' table and the script's ``AP: x.xxx. AP_50: x.xxx. AP_25: x.xxx`` line, then with
+--prob_thresholds one line per threshold (threshold, coverage, AP, AP_50, AP_25; in the JSON the list ``thresholds``).  The scene list,
 the file reading and the exit status (0 / 3 / 2) are eval_ps_labels' (``python -m gapro_amd.eval_ps_labels``).
 """
 from __future__ import annotations
@@ -43,7 +50,7 @@ import torch
 from . import _lib
 from ._lib import Context
 from .eval_ps_labels import (_FIELDS, _GT_CODES, _PS_CODES, CLASSES, _as_tensor, _cat, _common_dtype, _device_of,
-                             _id_caps)
+                             _id_caps, _nan_to_none)
 
 # ScanNetEval.ious: np.append(np.arange(0.5, 0.95, 0.05), 0.25)
 IOU_THRESHOLDS = np.append(np.arange(0.5, 0.95, 0.05), 0.25)
@@ -80,18 +87,74 @@ def _mean_prob(s, n):
                                                              * _PROB_SCALE)
 
 
-def ap_tables(scenes, confidence="one", scannet_remap=True, device=None):
-    """The AP tables of a batch of scenes in one set of launches (two kernels calls and one read of the key counts).
+class ApRows(NamedTuple):
+    """Result of ``ap_tables_rows``; row 0 = all points, row j = the points with ps_prob >= prob_thresholds[j - 1]."""
+    thresholds: tuple   # float32 values of the thresholds, in the caller's order
+    tables: list        # [row][scene] ApTable: the tables of the row's points
+    kept: np.ndarray    # int64 [scenes, rows]: points of the row
+
+
+class ApRowsResult(NamedTuple):
+    """Result of ``evaluate_ap_rows``, rows as in ApRows."""
+    thresholds: tuple
+    results: list         # [row] ApResult over all scenes
+    kept: np.ndarray      # int64 [rows]: points of the row, summed over the scenes
+    coverage: np.ndarray  # float64 [rows]: kept / kept[0] (NaN without a point)
+
+
+def table_from_raw(key_code, key_n, ps_n, ps_label, ps_void, ps_sum, pair, confidence="one"):
+    """One scene's row as the kernels leave it -> its ApTable (host only, NumPy).
+
+    ``key_code`` / ``key_n`` [K]: the keys of the whole scene in ascending code order and their points in this row;
+    ``ps_n`` / ``ps_label`` / ``ps_void`` / ``ps_sum`` [P]: per pseudo id the row's points, the label id (1..18, else 0)
+    of its first point in the row, its void points and its sum of rint(prob * 2**32); ``pair`` [(K + 1) * (P + 1)]:
+    points per (key + 1, id + 1), row 0 = void, column 0 = pseudo id -100.  A key without a point in the row is not a
+    GT instance of the row and an id without a class there is no prediction: both are dropped and the pair indices
+    count what is left."""
+    codes = np.asarray(key_code, dtype=np.int64)
+    key_n = np.asarray(key_n, dtype=np.int64)
+    K, P = len(codes), len(ps_n)
+    lab = np.asarray(ps_label, dtype=np.int64)
+    keys = np.flatnonzero(key_n > 0)
+    keep = np.flatnonzero(lab > 0)  # ids with points whose first point has a class in 1..18
+    n = np.asarray(ps_n, dtype=np.int64)[keep]
+    conf = _mean_prob(np.asarray(ps_sum)[keep], n) if confidence == "mean_prob" else np.ones(len(keep))
+    codes = codes[keys]
+    inter = np.asarray(pair).reshape(K + 1, P + 1)[1:, 1:][keys][:, keep].astype(np.int64)
+    same = (codes // 1000)[:, None] == lab[keep][None, :]
+    qg, qp = np.nonzero(same & (inter > 0))
+    return ApTable(codes, key_n[keys], keep.astype(np.int64), lab[keep], n, np.asarray(ps_void, dtype=np.int64)[keep],
+                   conf, qg.astype(np.int64), qp.astype(np.int64), inter[qg, qp])
+
+
+def _thresholds(prob_thresholds):
+    thr = np.asarray([float(t) for t in prob_thresholds], dtype=np.float32)
+    if len(thr) > _lib.GAPRO_EVAL_MAX_THRESHOLDS:
+        raise ValueError("at most %d probability thresholds" % _lib.GAPRO_EVAL_MAX_THRESHOLDS)
+    if np.isnan(thr).any():
+        raise ValueError("a probability threshold is NaN")
+    return thr
+
+
+def ap_tables_rows(scenes, prob_thresholds=(), confidence="one", scannet_remap=True, device=None):
+    """The AP tables of a batch of scenes, unfiltered and for every probability threshold, in one set of launches (two
+    kernel calls and one read of the key counts, one pass over the points).
 
     ``scenes``: as for eval_ps_labels.evaluate_scenes, mappings with the keys ``semantic_label``, ``instance_label``
     (GT: float64, int32 or int64), ``ps_semantic_label``, ``ps_instance_label`` (int32 or int64), ``ps_prob`` (float32
-    per point; needed for ``confidence="mean_prob"``) and optionally ``max_ps`` (pseudo id table size; by default
-    max id + 1), or tuples in that order.  ``scannet_remap`` applies the script's GT remap (:59-60) on the device.
-    Returns one ApTable per scene.  Raises ValueError naming the scenes with an instance id >= 999, a pseudo id < 0
-    other than -100 or beyond the table, or (mean_prob) a probability that is NaN or outside [0, 1]."""
+    per point; needed for ``confidence="mean_prob"`` and with thresholds) and optionally ``max_ps`` (pseudo id table
+    size; by default max id + 1), or tuples in that order.  ``scannet_remap`` applies the script's GT remap (:59-60) on
+    the device.  A threshold tau keeps the points with ps_prob >= float32(tau) in all four arrays, as
+    evaluate_scenes' rows do; a row's tables are the tables of those points alone: a pseudo id takes the label of its
+    first kept point, a GT instance without a kept point is not in the row, and mean_prob is over the kept points.
+    Thresholds in any order, at most 32.  Returns ApRows.  Raises ValueError before anything runs for a NaN threshold,
+    more than 32, or thresholds without ps_prob, and naming the scenes with an instance id >= 999, a pseudo id < 0
+    other than -100 or beyond the table, or (with ps_prob in use) a probability that is NaN or outside [0, 1]."""
     if confidence not in CONFIDENCE_MODES:
         raise ValueError("confidence must be one of %s, not %r" % (CONFIDENCE_MODES, confidence))
-    need_prob = confidence == "mean_prob"
+    thr = _thresholds(prob_thresholds)
+    T = len(thr)
+    need_prob = confidence == "mean_prob" or T > 0
     cols = {f: [] for f in _FIELDS}
     caps = []
     for i, sc in enumerate(scenes):
@@ -105,7 +168,8 @@ def ap_tables(scenes, confidence="one", scannet_remap=True, device=None):
         if need_prob:
             prob = sc.get("ps_prob")
             if prob is None:
-                raise ValueError("scene %d: confidence='mean_prob' needs ps_prob" % i)
+                raise ValueError("scene %d: %s ps_prob" % (i, "probability thresholds need" if T else
+                                                           "confidence='mean_prob' needs"))
             prob = _as_tensor(prob)
             if prob.numel() != n:
                 raise ValueError("scene %d: ps_prob has %d entries for %d points" % (i, prob.numel(), n))
@@ -128,9 +192,12 @@ def ap_tables(scenes, confidence="one", scannet_remap=True, device=None):
         d.point_offset, d.n_points = off, cols["semantic_label"][i].numel()
         d.max_ps = int(caps[i]) if caps[i] is not None else ps_caps[i]
         off += d.n_points
+    order = np.argsort(thr, kind="stable")
+    h_thr = (C.c_float * T)(*[float(v) for v in thr[order]]) if T else None
+    B = T + 1
     ctx = Context.get(dev.index)
     lib = ctx.lib
-    ws_bytes = int(lib.gapro_eval_ap_workspace_bytes(descs, S))
+    ws_bytes = int(lib.gapro_eval_ap_workspace_bytes_rows(descs, S, T))
     if ws_bytes == 0:
         raise ValueError("bad pseudo id table sizes")
     n_ids = int(descs[S - 1].id_offset) + int(descs[S - 1].max_ps)
@@ -151,37 +218,49 @@ def ap_tables(scenes, confidence="one", scannet_remap=True, device=None):
             d.n_keys = k
         n_cells = int(lib.gapro_eval_ap_pair_cells(descs, S))
         n_key_rows = int(descs[S - 1].key_offset) + int(descs[S - 1].n_keys)
-        i32 = lambda m: torch.empty(max(m, 1), dtype=torch.int32, device=dev)  # noqa: E731
+        i32 = lambda m: torch.empty(max(B * m, 1), dtype=torch.int32, device=dev)  # noqa: E731
         key_code, key_n = i32(n_key_rows), i32(n_key_rows)
         ps_n, ps_label, ps_void, pair = i32(n_ids), i32(n_ids), i32(n_ids), i32(n_cells)
-        ps_sum = torch.empty(n_ids, dtype=torch.int64, device=dev)
-        ctx.check(lib.gapro_eval_ap_tables(
+        ps_sum = torch.empty(B * n_ids, dtype=torch.int64, device=dev)
+        ctx.check(lib.gapro_eval_ap_tables_rows(
             ctx.handle, stream(), S, descs, d_descs.data_ptr(), off, _GT_CODES[sem.dtype], sem.data_ptr(),
             _GT_CODES[ins.dtype], ins.data_ptr(), _PS_CODES[ps_sem.dtype], ps_sem.data_ptr(), _PS_CODES[ps_ins.dtype],
-            ps_ins.data_ptr(), None if prob is None else prob.data_ptr(), remap, ws.data_ptr(), ws_bytes,
+            ps_ins.data_ptr(), None if prob is None else prob.data_ptr(), T, h_thr, remap, ws.data_ptr(), ws_bytes,
             key_code.data_ptr(), key_n.data_ptr(), ps_n.data_ptr(), ps_label.data_ptr(), ps_void.data_ptr(),
             ps_sum.data_ptr(), pair.data_ptr(), status.data_ptr()))
         host = [t.cpu().numpy() for t in (status, key_code, key_n, ps_n, ps_label, ps_void, ps_sum, pair)]
-    status, key_code, key_n, ps_n, ps_label, ps_void, ps_sum, pair = host
+    status = host[0]
     bad = np.flatnonzero(status).tolist()
     if bad:
         raise ValueError("scene(s) %s: a GT instance id >= 999, a pseudo instance id < 0 other than -100 or beyond "
                          "the id table, or a probability that is NaN or outside [0, 1]" % bad)
-    out = []
-    for d in descs:
+    # [B, whole batch] each; kernel rows follow the ascending thresholds: the caller's row j + 1 is kernel row
+    # 1 + rank of threshold j
+    key_code, key_n = (a[:B * n_key_rows].reshape(B, n_key_rows) for a in host[1:3])
+    ps_n, ps_label, ps_void, ps_sum = (a[:B * n_ids].reshape(B, n_ids) for a in host[3:7])
+    pair = host[7][:B * n_cells].reshape(B, n_cells)
+    perm = np.empty(B, dtype=np.int64)
+    perm[0] = 0
+    perm[1 + order] = 1 + np.arange(T)
+    tables = [[] for _ in range(B)]
+    kept = np.zeros((S, B), dtype=np.int64)
+    for i, d in enumerate(descs):
         k0, K, i0, P, c0 = int(d.key_offset), int(d.n_keys), int(d.id_offset), int(d.max_ps), int(d.pair_offset)
-        lab = ps_label[i0:i0 + P].astype(np.int64)
-        keep = np.flatnonzero(lab > 0)  # ids with points whose first point has a class in 1..18
-        n = ps_n[i0:i0 + P].astype(np.int64)[keep]
-        conf = _mean_prob(ps_sum[i0:i0 + P][keep], n) if need_prob else np.ones(len(keep))
-        codes = key_code[k0:k0 + K].astype(np.int64)
-        inter = pair[c0:c0 + (K + 1) * (P + 1)].reshape(K + 1, P + 1)[1:, 1:][:, keep].astype(np.int64)
-        same = (codes // 1000)[:, None] == lab[keep][None, :]
-        qg, qp = np.nonzero(same & (inter > 0))
-        out.append(ApTable(codes, key_n[k0:k0 + K].astype(np.int64), keep.astype(np.int64), lab[keep], n,
-                           ps_void[i0:i0 + P].astype(np.int64)[keep], conf, qg.astype(np.int64), qp.astype(np.int64),
-                           inter[qg, qp]))
-    return out
+        for j, r in enumerate(perm):
+            cells = pair[r, c0:c0 + (K + 1) * (P + 1)]
+            kept[i, j] = cells.sum(dtype=np.int64)  # every point of the row is in one pair cell
+            tables[j].append(table_from_raw(key_code[r, k0:k0 + K], key_n[r, k0:k0 + K], ps_n[r, i0:i0 + P],
+                                            ps_label[r, i0:i0 + P], ps_void[r, i0:i0 + P], ps_sum[r, i0:i0 + P], cells,
+                                            confidence))
+    return ApRows(tuple(float(v) for v in thr), tables, kept)
+
+
+def ap_tables(scenes, confidence="one", scannet_remap=True, device=None):
+    """The AP tables of a batch of scenes: ap_tables_rows without thresholds, its row 0.
+
+    Returns one ApTable per scene.  Raises ValueError naming the scenes with an instance id >= 999, a pseudo id < 0
+    other than -100 or beyond the table, or (mean_prob) a probability that is NaN or outside [0, 1]."""
+    return ap_tables_rows(scenes, (), confidence, scannet_remap, device).tables[0]
 
 
 def _curve(y_true, y_score, hard_false_negatives):
@@ -335,6 +414,24 @@ def evaluate_ap(scenes, confidence="one", scannet_remap=True, min_region_size=10
     return ap_from_tables(ap_tables(scenes, confidence, scannet_remap, device), min_region_size)
 
 
+def ap_from_tables_rows(tables, kept, min_region_size=100):
+    """ap_from_tables per row of ap_tables_rows' tables ([row][scene], of any number of batches) and the coverage from
+    ``kept`` (int64 [scenes, rows] or already summed [rows]) -> (list of ApResult, kept [rows], coverage [rows])."""
+    kept = np.asarray(kept, dtype=np.int64)
+    kept = kept.sum(axis=0) if kept.ndim == 2 else kept
+    with np.errstate(invalid="ignore", divide="ignore"):
+        coverage = kept.astype(np.float64) / np.float64(kept[0])
+    return [ap_from_tables(t, min_region_size) for t in tables], kept, coverage
+
+
+def evaluate_ap_rows(scenes, prob_thresholds=(), confidence="one", scannet_remap=True, min_region_size=100,
+                     device=None):
+    """ap_from_tables of every row of ap_tables_rows(scenes, prob_thresholds, ...) -> ApRowsResult: the AP of the
+    points the generator is at least that sure about, and the share of the points they are."""
+    rows = ap_tables_rows(scenes, prob_thresholds, confidence, scannet_remap, device)
+    return ApRowsResult(rows.thresholds, *ap_from_tables_rows(rows.tables, rows.kept, min_region_size))
+
+
 def format_results(avgs):
     """print_results (:433-485): the 64-column table, class rows and the average row."""
     sep, col1, lineLen = "", ":", 64
@@ -358,8 +455,6 @@ def format_results(avgs):
 
 
 def _json_avgs(avgs):
-    from .eval_ps_labels import _nan_to_none
-
     out = {k: _nan_to_none(v) for k, v in avgs.items() if k != "classes"}
     out["classes"] = {c: {k: _nan_to_none(v) for k, v in d.items()} for c, d in avgs["classes"].items()}
     return out
@@ -381,25 +476,38 @@ def main(argv=None):
     parser.add_argument("--stride", type=int, default=1)
     parser.add_argument("--confidence", type=str, default="one", choices=list(CONFIDENCE_MODES))
     parser.add_argument("--min_region_size", type=int, default=100)
+    parser.add_argument("--prob_thresholds", type=str, default="")
     parser.add_argument("--batch_scenes", type=int, default=64)
     parser.add_argument("--device", type=str, default=None)
     parser.add_argument("--json", type=str, default=None)
     args = parser.parse_args(argv)
     t0 = time.perf_counter()
+    try:
+        taus = [float(v) for v in args.prob_thresholds.split(",") if v.strip()]
+        _thresholds(taus)
+    except ValueError as e:
+        parser.error("--prob_thresholds: %s" % e)
     scanned = list_scenes(args.data_root, args.split, args.stride)
     present = [s for s in scanned if osp.exists(osp.join(args.ps_folder, s + ".pth"))]
     have = set(present)
     missing = [s for s in scanned if s not in have]
-    need_prob = args.confidence == "mean_prob"
-    tables, evaluated, failed = [], [], {}
+    need_prob = args.confidence == "mean_prob" or bool(taus)
+    tables, evaluated, failed = [[] for _ in range(len(taus) + 1)], [], {}
+    kept = np.zeros(len(taus) + 1, dtype=np.int64)
     t_eval = 0.0  # upload, kernels, download: the rest of the run is reading and the host reduction
-    for names, scenes in read_scene_batches(args, present, need_prob, failed, "--confidence mean_prob"):
+    for names, scenes in read_scene_batches(args, present, need_prob, failed,
+                                            "--confidence mean_prob" if args.confidence == "mean_prob"
+                                            else "--prob_thresholds"):
         t1 = time.perf_counter()
-        tables += ap_tables(scenes, args.confidence, scannet_remap=True, device=args.device)
+        rows = ap_tables_rows(scenes, taus, args.confidence, scannet_remap=True, device=args.device)
         t_eval += time.perf_counter() - t1
+        for r, per_scene in enumerate(rows.tables):
+            tables[r] += per_scene
+        kept += rows.kept.sum(axis=0)
         evaluated += names
     t1 = time.perf_counter()
-    res = ap_from_tables(tables, args.min_region_size) if evaluated else None
+    row_res, _, coverage = ap_from_tables_rows(tables, kept, args.min_region_size) if evaluated else ([None], kept, None)
+    res = row_res[0]
     t_ap = time.perf_counter() - t1
     elapsed = time.perf_counter() - t0
 
@@ -413,6 +521,18 @@ def main(argv=None):
                                                                  avgs["all_ap_25%"]))
         out.update(avgs=_json_avgs(avgs), n_gt=dict(zip(CLASSES, res.n_gt.tolist())),
                    n_pred=dict(zip(CLASSES, res.n_pred.tolist())))
+        if taus:
+            print("%-10s %10s %8s %8s %8s" % ("prob >=", "coverage", "AP", "AP_50", "AP_25"))
+            out["thresholds"] = []
+        for j, tau in enumerate(taus):
+            r = row_res[j + 1]
+            a = r.avgs
+            print("%-10g %10.4f %8.3f %8.3f %8.3f" % (tau, coverage[j + 1], a["all_ap"], a["all_ap_50%"],
+                                                        a["all_ap_25%"]))
+            out["thresholds"].append(dict(threshold=tau, kept_points=int(kept[j + 1]),
+                                          coverage=_nan_to_none(coverage[j + 1]), avgs=_json_avgs(a),
+                                          n_gt=dict(zip(CLASSES, r.n_gt.tolist())),
+                                          n_pred=dict(zip(CLASSES, r.n_pred.tolist()))))
     print("[eval_ap_ps_labels] %d scene(s) listed, %d evaluated, %d without a label file, %d failed in %.2f s"
           % (len(scanned), len(evaluated), len(missing), len(failed), elapsed), file=sys.stderr)
     if failed:

@@ -291,6 +291,38 @@ int gapro_eval_ap_tables(gapro_ctx* ctx, void* stream, int32_t n_scenes, const g
                          int32_t scannet_remap, void* d_workspace, size_t workspace_bytes, int32_t* d_key_code,
                          int32_t* d_key_n, int32_t* d_ps_n, int32_t* d_ps_label, int32_t* d_ps_void,
                          int64_t* d_ps_sum, int32_t* d_pair, int32_t* d_status);
+/* The AP tables with probability-threshold rows, as gapro_eval_batch has them: row 0 is the scene as it is, row t
+ * (1..n_thresholds) the scene restricted, in all four label arrays, to the points with prob >= thresholds[t-1]
+ * (float32 compare).  A row's tables are the tables of that filtered scene: an id's label is that of its first kept
+ * point, the counts and d_ps_sum are over the kept points.  Pass 1 is unchanged and ranks the keys of the whole
+ * scene, so a key without a kept point stays in its place with d_key_n = 0 (the caller drops it), as a pseudo id
+ * without a kept point has d_ps_n = 0 and d_ps_label = 0.  One pass over the points, one atomic of each kind per
+ * point, into the tables of the point's bin #{j : prob >= thresholds[j]}; a suffix sum / min over the bins makes
+ * the rows.
+ * gapro_eval_ap_workspace_bytes_rows: gapro_eval_ap_workspace_bytes (same ws_offset / id_offset, so the workspace
+ * serves gapro_eval_ap_keys as it is) plus n_thresholds first-point rows behind the scenes' blocks; 0 on a bad
+ * argument or n_thresholds outside [0, GAPRO_EVAL_MAX_THRESHOLDS]. */
+size_t gapro_eval_ap_workspace_bytes_rows(gapro_eval_ap_scene* h_scenes, int32_t n_scenes, int32_t n_thresholds);
+/* Pass 2 with rows.  in : as gapro_eval_ap_tables, plus h_thresholds f32[n_thresholds] (host), ascending; d_prob
+ *        is needed when n_thresholds > 0; the workspace of pass 1, sized by gapro_eval_ap_workspace_bytes_rows.
+ *   out: every per-key, per-id and pair output of gapro_eval_ap_tables with a leading row dimension of
+ *        n_thresholds + 1 whose stride is the output's size for the whole batch: d_key_code / d_key_n
+ *        i32[rows][key_offset[last] + n_keys[last]] (d_key_code is the same in every row), d_ps_n / d_ps_label /
+ *        d_ps_void i32 and d_ps_sum i64 [rows][id_offset[last] + max_ps[last]], d_pair i32[rows][pair cells].  Row
+ *        0's block is gapro_eval_ap_tables' output, bit for bit; gapro_eval_ap_tables is this call without
+ *        thresholds.  The points of a scene's row are the sum of its pair cells.  d_status i32[n_scenes] as for
+ *        gapro_eval_ap_tables: a probability that is NaN or outside [0, 1] is GAPRO_ERR_BAD_ARG for the scene.
+ * Refused with GAPRO_ERR_BAD_ARG: n_thresholds outside [0, GAPRO_EVAL_MAX_THRESHOLDS], thresholds that are NaN
+ * or not ascending (equal ones are allowed), thresholds without d_prob; GAPRO_ERR_WORKSPACE: a workspace
+ * without the first-point rows.  Enqueue only. */
+int gapro_eval_ap_tables_rows(gapro_ctx* ctx, void* stream, int32_t n_scenes, const gapro_eval_ap_scene* h_scenes,
+                              gapro_eval_ap_scene* d_scenes, int64_t n_total_points, int32_t sem_gt_dtype,
+                              const void* d_sem_gt, int32_t inst_gt_dtype, const void* d_inst_gt, int32_t sem_ps_dtype,
+                              const void* d_sem_ps, int32_t inst_ps_dtype, const void* d_inst_ps, const float* d_prob,
+                              int32_t n_thresholds, const float* h_thresholds, int32_t scannet_remap, void* d_workspace,
+                              size_t workspace_bytes, int32_t* d_key_code, int32_t* d_key_n, int32_t* d_ps_n,
+                              int32_t* d_ps_label, int32_t* d_ps_void, int64_t* d_ps_sum, int32_t* d_pair,
+                              int32_t* d_status);
 
 /* Heuristic labelers: gen_pseudo_label (gen_ps_utils.py:485-569; rule 0 = "volume",
  * 1 = "dist", 2 = "none") and gen_pseudo_label_box2mask (:242-290; rule 3).  Membership in the INSTANCE boxes
