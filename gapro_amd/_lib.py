@@ -323,6 +323,7 @@ DEBUG_SIGNATURES = {
     "gapro_debug_product_bench": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
                                             C.POINTER(C.c_float)]),
     "gapro_debug_wgloop": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_double)]),
+    "gapro_debug_exact_sum": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -8,21 +8,12 @@
 // the same launches (the reductions are float64 sums of float32 terms, so the values do not depend on the
 // launch shape beyond float64 rounding).
 #include "common.h"
+#include "launch_util.h"
+#include "wave_reduce.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-
-inline int grid_for(long long n, int cap = 1024) {
-  long long g = (n + kThreads - 1) / kThreads;
-  if (g < 1) g = 1;
-  return (int)(g > cap ? cap : g);
-}
-
-__device__ inline double wave_sum_d(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // block-reduce K doubles and add them to out[0..K) with one atomic per workgroup and value
 template <int K>
@@ -31,7 +22,7 @@ __device__ inline void block_accumulate(double (&v)[K], double* out) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    const double s = wave_sum_d(v[k]);
+    const double s = wave_sum(v[k]);
     if (lane == 0) sh[k][w] = s;
   }
   __syncthreads();
@@ -180,7 +171,7 @@ int gapro_label_pool_mean(gapro_ctx* ctx, void* stream_, int64_t n_points, int32
   hipStream_t stream = (hipStream_t)stream_;
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_sums_ws, 0, (size_t)n_out * 3 * sizeof(double), stream));
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_counts_ws, 0, (size_t)n_out * sizeof(int32_t), stream));
-  hipLaunchKernelGGL(k_pool3_sum, dim3(grid_for(n_points, 2048)), dim3(kThreads), 0, stream, (long long)n_points,
+  hipLaunchKernelGGL(k_pool3_sum, dim3(grid_for(n_points, 1, 2048)), dim3(kThreads), 0, stream, (long long)n_points,
                      (int)n_out, (const long long*)d_index, d_prob, d_mu, d_var, d_sums_ws, d_counts_ws);
   hipLaunchKernelGGL(k_pool3_mean, dim3((n_out + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, (int)n_out,
                      d_sums_ws, d_counts_ws, d_out_prob, d_out_mu, d_out_var);
@@ -197,9 +188,9 @@ int gapro_weighted_bce_with_logits(gapro_ctx* ctx, void* stream_, int32_t n_rows
   hipStream_t stream = (hipStream_t)stream_;
   const long long n = (long long)n_rows * n_cols;
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_acc2, 0, 2 * sizeof(double), stream));
-  hipLaunchKernelGGL(k_wbce_reduce, dim3(grid_for(n)), dim3(kThreads), 0, stream, (int)n_rows, (long long)n_cols,
+  hipLaunchKernelGGL(k_wbce_reduce, dim3(grid_for(n, 1, 1024)), dim3(kThreads), 0, stream, (int)n_rows, (long long)n_cols,
                      d_logits, d_targets, d_weights, d_acc2);
-  hipLaunchKernelGGL(k_wbce_grad, dim3(d_grad_logits ? grid_for(n) : 1), dim3(kThreads), 0, stream, (int)n_rows,
+  hipLaunchKernelGGL(k_wbce_grad, dim3(d_grad_logits ? grid_for(n, 1, 1024) : 1), dim3(kThreads), 0, stream, (int)n_rows,
                      (long long)n_cols, d_logits, d_targets, d_weights, (const double*)d_acc2, grad_out, d_loss,
                      d_grad_logits);
   GAPRO_LAUNCH_CHECK(ctx);
@@ -214,10 +205,10 @@ int gapro_kl_gp_loss(gapro_ctx* ctx, void* stream_, int64_t n, const float* d_mu
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_kl_gp_loss: bad argument");
   hipStream_t stream = (hipStream_t)stream_;
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_acc4, 0, 4 * sizeof(double), stream));
-  hipLaunchKernelGGL(k_kl_reduce, dim3(grid_for(n)), dim3(kThreads), 0, stream, (long long)n, d_mu_labels, d_var_labels,
+  hipLaunchKernelGGL(k_kl_reduce, dim3(grid_for(n, 1, 1024)), dim3(kThreads), 0, stream, (long long)n, d_mu_labels, d_var_labels,
                      d_mu_pred, d_logvar_pred, epsilon, d_acc4);
   const bool grads = d_grad_mu && d_grad_logvar;
-  hipLaunchKernelGGL(k_kl_grad, dim3(grads ? grid_for(n) : 1), dim3(kThreads), 0, stream, (long long)n, d_mu_labels,
+  hipLaunchKernelGGL(k_kl_grad, dim3(grads ? grid_for(n, 1, 1024) : 1), dim3(kThreads), 0, stream, (long long)n, d_mu_labels,
                      d_var_labels, d_mu_pred, d_logvar_pred, epsilon, weight, (const double*)d_acc4, grad_out, d_loss,
                      d_grad_mu, d_grad_logvar);
   GAPRO_LAUNCH_CHECK(ctx);

@@ -20,6 +20,8 @@
 // Integer atomics only: every table is bit-identical to a plain tally of the scene, whatever the batch.
 #include "common.h"
 #include "eval_labels.h"
+#include "exact_sum.h"
+#include "launch_util.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -34,14 +36,8 @@ constexpr int kApWords = (kApCodes + 31) / 32;        // presence bitmap words p
 constexpr int kPairLds = 8192;                        // pair cells kept in LDS ((keys + 1) x (ids + 1))
 constexpr int kIdLds = 512;                           // per-id first points / probability sums kept in LDS
 constexpr unsigned long long kFirstNone = ~0ull;
-constexpr double kProbScale = 4294967296.0;           // 2^32
+constexpr int kProbShift = 32;                        // a probability term is rint(prob * 2^32)
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-inline int blocks_for(long long items, int per_thread, int cap) {
-  long long g = (items + (long long)kThreads * per_thread - 1) / ((long long)kThreads * per_thread);
-  if (g < 1) g = 1;
-  return (int)(g > cap ? cap : g);
-}
 
 // one scene in the workspace: bitmap u32[kApWords] | exclusive rank of each word i32[kApWords] | first u64[max_ps]
 // (bin / row 0); the first points of the bins / rows 1..T follow the last scene's block as u64[T][ids of the batch]
@@ -214,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void k_ap_tally(const gapro_eval_ap_scene
       if (lds_id) atomicMin(&s_first[b * P + p], first);
       else atomicMin(&first_of(w, rows, s, b)[p], first);
       if (prob) {
-        const unsigned long long q = (unsigned long long)(long long)rint((double)pr * kProbScale);
+        const unsigned long long q = (unsigned long long)to_fixed((double)pr, kProbShift);
         if (lds_id) atomicAdd(&s_sum[b * P + p], q);
         else atomicAdd(&g_sum[b * rows.n_ids + p], q);
       }
@@ -400,14 +396,14 @@ int gapro_eval_ap_keys(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const ga
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_scenes, h_scenes, (size_t)n_scenes * sizeof(gapro_eval_ap_scene),
                                       hipMemcpyHostToDevice, stream));
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_status, 0, (size_t)n_scenes * sizeof(int32_t), stream));
-  hipLaunchKernelGGL(k_ap_init, dim3(blocks_for(kApWords + ps_max, 1, 64), n_scenes), dim3(kThreads), 0, stream,
+  hipLaunchKernelGGL(k_ap_init, dim3(grid_for(kApWords + ps_max, 1, 64), n_scenes), dim3(kThreads), 0, stream,
                      d_scenes, d_workspace);
   if (n_max > 0)
     with_gt_type(sem_gt_dtype, [&](auto sgt) {
       with_gt_type(inst_gt_dtype, [&](auto igt) {
         using TGS = std::remove_const_t<std::remove_pointer_t<decltype(sgt)>>;
         using TGI = std::remove_const_t<std::remove_pointer_t<decltype(igt)>>;
-        hipLaunchKernelGGL((k_ap_mark<TGS, TGI>), dim3(blocks_for(n_max, 8, 128), n_scenes), dim3(kThreads), 0,
+        hipLaunchKernelGGL((k_ap_mark<TGS, TGI>), dim3(grid_for(n_max, 8, 128), n_scenes), dim3(kThreads), 0,
                            stream, d_scenes, (const TGS*)d_sem_gt, (const TGI*)d_inst_gt, (int)(scannet_remap != 0),
                            d_workspace, (int*)d_status);
       });
@@ -473,7 +469,7 @@ static int ap_tables_rows(const char* fn, gapro_ctx* ctx, void* stream_, int32_t
             using TGI = std::remove_const_t<std::remove_pointer_t<decltype(igt)>>;
             using TPS = std::remove_const_t<std::remove_pointer_t<decltype(sps)>>;
             using TPI = std::remove_const_t<std::remove_pointer_t<decltype(ips)>>;
-            hipLaunchKernelGGL((k_ap_tally<TGS, TGI, TPS, TPI>), dim3(blocks_for(n_max, 8, 128), n_scenes),
+            hipLaunchKernelGGL((k_ap_tally<TGS, TGI, TPS, TPI>), dim3(grid_for(n_max, 8, 128), n_scenes),
                                dim3(kThreads), 0, stream, d_scenes, (const TGS*)d_sem_gt, (const TGI*)d_inst_gt,
                                (const TPS*)d_sem_ps, (const TPI*)d_inst_ps, d_prob, rows, (int)(scannet_remap != 0),
                                d_workspace, (int*)d_pair, (long long*)d_ps_sum, (int*)d_status);
@@ -482,9 +478,9 @@ static int ap_tables_rows(const char* fn, gapro_ctx* ctx, void* stream_, int32_t
       });
     });
   if (K > 0 && n_max > 0)
-    hipLaunchKernelGGL(k_ap_suffix, dim3(blocks_for(suffix_max, 4, 256), n_scenes), dim3(kThreads), 0, stream, d_scenes,
+    hipLaunchKernelGGL(k_ap_suffix, dim3(grid_for(suffix_max, 4, 256), n_scenes), dim3(kThreads), 0, stream, d_scenes,
                        d_workspace, rows, (int*)d_pair, (long long*)d_ps_sum);
-  hipLaunchKernelGGL(k_ap_finalize, dim3(blocks_for(fin_max, 1, 64), n_scenes, B), dim3(kThreads), 0, stream, d_scenes,
+  hipLaunchKernelGGL(k_ap_finalize, dim3(grid_for(fin_max, 1, 64), n_scenes, B), dim3(kThreads), 0, stream, d_scenes,
                      d_workspace, rows, (const int*)d_pair, (int*)d_key_code, (int*)d_key_n, (int*)d_ps_n,
                      (int*)d_ps_label, (int*)d_ps_void);
   GAPRO_LAUNCH_CHECK(ctx);

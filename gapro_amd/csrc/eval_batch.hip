@@ -11,6 +11,7 @@
 // scene, whatever the batch composition.  Without instance arrays only the confusion and the counts are tallied.
 #include "common.h"
 #include "eval_labels.h"
+#include "launch_util.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -24,12 +25,6 @@ constexpr int kConfLds = 2048;  // (bin, gt class, ps class) confusion bins kept
 constexpr int kMaxBins = GAPRO_EVAL_MAX_THRESHOLDS + 1;
 constexpr unsigned long long kKeyMax = ~0ull;
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-inline int blocks_for(long long items, int per_thread, int cap) {
-  long long g = (items + (long long)kThreads * per_thread - 1) / ((long long)kThreads * per_thread);
-  if (g < 1) g = 1;
-  return (int)(g > cap ? cap : g);
-}
 
 // one scene's tables in the workspace: B bins (rows after the suffix pass) of each
 struct SceneTables {
@@ -306,7 +301,7 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapr
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_kept, 0, (size_t)n_scenes * B * sizeof(int64_t), stream));
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_status, 0, (size_t)n_scenes * sizeof(int32_t), stream));
   const long long words_max = (long long)B * std::max<long long>(gt_max + ps_max, (gt_max + 1) * (ps_max + 1) + ps_max);
-  hipLaunchKernelGGL(k_evb_init, dim3(blocks_for(words_max, 4, 256), n_scenes), dim3(kThreads), 0, stream, d_scenes,
+  hipLaunchKernelGGL(k_evb_init, dim3(grid_for(words_max, 4, 256), n_scenes), dim3(kThreads), 0, stream, d_scenes,
                      d_workspace, B);
   if (n_max > 0)
     with_gt_type(sem_gt_dtype, [&](auto sgt) {
@@ -317,7 +312,7 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapr
             using TGI = std::remove_const_t<std::remove_pointer_t<decltype(igt)>>;
             using TPS = std::remove_const_t<std::remove_pointer_t<decltype(sps)>>;
             using TPI = std::remove_const_t<std::remove_pointer_t<decltype(ips)>>;
-            hipLaunchKernelGGL((k_evb_points<TGS, TGI, TPS, TPI>), dim3(blocks_for(n_max, 4, 128), n_scenes),
+            hipLaunchKernelGGL((k_evb_points<TGS, TGI, TPS, TPI>), dim3(grid_for(n_max, 4, 128), n_scenes),
                                dim3(kThreads), 0, stream, d_scenes, (const TGS*)d_sem_gt, (const TGI*)d_inst_gt,
                                (const TPS*)d_sem_ps, (const TPI*)d_inst_ps, d_prob, thr, K, (int)(scannet_remap != 0),
                                C, d_workspace, (long long*)d_conf, (long long*)d_kept, (int*)d_status);
@@ -326,19 +321,19 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapr
       });
     });
   if (B > 1) {
-    hipLaunchKernelGGL(k_evb_suffix, dim3(blocks_for(cells_max, 4, 256), n_scenes), dim3(kThreads), 0, stream, d_scenes,
+    hipLaunchKernelGGL(k_evb_suffix, dim3(grid_for(cells_max, 4, 256), n_scenes), dim3(kThreads), 0, stream, d_scenes,
                        d_workspace, B);
-    hipLaunchKernelGGL(k_evb_suffix_counts, dim3(blocks_for((long long)CC + n_scenes, 1, 64)), dim3(kThreads), 0, stream,
+    hipLaunchKernelGGL(k_evb_suffix_counts, dim3(grid_for((long long)CC + n_scenes, 1, 64)), dim3(kThreads), 0, stream,
                        (long long*)d_conf, CC, (long long*)d_kept, (int)n_scenes, B);
   }
   if (d_max_iou && d_gt_cls) {
-    hipLaunchKernelGGL(k_evb_ps_count, dim3(blocks_for((long long)B * ps_max, 1, 64), n_scenes), dim3(kThreads), 0,
+    hipLaunchKernelGGL(k_evb_ps_count, dim3(grid_for((long long)B * ps_max, 1, 64), n_scenes), dim3(kThreads), 0,
                        stream, d_scenes, d_workspace, B);
     with_gt_type(sem_gt_dtype, [&](auto sgt) {
       with_ps_type(sem_ps_dtype, [&](auto sps) {
         using TGS = std::remove_const_t<std::remove_pointer_t<decltype(sgt)>>;
         using TPS = std::remove_const_t<std::remove_pointer_t<decltype(sps)>>;
-        hipLaunchKernelGGL((k_evb_finalize<TGS, TPS>), dim3(blocks_for((long long)B * gt_max, 1, 64), n_scenes),
+        hipLaunchKernelGGL((k_evb_finalize<TGS, TPS>), dim3(grid_for((long long)B * gt_max, 1, 64), n_scenes),
                            dim3(kThreads), 0, stream, d_scenes, (const TGS*)d_sem_gt, (const TPS*)d_sem_ps,
                            (int)(scannet_remap != 0), d_workspace, B, d_max_iou, d_gt_cls);
       });

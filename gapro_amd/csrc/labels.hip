@@ -6,6 +6,8 @@
 // bit-reproducible and independent of the launch shape).  The quality evaluator (get_miou_scene,
 // get_scene_sem_conf) lives in eval_batch.hip.
 #include "common.h"
+#include "launch_util.h"
+#include "wave_reduce.h"
 
 #include <algorithm>
 
@@ -15,12 +17,6 @@ constexpr int kThreads = 256;
 constexpr int kLdsIds = 512;            // instance ids whose tallies fit the per-workgroup LDS table
 constexpr unsigned long long kKeyMax = ~0ull;
 
-inline int grid_for(long long n, int cap = 1024) {
-  long long g = (n + kThreads - 1) / kThreads;
-  if (g < 1) g = 1;
-  return (int)(g > cap ? cap : g);
-}
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // order-preserving map double -> uint64 (and back): integer min/max atomics then order doubles exactly
 __device__ inline unsigned long long key_of(double x) {
@@ -269,7 +265,7 @@ __global__ __launch_bounds__(kThreads) void k_lab_chunk_count(long long n, LabWs
     if (i < n && t.raw[i] == -3) ++c;
   }
   __shared__ int sh[kThreads / 64];
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -423,12 +419,12 @@ int gapro_instance_info(gapro_ctx* ctx, void* stream_, int64_t n_points, const d
   hipStream_t stream = (hipStream_t)stream_;
   const int cap = max_instances;
   hipLaunchKernelGGL(k_inst_init, dim3((3 * cap + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, d_workspace, cap);
-  hipLaunchKernelGGL(k_inst_minmax, dim3(grid_for(n_points, 512)), dim3(kThreads), 0, stream, (long long)n_points,
+  hipLaunchKernelGGL(k_inst_minmax, dim3(grid_for(n_points, 1, 512)), dim3(kThreads), 0, stream, (long long)n_points,
                      d_coords, d_instance_label, d_workspace, cap);
   hipLaunchKernelGGL(k_inst_finalize, dim3(1), dim3(kThreads), 0, stream, d_workspace, cap, (int)scannet_class_shift,
                      d_semantic_label, d_box, d_cls, d_volume, d_header);
   if (d_corners)
-    hipLaunchKernelGGL(k_inst_corners, dim3(grid_for(n_points)), dim3(kThreads), 0, stream, (long long)n_points,
+    hipLaunchKernelGGL(k_inst_corners, dim3(grid_for(n_points, 1, 1024)), dim3(kThreads), 0, stream, (long long)n_points,
                        d_coords, d_instance_label, (const void*)d_workspace, cap, d_corners);
   GAPRO_LAUNCH_CHECK(ctx);
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(h_header_pinned, d_header, sizeof(gapro_instance_header), hipMemcpyDeviceToHost,
@@ -459,7 +455,7 @@ int gapro_label_heuristic(gapro_ctx* ctx, void* stream_, int64_t n_points, const
   const int B = n_boxes, S = align ? n_spps : 1;
   LabWs t = lab_ws(d_workspace, n_points, n_spps, n_boxes);
   const int box2mask = rule == 3;  // volume rule, alignment without the occupancy mask (:277-283)
-  hipLaunchKernelGGL(k_lab_points, dim3(grid_for(n_points, 2048)), dim3(kThreads), (size_t)B * 6 * sizeof(double), stream,
+  hipLaunchKernelGGL(k_lab_points, dim3(grid_for(n_points, 1, 2048)), dim3(kThreads), (size_t)B * 6 * sizeof(double), stream,
                      (long long)n_points, d_coords, B, d_box, d_volume, box2mask ? 0 : (int)rule, t);
   if (rule == 1) {
     const int n_chunks = (int)((n_points + kLabChunk - 1) / kLabChunk);
@@ -473,11 +469,11 @@ int gapro_label_heuristic(gapro_ctx* ctx, void* stream_, int64_t n_points, const
     GAPRO_HIP_CHECK(ctx, hipMemsetAsync(t.label_count, 0, (size_t)S * (B + 1) * 4, stream));
     GAPRO_HIP_CHECK(ctx, hipMemsetAsync(t.occ_count, 0, (size_t)S * B * 4, stream));
     GAPRO_HIP_CHECK(ctx, hipMemsetAsync(t.point_count, 0, (size_t)S * 4, stream));
-    hipLaunchKernelGGL(k_lab_tally, dim3(grid_for(n_points, 2048)), dim3(kThreads), 0, stream, (long long)n_points,
+    hipLaunchKernelGGL(k_lab_tally, dim3(grid_for(n_points, 1, 2048)), dim3(kThreads), 0, stream, (long long)n_points,
                        d_spp_inv, B, masked, t);
     hipLaunchKernelGGL(k_lab_argmax, dim3((S + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, S, B, masked, t);
   }
-  hipLaunchKernelGGL(k_lab_final, dim3(grid_for(n_points, 2048)), dim3(kThreads), 0, stream, (long long)n_points,
+  hipLaunchKernelGGL(k_lab_final, dim3(grid_for(n_points, 1, 2048)), dim3(kThreads), 0, stream, (long long)n_points,
                      d_spp_inv, (int)(align != 0), (const long long*)d_cls, (int)instance_classes, t, d_sem, d_inst);
   GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;

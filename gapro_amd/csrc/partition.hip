@@ -8,6 +8,9 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "exact_sum.h"
+#include "launch_util.h"
+#include "wave_reduce.h"
 
 #include <algorithm>
 
@@ -17,13 +20,6 @@ constexpr int kThreads = 256;
 constexpr int kMaxStatBlocks = 1024;
 constexpr int kScanChunk = 2048;  // elements per block in the rank scan (256 threads x 8)
 
-struct StatsPartial {
-  double mn[3], mx[3];
-  long long smin, smax;
-  float fabsmax;
-  int pad;
-};
-
 struct PrepareWorkspace {  // device layout, all offsets 16-byte aligned
   gapro_scene_header header;
   StatsPartial partials[kMaxStatBlocks];
@@ -31,33 +27,6 @@ struct PrepareWorkspace {  // device layout, all offsets 16-byte aligned
 
 static_assert(sizeof(gapro_scene_task) == 176, "gapro_scene_task layout is part of the ABI (ctypes mirror)");
 constexpr size_t kFlagsOffset = (sizeof(PrepareWorkspace) + 255) / 256 * 256;
-
-__device__ inline double wave_min(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ inline double wave_max(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ inline long long wave_min_ll(long long v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    long long t = __shfl_xor(v, o, 64);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ inline long long wave_max_ll(long long v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    long long t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ inline float wave_max_f(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // ---- K1: per-block partial statistics ---------------------------------------------------------
 // Every kernel below handles scene blockIdx.y of a batch: its pointers come from tasks[blockIdx.y].
@@ -78,45 +47,26 @@ __global__ __launch_bounds__(kThreads) void k_stats(const gapro_scene_task* __re
   StatsPartial* __restrict__ partials = prep_ws(t)->partials;
   const long long tid = (long long)blockIdx.x * kThreads + threadIdx.x;
   const long long stride = (long long)gridDim.x * kThreads;
-  double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  long long smin = 0x7fffffffffffffffLL, smax = -0x7fffffffffffffffLL - 1;
-  float fa = 0.f;
+  StatsPartial p = stats_identity();
   for (long long i = tid; i < n; i += stride) {
     const double x = coords[3 * i], y = coords[3 * i + 1], z = coords[3 * i + 2];
-    mn[0] = fmin(mn[0], x); mx[0] = fmax(mx[0], x);
-    mn[1] = fmin(mn[1], y); mx[1] = fmax(mx[1], y);
-    mn[2] = fmin(mn[2], z); mx[2] = fmax(mx[2], z);
+    p.mn[0] = fmin(p.mn[0], x); p.mx[0] = fmax(p.mx[0], x);
+    p.mn[1] = fmin(p.mn[1], y); p.mx[1] = fmax(p.mx[1], y);
+    p.mn[2] = fmin(p.mn[2], z); p.mx[2] = fmax(p.mx[2], z);
     // fmin / fmax drop NaNs: a non-finite coordinate is carried in the feature statistic (+inf = "scene not finite")
-    if (!(isfinite(x) && isfinite(y) && isfinite(z))) fa = INFINITY;
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) p.fabsmax = INFINITY;
     const long long s = spp[i];
-    smin = s < smin ? s : smin;
-    smax = s > smax ? s : smax;
+    p.smin = s < p.smin ? s : p.smin;
+    p.smax = s > p.smax ? s : p.smax;
   }
   const long long nf = n * d;
   for (long long i = tid; i < nf; i += stride) {
     const float v = feats[i];
-    fa = fmaxf(fa, isfinite(v) ? fabsf(v) : INFINITY);  // fmaxf would drop a NaN; the reference would propagate it
+    // fmaxf would drop a NaN; the reference would propagate it
+    p.fabsmax = fmaxf(p.fabsmax, isfinite(v) ? fabsf(v) : INFINITY);
   }
-
-  __shared__ StatsPartial sh[kThreads / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int k = 0; k < 3; ++k) { mn[k] = wave_min(mn[k]); mx[k] = wave_max(mx[k]); }
-  smin = wave_min_ll(smin); smax = wave_max_ll(smax); fa = wave_max_f(fa);
-  if (lane == 0) {
-    for (int k = 0; k < 3; ++k) { sh[w].mn[k] = mn[k]; sh[w].mx[k] = mx[k]; }
-    sh[w].smin = smin; sh[w].smax = smax; sh[w].fabsmax = fa;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    StatsPartial p = sh[0];
-    for (int j = 1; j < kThreads / 64; ++j) {
-      for (int k = 0; k < 3; ++k) { p.mn[k] = fmin(p.mn[k], sh[j].mn[k]); p.mx[k] = fmax(p.mx[k], sh[j].mx[k]); }
-      p.smin = sh[j].smin < p.smin ? sh[j].smin : p.smin;
-      p.smax = sh[j].smax > p.smax ? sh[j].smax : p.smax;
-      p.fabsmax = fmaxf(p.fabsmax, sh[j].fabsmax);
-    }
-    partials[blockIdx.x] = p;
-  }
+  p = stats_block_fold<kThreads>(p);
+  if (threadIdx.x == 0) partials[blockIdx.x] = p;
 }
 
 // ---- K1b: fold partials into the scene header --------------------------------------------------
@@ -125,45 +75,14 @@ __global__ __launch_bounds__(kThreads) void k_stats_final(const gapro_scene_task
   const gapro_scene_task& t = tasks[blockIdx.y];
   const long long n = t.n_points, range_cap = t.spp_range_cap;
   PrepareWorkspace* ws = prep_ws(t);
-  double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-  long long smin = 0x7fffffffffffffffLL, smax = -0x7fffffffffffffffLL - 1;
-  float fa = 0.f;
-  for (int j = threadIdx.x; j < n_partials; j += kThreads) {
-    const StatsPartial& q = ws->partials[j];
-    for (int k = 0; k < 3; ++k) { mn[k] = fmin(mn[k], q.mn[k]); mx[k] = fmax(mx[k], q.mx[k]); }
-    smin = q.smin < smin ? q.smin : smin;
-    smax = q.smax > smax ? q.smax : smax;
-    fa = fmaxf(fa, q.fabsmax);
-  }
-  __shared__ StatsPartial sh[kThreads / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int k = 0; k < 3; ++k) { mn[k] = wave_min(mn[k]); mx[k] = wave_max(mx[k]); }
-  smin = wave_min_ll(smin); smax = wave_max_ll(smax); fa = wave_max_f(fa);
-  if (lane == 0) {
-    for (int k = 0; k < 3; ++k) { sh[w].mn[k] = mn[k]; sh[w].mx[k] = mx[k]; }
-    sh[w].smin = smin; sh[w].smax = smax; sh[w].fabsmax = fa;
-  }
-  __syncthreads();
+  StatsPartial p = stats_identity();
+  for (int j = threadIdx.x; j < n_partials; j += kThreads) stats_merge(p, ws->partials[j]);
+  p = stats_block_fold<kThreads>(p);
   if (threadIdx.x != 0) return;
-  StatsPartial p = sh[0];
-  for (int j = 1; j < kThreads / 64; ++j) {
-    for (int k = 0; k < 3; ++k) { p.mn[k] = fmin(p.mn[k], sh[j].mn[k]); p.mx[k] = fmax(p.mx[k], sh[j].mx[k]); }
-    p.smin = sh[j].smin < p.smin ? sh[j].smin : p.smin;
-    p.smax = sh[j].smax > p.smax ? sh[j].smax : p.smax;
-    p.fabsmax = fmaxf(p.fabsmax, sh[j].fabsmax);
-  }
   gapro_scene_header h;
   for (int k = 0; k < 3; ++k) { h.coord_min[k] = p.mn[k]; h.coord_max[k] = p.mx[k]; }
   h.spp_min = p.smin; h.spp_max = p.smax; h.feat_absmax = p.fabsmax;
-  // fixed-point exponent: |rint(x 2^k)| * n < 2^61  (same rule as oracle/gen_ps_oracle.py:fixed_point_shift)
-  int k = 0;
-  if (p.fabsmax > 0.f && isfinite(p.fabsmax)) {
-    int e; (void)frexpf(p.fabsmax, &e);
-    const int lg = n > 1 ? 64 - __clzll((unsigned long long)(n - 1)) : 0;
-    k = 61 - e - lg;
-    k = k < -1000 ? -1000 : (k > 1000 ? 1000 : k);
-  }
-  h.fixed_shift = k;
+  h.fixed_shift = fixed_point_shift((double)p.fabsmax, n);
   h.n_spps = 0;
   h.status = GAPRO_OK;
   const unsigned long long range = (unsigned long long)p.smax - (unsigned long long)p.smin;
@@ -308,7 +227,6 @@ __global__ __launch_bounds__(kThreads) void k_rank_lookup(const gapro_scene_task
 // words: scattered atomics are ~17x slower on gfx950, MI355X_MICROARCH.md "Global float atomics"), lane
 // D%8 adds the point count, and lane k tests boxes k, k+8, ...  Box corners (with the +-0.005 margin
 // applied in float64, as gen_ps_utils.py:350 does) sit in LDS.
-constexpr int kLanesPerPoint = 8;
 // zero the integer tallies of every scene (feat_sum, occ_count, point_count)
 __global__ __launch_bounds__(kThreads) void k_pool_clear(const gapro_scene_task* __restrict__ tasks, int d) {
   const gapro_scene_task& t = tasks[blockIdx.y];
@@ -345,17 +263,10 @@ __global__ __launch_bounds__(kThreads) void k_pool(const gapro_scene_task* __res
     const double x = coords[3 * i], y = coords[3 * i + 1], z = coords[3 * i + 2];
     const int r = spp_inv[i];
     if (k == (d & (kLanesPerPoint - 1))) atomicAdd(&point_count[r], 1);
-    const float* f = feats + i * d;
-    for (int c = k; c < d; c += kLanesPerPoint) {
-      const long long q = __double2ll_rn(ldexp((double)f[c], shift));
-      atomicAdd(&feat_sum[(long long)r * d + c], (unsigned long long)q);
-    }
+    accumulate_features(feat_sum + (long long)r * d, feats + i * d, d, k, shift);
     int* occ_row = occ_count + (long long)r * nb;
-    for (int b = k; b < nb; b += kLanesPerPoint) {
-      const double* bx = sh_box + 6 * b;
-      const bool in = (x >= bx[0]) & (y >= bx[1]) & (z >= bx[2]) & (x <= bx[3]) & (y <= bx[4]) & (z <= bx[5]);
-      if (in) atomicAdd(&occ_row[b], 1);
-    }
+    for (int b = k; b < nb; b += kLanesPerPoint)
+      if (in_box(sh_box + 6 * b, x, y, z)) atomicAdd(&occ_row[b], 1);
   }
 }
 
@@ -433,19 +344,13 @@ __global__ __launch_bounds__(kThreads) void k_pool_lds(const gapro_scene_task* _
     if (one_spp) {
       const bool head = (threadIdx.x & 63) < kLanesPerPoint;
       if (head && k == (d & (kLanesPerPoint - 1))) atomicAdd(&cnt[slot], (unsigned)(64 / kLanesPerPoint));
-      for (int c0 = 0; c0 < d; c0 += kLanesPerPoint) {
-        const int c = c0 + k;
-        long long q = c < d ? __double2ll_rn(ldexp((double)f[c], shift)) : 0ll;
-        q += __shfl_down(q, 8, 64);
-        q += __shfl_down(q, 16, 64);
-        q += __shfl_down(q, 32, 64);
-        if (head && c < d) atomicAdd(&fsum[(size_t)slot * d + c], (unsigned long long)q);
-      }
+      accumulate_features_wave8(fsum + (size_t)slot * d, f, d, k, shift, head);
       unsigned* occ_row = occ + (size_t)slot * nb;
       for (int b0 = 0; b0 < nb; b0 += kLanesPerPoint) {
         const int b = b0 + k;
         int in = 0;
-        if (b < nb) {
+        if (b < nb) {  // in_box's expression written out: through the call the compiler packs the compares into a bit
+          //            mask here (14 more instructions per round of this, the hot branch; LABNOTES "One exact-sum rule")
           const double* bx = sh_box + 6 * b;
           in = (x >= bx[0]) & (y >= bx[1]) & (z >= bx[2]) & (x <= bx[3]) & (y <= bx[4]) & (z <= bx[5]);
         }
@@ -456,28 +361,16 @@ __global__ __launch_bounds__(kThreads) void k_pool_lds(const gapro_scene_task* _
       }
     } else if (slot >= 0) {
       if (k == (d & (kLanesPerPoint - 1))) atomicAdd(&cnt[slot], 1u);
-      for (int c = k; c < d; c += kLanesPerPoint) {
-        const long long q = __double2ll_rn(ldexp((double)f[c], shift));
-        atomicAdd(&fsum[(size_t)slot * d + c], (unsigned long long)q);
-      }
+      accumulate_features(fsum + (size_t)slot * d, f, d, k, shift);
       unsigned* occ_row = occ + (size_t)slot * nb;
-      for (int b = k; b < nb; b += kLanesPerPoint) {
-        const double* bx = sh_box + 6 * b;
-        const bool in = (x >= bx[0]) & (y >= bx[1]) & (z >= bx[2]) & (x <= bx[3]) & (y <= bx[4]) & (z <= bx[5]);
-        if (in) atomicAdd(&occ_row[b], 1u);
-      }
+      for (int b = k; b < nb; b += kLanesPerPoint)
+        if (in_box(sh_box + 6 * b, x, y, z)) atomicAdd(&occ_row[b], 1u);
     } else {  // table full around this hash: straight to global memory, as k_pool does
       if (k == (d & (kLanesPerPoint - 1))) atomicAdd(&point_count[r], 1);
-      for (int c = k; c < d; c += kLanesPerPoint) {
-        const long long q = __double2ll_rn(ldexp((double)f[c], shift));
-        atomicAdd(&feat_sum[(long long)r * d + c], (unsigned long long)q);
-      }
+      accumulate_features(feat_sum + (long long)r * d, f, d, k, shift);
       int* occ_row = occ_count + (long long)r * nb;
-      for (int b = k; b < nb; b += kLanesPerPoint) {
-        const double* bx = sh_box + 6 * b;
-        const bool in = (x >= bx[0]) & (y >= bx[1]) & (z >= bx[2]) & (x <= bx[3]) & (y <= bx[4]) & (z <= bx[5]);
-        if (in) atomicAdd(&occ_row[b], 1);
-      }
+      for (int b = k; b < nb; b += kLanesPerPoint)
+        if (in_box(sh_box + 6 * b, x, y, z)) atomicAdd(&occ_row[b], 1);
     }
   }
   __syncthreads();
@@ -530,7 +423,7 @@ __global__ __launch_bounds__(kThreads) void k_pool_finalize(const gapro_scene_ta
   n_bbs[s] = nbb;
   const double pcd = (double)pc;
   for (int k = 0; k < d; ++k)
-    feats_spp[(long long)s * d + k] = (float)(ldexp((double)feat_sum[(long long)s * d + k], -shift) / pcd);
+    feats_spp[(long long)s * d + k] = (float)fixed_mean(feat_sum[(long long)s * d + k], shift, pcd);
 }
 
 // ---- K6: superpoint -> point broadcast ----------------------------------------------------------
@@ -552,14 +445,6 @@ __global__ __launch_bounds__(kThreads) void k_broadcast(const gapro_scene_task* 
     prob[i] = prob_spp[r];
   }
 }
-
-inline int grid_for(long long n, int cap = 2048) {
-  long long g = (n + kThreads - 1) / kThreads;
-  if (g < 1) g = 1;
-  return (int)(g > cap ? cap : g);
-}
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // LDS of the pooling kernels: the box corners (both kernels), and k_pool_lds's table of 2^log2_slots slots of
 // {key, count, n_boxes occupancy counts, feat_dim 64-bit sums}
@@ -609,12 +494,12 @@ int gapro_partition_prepare_batch(gapro_ctx* ctx, void* stream_, int32_t n_scene
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_tasks, h_tasks, (size_t)n_scenes * sizeof(gapro_scene_task),
                                       hipMemcpyHostToDevice, stream));
   const unsigned ny = (unsigned)n_scenes;
-  const int g_stats = grid_for(n_max, kMaxStatBlocks);
-  const int g_pts = grid_for(n_max);
+  const int g_stats = grid_for(n_max, 1, kMaxStatBlocks);
+  const int g_pts = grid_for(n_max, 1, 2048);
   const int g_scan = (int)((cap_max + kScanChunk - 1) / kScanChunk);
   hipLaunchKernelGGL(k_stats, dim3(g_stats, ny), dim3(kThreads), 0, stream, d_tasks, (int)feat_dim);
   hipLaunchKernelGGL(k_stats_final, dim3(1, ny), dim3(kThreads), 0, stream, d_tasks, g_stats, d_headers);
-  hipLaunchKernelGGL(k_clear_flags, dim3(grid_for(cap_max, 512), ny), dim3(kThreads), 0, stream, d_tasks);
+  hipLaunchKernelGGL(k_clear_flags, dim3(grid_for(cap_max, 1, 512), ny), dim3(kThreads), 0, stream, d_tasks);
   hipLaunchKernelGGL(k_flags, dim3(g_pts, ny), dim3(kThreads), 0, stream, d_tasks);
   hipLaunchKernelGGL(k_scan_blocksum, dim3(g_scan, ny), dim3(kThreads), 0, stream, d_tasks);
   hipLaunchKernelGGL(k_scan_offsets, dim3(1, ny), dim3(kThreads), 0, stream, d_tasks, d_headers);
@@ -665,7 +550,7 @@ int gapro_partition_pool_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, 
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_tasks, h_tasks, (size_t)n_scenes * sizeof(gapro_scene_task),
                                       hipMemcpyHostToDevice, stream));
   const unsigned ny = (unsigned)n_scenes;
-  hipLaunchKernelGGL(k_pool_clear, dim3(grid_for(clear_max, 256), ny), dim3(kThreads), 0, stream, d_tasks, (int)feat_dim);
+  hipLaunchKernelGGL(k_pool_clear, dim3(grid_for(clear_max, 1, 256), ny), dim3(kThreads), 0, stream, d_tasks, (int)feat_dim);
   // LDS-privatised tallies (k_pool_lds): a table of 16 .. 64 slots beside the box corners, or round 1's kernel: the
   // choice is gapro_partition_pool_plan's
   if (plan > 0) {
@@ -680,7 +565,7 @@ int gapro_partition_pool_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, 
   } else {
     // the whole batch shares the GPU: cap the per-scene grid so that the batch is a few waves of workgroups
     const int cap = n_scenes >= 8 ? 512 : 4096;
-    hipLaunchKernelGGL(k_pool, dim3(grid_for(n_max * kLanesPerPoint, cap), ny), dim3(kThreads), lds, stream, d_tasks,
+    hipLaunchKernelGGL(k_pool, dim3(grid_for(n_max * kLanesPerPoint, 1, cap), ny), dim3(kThreads), lds, stream, d_tasks,
                        (int)feat_dim);
   }
   hipLaunchKernelGGL(k_pool_finalize, dim3((s_max + kThreads - 1) / kThreads, ny), dim3(kThreads), 0, stream, d_tasks,
@@ -703,7 +588,7 @@ int gapro_broadcast_labels_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes
   hipStream_t stream = (hipStream_t)stream_;
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_tasks, h_tasks, (size_t)n_scenes * sizeof(gapro_scene_task),
                                       hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(k_broadcast, dim3(grid_for(n_max, n_scenes >= 8 ? 256 : 2048), (unsigned)n_scenes), dim3(kThreads),
+  hipLaunchKernelGGL(k_broadcast, dim3(grid_for(n_max, 1, n_scenes >= 8 ? 256 : 2048), (unsigned)n_scenes), dim3(kThreads),
                      0, stream, d_tasks);
   GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;

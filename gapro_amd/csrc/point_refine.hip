@@ -7,6 +7,9 @@
 // No reference counterpart: the reference labels whole superpoints (gen_ps_utils.py:438-480).  Batched over the scenes of
 // a batch like gapro_broadcast_labels_batch (grid.y = scene), with a per-scene struct of its own.
 #include "common.h"
+#include "exact_sum.h"
+#include "launch_util.h"
+#include "wave_reduce.h"
 
 #include <algorithm>
 
@@ -15,12 +18,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr long long kMaxRows = 0x7fffffffLL;  // row indices are int32 (the predict ABI)
 constexpr int kMaxGridY = 65535;
-
-inline int grid_for(long long n, int cap) {
-  long long g = (n + kThreads - 1) / kThreads;
-  if (g < 1) g = 1;
-  return (int)(g > cap ? cap : g);
-}
 
 __global__ __launch_bounds__(kThreads) void k_refine_clear(const gapro_point_refine_scene* __restrict__ scenes) {
   const gapro_point_refine_scene& t = scenes[blockIdx.y];
@@ -226,39 +223,14 @@ __global__ __launch_bounds__(kThreads) void k_refine_compete(
 // gather order nor the order of the lanes reaches a result bit.
 constexpr int kVoteMaxSeg = 2048;  // 2 * 2 * kVoteMaxSeg ints of dynamic LDS = 32 KiB at most
 
-__device__ __forceinline__ int vote_shift(unsigned absmax_bits, int n) {  // oracle/gen_ps_oracle.py:fixed_point_shift
-  const float a = __uint_as_float(absmax_bits);
-  int k = 0;
-  if (a > 0.f && isfinite(a)) {
-    int e; (void)frexpf(a, &e);
-    const int lg = n > 1 ? 32 - __clz((unsigned)(n - 1)) : 0;
-    k = 61 - e - lg;
-    k = k < -1000 ? -1000 : (k > 1000 ? 1000 : k);
-  }
-  return k;
-}
-
-// wave-level reductions in front of the LDS atomics: one atomic per wave and quantity instead of one per lane
-__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
-  for (int o = 32; o > 0; o >>= 1) { const unsigned w = (unsigned)__shfl_xor((int)v, o); v = w > v ? w : v; }
-  return v;
-}
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(unsigned long long)v, o);
-    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)((unsigned long long)v >> 32), o);
-    v = (long long)((unsigned long long)v + (((unsigned long long)hi << 32) | lo));  // wraps like the atomic would
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_or_i(int v) {
-  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
-  return v;
+// the shift of a block's exact sums (exact_sum.h) from the bits of the largest finite magnitude among its voting rows
+__device__ __forceinline__ int vote_shift(unsigned absmax_bits, int n) {
+  return fixed_point_shift((double)__uint_as_float(absmax_bits), n);
 }
 
 __device__ __forceinline__ float vote_mean(long long sum, int k, int count, bool poisoned) {
   if (poisoned) return __uint_as_float(0x7fc00000u);
-  return (float)(ldexp((double)sum, -k) / (double)count);
+  return (float)fixed_mean(sum, k, (double)count);
 }
 
 __global__ __launch_bounds__(kThreads) void k_refine_vote(
@@ -300,9 +272,9 @@ __global__ __launch_bounds__(kThreads) void k_refine_vote(
       if (isfinite(m)) a1 = fmaxf(a1, fabsf(m));
       if (isfinite(v)) a2 = fmaxf(a2, fabsf(v));
     }
-    {  // every lane is here (the row loop has ended): non-negative floats order like their bits
-      const unsigned m0 = wave_max_u(__float_as_uint(a0)), m1 = wave_max_u(__float_as_uint(a1)),
-                     m2 = wave_max_u(__float_as_uint(a2));
+    {  // one atomic per wave; every lane is here (the row loop has ended): non-negative floats order like their bits
+      const unsigned m0 = wave_max(__float_as_uint(a0)), m1 = wave_max(__float_as_uint(a1)),
+                     m2 = wave_max(__float_as_uint(a2));
       if ((tid & 63) == 0) {
         if (m0) atomicMax(&s_amax[0], m0);
         if (m1) atomicMax(&s_amax[1], m1);
@@ -345,14 +317,14 @@ __global__ __launch_bounds__(kThreads) void k_refine_vote(
       long long at;
       const int s = take_row(blk, j, segs, n_rows2, probs_new, status, &best, &at);
       if (s < 0 || s_box[2 * s + (labels[at] != 0 ? 1 : 0)] != X) continue;
-      if (isfinite(best)) q0 += (long long)rint(ldexp((double)best, k0)); else poison |= 1;
+      if (isfinite(best)) q0 += to_fixed((double)best, k0); else poison |= 1;
       if (s != sf) continue;
       const float m = mu_r[at], v = var_r[at];
-      if (isfinite(m)) q1 += (long long)rint(ldexp((double)m, k1)); else poison |= 2;
-      if (isfinite(v)) q2 += (long long)rint(ldexp((double)v, k2)); else poison |= 4;
+      if (isfinite(m)) q1 += to_fixed((double)m, k1); else poison |= 2;
+      if (isfinite(v)) q2 += to_fixed((double)v, k2); else poison |= 4;
     }
-    q0 = wave_sum_ll(q0); q1 = wave_sum_ll(q1); q2 = wave_sum_ll(q2);
-    poison = wave_or_i(poison);
+    q0 = wave_sum(q0); q1 = wave_sum(q1); q2 = wave_sum(q2);
+    poison = wave_or(poison);
     if ((tid & 63) == 0) {
       if (q0) atomicAdd(&s_sum[0], (unsigned long long)q0);
       if (q1) atomicAdd(&s_sum[1], (unsigned long long)q1);
@@ -426,8 +398,8 @@ int gapro_point_refine_gather(gapro_ctx* ctx, void* stream_, int32_t n_scenes, i
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_scenes, h_scenes, (size_t)n_scenes * sizeof(gapro_point_refine_scene),
                                       hipMemcpyHostToDevice, stream));
   const unsigned ny = (unsigned)n_scenes;
-  hipLaunchKernelGGL(k_refine_clear, dim3(grid_for(s_max, 256), ny), dim3(kThreads), 0, stream, d_scenes);
-  hipLaunchKernelGGL(k_refine_gather, dim3(grid_for(n_max, n_scenes >= 8 ? 256 : 2048), ny), dim3(kThreads), 0, stream,
+  hipLaunchKernelGGL(k_refine_clear, dim3(grid_for(s_max, 1, 256), ny), dim3(kThreads), 0, stream, d_scenes);
+  hipLaunchKernelGGL(k_refine_gather, dim3(grid_for(n_max, 1, n_scenes >= 8 ? 256 : 2048), ny), dim3(kThreads), 0, stream,
                      d_scenes, (int)feat_dim, (long long)n_rows, d_row_feats, d_row_point);
   GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;
@@ -467,12 +439,12 @@ int gapro_point_refine_apply(gapro_ctx* ctx, void* stream_, int32_t n_scenes, co
   hipStream_t stream = (hipStream_t)stream_;
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_scenes, h_scenes, (size_t)n_scenes * sizeof(gapro_point_refine_scene),
                                       hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(k_refine_mu_var, dim3(grid_for(n_max, n_scenes >= 8 ? 256 : 2048), (unsigned)n_scenes),
+  hipLaunchKernelGGL(k_refine_mu_var, dim3(grid_for(n_max, 1, n_scenes >= 8 ? 256 : 2048), (unsigned)n_scenes),
                      dim3(kThreads), 0, stream, d_scenes);
   if (n_models > 0 && t_max > 0) {
     GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_models, h_models, (size_t)n_models * sizeof(gapro_point_refine_model),
                                         hipMemcpyHostToDevice, stream));
-    const int gx = grid_for(t_max, n_models >= 64 ? 64 : 1024);
+    const int gx = grid_for(t_max, 1, n_models >= 64 ? 64 : 1024);
     for (int lo = 0; lo < n_models; lo += kMaxGridY) {  // grid.y holds at most 65535 models per launch
       const int ny = std::min(kMaxGridY, n_models - lo);
       hipLaunchKernelGGL(k_refine_apply, dim3(gx, (unsigned)ny), dim3(kThreads), 0, stream, d_scenes, d_models + lo,
@@ -502,7 +474,7 @@ int gapro_point_refine_expand(gapro_ctx* ctx, void* stream_, int32_t n_blocks, c
                                       hipMemcpyHostToDevice, stream));
   GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_segs, h_segs, (size_t)n_segs * sizeof(gapro_point_refine_segment),
                                       hipMemcpyHostToDevice, stream));
-  hipLaunchKernelGGL(k_refine_expand, dim3(grid_for(n_rows, 2048)), dim3(kThreads), 0, stream, d_blocks, (int)n_blocks,
+  hipLaunchKernelGGL(k_refine_expand, dim3(grid_for(n_rows, 1, 2048)), dim3(kThreads), 0, stream, d_blocks, (int)n_blocks,
                      d_segs, (long long)n_rows, (long long)n_rows2, d_rows);
   GAPRO_LAUNCH_CHECK(ctx);
   return GAPRO_OK;
@@ -552,7 +524,7 @@ int gapro_point_refine_compete(gapro_ctx* ctx, void* stream_, int32_t n_scenes, 
     GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(d_segs, h_segs, (size_t)n_segs * sizeof(gapro_point_refine_segment),
                                         hipMemcpyHostToDevice, stream));
   }
-  hipLaunchKernelGGL(k_refine_compete, dim3(grid_for(n_rows, 2048)), dim3(kThreads), 0, stream, d_scenes, d_models,
+  hipLaunchKernelGGL(k_refine_compete, dim3(grid_for(n_rows, 1, 2048)), dim3(kThreads), 0, stream, d_scenes, d_models,
                      d_blocks, (int)n_blocks, d_segs, (long long)n_rows, (long long)n_rows2, d_row_point, d_probs_new,
                      d_labels, d_mu, d_var, d_model_status, d_row_model);
   GAPRO_LAUNCH_CHECK(ctx);

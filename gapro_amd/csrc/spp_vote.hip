@@ -8,6 +8,8 @@
 // A refusal raised by tally is a status word in the workspace: every later kernel returns at once and the outputs stay
 // untouched.  The heuristic labelers keep their own welded vote (labels.hip k_lab_tally / k_lab_argmax, LabWs).
 #include "common.h"
+#include "exact_sum.h"
+#include "launch_util.h"
 
 namespace {
 
@@ -43,24 +45,6 @@ VoteWs carve(void* base, long long S, long long C) {
   w.prob_spp = (float*)p; p += up16((size_t)S * 4);
   w.bytes = (size_t)(p - (char*)base);
   return w;
-}
-
-inline int grid_for(long long n) {
-  long long g = (n + kThreads - 1) / kThreads;
-  if (g < 1) g = 1;
-  return (int)(g > 4096 ? 4096 : g);
-}
-
-// |rint(x 2^k)| * n < 2^61: the rule of oracle/gen_ps_oracle.py:fixed_point_shift and partition.hip's k_stats
-__device__ __forceinline__ int fixed_shift(float absmax, long long n) {
-  int k = 0;
-  if (absmax > 0.f && isfinite(absmax)) {
-    int e; (void)frexpf(absmax, &e);
-    const int lg = n > 1 ? 64 - __clzll((unsigned long long)(n - 1)) : 0;
-    k = 61 - e - lg;
-    k = k < -1000 ? -1000 : (k > 1000 ? 1000 : k);
-  }
-  return k;
 }
 
 template <typename LabelT>
@@ -108,10 +92,10 @@ __global__ __launch_bounds__(kThreads) void k_vote_sums(long long n, int C, cons
                                                         const float* __restrict__ prob, const VoteHeader* hdr,
                                                         long long* __restrict__ P) {
   if (hdr->status != 0) return;
-  const int k = fixed_shift(__uint_as_float(hdr->absmax_bits), n);
+  const int k = fixed_point_shift((double)__uint_as_float(hdr->absmax_bits), n);
   const long long stride = (long long)gridDim.x * kThreads;
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
-    const long long q = (long long)rint(ldexp((double)prob[i], k));
+    const long long q = to_fixed((double)prob[i], k);
     if (q) atomicAdd((unsigned long long*)&P[(long long)ids[i] * C + (long long)label[i]], (unsigned long long)q);
   }
 }
@@ -120,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void k_vote_sums(long long n, int C, cons
 __global__ __launch_bounds__(kThreads) void k_vote_final(long long n, int S, int C, int major, int has_prob,
                                                          const unsigned char* __restrict__ gate, VoteWs w) {
   if (w.hdr->status != 0) return;
-  const int k = fixed_shift(__uint_as_float(w.hdr->absmax_bits), n);
+  const int k = fixed_point_shift((double)__uint_as_float(w.hdr->absmax_bits), n);
   for (int s = blockIdx.x * kThreads + threadIdx.x; s < S; s += gridDim.x * kThreads) {
     const int* __restrict__ cnt = w.cnt + (long long)s * C;
     const long long* __restrict__ P = w.P + (long long)s * C;
@@ -140,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void k_vote_final(long long n, int S, int
       if (has_prob) {
         if (major) {
 #pragma clang fp contract(off)
-          const double mean = ldexp((double)P[c], -k) / ((double)cnt[c] + 1e-4);
+          const double mean = fixed_mean(P[c], k, (double)cnt[c] + 1e-4);
           const double share = ns > 0 ? (double)m / (double)ns : 0.0;  // ns == 0: S beyond the ranks present
           const double term = mean * share;
           acc = acc + term;
@@ -150,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void k_vote_final(long long n, int S, int
       }
     }
     w.label_spp[s] = best;
-    if (has_prob) w.prob_spp[s] = major ? (float)acc : (ns > 0 ? (float)(ldexp((double)p_all, -k) / (double)ns) : 0.f);
+    if (has_prob) w.prob_spp[s] = major ? (float)acc : (ns > 0 ? (float)fixed_mean(p_all, k, (double)ns) : 0.f);
   }
 }
 
@@ -198,7 +182,7 @@ int gapro_spp_vote(gapro_ctx* ctx, void* stream_, int32_t mode, int64_t n_points
     return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_spp_vote: workspace of %zu bytes, %zu needed", ws_bytes, w.bytes);
   hipStream_t stream = (hipStream_t)stream_;
   const long long n = n_points;
-  const int S = n_spps, C = n_classes, g = grid_for(n);
+  const int S = n_spps, C = n_classes, g = grid_for(n, 1, 4096);
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_ws, 0, w.bytes, stream));
   if (label_is_i64)
     hipLaunchKernelGGL(k_vote_tally<long long>, dim3(g), dim3(kThreads), 0, stream, n, S, C, (int)major, d_ids,
@@ -207,7 +191,7 @@ int gapro_spp_vote(gapro_ctx* ctx, void* stream_, int32_t mode, int64_t n_points
     hipLaunchKernelGGL(k_vote_tally<int>, dim3(g), dim3(kThreads), 0, stream, n, S, C, (int)major, d_ids,
                        (const int*)d_label, d_prob, w.hdr, w.cnt);
   if (major && C > 1)
-    hipLaunchKernelGGL(k_vote_occ, dim3(grid_for(n * (C - 1))), dim3(kThreads), 0, stream, n, S, C, d_ids, d_gate,
+    hipLaunchKernelGGL(k_vote_occ, dim3(grid_for(n * (C - 1), 1, 4096)), dim3(kThreads), 0, stream, n, S, C, d_ids, d_gate,
                        w.occn);
   if (d_prob) {
     if (label_is_i64)
@@ -217,7 +201,7 @@ int gapro_spp_vote(gapro_ctx* ctx, void* stream_, int32_t mode, int64_t n_points
       hipLaunchKernelGGL(k_vote_sums<int>, dim3(g), dim3(kThreads), 0, stream, n, C, d_ids, (const int*)d_label,
                          d_prob, w.hdr, w.P);
   }
-  hipLaunchKernelGGL(k_vote_final, dim3(grid_for(S)), dim3(kThreads), 0, stream, n, S, C, (int)major,
+  hipLaunchKernelGGL(k_vote_final, dim3(grid_for(S, 1, 4096)), dim3(kThreads), 0, stream, n, S, C, (int)major,
                      d_prob ? 1 : 0, major ? nullptr : d_gate, w);
   hipLaunchKernelGGL(k_vote_back, dim3(g), dim3(kThreads), 0, stream, n, d_ids, w, (long long*)d_label_out,
                      d_prob_out);

@@ -11,6 +11,9 @@
 // A batch is ragged (sides of 1 .. 1e5 points): grid.y = (problem, side), grid.x strides over the side's list, and a
 // workgroup whose share of a short list is empty leaves at once.
 #include "common.h"
+#include "exact_sum.h"
+#include "launch_util.h"
+#include "wave_reduce.h"
 
 #include <algorithm>
 
@@ -19,12 +22,9 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kSelThreads = 1024;  // one workgroup per (problem, side) in the selection kernel
 constexpr int kMaxNearest = GAPRO_TRAINSET_MAX_NEAREST;  // survivors are ordered in LDS
-constexpr int kLanesPerPoint = 8;
 static_assert(kSelThreads == kMaxNearest, "k_ts_nearest orders one survivor per thread");
 
 static_assert(sizeof(gapro_trainset_desc) == 40, "gapro_trainset_desc layout is part of the ABI (ctypes mirror)");
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 struct SideRef {
   const int* list;  // the side's point indices
@@ -132,41 +132,28 @@ __global__ __launch_bounds__(kThreads) void k_ts_accum(const gapro_trainset_desc
         atomicAdd(&cnt[row], 64 / kLanesPerPoint);
         sel[row] = spp[p];
       }
-      for (int c0 = 0; c0 < d; c0 += kLanesPerPoint) {
-        const int c = c0 + k;
-        long long q = c < d ? __double2ll_rn(ldexp((double)f[c], shift)) : 0ll;
-        q += __shfl_down(q, 8, 64);
-        q += __shfl_down(q, 16, 64);
-        q += __shfl_down(q, 32, 64);
-        if (head && c < d) atomicAdd(&sums[row * d + c], (unsigned long long)q);
-      }
+      accumulate_features_wave8(sums + row * d, f, d, k, shift, head);
     } else if (row >= 0) {
       if (k == (d & (kLanesPerPoint - 1))) {
         atomicAdd(&cnt[row], 1);
         sel[row] = spp[p];  // every writer of a row holds the same id
       }
-      for (int c = k; c < d; c += kLanesPerPoint)
-        atomicAdd(&sums[row * d + c], (unsigned long long)__double2ll_rn(ldexp((double)f[c], shift)));
+      accumulate_features(sums + row * d, f, d, k, shift);
     }
   }
 }
 
-// mean = ldexp(sum, -shift) / count in float64, rounded once to float32 (k_pool_finalize's expression)
+// mean = fixed_mean (exact_sum.h), rounded once to float32; an empty row's count is clamped at 1 as in k_pool_finalize
 __global__ __launch_bounds__(kThreads) void k_ts_pool_finalize(long long n_rows, int d, int shift,
                                                                const long long* __restrict__ sums,
                                                                const int* __restrict__ cnt, float* __restrict__ train) {
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n_rows * d) return;
   const int c = cnt[i / d];
-  train[i] = (float)(ldexp((double)sums[i], -shift) / (double)(c > 0 ? c : 1));
+  train[i] = (float)fixed_mean(sums[i], shift, (double)(c > 0 ? c : 1));
 }
 
 // ---- nearest: the intersection's centroid as exact fixed-point sums -----------------------------------------------
-__device__ inline long long wave_sum_ll(long long v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // Largest |coordinate| among the FINITE coordinates of the input, as the bit pattern of a non-negative double (orders as
 // an integer): the scale of the centroid's fixed-point sums must not depend on a non-finite coordinate somewhere in the
 // input (the scene header's range does: an infinite coordinate would round every problem's terms to integers).
@@ -178,19 +165,8 @@ __global__ __launch_bounds__(kThreads) void k_ts_coord_absmax(const double* __re
     const double v = fabs(coords[i]);
     if (isfinite(v)) m = fmax(m, v);
   }
-  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+  m = wave_max(m);
   if ((threadIdx.x & 63) == 0 && m > 0.0) atomicMax(amax_bits, (unsigned long long)__double_as_longlong(m));
-}
-
-// exponent k of the exact sums, |rint(x 2^k)| n < 2^61: k_stats_final's rule (partition.hip) for max |x| = amax
-__device__ inline int fixed_shift_of(unsigned long long amax_bits, long long n) {
-  const double amax = __longlong_as_double((long long)amax_bits);
-  if (!(amax > 0.0)) return 0;
-  int e;
-  (void)frexp(amax, &e);
-  const int lg = n > 1 ? 64 - __clzll((unsigned long long)(n - 1)) : 0;
-  const int k = 61 - e - lg;
-  return k < -1000 ? -1000 : (k > 1000 ? 1000 : k);
 }
 
 __global__ __launch_bounds__(kThreads) void k_ts_centroid(const gapro_trainset_desc* __restrict__ descs,
@@ -199,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void k_ts_centroid(const gapro_trainset_d
                                                           const unsigned long long* __restrict__ amax_bits,
                                                           unsigned long long* __restrict__ csum, int* __restrict__ status) {
   const gapro_trainset_desc& ds = descs[blockIdx.y];
-  const int coord_shift = fixed_shift_of(*amax_bits, n_points);
+  const int coord_shift = fixed_point_shift(__longlong_as_double((long long)*amax_bits), n_points);
   const int* __restrict__ list = idx + ds.idx_offset + ds.n1 + ds.n2;
   const int t = ds.t;
   if (blockIdx.x * kThreads >= t) return;
@@ -209,16 +185,16 @@ __global__ __launch_bounds__(kThreads) void k_ts_centroid(const gapro_trainset_d
     const int p = checked_point(list[j], n_points, &status[blockIdx.y]);
     const double x = coords[3LL * p], y = coords[3LL * p + 1], z = coords[3LL * p + 2];
     if (isfinite(x) && isfinite(y) && isfinite(z)) {
-      a[0] += __double2ll_rn(ldexp(x, coord_shift));
-      a[1] += __double2ll_rn(ldexp(y, coord_shift));
-      a[2] += __double2ll_rn(ldexp(z, coord_shift));
+      a[0] += to_fixed(x, coord_shift);
+      a[1] += to_fixed(y, coord_shift);
+      a[2] += to_fixed(z, coord_shift);
     } else {
       status[blockIdx.y] = GAPRO_ERR_NOT_FINITE;
     }
   }
   __shared__ long long sh[kThreads / 64][3];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int c = 0; c < 3; ++c) a[c] = wave_sum_ll(a[c]);
+  for (int c = 0; c < 3; ++c) a[c] = wave_sum(a[c]);
   if (lane == 0) for (int c = 0; c < 3; ++c) sh[w][c] = a[c];
   __syncthreads();
   if (threadIdx.x < 3) {
@@ -274,11 +250,11 @@ __global__ __launch_bounds__(kSelThreads) void k_ts_nearest(const gapro_trainset
     }
   } else {
     double cx = 0.0, cy = 0.0, cz = 0.0;
-    const int coord_shift = fixed_shift_of(*amax_bits, n_points);
+    const int coord_shift = fixed_point_shift(__longlong_as_double((long long)*amax_bits), n_points);
     if (t > 0) {
-      cx = ldexp((double)csum[3LL * s.prob], -coord_shift) / (double)t;
-      cy = ldexp((double)csum[3LL * s.prob + 1], -coord_shift) / (double)t;
-      cz = ldexp((double)csum[3LL * s.prob + 2], -coord_shift) / (double)t;
+      cx = fixed_mean(csum[3LL * s.prob], coord_shift, (double)t);
+      cy = fixed_mean(csum[3LL * s.prob + 1], coord_shift, (double)t);
+      cz = fixed_mean(csum[3LL * s.prob + 2], coord_shift, (double)t);
     } else if (tid == 0) {
       status[s.prob] = GAPRO_ERR_BAD_ARG;  // no centroid
     }
@@ -389,11 +365,6 @@ bool plan(int mode, const gapro_trainset_desc* h, int n_problems, int n_spps, in
   return true;
 }
 
-inline unsigned grid_x(long long n, int per_block, int cap) {
-  long long g = (n + per_block - 1) / per_block;
-  return (unsigned)std::max<long long>(1, std::min<long long>(g, cap));
-}
-
 }  // namespace
 
 extern "C" {
@@ -426,7 +397,7 @@ int gapro_trainset_count(gapro_ctx* ctx, void* stream_, int32_t n_problems, int3
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(marks, 0, (size_t)2 * n_problems * n_spps * sizeof(int), stream));
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_status, 0, (size_t)n_problems * sizeof(int), stream));
   const unsigned ny = 2u * (unsigned)n_problems;
-  hipLaunchKernelGGL(k_ts_mark, dim3(grid_x(p.n_max, 4 * kThreads, 128), ny), dim3(kThreads), 0, stream, d_descs, d_idx,
+  hipLaunchKernelGGL(k_ts_mark, dim3(grid_for(p.n_max, 4, 128), ny), dim3(kThreads), 0, stream, d_descs, d_idx,
                      d_spp_inv, (long long)n_points, (int)n_spps, marks, d_status);
   hipLaunchKernelGGL(k_ts_rank, dim3(ny), dim3(kThreads), 0, stream, (int)n_spps, marks, d_counts);
   GAPRO_LAUNCH_CHECK(ctx);
@@ -474,7 +445,7 @@ int gapro_trainset_fill(gapro_ctx* ctx, void* stream_, int32_t mode, int32_t n_p
     int* cnt = (int*)((char*)d_workspace + p.cnt);
     GAPRO_HIP_CHECK(ctx, hipMemsetAsync(sums, 0, (size_t)n_rows * feat_dim * sizeof(long long), stream));
     GAPRO_HIP_CHECK(ctx, hipMemsetAsync(cnt, 0, (size_t)n_rows * sizeof(int), stream));
-    hipLaunchKernelGGL(k_ts_accum, dim3(grid_x(p.n_max, 4 * kThreads / kLanesPerPoint, 256), ny), dim3(kThreads), 0,
+    hipLaunchKernelGGL(k_ts_accum, dim3(grid_for((long long)p.n_max * kLanesPerPoint, 4, 256), ny), dim3(kThreads), 0,
                        stream, d_descs, d_idx, d_spp_inv, (const long long*)d_spp, d_feats, (long long)n_points,
                        (int)n_spps, (int)feat_dim, (int)fixed_shift, (const int*)((char*)d_workspace + p.marks), sums,
                        cnt, (long long*)d_sel, (long long)n_rows, d_status);
@@ -486,9 +457,9 @@ int gapro_trainset_fill(gapro_ctx* ctx, void* stream_, int32_t mode, int32_t n_p
     unsigned long long* amax = csum + 3 * (size_t)n_problems;
     GAPRO_HIP_CHECK(ctx, hipMemsetAsync(csum, 0, (size_t)(3 * n_problems + 1) * sizeof(long long), stream));
     GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_status, 0, (size_t)n_problems * sizeof(int), stream));
-    hipLaunchKernelGGL(k_ts_coord_absmax, dim3(grid_x(3 * (long long)n_points, 8 * kThreads, 512)), dim3(kThreads), 0,
+    hipLaunchKernelGGL(k_ts_coord_absmax, dim3(grid_for(3 * (long long)n_points, 8, 512)), dim3(kThreads), 0,
                        stream, d_coords, 3 * (long long)n_points, amax);
-    hipLaunchKernelGGL(k_ts_centroid, dim3(grid_x(p.t_max, 4 * kThreads, 64), (unsigned)n_problems), dim3(kThreads), 0,
+    hipLaunchKernelGGL(k_ts_centroid, dim3(grid_for(p.t_max, 4, 64), (unsigned)n_problems), dim3(kThreads), 0,
                        stream, d_descs, d_idx, d_coords, (long long)n_points, (const unsigned long long*)amax, csum,
                        d_status);
     hipLaunchKernelGGL(k_ts_nearest, dim3(ny), dim3(kSelThreads), 0, stream, d_descs, d_idx, d_coords, d_feats,

@@ -62,6 +62,14 @@ int gapro_debug_wgloop(gapro_ctx* ctx, void* stream, int32_t iters, int32_t mode
 int gapro_debug_product_bench(gapro_ctx* ctx, void* stream, int32_t engine, int32_t shape, int32_t mp, int32_t reps,
                               int32_t n_wg, double* d_slab, float* out_ms);
 
+/* The exact-sum helpers of csrc/exact_sum.h, elementwise over three groups of arrays: shift_out[i] =
+ * fixed_point_shift(absmax[i], n[i]) for i < n_shift, fixed_out[i] = to_fixed(x[i], xk[i]) for i < n_fixed, mean_out[i] =
+ * fixed_mean(sum[i], mk[i], count[i]) for i < n_mean.  ctx and stream NULL: the host's build of the helpers on host
+ * arrays; with a ctx: the device's, in one workgroup on `stream`, on device arrays (tests/test_exact_sum_*.py). */
+int gapro_debug_exact_sum(gapro_ctx* ctx, void* stream, int32_t n_shift, const double* absmax, const int64_t* n,
+                          int32_t* shift_out, int32_t n_fixed, const double* x, const int32_t* xk, int64_t* fixed_out,
+                          int32_t n_mean, const int64_t* sum, const int32_t* mk, const double* count, double* mean_out);
+
 #ifdef __cplusplus
 }
 #endif

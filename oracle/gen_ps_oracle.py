@@ -88,8 +88,8 @@ def is_box1_in_box2(box1, box2, offset=CONTAIN_OFFSET):
 def fixed_point_shift(fmax: float, n_points: int) -> int:
     """Exponent k of the exact pooled-feature sum: q = rint(x * 2**k) summed in int64.
 
-    Chosen so that |q| * n_points < 2**61.  Shared spec with the HIP kernel
-    (gapro_amd/csrc/partition.hip, ``stats_finalize``).
+    Chosen so that |q| * n_points stays within 2**61.  Shared spec with the HIP library's one statement of the rule
+    (gapro_amd/csrc/exact_sum.h, ``fixed_point_shift``).
     """
     if not (fmax > 0.0) or not math.isfinite(fmax):
         return 0
