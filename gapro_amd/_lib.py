@@ -104,6 +104,7 @@ class TrainsetDesc(C.Structure):
 TRAINSET_POOL, TRAINSET_NEAREST = 0, 1
 TRAINSET_MAX_NEAREST = 1024
 TRAINSET_MAX_LIST_FACTOR = 2  # a list holds at most so many times N entries (the exact sums' headroom)
+TRAINSET_MAX_PROBLEMS = 32767  # problems of one call (GAPRO_TRAINSET_MAX_PROBLEMS: two grid rows per problem)
 
 
 class SceneTask(C.Structure):

@@ -345,7 +345,7 @@ struct Plan {
 // pool: marks i32[2 P S] | sums i64[R D] | counts i32[R], R = sum over the sides of min(n, S) >= the rows of any
 // outcome of the count; nearest: centroid sums i64[3 P] | max |finite coordinate| u64
 bool plan(int mode, const gapro_trainset_desc* h, int n_problems, int n_spps, int d, Plan* out) {
-  if (!h || n_problems <= 0 || n_problems > 32767 || d <= 0 || (mode == GAPRO_TRAINSET_POOL && n_spps <= 0)) return false;
+  if (!h || n_problems <= 0 || n_problems > GAPRO_TRAINSET_MAX_PROBLEMS || d <= 0 || (mode == GAPRO_TRAINSET_POOL && n_spps <= 0)) return false;
   Plan p;
   for (int i = 0; i < n_problems; ++i) {
     if (h[i].n1 <= 0 || h[i].n2 <= 0 || h[i].t < 0 || h[i].idx_offset < 0) return false;

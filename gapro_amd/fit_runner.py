@@ -194,6 +194,8 @@ def pack_point_problems(problems, n_points: int, npoint_nearest: int, spp_pool: 
     n = len(problems)
     if n == 0:
         raise ValueError("no problem given")
+    if n > _lib.TRAINSET_MAX_PROBLEMS:
+        raise ValueError("%d problems in one call: at most %d (split the batch)" % (n, _lib.TRAINSET_MAX_PROBLEMS))
     descs = (TrainsetDesc * n)()
     idx, io = [], 0
     for i, prob in enumerate(problems):

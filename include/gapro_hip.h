@@ -816,6 +816,7 @@ enum {
 };
 #define GAPRO_TRAINSET_MAX_NEAREST 1024
 #define GAPRO_TRAINSET_MAX_LIST_FACTOR 2
+#define GAPRO_TRAINSET_MAX_PROBLEMS 32767 /* of one call: grid.y = (problem, side) stays below 65 536 */
 
 /* One problem: its lists lie back to back, [b1 (n1) | b2 (n2) | intersect (t)], at idx_offset of one int32 index array. */
 typedef struct {

@@ -113,6 +113,7 @@ def _inputs(n=40):
 @pytest.mark.parametrize("fn", ["gp_train_sets", "fit_gp_batch"])
 def test_bad_arguments_raise_before_a_device_is_touched(fn, monkeypatch):
     import gapro_amd
+    from gapro_amd import _lib
     from gapro_amd import gaussian_process_utils as G
 
     def no_device(*a, **k):
@@ -137,6 +138,10 @@ def test_bad_arguments_raise_before_a_device_is_touched(fn, monkeypatch):
         # the exact sums have room for 4 N terms: a list (indices may repeat) holds at most 2 N entries
         with pytest.raises(ValueError, match="longer than 2 times"):
             call(coords, feats, spp, [(np.tile(np.arange(5), 17), np.arange(5, 12), np.arange(3))], spp_pool=mode)
+        # two grid rows per problem: a call holds at most TRAINSET_MAX_PROBLEMS of them, and says so
+        assert _lib.TRAINSET_MAX_PROBLEMS == 32767
+        with pytest.raises(ValueError, match="at most 32767"):
+            call(coords, feats, spp, [ok] * (_lib.TRAINSET_MAX_PROBLEMS + 1), npoint_nearest=6, spp_pool=mode)
     # what is NOT an error: npoint_nearest is ignored when pooling; an empty intersection with short sides; a list of
     # exactly 2 N entries
     with pytest.raises(AssertionError, match="a device was asked for"):

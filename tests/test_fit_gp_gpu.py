@@ -5,21 +5,11 @@ import numpy as np
 import pytest
 
 import fit_gp_ref as R
+from trainset_cases import same_sets as _same_sets  # shared with tests/test_trainset_edges_gpu.py
 
 pytestmark = pytest.mark.gpu
 
 VAR_RTOL, MU_RTOL, MU_ATOL, P_ATOL = 1e-5, 1e-5, 1e-7, 2e-7  # tests/test_fit_gpu.py::_compare
-
-
-def _same_sets(got, coords, feats, spp, problems, k=800, pool=True, what=""):
-    assert len(got) == len(problems)
-    for i, (g, prob) in enumerate(zip(got, problems)):
-        x, m1, m2, s1, s2, _ = R.train_set(coords, feats, spp, prob, k, pool)
-        tag = "%s problem %d" % (what, i)
-        assert (g[1], g[2]) == (m1, m2), tag
-        assert g[0].dtype == np.float32 and g[3].dtype == np.int64 and g[4].dtype == np.int64, tag
-        assert np.array_equal(g[3], s1) and np.array_equal(g[4], s2), tag
-        assert np.array_equal(g[0], x), tag
 
 
 # ---------------------------------------------------------------------------------------------- 1. pool, goldens
