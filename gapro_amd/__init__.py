@@ -14,10 +14,11 @@ __version__ = "0.1.0"
 _EXPORTS = {
     "gen_ps_utils": ("batch_giou_cross", "gen_pseudo_label", "gen_pseudo_label_box2mask",
                      "gen_pseudo_label_gaussian_process", "gen_pseudo_label_gaussian_process_batch", "getInstanceInfo",
-                     "getInstanceInfo_device", "is_box1_in_box2"),
+                     "getInstanceInfo_device", "is_box1_in_box2", "get_cropped_instance_label"),
     "gaussian_process_utils": ("fit_gp_spp", "fit_gp_spp_batch", "predict_gp_batch", "GPModel", "fit_gp", "fit_gp_batch",
                                "gp_train_sets"),
     "scannet_planes": ("get_wall_boxes",),
+    "consumer_ops": ("get_instance_info", "prepare_instance_labels"),
 }
 __all__ = [n for names in _EXPORTS.values() for n in names]
 

@@ -14,10 +14,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgapro_hip.so")
 
 GAPRO_OK = 0
+GAPRO_ERR_BAD_ARG = -1
 GAPRO_ERR_NOT_FINITE = -4
 GAPRO_ERR_CHOLESKY = -5
 STATUS_NAMES = {0: "OK", -1: "BAD_ARG", -2: "OOM", -3: "HIP", -4: "NOT_FINITE", -5: "CHOLESKY", -6: "SPP_RANGE",
                 -7: "WORKSPACE", -8: "TIMEOUT", -9: "IO", -10: "UNSUPPORTED"}
+GAPRO_ERR_WORKSPACE = -7
 GAPRO_ERR_TIMEOUT = -8
 GAPRO_ERR_IO = -9
 GAPRO_ERR_UNSUPPORTED = -10
@@ -142,6 +144,17 @@ class EvalApScene(C.Structure):
 
 
 GAPRO_LABEL_F64, GAPRO_LABEL_I32, GAPRO_LABEL_I64 = 1, 2, 3
+
+
+class InstPrepHeader(C.Structure):
+    """gapro_inst_prep_header: what gapro_inst_crop / gapro_inst_info / gapro_inst_prepare report."""
+    _fields_ = [("instance_num", C.c_int32), ("n_ids", C.c_int32), ("max_id", C.c_int32), ("status", C.c_int32),
+                ("fixed_shift", C.c_int32), ("flags", C.c_int32)]
+
+
+INST_PREP_MAX_IDS = 1 << 20   # GAPRO_INST_PREP_MAX_IDS: an id at or beyond it is refused
+INST_PREP_GRID_CAP = 512      # GAPRO_INST_PREP_GRID_CAP: workgroups (of 256 threads) of a pass over the points
+INST_PREP_LDS_IDS = 512       # GAPRO_INST_PREP_LDS_IDS: ids tallied in LDS
 GAPRO_EVAL_MAX_THRESHOLDS = 32
 
 
@@ -208,6 +221,12 @@ SIGNATURES = {
     "gapro_weighted_bce_with_logits": (C.c_int, [_P, _P, C.c_int32, C.c_int64, _P, _P, _P, C.c_float, _P, _P, _P]),
     "gapro_kl_gp_loss": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, _P, _P, _P,
                                    _P]),
+    "gapro_inst_prep_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "gapro_inst_crop": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32, _P, C.c_size_t, _P, _P]),
+    "gapro_inst_info": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, _P,
+                                  C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "gapro_inst_prepare": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, _P,
+                                     C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "gapro_schedule_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "gapro_schedule_free": (None, [_P]),
     "gapro_schedule_get_counts": (C.c_int, [_P, C.POINTER(ScheduleCounts)]),
@@ -389,7 +408,7 @@ def load() -> C.CDLL:
             if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state",
                                             "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex",
                                             "gapro_schedule_export_testers", "gapro_spp_vote",
-                                            "gapro_fit_launch_plan")):
+                                            "gapro_fit_launch_plan", "gapro_inst_")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

@@ -6,10 +6,12 @@ uses the gradients the forward launch already produced.  There is no CPU path.
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
-from ._lib import Context
+from . import _lib
+from ._lib import Context, GaproError
 
 
 def _ctx_stream(t):
@@ -115,3 +117,132 @@ class _KLToGP(torch.autograd.Function):
 def kl_to_gp_loss(mu_pred, logvar_pred, mu_labels, var_labels, weight=1.0, epsilon=1e-4):
     """The KL-to-GP auxiliary loss of ISBNet/isbnet/model/criterion.py:435-463 (``weight`` = loss_weight["kl_loss"])."""
     return _KLToGP.apply(mu_pred, logvar_pred, mu_labels, var_labels, weight, epsilon)
+
+
+# ---- instance-label preparation (gapro_amd/csrc/inst_prep.hip; DESIGN.md 4.7) ----------------------------------------
+ID_TABLE = 1024  # ids the first launch of a call has room for; a larger id regrows the table from the data
+InstanceLabels = namedtuple("InstanceLabels", ["instance_labels", "instance_cls", "instance_box", "instance_pointnum",
+                                               "centroid_offset_labels", "corners_offset_labels"])
+_LABEL_CODES = {torch.float64: _lib.GAPRO_LABEL_F64, torch.int32: _lib.GAPRO_LABEL_I32,
+                torch.int64: _lib.GAPRO_LABEL_I64}
+
+
+def _label_code(t, what):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: a tensor is expected, not %s" % (what, type(t).__name__))
+    if t.dtype not in _LABEL_CODES:
+        raise ValueError("%s: dtype %s; int32, int64 or float64 is expected" % (what, t.dtype))
+    if t.dim() != 1:
+        raise ValueError("%s: shape %s; one label per point is expected" % (what, tuple(t.shape)))
+    return _LABEL_CODES[t.dtype]
+
+
+def _check_info_args(coords_float, instance_labels, semantic_labels, who):
+    """What is refused before a device is touched."""
+    if not isinstance(coords_float, torch.Tensor) or coords_float.dim() != 2 or coords_float.shape[1] != 3 \
+            or coords_float.dtype != torch.float32:
+        raise ValueError("%s: coords_float must be a float32 tensor of shape [V, 3]" % who)
+    _label_code(instance_labels, who + ": instance_labels")
+    _label_code(semantic_labels, who + ": semantic_labels")
+    v = int(coords_float.shape[0])
+    if int(instance_labels.shape[0]) != v or int(semantic_labels.shape[0]) != v:
+        raise ValueError("%s: %d points, %d instance labels, %d semantic labels"
+                         % (who, v, int(instance_labels.shape[0]), int(semantic_labels.shape[0])))
+    if v == 0:
+        raise ValueError("%s: no points" % who)
+    if not (coords_float.is_cuda and instance_labels.is_cuda and semantic_labels.is_cuda):
+        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+
+
+def _refusal(who, hdr):
+    if hdr.max_id >= _lib.INST_PREP_MAX_IDS:
+        why = "an instance id at or beyond %d" % _lib.INST_PREP_MAX_IDS
+    elif hdr.status == _lib.GAPRO_ERR_NOT_FINITE:
+        why = "a non-finite coordinate on a point that carries an instance id"
+    elif hdr.flags & 2:
+        why = "a float64 label that is no integer"
+    elif hdr.n_ids == 0:
+        why = "no instance id >= 0"
+    else:
+        why = "%d distinct ids below the largest id %d: an id in between is empty" % (hdr.n_ids, hdr.max_id)
+    return GaproError(hdr.status, "%s: %s" % (who, why))
+
+
+def _inst_prep(who, labels, coords=None, sem=None, label_shift=0, crop=True):
+    """One chain of gapro_inst_crop / gapro_inst_info / gapro_inst_prepare on the caller's stream and the one read of
+    its header; an id beyond the id table regrows the table from the header's largest id and runs again (a refused
+    call has written nothing).  ``labels`` is contiguous and is overwritten when ``crop``."""
+    ctx, stream = _ctx_stream(labels)
+    lib, dev = ctx.lib, labels.device
+    n = int(labels.shape[0])
+    info = coords is not None
+    cap = ID_TABLE
+    with torch.cuda.device(dev):
+        while True:
+            ws_bytes = int(lib.gapro_inst_prep_workspace_bytes(cap))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            d_hdr = torch.empty(C.sizeof(_lib.InstPrepHeader), dtype=torch.uint8, device=dev)
+            h_hdr = torch.empty(C.sizeof(_lib.InstPrepHeader), dtype=torch.uint8, pin_memory=True)
+            outs = None
+            if info:
+                outs = (torch.empty(cap, dtype=torch.int64, device=dev),
+                        torch.empty((cap, 6), dtype=torch.float32, device=dev),
+                        torch.empty(cap, dtype=torch.int32, device=dev),
+                        torch.empty((n, 3), dtype=torch.float32, device=dev),
+                        torch.empty((n, 6), dtype=torch.float32, device=dev))
+                fn = lib.gapro_inst_prepare if crop else lib.gapro_inst_info
+                ctx.check(fn(ctx.handle, stream, n, coords.data_ptr(), labels.data_ptr(), _LABEL_CODES[labels.dtype],
+                             sem.data_ptr(), _LABEL_CODES[sem.dtype], int(label_shift), cap, ws.data_ptr(), ws_bytes,
+                             *(o.data_ptr() for o in outs), d_hdr.data_ptr(), h_hdr.data_ptr()))
+            else:
+                ctx.check(lib.gapro_inst_crop(ctx.handle, stream, n, labels.data_ptr(), _LABEL_CODES[labels.dtype], cap,
+                                              ws.data_ptr(), ws_bytes, d_hdr.data_ptr(), h_hdr.data_ptr()))
+            torch.cuda.current_stream(dev).synchronize()  # the call's one host read
+            hdr = _lib.InstPrepHeader.from_buffer_copy(h_hdr.numpy().tobytes())
+            if hdr.status == _lib.GAPRO_ERR_WORKSPACE and cap <= hdr.max_id < _lib.INST_PREP_MAX_IDS:
+                cap = hdr.max_id + 1
+                continue
+            if hdr.status != 0:
+                raise _refusal(who, hdr)
+            return hdr, outs
+
+
+def get_cropped_instance_label(instance_label, valid_idxs=None):
+    """``get_cropped_instance_label`` (ISBNet/isbnet/model/model_utils.py:589-597) without its loop over the ids: the
+    holes of [0, K), K = the number of distinct ids >= 0, take the ids >= K, the largest first.  As in the reference the
+    given tensor is overwritten and returned; with ``valid_idxs`` the indexed copy is.  int32, int64 or float64 labels."""
+    _label_code(instance_label, "get_cropped_instance_label: instance_label")
+    if valid_idxs is not None:
+        instance_label = instance_label[valid_idxs]
+    if instance_label.numel() == 0:
+        raise ValueError("get_cropped_instance_label: no labels")
+    work = instance_label if instance_label.is_contiguous() else instance_label.contiguous()
+    _inst_prep("get_cropped_instance_label", work)
+    if work is not instance_label:
+        instance_label.copy_(work)
+    return instance_label
+
+
+def get_instance_info(coords_float, instance_labels, semantic_labels, label_shift=0):
+    """``get_instance_info`` (ISBNet/isbnet/model/model_utils.py:519-555) in one pass over the points: ``(instance_cls
+    i64[I], instance_box f32[I,6], centroid_offset_labels f32[V,3], corners_offset_labels f32[V,6])``, I = max id + 1.
+    The centroid is the exact mean rounded once, everything else the reference's bits.  Labels with an
+    empty id below the largest, or without an id >= 0, are refused, where the reference fails."""
+    _check_info_args(coords_float, instance_labels, semantic_labels, "get_instance_info")
+    hdr, (cls, box, _, cen, cor) = _inst_prep("get_instance_info", instance_labels.contiguous(),
+                                              coords_float.contiguous(), semantic_labels.contiguous(), label_shift,
+                                              crop=False)
+    num = int(hdr.instance_num)
+    return cls[:num], box[:num], cen, cor
+
+
+def prepare_instance_labels(coords_float, instance_labels, semantic_labels, label_shift=0):
+    """``get_cropped_instance_label`` followed by ``get_instance_info`` (isbnet.py:254-270) as one chain of kernels with
+    one host read: an ``InstanceLabels`` tuple of the compacted labels (a new tensor), the class, box and point count
+    per instance and the two offset tables."""
+    _check_info_args(coords_float, instance_labels, semantic_labels, "prepare_instance_labels")
+    labels = instance_labels.clone(memory_format=torch.contiguous_format)
+    hdr, (cls, box, num_pts, cen, cor) = _inst_prep("prepare_instance_labels", labels, coords_float.contiguous(),
+                                                    semantic_labels.contiguous(), label_shift)
+    num = int(hdr.instance_num)
+    return InstanceLabels(labels, cls[:num], box[:num], num_pts[:num], cen, cor)

@@ -222,6 +222,31 @@ def spp_major_voting(spp, label, prob_label, bb_occupancy, n_classes):
     return _spp_vote(1, spp, label, n_classes, bb_occupancy, prob_label)
 
 
+def get_cropped_instance_label(instance_label, valid_idxs=None):
+    """Reference gen_ps_utils.py:64-72 on the GPU behind ``gapro_inst_crop`` (consumer_ops.get_cropped_instance_label
+    is the same function): the instance ids are compacted to [0, K) by moving the largest ids into the holes.  A device
+    tensor is handled in place; a NumPy array or a CPU tensor is moved to the device and back, and without
+    ``valid_idxs`` the given array is overwritten and returned, as in the reference."""
+    from . import consumer_ops
+
+    if isinstance(instance_label, torch.Tensor) and instance_label.is_cuda:
+        return consumer_ops.get_cropped_instance_label(instance_label, valid_idxs)
+    if not torch.cuda.is_available():
+        raise RuntimeError("get_cropped_instance_label runs on a HIP device; there is no CPU fallback")
+    is_np = not isinstance(instance_label, torch.Tensor)
+    host = np.asarray(instance_label) if is_np else instance_label
+    if valid_idxs is not None:
+        host = host[valid_idxs.cpu() if isinstance(valid_idxs, torch.Tensor) and not is_np else valid_idxs]
+    moved = (torch.from_numpy(np.ascontiguousarray(host)) if is_np else host).to(torch.device("cuda",
+                                                                                  torch.cuda.current_device()))
+    out = consumer_ops.get_cropped_instance_label(moved).cpu()
+    if is_np:
+        host[...] = out.numpy()
+    else:
+        host.copy_(out)
+    return host
+
+
 def getInstanceInfo(xyz, instance_label, semantic_label, dataset_name="scannetv2"):
     """Reference gen_ps_utils.py:195-239 (host NumPy, as in the reference).
 

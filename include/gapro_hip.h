@@ -793,6 +793,68 @@ int gapro_spp_vote(gapro_ctx* ctx, void* stream, int32_t mode, int64_t n_points,
                    int32_t* d_status);
 
 /* ------------------------------------------------------------------------------------------
+ * Instance-label preparation of the consumer's training step (csrc/inst_prep.hip).  Replaces ISBNet's
+ * get_cropped_instance_label (isbnet/model/model_utils.py:589-597; gapro/gen_ps_utils.py:64-72 is the same function)
+ * and get_instance_info (model_utils.py:519-555), which loop over the instance ids on the host.
+ *   d_instance_label, d_semantic_label: GAPRO_LABEL_F64 / _I32 / _I64 arrays of n_points entries; a label < 0 (or NaN)
+ *   names no instance.  d_coords f32[N,3].
+ * Crop: P = the distinct ids >= 0, K = |P|.  Ids of P below K stay; the holes h_0 < h_1 < .. of [0, K) take the ids of P
+ * that are >= K in descending order (the largest goes to h_0).  Negative labels are untouched; without an id >= 0 nothing
+ * changes.  This closed form equals the reference's loop.
+ * Info, per instance id r in [0, I), I = max id + 1:
+ *   d_instance_cls i64[r]      semantic label of the instance's first point (lowest index), minus label_shift unless -100
+ *   d_instance_box f32[r,6]    [min xyz | max xyz] (-0.0 orders below +0.0)
+ *   d_instance_pointnum i32[r] its points
+ *   d_centroid_offset f32[N,3] centroid - p with one float32 subtraction; centroid = the exact mean: int64 sums of
+ *                              rint(x 2^k), k = fixed_point_shift(largest |coordinate| of the labelled points, N), then
+ *                              ldexp(sum, -k) / count in float64, rounded once to float32 (the reference's float32 mean
+ *                              has no stated order: DESIGN.md 4.7)
+ *   d_corners_offset f32[N,6]  (min - p | max - p), one float32 subtraction per component
+ *   rows of points without an instance are -100.  The per-instance outputs hold max_ids rows.
+ * gapro_inst_prepare = the crop (in place) followed by the info on the cropped labels, in one chain: I = K.
+ * The header (device + page-locked host copy when h_header_pinned is given) carries the result of the call:
+ *   GAPRO_ERR_BAD_ARG     an id >= GAPRO_INST_PREP_MAX_IDS or a float64 label that is no integer; info / prepare:
+ *                         no id >= 0 (the reference fails on torch.stack([])); info: an empty id below the largest (the
+ *                         reference fails on min of an empty tensor)
+ *   GAPRO_ERR_WORKSPACE   an id >= max_ids: run again with max_ids > header.max_id
+ *   GAPRO_ERR_NOT_FINITE  info / prepare: a non-finite coordinate on a point with an id >= 0 (one without is ignored)
+ * BAD_ARG wins over WORKSPACE, which wins over NOT_FINITE.  With a non-zero status neither the labels nor the outputs
+ * are written.  Refused before anything is launched (GAPRO_ERR_BAD_ARG): a null or non-positive argument, an unknown
+ * label type, max_ids outside [1, GAPRO_INST_PREP_MAX_IDS]; GAPRO_ERR_WORKSPACE: a workspace smaller than
+ * gapro_inst_prep_workspace_bytes (0 for a max_ids the calls refuse).  Enqueue only; the results are the same bits for
+ * every run.  The passes over the points run at most GAPRO_INST_PREP_GRID_CAP workgroups of 256 threads; new ids below
+ * GAPRO_INST_PREP_LDS_IDS are tallied in LDS.
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_INST_PREP_MAX_IDS 1048576 /* 2^20 */
+#define GAPRO_INST_PREP_GRID_CAP 512
+#define GAPRO_INST_PREP_LDS_IDS 512
+typedef struct {
+  int32_t instance_num; /* I: crop / prepare: K; info: max id + 1 */
+  int32_t n_ids;        /* K distinct ids >= 0 */
+  int32_t max_id;       /* largest id met, clamped to GAPRO_INST_PREP_MAX_IDS; -1 without one */
+  int32_t status;
+  int32_t fixed_shift;  /* k of the centroid sums */
+  int32_t flags;        /* 1: non-finite coordinate, 2: id beyond the bound or not an integer, 4: id >= max_ids */
+} gapro_inst_prep_header; /* 24 bytes */
+
+size_t gapro_inst_prep_workspace_bytes(int32_t max_ids);
+int gapro_inst_crop(gapro_ctx* ctx, void* stream, int64_t n_points, void* d_instance_label, int32_t label_type,
+                    int32_t max_ids, void* d_workspace, size_t workspace_bytes, gapro_inst_prep_header* d_header,
+                    gapro_inst_prep_header* h_header_pinned);
+int gapro_inst_info(gapro_ctx* ctx, void* stream, int64_t n_points, const float* d_coords,
+                    const void* d_instance_label, int32_t label_type, const void* d_semantic_label, int32_t semantic_type,
+                    int64_t label_shift, int32_t max_ids, void* d_workspace, size_t workspace_bytes,
+                    int64_t* d_instance_cls, float* d_instance_box, int32_t* d_instance_pointnum,
+                    float* d_centroid_offset, float* d_corners_offset, gapro_inst_prep_header* d_header,
+                    gapro_inst_prep_header* h_header_pinned);
+int gapro_inst_prepare(gapro_ctx* ctx, void* stream, int64_t n_points, const float* d_coords, void* d_instance_label,
+                       int32_t label_type, const void* d_semantic_label, int32_t semantic_type, int64_t label_shift,
+                       int32_t max_ids, void* d_workspace, size_t workspace_bytes, int64_t* d_instance_cls,
+                       float* d_instance_box, int32_t* d_instance_pointnum, float* d_centroid_offset,
+                       float* d_corners_offset, gapro_inst_prep_header* d_header,
+                       gapro_inst_prep_header* h_header_pinned);
+
+/* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
  * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
  * to superpoint means (:64-69) or by keeping the npoint_nearest points of each side nearest to the centroid of the
