@@ -155,6 +155,19 @@ class InstPrepHeader(C.Structure):
 INST_PREP_MAX_IDS = 1 << 20   # GAPRO_INST_PREP_MAX_IDS: an id at or beyond it is refused
 INST_PREP_GRID_CAP = 512      # GAPRO_INST_PREP_GRID_CAP: workgroups (of 256 threads) of a pass over the points
 INST_PREP_LDS_IDS = 512       # GAPRO_INST_PREP_LDS_IDS: ids tallied in LDS
+
+
+class SppGtHeader(C.Structure):
+    """gapro_spp_gt_header: what gapro_spp_gt_count reports; batch_size pairs (n_inst_gt, n_spp) of int32 follow it."""
+    _fields_ = [("status", C.c_int32), ("bad_sample", C.c_int32), ("flags", C.c_int32), ("batch_size", C.c_int32),
+                ("total_rows", C.c_int64), ("total_cols", C.c_int64), ("total_cells", C.c_int64)]
+
+
+SPP_GT_MAX_SAMPLES = 1024             # GAPRO_SPP_GT_MAX_SAMPLES: samples of one call
+SPP_GT_MAX_BATCH_SPPS = (1 << 31) - 1  # GAPRO_SPP_GT_MAX_BATCH_SPPS: batch_size * n_spps of one call
+SPP_GT_GRID_CAP = 512                 # GAPRO_SPP_GT_GRID_CAP: workgroups (of 256 threads) of a pass over the points
+SPP_GT_HALF, SPP_GT_STRICT = 0, 1     # the rule of gapro_spp_gt_fill: 2 c >= n, 2 c > n
+GAPRO_ERR_SPP_RANGE = -6
 GAPRO_EVAL_MAX_THRESHOLDS = 32
 
 
@@ -227,6 +240,12 @@ SIGNATURES = {
                                   C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     "gapro_inst_prepare": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32, _P,
                                      C.c_size_t, _P, _P, _P, _P, _P, _P, _P]),
+    "gapro_spp_gt_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "gapro_spp_gt_count": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P,
+                                     C.c_int32, C.c_int32, _P, C.c_int32, C.c_int64, _P, C.c_size_t, _P, _P]),
+    "gapro_spp_gt_fill": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P,
+                                    C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, C.c_int32, _P, C.c_size_t, _P,
+                                    C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "gapro_schedule_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "gapro_schedule_free": (None, [_P]),
     "gapro_schedule_get_counts": (C.c_int, [_P, C.POINTER(ScheduleCounts)]),
@@ -408,7 +427,7 @@ def load() -> C.CDLL:
             if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state",
                                             "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex",
                                             "gapro_schedule_export_testers", "gapro_spp_vote",
-                                            "gapro_fit_launch_plan", "gapro_inst_")):
+                                            "gapro_fit_launch_plan", "gapro_inst_", "gapro_spp_gt_")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

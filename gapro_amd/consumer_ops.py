@@ -246,3 +246,172 @@ def prepare_instance_labels(coords_float, instance_labels, semantic_labels, labe
                                                     semantic_labels.contiguous(), label_shift)
     num = int(hdr.instance_num)
     return InstanceLabels(labels, cls[:num], box[:num], num_pts[:num], cen, cor)
+
+
+# ---- ground-truth instance masks per sample (gapro_amd/csrc/spp_gt.hip) ----------------------------------
+_SPP_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
+_GT_CAUSES = ((1, "batch offsets that decrease or leave [0, n_points]"),
+              (2, "a subsample index outside the labels"),
+              (4, "an instance label that is not ignore_label and is negative, at or beyond len(instance_cls), or no "
+                  "integer"),
+              (8, "a superpoint id outside [0, n_spps)"))
+
+
+def _offsets_arg(batch_offsets, batch_size, who):
+    """The offsets as the host sees them before a device is touched: a tensor (device or host) or a sequence."""
+    if isinstance(batch_offsets, torch.Tensor):
+        if batch_offsets.dim() != 1 or batch_offsets.dtype not in (torch.int32, torch.int64):
+            raise ValueError("%s: batch_offsets must be a 1-D int32 or int64 tensor" % who)
+        off = batch_offsets
+    else:
+        try:
+            off = torch.as_tensor([int(v) for v in batch_offsets], dtype=torch.int64)
+        except (TypeError, ValueError):
+            raise ValueError("%s: batch_offsets must be an integer tensor or a sequence of integers" % who) from None
+    if int(off.shape[0]) != batch_size + 1:
+        raise ValueError("%s: %d batch offsets for batch_size %d; batch_size + 1 are expected"
+                         % (who, int(off.shape[0]), batch_size))
+    return off
+
+
+def _check_gt_args(who, instance_labels, instance_cls, instance_box, batch_size):
+    """What both functions refuse before a device is touched; returns the label and class codes."""
+    code = _label_code(instance_labels, who + ": instance_labels")
+    cls_code = _label_code(instance_cls, who + ": instance_cls")
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int):
+        raise ValueError("%s: batch_size must be an int" % who)
+    if not 1 <= batch_size <= _lib.SPP_GT_MAX_SAMPLES:
+        raise ValueError("%s: batch_size %d outside [1, %d]" % (who, batch_size, _lib.SPP_GT_MAX_SAMPLES))
+    n_cls = int(instance_cls.shape[0])
+    if not isinstance(instance_box, torch.Tensor) or instance_box.dtype != torch.float32 \
+            or instance_box.dim() != 2 or tuple(instance_box.shape) != (n_cls, 6):
+        raise ValueError("%s: instance_box must be a float32 tensor of shape [%d, 6], one row per instance_cls entry"
+                         % (who, n_cls))
+    if int(instance_labels.shape[0]) == 0:
+        raise ValueError("%s: no points" % who)
+    if n_cls == 0 or n_cls > _lib.INST_PREP_MAX_IDS:
+        raise ValueError("%s: %d instance_cls entries outside [1, %d]" % (who, n_cls, _lib.INST_PREP_MAX_IDS))
+    return code, cls_code
+
+
+def _gt_run(who, labels, gather, spps, n_spps, cls, box, offsets, batch_size, ignore_label, rule, return_ids):
+    """gapro_spp_gt_count, the call's one host read of its header, gapro_spp_gt_fill; the per-sample views."""
+    if not (labels.is_cuda and cls.is_cuda and box.is_cuda and (gather is None or gather.is_cuda)
+            and (spps is None or spps.is_cuda)):
+        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    ctx, stream = _ctx_stream(labels)
+    lib, dev = ctx.lib, labels.device
+    labels, cls, box = labels.contiguous(), cls.contiguous(), box.contiguous()
+    off = offsets.to(device=dev, dtype=torch.int64).contiguous()
+    if gather is not None:
+        gather = gather.to(dtype=torch.int64).contiguous()
+    spp_i64 = 0
+    if spps is not None:
+        if spps.dtype not in (torch.int32, torch.int64):
+            spps = spps.to(torch.int32)
+        spps = spps.contiguous()
+        spp_i64 = int(spps.dtype == torch.int64)
+    n = int(gather.shape[0]) if gather is not None else int(labels.shape[0])
+    n_cls = int(cls.shape[0])
+    hdr_bytes = C.sizeof(_lib.SppGtHeader) + 8 * batch_size
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.gapro_spp_gt_workspace_bytes(n, batch_size, n_cls, n_spps))
+        if ws_bytes == 0:
+            raise ValueError("%s: %d points, batch_size %d and %d superpoint ids are beyond the library's bounds"
+                             % (who, n, batch_size, n_spps))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        d_hdr = torch.empty(hdr_bytes, dtype=torch.uint8, device=dev)
+        h_hdr = torch.empty(hdr_bytes, dtype=torch.uint8, pin_memory=True)
+        common = (n, int(labels.shape[0]), labels.data_ptr(), _LABEL_CODES[labels.dtype],
+                  gather.data_ptr() if gather is not None else None, spps.data_ptr() if spps is not None else None,
+                  spp_i64, n_spps, cls.data_ptr(), _LABEL_CODES[cls.dtype], n_cls)
+        ctx.check(lib.gapro_spp_gt_count(ctx.handle, stream, *common, off.data_ptr(), batch_size, int(ignore_label),
+                                         ws.data_ptr(), ws_bytes, d_hdr.data_ptr(), h_hdr.data_ptr()))
+        torch.cuda.current_stream(dev).synchronize()  # the call's one host read
+        raw = h_hdr.numpy().tobytes()
+        hdr = _lib.SppGtHeader.from_buffer_copy(raw)
+        if hdr.status != 0:
+            why = next(text for bit, text in _GT_CAUSES if hdr.flags & bit)
+            raise GaproError(hdr.status, "%s: sample %d: %s" % (who, hdr.bad_sample, why))
+        counts = (C.c_int32 * (2 * batch_size)).from_buffer_copy(raw, C.sizeof(_lib.SppGtHeader))
+        if hdr.total_rows == 0:
+            return [None] * batch_size
+        cells, rows = max(int(hdr.total_cells), 1), int(hdr.total_rows)
+        mask = torch.empty(cells, dtype=torch.float32, device=dev)
+        out_cls = torch.empty(rows, dtype=cls.dtype, device=dev)
+        out_box = torch.empty((rows, 6), dtype=torch.float32, device=dev)
+        out_ids = torch.empty(rows, dtype=torch.int64, device=dev) if return_ids else None
+        ctx.check(lib.gapro_spp_gt_fill(ctx.handle, stream, *common, box.data_ptr(), off.data_ptr(), batch_size,
+                                        int(ignore_label), rule, ws.data_ptr(), ws_bytes, mask.data_ptr(), cells,
+                                        out_cls.data_ptr(), out_box.data_ptr(),
+                                        out_ids.data_ptr() if return_ids else None, rows, None))
+    out, r0, c0 = [], 0, 0
+    for b in range(batch_size):
+        ni, ns = int(counts[2 * b]), int(counts[2 * b + 1])
+        if ni == 0:
+            out.append(None)
+            continue
+        entry = {"mask": mask[c0:c0 + ni * ns].view(ni, ns), "cls": out_cls[r0:r0 + ni], "box": out_box[r0:r0 + ni]}
+        if return_ids:
+            entry["ids"] = out_ids[r0:r0 + ni]
+        out.append(entry)
+        r0 += ni
+        c0 += ni * ns
+    return out
+
+
+def get_spp_gt(instance_labels, spps, instance_cls, instance_box, batch_offsets, batch_size, ignore_label=-100,
+               pool=True, *, n_spps=None, strict=False, return_ids=False):
+    """``get_spp_gt`` (ISBNet/isbnet/model/model_utils.py:692-738, called at isbnet.py:377-385) without its loops over
+    the samples and the instance ids: a list of ``batch_size`` entries, ``None`` for a sample without a kept instance
+    (or without points), else ``{"mask": f32[n_inst_gt, n_spp], "cls": instance_cls[ids], "box": instance_box[ids]}``
+    and, with ``return_ids``, ``"ids"`` (int64).  All masks of a call are views into one allocation; so are all
+    ``cls``, ``box`` and ``ids``.
+
+    Sample ``b`` holds the points ``[batch_offsets[b], batch_offsets[b + 1])``.  Its columns are the distinct superpoint
+    ids of its points, ascending; its rows the distinct labels, ascending, that differ from ``ignore_label`` and have
+    ``instance_cls[id] >= 0``.  With c(i, s) the points of superpoint s labelled i and n(s) all points of s, ignored
+    ones included, ``mask[i, s] = 1`` iff ``2 c >= n`` -- with ``strict`` iff ``2 c > n`` (the ``> 0.5`` of
+    SPFormer/spformer/dataset/scannetv2.py:252-253).  For n(s) < 2^24 the integer rule is the reference's float32
+    ``scatter_mean(mask) >= 0.5`` to the bit; beyond that count the integer rule is the definition.
+
+    ``n_spps`` bounds the ids (``[0, n_spps)``); ``None`` takes ``int(spps.max()) + 1``, a second host read beside the
+    call's one -- ISBNet callers pass the pooled length they hold.  ``batch_offsets`` is an int32 / int64 tensor on
+    either side or a sequence.  ``pool=False`` is what ``get_subsample_gt`` does.  Data the reference would mis-index
+    or fail on (a label outside ``instance_cls``, a superpoint id outside the bound, offsets out of order) is a
+    ``GaproError`` and nothing is written.  No autograd: these are targets."""
+    who = "get_spp_gt"
+    if not pool:
+        raise ValueError("get_spp_gt: pool=False makes every point its own column, which is get_subsample_gt (with "
+                         "subsample_idxs = arange): call get_subsample_gt")
+    _check_gt_args(who, instance_labels, instance_cls, instance_box, batch_size)
+    if not isinstance(spps, torch.Tensor) or spps.dim() != 1 or spps.dtype not in _SPP_DTYPES:
+        raise ValueError("%s: spps must be a 1-D integer tensor" % who)
+    if int(spps.shape[0]) != int(instance_labels.shape[0]):
+        raise ValueError("%s: %d labels, %d superpoint ids" % (who, int(instance_labels.shape[0]), int(spps.shape[0])))
+    off = _offsets_arg(batch_offsets, batch_size, who)
+    if n_spps is not None and (isinstance(n_spps, bool) or not isinstance(n_spps, int) or n_spps < 1):
+        raise ValueError("%s: n_spps must be a positive int" % who)
+    if not spps.is_cuda:
+        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    if n_spps is None:
+        n_spps = max(int(spps.max()) + 1, 1)  # a host read; a negative id is refused by the device below
+    return _gt_run(who, instance_labels, None, spps, n_spps, instance_cls, instance_box, off, batch_size, ignore_label,
+                   _lib.SPP_GT_STRICT if strict else _lib.SPP_GT_HALF, return_ids)
+
+
+def get_subsample_gt(instance_labels, subsample_idxs, instance_cls, instance_box, subsample_batch_offsets, batch_size,
+                     ignore_label=-100, *, return_ids=False):
+    """``get_subsample_gt`` (ISBNet/isbnet/model/model_utils.py:647-689, isbnet.py:399-401): the rows of ``get_spp_gt``
+    over the sample's subsampled points, ``mask[i, p] = (instance_labels[subsample_idxs[p]] == id_i)`` for the ``p`` of
+    ``[subsample_batch_offsets[b], subsample_batch_offsets[b + 1])``.  Same return, refusals and single host read."""
+    who = "get_subsample_gt"
+    _check_gt_args(who, instance_labels, instance_cls, instance_box, batch_size)
+    if not isinstance(subsample_idxs, torch.Tensor) or subsample_idxs.dim() != 1 \
+            or subsample_idxs.dtype not in _SPP_DTYPES:
+        raise ValueError("%s: subsample_idxs must be a 1-D integer tensor" % who)
+    if int(subsample_idxs.shape[0]) == 0:
+        raise ValueError("%s: no points" % who)
+    off = _offsets_arg(subsample_batch_offsets, batch_size, who)
+    return _gt_run(who, instance_labels, subsample_idxs, None, 0, instance_cls, instance_box, off, batch_size,
+                   ignore_label, _lib.SPP_GT_HALF, return_ids)

@@ -855,6 +855,83 @@ int gapro_inst_prepare(gapro_ctx* ctx, void* stream, int64_t n_points, const flo
                        gapro_inst_prep_header* h_header_pinned);
 
 /* ------------------------------------------------------------------------------------------
+ * Ground-truth instance masks per batch sample of the consumer's training step (csrc/spp_gt.hip).  Replaces ISBNet's
+ * get_spp_gt (isbnet/model/model_utils.py:692-738) and get_subsample_gt (:647-689), which loop over the samples and,
+ * on the host, over a device tensor of instance ids.  Two calls with one host read between them: gapro_spp_gt_count
+ * reports how many rows and columns every sample has, the caller allocates, gapro_spp_gt_fill writes.
+ *   d_labels        GAPRO_LABEL_F64 / _I32 / _I64 [n_labels]: the instance id of a point, or ignore_label
+ *   d_gather        i64[n_points] or NULL.  Point p of the call reads its label (and superpoint) at d_gather[p]; NULL:
+ *                   at p, and n_labels == n_points
+ *   d_spps          i32 (spp_is_i64 == 0) or i64 [n_labels] superpoint ids in [0, n_spps), or NULL with n_spps == 0:
+ *                   every point is its own column
+ *   d_instance_cls  GAPRO_LABEL_F64 / _I32 / _I64 [n_cls]: the class of every instance id
+ *   d_offsets       i64[batch_size + 1]: sample b holds the points [d_offsets[b], d_offsets[b + 1]); points before the
+ *                   first and after the last offset belong to no sample and are not read at all
+ * Per sample b:
+ *   rows     the distinct labels of its points, ascending, that differ from ignore_label and whose class is >= 0
+ *   columns  the distinct superpoint ids of its points, ascending (the same id may occur in two samples); without
+ *            d_spps its points in their order
+ *   mask     f32[rows, columns], row-major.  c(i, s) = points of column s labelled i, n(s) = all points of column s,
+ *            ignored ones included:  mask = 1.0f where 2 c >= n (GAPRO_SPP_GT_HALF) or 2 c > n (GAPRO_SPP_GT_STRICT),
+ *            else 0.0f.  For n(s) < 2^24 the first is the reference's float32 scatter_mean(label == i) >= 0.5 to the
+ *            bit (two integers below 2^24 are exact in float32 and their correctly rounded quotient cannot reach or
+ *            cross 0.5 from the other side); beyond, the integer rule is the definition.  Without d_spps n = 1 and
+ *            the mask is (label == i).
+ * gapro_spp_gt_count writes d_header (and its page-locked host copy when h_header_pinned is given): the struct below
+ * followed by batch_size pairs {int32 n_inst_gt, int32 n_spp}, GAPRO_SPP_GT_HEADER_BYTES(batch_size) in all.  It leaves
+ * the presence bit-words, their prefix popcounts (rank of an id = prefix of its word + set bits below it) and the packed
+ * offsets in the workspace, which gapro_spp_gt_fill reads: same inputs, same workspace, nothing in between.
+ * gapro_spp_gt_fill writes, packed sample after sample,
+ *   d_mask f32[total_cells]   the masks; during the call the buffer holds the counts c as uint32
+ *   d_cls  [total_rows]       d_instance_cls[id] of every row, in cls_type (NULL = not wanted)
+ *   d_box  f32[total_rows, 6] d_instance_box[id] (f32[n_cls, 6]), bit copies (both NULL = not wanted)
+ *   d_ids  i64[total_rows]    the id of every row (NULL = not wanted)
+ * mask_cells / n_rows are the lengths the caller allocated; smaller ones than the header's totals: GAPRO_ERR_WORKSPACE
+ * in d_header->status (when given), nothing written.
+ * Refusals of the data, header.status of gapro_spp_gt_count; flags names every cause met, bad_sample the lowest sample
+ * of the winning one.  In this order of precedence:
+ *   GAPRO_ERR_BAD_ARG    flags & 1: offsets that decrease or leave [0, n_points] (bad_sample = the first such b; the
+ *                        points are not looked at)
+ *   GAPRO_ERR_BAD_ARG    flags & 2: a d_gather entry outside [0, n_labels)
+ *   GAPRO_ERR_BAD_ARG    flags & 4: a label that is not ignore_label and is negative, >= n_cls, or (float64) no integer
+ *   GAPRO_ERR_SPP_RANGE  flags & 8: a superpoint id outside [0, n_spps)
+ * With a non-zero status gapro_spp_gt_fill writes nothing.  Refused before anything is launched (GAPRO_ERR_BAD_ARG): a
+ * null or non-positive argument, an unknown type code or rule, d_spps without n_spps or the reverse, d_gather == NULL
+ * with n_labels != n_points, n_points or n_labels > 2^31 - 1, batch_size > GAPRO_SPP_GT_MAX_SAMPLES, n_cls >
+ * GAPRO_INST_PREP_MAX_IDS, batch_size * n_spps > GAPRO_SPP_GT_MAX_BATCH_SPPS, d_box without d_instance_box;
+ * GAPRO_ERR_WORKSPACE: a workspace smaller than gapro_spp_gt_workspace_bytes (0 for sizes the calls refuse).  Both calls
+ * only enqueue; integer atomics only, so the results are the same bits for every run.  The passes over the points run at
+ * most GAPRO_SPP_GT_GRID_CAP workgroups of 256 threads.
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_SPP_GT_MAX_SAMPLES 1024
+#define GAPRO_SPP_GT_MAX_BATCH_SPPS 2147483647 /* 2^31 - 1 */
+#define GAPRO_SPP_GT_GRID_CAP 512
+enum { GAPRO_SPP_GT_HALF = 0, GAPRO_SPP_GT_STRICT = 1 };
+typedef struct {
+  int32_t status;
+  int32_t bad_sample;   /* lowest sample of the winning refusal; -1 without one */
+  int32_t flags;        /* 1: offsets, 2: gather index, 4: label, 8: superpoint id */
+  int32_t batch_size;
+  int64_t total_rows;   /* sum of n_inst_gt */
+  int64_t total_cols;   /* sum of n_spp */
+  int64_t total_cells;  /* sum of n_inst_gt * n_spp */
+} gapro_spp_gt_header; /* 40 bytes; batch_size x {int32_t n_inst_gt, n_spp} follow */
+#define GAPRO_SPP_GT_HEADER_BYTES(batch_size) (40 + 8 * (size_t)(batch_size))
+
+size_t gapro_spp_gt_workspace_bytes(int64_t n_points, int32_t batch_size, int32_t n_cls, int32_t n_spps);
+int gapro_spp_gt_count(gapro_ctx* ctx, void* stream, int64_t n_points, int64_t n_labels, const void* d_labels,
+                       int32_t label_type, const int64_t* d_gather, const void* d_spps, int32_t spp_is_i64,
+                       int32_t n_spps, const void* d_instance_cls, int32_t cls_type, int32_t n_cls,
+                       const int64_t* d_offsets, int32_t batch_size, int64_t ignore_label, void* d_workspace,
+                       size_t workspace_bytes, gapro_spp_gt_header* d_header, gapro_spp_gt_header* h_header_pinned);
+int gapro_spp_gt_fill(gapro_ctx* ctx, void* stream, int64_t n_points, int64_t n_labels, const void* d_labels,
+                      int32_t label_type, const int64_t* d_gather, const void* d_spps, int32_t spp_is_i64,
+                      int32_t n_spps, const void* d_instance_cls, int32_t cls_type, int32_t n_cls,
+                      const float* d_instance_box, const int64_t* d_offsets, int32_t batch_size, int64_t ignore_label,
+                      int32_t rule, void* d_workspace, size_t workspace_bytes, float* d_mask, int64_t mask_cells,
+                      void* d_cls, float* d_box, int64_t* d_ids, int64_t n_rows, gapro_spp_gt_header* d_header);
+
+/* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
  * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
  * to superpoint means (:64-69) or by keeping the npoint_nearest points of each side nearest to the centroid of the
