@@ -18,7 +18,8 @@ _EXPORTS = {
     "gaussian_process_utils": ("fit_gp_spp", "fit_gp_spp_batch", "predict_gp_batch", "GPModel", "fit_gp", "fit_gp_batch",
                                "gp_train_sets"),
     "scannet_planes": ("get_wall_boxes",),
-    "consumer_ops": ("get_instance_info", "prepare_instance_labels", "get_spp_gt", "get_subsample_gt"),
+    "consumer_ops": ("get_instance_info", "prepare_instance_labels", "get_spp_gt", "get_subsample_gt", "match_cost",
+                     "linear_sum_assignment", "hungarian_match"),
 }
 __all__ = [n for names in _EXPORTS.values() for n in names]
 

@@ -171,6 +171,21 @@ GAPRO_ERR_SPP_RANGE = -6
 GAPRO_EVAL_MAX_THRESHOLDS = 32
 
 
+class MatchTask(C.Structure):
+    """gapro_match_task: one sample of gapro_match_cost."""
+    _fields_ = [("d_mask_logits", C.c_void_p), ("ld_logits", C.c_int64), ("d_mask", C.c_void_p), ("d_cls", C.c_void_p),
+                ("d_box", C.c_void_p), ("n_inst", C.c_int32), ("n_cols", C.c_int32), ("cost_offset", C.c_int64)]
+
+
+class MatchWeights(C.Structure):
+    """gapro_match_weights: the weights of the five cost terms (matcher.py:192 is the default)."""
+    _fields_ = [("w_class", C.c_double), ("w_dice", C.c_double), ("w_bce", C.c_double), ("w_conf", C.c_double),
+                ("w_giou", C.c_double)]
+
+
+MATCH_STATUS_WORDS = 4  # GAPRO_MATCH_STATUS_WORDS: status, sample, flags (1: class label, 2: mask value), 0
+
+
 class FitOptions(C.Structure):
     _fields_ = [("training_iter", C.c_int32), ("lr", C.c_double), ("jitter", C.c_double),
                 ("min_variance", C.c_double), ("eval_stale_chol", C.c_int32), ("reserved", C.c_int32),
@@ -246,6 +261,10 @@ SIGNATURES = {
     "gapro_spp_gt_fill": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P,
                                     C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, C.c_int32, _P, C.c_size_t, _P,
                                     C.c_int64, _P, _P, _P, C.c_int64, _P]),
+    "gapro_match_cost_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
+    "gapro_match_cost": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                   C.c_size_t, _P, C.c_int64, _P, _P, _P]),
+    "gapro_lsap_solve": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _P, _P]),
     "gapro_schedule_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "gapro_schedule_free": (None, [_P]),
     "gapro_schedule_get_counts": (C.c_int, [_P, C.POINTER(ScheduleCounts)]),
@@ -427,7 +446,8 @@ def load() -> C.CDLL:
             if variant and name.startswith(("gapro_gp_state_", "gapro_svgp_predict_", "gapro_svgp_fit_batch_state",
                                             "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex",
                                             "gapro_schedule_export_testers", "gapro_spp_vote",
-                                            "gapro_fit_launch_plan", "gapro_inst_", "gapro_spp_gt_")):
+                                            "gapro_fit_launch_plan", "gapro_inst_", "gapro_spp_gt_", "gapro_match_",
+                                            "gapro_lsap_")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

@@ -415,3 +415,242 @@ def get_subsample_gt(instance_labels, subsample_idxs, instance_cls, instance_box
     off = _offsets_arg(subsample_batch_offsets, batch_size, who)
     return _gt_run(who, instance_labels, subsample_idxs, None, 0, instance_cls, instance_box, off, batch_size,
                    ignore_label, _lib.SPP_GT_HALF, return_ids)
+
+
+# ---- the Hungarian matcher (gapro_amd/csrc/match_cost.hip, lsap.cc) --------------------------------------
+MATCH_WEIGHTS = (0.5, 1.0, 1.0, 0.2, 0.2)  # class, dice, bce, conf, giou (ISBNet/isbnet/model/matcher.py:192)
+_WEIGHT_NAMES = ("class", "dice", "bce", "conf", "giou")
+_MATCH_CAUSES = ((1, "a class label outside [0, n_classes)"), (2, "a mask value that is neither 0 nor 1"))
+_GT_KEYS = ("row_indices", "inst_labels", "cls_labels", "box_labels")
+
+
+def _weights_arg(weights, who):
+    if weights is None:
+        return None
+    try:
+        vals = [float(weights[k]) for k in _WEIGHT_NAMES] if isinstance(weights, dict) else [float(v) for v in weights]
+    except (TypeError, ValueError, KeyError):
+        raise ValueError("%s: weights must be five numbers (class, dice, bce, conf, giou) or a dict with these keys"
+                         % who) from None
+    if len(vals) != 5 or (isinstance(weights, dict) and len(weights) != 5):
+        raise ValueError("%s: weights must be five numbers (class, dice, bce, conf, giou) or a dict with these keys" % who)
+    if any(v != v or v < 0.0 or v == float("inf") for v in vals):
+        raise ValueError("%s: a weight is negative or not finite" % who)
+    return _lib.MatchWeights(*vals)
+
+
+def _check_match_args(who, cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mask_arr):
+    """What is refused before a device is touched; returns the samples that have instances and the class dtype."""
+    if not isinstance(cls_logits, torch.Tensor) or cls_logits.dim() != 3 or cls_logits.dtype != torch.float32 \
+            or 0 in cls_logits.shape:
+        raise ValueError("%s: cls_logits must be a non-empty float32 tensor of shape [B, Q, C]" % who)
+    B, Q, _ = (int(v) for v in cls_logits.shape)
+    dev = cls_logits.device
+    if not isinstance(conf_logits, torch.Tensor) or conf_logits.dtype != torch.float32 \
+            or tuple(conf_logits.shape) != (B, Q):
+        raise ValueError("%s: conf_logits must be a float32 tensor of shape [%d, %d]" % (who, B, Q))
+    if not isinstance(box_preds, torch.Tensor) or box_preds.dtype != torch.float32 \
+            or tuple(box_preds.shape) != (B, Q, 6):
+        raise ValueError("%s: box_preds must be a float32 tensor of shape [%d, %d, 6]" % (who, B, Q))
+    if B > _lib.SPP_GT_MAX_SAMPLES:
+        raise ValueError("%s: batch size %d beyond %d" % (who, B, _lib.SPP_GT_MAX_SAMPLES))
+    for name, seq in (("mask_logits", mask_logits), ("dc_inst_mask_arr", dc_inst_mask_arr)):
+        if not isinstance(seq, (list, tuple)) or len(seq) != B:
+            raise ValueError("%s: %s must be a list of %d entries, one per sample" % (who, name, B))
+    tensors = [conf_logits, box_preds]
+    kept, cls_dtype = [], None
+    for b, entry in enumerate(dc_inst_mask_arr):
+        if entry is None:
+            continue
+        if not isinstance(entry, dict) or any(not isinstance(entry.get(k), torch.Tensor) for k in ("mask", "cls", "box")):
+            raise ValueError("%s: sample %d: a dict with the tensors mask, cls and box, or None, is expected" % (who, b))
+        mask, cls, box, x = entry["mask"], entry["cls"], entry["box"], mask_logits[b]
+        if mask.dim() != 2 or mask.dtype != torch.float32 or 0 in mask.shape:
+            raise ValueError("%s: sample %d: mask must be a non-empty float32 tensor of shape [I, S]" % (who, b))
+        n_inst, n_cols = (int(v) for v in mask.shape)
+        if cls.dtype not in (torch.int32, torch.int64) or tuple(cls.shape) != (n_inst,):
+            raise ValueError("%s: sample %d: cls must be an int32 or int64 tensor of shape [%d]" % (who, b, n_inst))
+        if cls_dtype not in (None, cls.dtype):
+            raise ValueError("%s: sample %d: cls is %s, an earlier sample's %s" % (who, b, cls.dtype, cls_dtype))
+        cls_dtype = cls.dtype
+        if box.dtype != torch.float32 or tuple(box.shape) != (n_inst, 6):
+            raise ValueError("%s: sample %d: box must be a float32 tensor of shape [%d, 6]" % (who, b, n_inst))
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError("%s: sample %d: mask_logits must be a float32 tensor of shape [Q, S]" % (who, b))
+        if int(x.shape[0]) != Q or int(x.shape[1]) != n_cols:
+            raise ValueError("%s: sample %d: mask_logits is %s, [%d, %d] is expected: one row per query and one column "
+                             "per column of the mask" % (who, b, tuple(x.shape), Q, n_cols))
+        tensors += [mask, cls, box, x]
+        kept.append(b)
+    for t in tensors:
+        if t.device != dev:
+            raise ValueError("%s: tensors on %s and on %s; one device is expected" % (who, dev, t.device))
+    return kept, cls_dtype
+
+
+def _match_run(who, cls_logits, mask_logits, conf_logits, box_preds, entries, kept, cls_dtype, weights, pinned):
+    """One gapro_match_cost on the caller's stream and one synchronisation for its status (and, with ``pinned``, the
+    cost in page-locked memory): the per-sample device views and the host array."""
+    ctx, stream = _ctx_stream(cls_logits)
+    lib, dev = ctx.lib, cls_logits.device
+    B, Q, n_classes = (int(v) for v in cls_logits.shape)
+    cls_logits, conf_logits, box_preds = cls_logits.contiguous(), conf_logits.contiguous(), box_preds.contiguous()
+    tasks = (_lib.MatchTask * B)()
+    keep, offsets, total, total_inst, total_cols = [], {}, 0, 0, 0
+    for b in kept:
+        e, x = entries[b], mask_logits[b]
+        if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+            x = x.contiguous()
+        mask, cls, box = e["mask"].contiguous(), e["cls"].contiguous(), e["box"].contiguous()
+        keep += [x, mask, cls, box]  # alive until the call has been enqueued and synchronised
+        n_inst, n_cols = (int(v) for v in mask.shape)
+        tasks[b] = _lib.MatchTask(x.data_ptr(), int(x.stride(0)), mask.data_ptr(), cls.data_ptr(), box.data_ptr(),
+                                  n_inst, n_cols, total)
+        offsets[b] = (total, n_inst)
+        total += Q * n_inst
+        total_inst += n_inst
+        total_cols += n_cols
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.gapro_match_cost_workspace_bytes(B, Q, total_inst, total_cols))
+        if ws_bytes == 0:
+            raise ValueError("%s: %d samples, %d queries and %d instances are beyond the library's bounds"
+                             % (who, B, Q, total_inst))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        cost = torch.empty(total, dtype=torch.float32, device=dev)
+        d_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, device=dev)
+        h_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, pin_memory=True)
+        h_cost = torch.empty(total, dtype=torch.float32, pin_memory=True) if pinned else None
+        ctx.check(lib.gapro_match_cost(ctx.handle, stream, C.cast(tasks, C.c_void_p), B, Q, n_classes,
+                                       _LABEL_CODES[cls_dtype], cls_logits.data_ptr(), conf_logits.data_ptr(),
+                                       box_preds.data_ptr(), C.byref(weights) if weights is not None else None,
+                                       ws.data_ptr(), ws_bytes, cost.data_ptr(), total,
+                                       h_cost.data_ptr() if pinned else None, d_status.data_ptr(),
+                                       h_status.data_ptr()))
+        torch.cuda.current_stream(dev).synchronize()  # the call's one host read
+    status, bad, flags = (int(v) for v in h_status[:3])
+    if status != 0:
+        why = next(text for bit, text in _MATCH_CAUSES if flags & bit)
+        raise GaproError(status, "%s: sample %d: %s" % (who, bad, why))
+    views = [None] * B
+    host = [None] * B
+    for b, (off, n_inst) in offsets.items():
+        views[b] = cost[off:off + Q * n_inst].view(Q, n_inst)
+        if pinned:
+            host[b] = h_cost.numpy()[off:off + Q * n_inst].reshape(Q, n_inst)
+    return views, host
+
+
+def match_cost(cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mask_arr, *, weights=None):
+    """The cost matrices of ``HungarianMatcher.get_match`` (ISBNet/isbnet/model/matcher.py:156-197) for a whole batch in
+    one call: a list with ``None`` (a sample whose ``dc_inst_mask_arr`` entry is ``None``) or a device ``f32[Q, I_b]``
+    tensor per sample, all of them views into one allocation.
+
+    ``cls_logits`` is ``f32[B, Q, C]``, ``conf_logits`` ``f32[B, Q]``, ``box_preds`` ``f32[B, Q, 6]``; ``mask_logits``
+    the reference's list (``None`` or ``f32[Q, S_b]`` per sample; an entry whose rows are not contiguous is copied);
+    ``dc_inst_mask_arr`` what ``get_spp_gt`` / ``get_subsample_gt`` return.  ``weights`` are five numbers (class, dice,
+    bce, conf, giou) or a dict with these keys; ``None`` is the reference's 0.5, 1, 1, 0.2, 0.2.
+
+    Every term is evaluated in float64 and the cost rounded to float32 once; an entry that is then NaN
+    or infinite becomes 100000.  Shape, dtype and device mismatches are ``ValueError``s before a device is touched; a
+    class label outside ``[0, C)`` or a mask value other than 0 / 1 is a ``GaproError`` and nothing is written.  One
+    host read (the status).  No autograd: the reference runs this under ``no_grad``."""
+    who = "match_cost"
+    kept, cls_dtype = _check_match_args(who, cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mask_arr)
+    w = _weights_arg(weights, who)
+    if not kept:
+        return [None] * len(dc_inst_mask_arr)
+    return _match_run(who, cls_logits.detach(), [None if x is None else x.detach() for x in mask_logits],
+                      conf_logits.detach(), box_preds.detach(), dc_inst_mask_arr, kept, cls_dtype, w, False)[0]
+
+
+def linear_sum_assignment(cost, dup=1):
+    """``scipy.optimize.linear_sum_assignment`` of a float32 NumPy matrix by the library's own solver (no device):
+    ``(rows, cols)`` as int64 arrays, rows ascending.  ``dup > 1`` solves ``np.tile(cost, (1, dup))`` without building
+    it and returns the ORIGINAL column ``j % cost.shape[1]`` of every pair.  Among equal-cost optima the choice is the
+    solver's own (include/gapro_hip.h) and the same for every run.  A non-finite entry is a ``GaproError``."""
+    import numpy as np
+
+    who = "linear_sum_assignment"
+    if not isinstance(cost, np.ndarray) or cost.ndim != 2 or cost.dtype != np.float32:
+        raise ValueError("%s: a two-dimensional float32 NumPy array is expected" % who)
+    if isinstance(dup, bool) or not isinstance(dup, (int, np.integer)) or dup < 1:
+        raise ValueError("%s: dup must be a positive int" % who)
+    n_rows, n_cols = cost.shape
+    if n_rows == 0 or n_cols == 0:
+        raise ValueError("%s: an empty matrix" % who)
+    if cost.strides[1] != 4 or cost.strides[0] < 4 * n_cols or cost.strides[0] % 4:
+        cost = np.ascontiguousarray(cost)
+    n = min(n_rows, int(dup) * n_cols)
+    rows, cols, n_out = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), C.c_int32(0)
+    rc = _lib.load().gapro_lsap_solve(n_rows, n_cols, cost.ctypes.data, cost.strides[0] // 4, int(dup), C.byref(n_out),
+                                      rows.ctypes.data, cols.ctypes.data)
+    if rc != 0:
+        raise GaproError(rc, "%s: %s" % (who, "a non-finite cost" if rc == _lib.GAPRO_ERR_NOT_FINITE else "bad argument"))
+    assert n_out.value == n
+    return rows.astype(np.int64), cols.astype(np.int64)
+
+
+MATCH_SOLVER_THREADS = 4  # host threads hungarian_match solves a batch's assignments on; 1: in the caller's thread
+_solver_pool = None
+
+
+def _solve_all(problems):
+    """``linear_sum_assignment(cost, dup)`` of every problem, in their order.  The solver is a C call that holds no
+    Python state, so the problems of a batch (two per sample, independent) run on a few threads: the largest first."""
+    global _solver_pool
+    if MATCH_SOLVER_THREADS <= 1 or len(problems) < 2:
+        return [linear_sum_assignment(c, d) for c, d in problems]
+    if _solver_pool is None or _solver_pool[0] != MATCH_SOLVER_THREADS:
+        from concurrent.futures import ThreadPoolExecutor
+
+        _solver_pool = (MATCH_SOLVER_THREADS,
+                        ThreadPoolExecutor(max_workers=MATCH_SOLVER_THREADS, thread_name_prefix="gapro-lsap"))
+    order = sorted(range(len(problems)), key=lambda k: -min(problems[k][0].shape[0],
+                                                            problems[k][1] * problems[k][0].shape[1]))
+    futures = {k: _solver_pool[1].submit(linear_sum_assignment, *problems[k]) for k in order}
+    return [futures[k].result() for k in range(len(problems))]
+
+
+def hungarian_match(cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mask_arr, dup_gt=1):
+    """``HungarianMatcher.forward_dup`` (ISBNet/isbnet/model/matcher.py:208-284, called at criterion.py:398) without its
+    loop of small launches and host copies: ``(gt_dict, aux_gt_dict)``, each with the lists ``row_indices`` (NumPy
+    int64, as the reference's), ``inst_labels``, ``cls_labels`` and ``box_labels`` (device tensors: the matched rows of
+    the sample's mask, cls and box), ``None`` for a sample without an instance.  ``aux_gt_dict`` is the assignment with
+    every instance offered ``dup_gt`` times.
+
+    One ``match_cost`` call writes the batch's costs into page-locked memory, ONE stream synchronisation covers the whole
+    batch, the ``2 B`` assignments are solved by the library on the host (on ``MATCH_SOLVER_THREADS`` threads; the
+    result does not depend on their number), and one upload carries all matched columns to the gathers.  A batch of
+    ``None``s returns without a launch.  Among equal-cost optima the assignment is the solver's own, not necessarily
+    SciPy's."""
+    import numpy as np
+
+    who = "hungarian_match"
+    kept, cls_dtype = _check_match_args(who, cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mask_arr)
+    if isinstance(dup_gt, bool) or not isinstance(dup_gt, int) or dup_gt < 1:
+        raise ValueError("%s: dup_gt must be a positive int" % who)
+    B = len(dc_inst_mask_arr)
+    gt, aux = ({k: [None] * B for k in _GT_KEYS} for _ in range(2))
+    if not kept:
+        return gt, aux
+    _, host = _match_run(who, cls_logits.detach(), [None if x is None else x.detach() for x in mask_logits],
+                         conf_logits.detach(), box_preds.detach(), dc_inst_mask_arr, kept, cls_dtype, None, True)
+    problems = [(out, b, dup) for b in kept for out, dup in ((gt, 1), (aux, dup_gt))]
+    solved = _solve_all([(host[b], dup) for _, b, dup in problems])
+    picks = []  # (dict, sample, first, count) of the columns in `cols`
+    cols, n = [], 0
+    for (out, b, _), (r, c) in zip(problems, solved):
+        out["row_indices"][b] = r
+        picks.append((out, b, n, len(c)))
+        cols.append(c)
+        n += len(c)
+    dev = cls_logits.device
+    staged = torch.empty(n, dtype=torch.int64, pin_memory=True)
+    staged.numpy()[:] = np.concatenate(cols)
+    index = staged.to(dev, non_blocking=True)  # the one upload
+    for out, b, first, count in picks:
+        idx, e = index[first:first + count], dc_inst_mask_arr[b]
+        out["inst_labels"][b] = e["mask"].index_select(0, idx)
+        out["cls_labels"][b] = e["cls"].index_select(0, idx)
+        out["box_labels"][b] = e["box"].index_select(0, idx)
+    return gt, aux

@@ -932,6 +932,69 @@ int gapro_spp_gt_fill(gapro_ctx* ctx, void* stream, int64_t n_points, int64_t n_
                       void* d_cls, float* d_box, int64_t* d_ids, int64_t n_rows, gapro_spp_gt_header* d_header);
 
 /* ------------------------------------------------------------------------------------------
+ * Cost matrices of the consumer's Hungarian matcher (csrc/match_cost.hip).  Replaces the per-sample expression chain of
+ * ISBNet's HungarianMatcher.get_match (isbnet/model/matcher.py:144-199): one call enqueues the cost matrices of every
+ * sample of a batch.  Sample b has n_queries queries, n_inst kept instances, n_cols columns (superpoints or subsampled
+ * points) and n_classes classes.  With x = d_mask_logits (f32[n_queries, n_cols]) and t = d_mask (f32[n_inst, n_cols]
+ * holding 0 / 1, as gapro_spp_gt_fill writes it), sig = sigmoid(x), sp = softplus(x) = log(1 + exp(x)):
+ *   dice[q,i]  = 1 - (2 sum_s sig[q,s] t[i,s] + 1) / (sum_s sig[q,s] + sum_s t[i,s] + 1)             (matcher.py:43-47)
+ *   bce[q,i]   = (sum_s sp[q,s] - sum_s x[q,s] t[i,s]) / n_cols                                      (:74-81)
+ *   class[q,i] = -softmax(d_cls_logits[b,q,:])[cls[i]]                                               (:173-175)
+ *   conf[q,i]  = -d_conf_logits[b,q]                                                                 (:177)
+ *   giou[q,i]  = -GIoU(d_box_preds[b,q], box[i]), with the clamps at 0 and the two + 1e-6 of model_utils.py:385-413
+ *   cost       = w_class class + w_dice dice + w_bce bce + w_conf conf + w_giou giou                 (:192)
+ * The bce line is the reference's BCE(x,1) . t + BCE(x,0) . (1 - t): BCE(x,0) = sp, BCE(x,1) = sp - x, so their
+ * difference is -x, and since t is 0 or 1 the identity is exact.  Every term is evaluated in float64 from the float32
+ * inputs, every sum over s is a float64 sum in a fixed order, the cost is combined in float64 and rounded to float32 once;
+ * an entry that is then NaN or +-inf becomes 100000.0f (:196-197).  No floating-point atomics: two calls on the same
+ * input give the same bytes.  A NaN propagates as in the reference: through the min / max / clamp of the boxes too.
+ *
+ * h_tasks is read during the call only.  A task with n_inst == 0 is a sample without a kept instance: its pointers are
+ * not looked at and nothing is written for it.  The call uploads one table, launches two kernels and, when given, copies
+ * d_cost to h_cost_pinned and d_status to h_status_pinned behind them; it only enqueues.
+ * d_status i32[GAPRO_MATCH_STATUS_WORDS] = {status, the lowest sample of the refusal or -1, flags, 0}.  Refusals of the
+ * data, with nothing written to d_cost:
+ *   GAPRO_ERR_BAD_ARG  flags & 1: a class label outside [0, n_classes);  flags & 2: a mask value that is neither 0 nor 1
+ * Refused before anything is launched (GAPRO_ERR_BAD_ARG): a null or non-positive argument, ld_logits < n_cols, an
+ * unknown cls_type (GAPRO_LABEL_I32 / _I64 only), no task with an instance, cost_offsets whose [n_queries, n_inst]
+ * blocks overlap or leave [0, cost_floats), a weight that is negative or not finite, batch_size >
+ * GAPRO_SPP_GT_MAX_SAMPLES; GAPRO_ERR_WORKSPACE: a workspace smaller than gapro_match_cost_workspace_bytes (0 for sizes
+ * the call refuses; total_inst / total_cols = the sums of n_inst / n_cols over the tasks with n_inst > 0).
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_MATCH_STATUS_WORDS 4
+typedef struct {            /* one per sample; n_inst == 0: the sample has no kept instance, nothing is written */
+  const float* d_mask_logits;   /* f32[n_queries, n_cols], row stride ld_logits */
+  int64_t      ld_logits;
+  const float* d_mask;          /* f32[n_inst, n_cols], packed, 0 / 1 */
+  const void*  d_cls;           /* GAPRO_LABEL_I32 / _I64 [n_inst] */
+  const float* d_box;           /* f32[n_inst, 6] */
+  int32_t      n_inst, n_cols;
+  int64_t      cost_offset;     /* floats from d_cost to this sample's f32[n_queries, n_inst] */
+} gapro_match_task;
+typedef struct { double w_class, w_dice, w_bce, w_conf, w_giou; } gapro_match_weights; /* defaults 0.5, 1, 1, 0.2, 0.2 */
+size_t gapro_match_cost_workspace_bytes(int32_t batch_size, int32_t n_queries, int64_t total_inst, int64_t total_cols);
+int gapro_match_cost(gapro_ctx* ctx, void* stream, const gapro_match_task* h_tasks, int32_t batch_size,
+                     int32_t n_queries, int32_t n_classes, int32_t cls_type,
+                     const float* d_cls_logits /* [B,Q,C] */, const float* d_conf_logits /* [B,Q] */,
+                     const float* d_box_preds /* [B,Q,6] */, const gapro_match_weights* w /* NULL: defaults */,
+                     void* d_workspace, size_t workspace_bytes, float* d_cost, int64_t cost_floats,
+                     float* h_cost_pinned /* NULL or cost_floats: async copy behind the kernels */,
+                     int32_t* d_status, int32_t* h_status_pinned);
+
+/* Rectangular linear sum assignment on the host (csrc/lsap.cc; no device, no ctx): the scipy.optimize call of
+ * matcher.py:201-204.  cost is f32[n_rows, n_cols] with row stride ld; dup >= 1 solves the problem whose column j, j in
+ * [0, dup n_cols), is cost[:, j % n_cols] -- the reference's final_cost.repeat(1, dup_gt) without the repeated matrix.
+ * Shortest augmenting paths with float64 duals (Jonker and Volgenant 1987 in the rectangular form of Crouse 2016); the
+ * side with fewer entries is the one whose every entry is assigned.  *n_out = min(n_rows, dup n_cols) pairs: rows
+ * ascending, cols the ORIGINAL column j % n_cols.  The assignment is optimal; among equal-cost optima it is the one this
+ * search finds, the same for every run: a search step that can close several columns at the same distance closes an
+ * unassigned one before an assigned one and, among those, the one with the lowest index j.
+ * GAPRO_ERR_BAD_ARG: a null or non-positive argument, ld < n_cols, dup n_cols beyond 2^31 - 1; GAPRO_ERR_NOT_FINITE: a
+ * NaN or infinite entry (gapro_match_cost has replaced them). */
+int gapro_lsap_solve(int32_t n_rows, int32_t n_cols, const float* cost, int64_t ld, int32_t dup,
+                     int32_t* n_out, int32_t* rows /* [min(n_rows, dup*n_cols)] */, int32_t* cols);
+
+/* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
  * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
  * to superpoint means (:64-69) or by keeping the npoint_nearest points of each side nearest to the centroid of the
