@@ -186,6 +186,17 @@ class MatchWeights(C.Structure):
 MATCH_STATUS_WORDS = 4  # GAPRO_MATCH_STATUS_WORDS: status, sample, flags (1: class label, 2: mask value), 0
 
 
+class MatchLossTask(C.Structure):
+    """gapro_match_loss_task: one sample of gapro_match_loss_forward."""
+    _fields_ = [("d_mask_logits", C.c_void_p), ("ld_logits", C.c_int64), ("d_inst_labels", C.c_void_p),
+                ("d_cls_labels", C.c_void_p), ("d_box_labels", C.c_void_p), ("n_gt", C.c_int32), ("n_cols", C.c_int32),
+                ("col_offset", C.c_int64), ("row_offset", C.c_int64)]
+
+
+MATCH_LOSS_N = 7          # GAPRO_MATCH_LOSS_N: dice, bce, cls, iou, box, giou, levelset
+MATCH_LOSS_MAX_FEATS = 8  # GAPRO_MATCH_LOSS_MAX_FEATS
+
+
 class FitOptions(C.Structure):
     _fields_ = [("training_iter", C.c_int32), ("lr", C.c_double), ("jitter", C.c_double),
                 ("min_variance", C.c_double), ("eval_stale_chol", C.c_int32), ("reserved", C.c_int32),
@@ -264,6 +275,12 @@ SIGNATURES = {
     "gapro_match_cost_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
     "gapro_match_cost": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                    C.c_size_t, _P, C.c_int64, _P, _P, _P]),
+    "gapro_match_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64]),
+    "gapro_match_loss_forward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                           _P, _P, _P, _P, _P, C.c_int64, _P, C.c_double, _P, C.c_size_t, _P, _P, _P]),
+    "gapro_match_loss_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                            _P, _P, _P, _P, _P, _P, _P, C.c_double, _P, C.c_size_t, _P, _P, _P, _P,
+                                            _P]),
     "gapro_lsap_solve": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _P, _P]),
     "gapro_schedule_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "gapro_schedule_free": (None, [_P]),

@@ -654,3 +654,249 @@ def hungarian_match(cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mas
         out["cls_labels"][b] = e["cls"].index_select(0, idx)
         out["box_labels"][b] = e["box"].index_select(0, idx)
     return gt, aux
+
+
+# ---- the matched losses (gapro_amd/csrc/match_loss.hip) -------------------------------------------------
+LOSS_NAMES = ("dice_loss", "bce_loss", "cls_loss", "iou_loss", "box_loss", "giou_loss", "levelset_loss")
+_default_weights = {}  # (device, C) -> ones with the last entry 0.1
+
+
+def _default_empty_weight(dev, n_classes):
+    key = (dev, n_classes)
+    if key not in _default_weights:
+        w = torch.ones(n_classes, dtype=torch.float32)
+        w[-1] = 0.1
+        _default_weights[key] = w.to(dev)
+    return _default_weights[key]
+
+
+def _check_loss_args(who, cls_logits, mask_logits, conf_logits, box_preds, prob_labels, batch_offsets, levelset_feats,
+                     levelset_coords, gt_dict, empty_weight, voxel_scale):
+    """What is refused before a device is touched; returns the kept samples, their host row indices (int32 NumPy), the
+    offsets as ints and the class dtype."""
+    import numpy as np
+
+    if not isinstance(cls_logits, torch.Tensor) or cls_logits.dim() != 3 or cls_logits.dtype != torch.float32 \
+            or 0 in cls_logits.shape:
+        raise ValueError("%s: cls_logits must be a non-empty float32 tensor of shape [B, Q, C]" % who)
+    B, Q, n_classes = (int(v) for v in cls_logits.shape)
+    dev = cls_logits.device
+    if not isinstance(conf_logits, torch.Tensor) or conf_logits.dtype != torch.float32 \
+            or tuple(conf_logits.shape) != (B, Q):
+        raise ValueError("%s: conf_logits must be a float32 tensor of shape [%d, %d]" % (who, B, Q))
+    if not isinstance(box_preds, torch.Tensor) or box_preds.dtype != torch.float32 \
+            or tuple(box_preds.shape) != (B, Q, 6):
+        raise ValueError("%s: box_preds must be a float32 tensor of shape [%d, %d, 6]" % (who, B, Q))
+    if B > _lib.SPP_GT_MAX_SAMPLES:
+        raise ValueError("%s: batch size %d beyond %d" % (who, B, _lib.SPP_GT_MAX_SAMPLES))
+    if not isinstance(mask_logits, (list, tuple)) or len(mask_logits) != B:
+        raise ValueError("%s: mask_logits must be a list of %d entries, one per sample" % (who, B))
+    if not isinstance(gt_dict, dict) or any(not isinstance(gt_dict.get(k), (list, tuple)) or len(gt_dict[k]) != B
+                                            for k in _GT_KEYS):
+        raise ValueError("%s: gt_dict must hold the lists %s of %d entries, as hungarian_match returns them"
+                         % (who, ", ".join(_GT_KEYS), B))
+    if not isinstance(prob_labels, torch.Tensor) or prob_labels.dim() != 1 or prob_labels.dtype != torch.float32 \
+            or int(prob_labels.shape[0]) == 0:
+        raise ValueError("%s: prob_labels must be a non-empty float32 tensor of shape [N]" % who)
+    N = int(prob_labels.shape[0])
+    if not isinstance(levelset_feats, torch.Tensor) or levelset_feats.dim() != 2 \
+            or levelset_feats.dtype != torch.float32 or int(levelset_feats.shape[0]) != N:
+        raise ValueError("%s: levelset_feats must be a float32 tensor of shape [%d, F]" % (who, N))
+    if not 1 <= int(levelset_feats.shape[1]) <= _lib.MATCH_LOSS_MAX_FEATS:
+        raise ValueError("%s: %d level-set features; 1 to %d are expected"
+                         % (who, int(levelset_feats.shape[1]), _lib.MATCH_LOSS_MAX_FEATS))
+    if not isinstance(levelset_coords, torch.Tensor) or levelset_coords.dtype != torch.float32 \
+            or tuple(levelset_coords.shape) != (N, 3):
+        raise ValueError("%s: levelset_coords must be a float32 tensor of shape [%d, 3]" % (who, N))
+    if empty_weight is not None and (not isinstance(empty_weight, torch.Tensor) or empty_weight.dtype != torch.float32
+                                     or tuple(empty_weight.shape) != (n_classes,)):
+        raise ValueError("%s: empty_weight must be a float32 tensor of shape [%d]" % (who, n_classes))
+    if isinstance(voxel_scale, bool) or not isinstance(voxel_scale, (int, float)) \
+            or voxel_scale != voxel_scale or abs(voxel_scale) == float("inf"):
+        raise ValueError("%s: voxel_scale must be a finite number" % who)
+    if isinstance(batch_offsets, torch.Tensor):
+        if batch_offsets.device.type != "cpu":
+            raise ValueError("%s: batch_offsets must be on the host (a sequence, a NumPy array or a CPU tensor)" % who)
+        batch_offsets = batch_offsets.tolist()
+    try:
+        off = [int(v) for v in batch_offsets]
+        if any(o != v for o, v in zip(off, batch_offsets)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("%s: batch_offsets must be a host sequence of integers" % who) from None
+    if len(off) != B + 1:
+        raise ValueError("%s: %d batch offsets for batch_size %d; batch_size + 1 are expected" % (who, len(off), B))
+    if off[0] < 0 or off[-1] > N or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError("%s: batch_offsets must not decrease and must stay inside [0, %d]" % (who, N))
+    tensors = [conf_logits, box_preds, prob_labels, levelset_feats, levelset_coords]
+    if empty_weight is not None:
+        tensors.append(empty_weight)
+    kept, rows_host, cls_dtype = [], {}, None
+    for b in range(B):
+        x, rows = mask_logits[b], gt_dict["row_indices"][b]
+        if x is None or rows is None:
+            continue
+        if isinstance(rows, torch.Tensor):
+            if rows.device.type != "cpu":
+                raise ValueError("%s: sample %d: row_indices must be on the host (NumPy or a CPU tensor)" % (who, b))
+            rows = rows.numpy()
+        if not isinstance(rows, np.ndarray) or rows.ndim != 1 or rows.dtype.kind not in "iu":
+            raise ValueError("%s: sample %d: row_indices must be a 1-D integer NumPy array or CPU tensor" % (who, b))
+        n_gt = int(rows.shape[0])
+        if n_gt == 0:
+            raise ValueError("%s: sample %d: row_indices is empty; a sample without a match is None" % (who, b))
+        if int(rows.min()) < 0 or int(rows.max()) >= Q:
+            raise ValueError("%s: sample %d: a row index outside [0, %d)" % (who, b, Q))
+        if len(np.unique(rows)) != n_gt:
+            raise ValueError("%s: sample %d: a row index is listed twice" % (who, b))
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError("%s: sample %d: mask_logits must be a float32 tensor of shape [Q, S]" % (who, b))
+        n_cols = off[b + 1] - off[b]
+        if int(x.shape[0]) != Q or int(x.shape[1]) != n_cols or n_cols == 0:
+            raise ValueError("%s: sample %d: mask_logits is %s, [%d, %d] is expected: one row per query and one column "
+                             "per point of batch_offsets, at least one" % (who, b, tuple(x.shape), Q, n_cols))
+        inst, cls, box = (gt_dict[k][b] for k in ("inst_labels", "cls_labels", "box_labels"))
+        if not isinstance(inst, torch.Tensor) or inst.dtype != torch.float32 or tuple(inst.shape) != (n_gt, n_cols):
+            raise ValueError("%s: sample %d: inst_labels must be a float32 tensor of shape [%d, %d]"
+                             % (who, b, n_gt, n_cols))
+        if not isinstance(cls, torch.Tensor) or cls.dtype not in (torch.int32, torch.int64) \
+                or tuple(cls.shape) != (n_gt,):
+            raise ValueError("%s: sample %d: cls_labels must be an int32 or int64 tensor of shape [%d]" % (who, b, n_gt))
+        if cls_dtype not in (None, cls.dtype):
+            raise ValueError("%s: sample %d: cls_labels is %s, an earlier sample's %s" % (who, b, cls.dtype, cls_dtype))
+        cls_dtype = cls.dtype
+        if not isinstance(box, torch.Tensor) or box.dtype != torch.float32 or tuple(box.shape) != (n_gt, 6):
+            raise ValueError("%s: sample %d: box_labels must be a float32 tensor of shape [%d, 6]" % (who, b, n_gt))
+        tensors += [x, inst, cls, box]
+        kept.append(b)
+        rows_host[b] = rows.astype(np.int32)
+    for t in tensors:
+        if t.device != dev:
+            raise ValueError("%s: tensors on %s and on %s; one device is expected" % (who, dev, t.device))
+    return kept, rows_host, off, cls_dtype
+
+
+class _MatchedLosses(torch.autograd.Function):
+    """The one autograd node of ``matched_losses``: ``f32[7]`` forward, one kernel backward."""
+
+    @staticmethod
+    def forward(fctx, plan, cls_logits, conf_logits, box_preds, *mask_logits):
+        import numpy as np
+
+        who = "matched_losses"
+        ctx, stream = _ctx_stream(cls_logits)
+        lib, dev = ctx.lib, cls_logits.device
+        B, Q, n_classes = (int(v) for v in cls_logits.shape)
+        cls_logits, conf_logits, box_preds = cls_logits.contiguous(), conf_logits.contiguous(), box_preds.contiguous()
+        gt, off = plan["gt"], plan["off"]
+        tasks = (_lib.MatchLossTask * B)()
+        keep, xs, total_gt, grad_spans, grad_floats = [], [], 0, [], 0
+        for b, x in zip(plan["kept"], mask_logits):
+            if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+                x = x.contiguous()
+            inst, cls, box = (gt[k][b].contiguous() for k in ("inst_labels", "cls_labels", "box_labels"))
+            keep += [inst, cls, box]  # alive until the backward has run
+            xs.append(x)
+            n_gt, n_cols = (int(v) for v in inst.shape)
+            tasks[b] = _lib.MatchLossTask(x.data_ptr(), int(x.stride(0)), inst.data_ptr(), cls.data_ptr(),
+                                          box.data_ptr(), n_gt, n_cols, off[b], total_gt)
+            total_gt += n_gt
+            grad_spans.append((grad_floats, n_cols))
+            grad_floats += Q * n_cols
+        rows = np.ascontiguousarray(np.concatenate([plan["rows"][b] for b in plan["kept"]]), dtype=np.int32)
+        prob, feats, coords = (plan[k].contiguous() for k in ("prob", "feats", "coords"))
+        weight = plan["weight"].contiguous()
+        with torch.cuda.device(dev):
+            ws_bytes = int(lib.gapro_match_loss_workspace_bytes(B, Q, total_gt))
+            if ws_bytes == 0:
+                raise ValueError("%s: %d samples, %d queries and %d matched rows are beyond the library's bounds"
+                                 % (who, B, Q, total_gt))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            out = torch.empty(_lib.MATCH_LOSS_N, dtype=torch.float32, device=dev)
+            d_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, device=dev)
+            h_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, pin_memory=True) if plan["check"] else None
+            args = (B, Q, n_classes, _LABEL_CODES[plan["cls_dtype"]], int(feats.shape[1]))
+            ctx.check(lib.gapro_match_loss_forward(ctx.handle, stream, C.cast(tasks, C.c_void_p), rows.ctypes.data,
+                                                   *args, cls_logits.data_ptr(), conf_logits.data_ptr(),
+                                                   box_preds.data_ptr(), prob.data_ptr(), feats.data_ptr(),
+                                                   coords.data_ptr(), int(prob.shape[0]), weight.data_ptr(),
+                                                   plan["voxel_scale"], ws.data_ptr(), ws_bytes, out.data_ptr(),
+                                                   d_status.data_ptr(),
+                                                   h_status.data_ptr() if h_status is not None else None))
+            if h_status is not None:
+                torch.cuda.current_stream(dev).synchronize()  # the call's one host read, asked for by check=True
+                status, bad, flags = (int(v) for v in h_status[:3])
+                if status != 0:
+                    raise GaproError(status, "%s: sample %d: a class label outside [0, n_classes)" % (who, bad))
+        fctx.save_for_backward(cls_logits, conf_logits, box_preds, *xs)
+        fctx.held = (keep, prob, feats, coords, weight, ws, ws_bytes, args, total_gt, plan["voxel_scale"],
+                     grad_spans, grad_floats)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad_out):
+        cls_logits, conf_logits, box_preds, *xs = fctx.saved_tensors
+        _, prob, feats, coords, weight, ws, ws_bytes, args, total_gt, voxel_scale, grad_spans, grad_floats = fctx.held
+        ctx, stream = _ctx_stream(cls_logits)
+        dev = cls_logits.device
+        need = fctx.needs_input_grad
+        B, Q = args[0], args[1]
+        grad_out = grad_out.to(dtype=torch.float32).contiguous()
+        g_cls = torch.empty_like(cls_logits) if need[1] else None
+        g_conf = torch.empty_like(conf_logits) if need[2] else None
+        g_box = torch.empty_like(box_preds) if need[3] else None
+        g_mask = torch.empty(grad_floats, dtype=torch.float32, device=dev) if any(need[4:]) else None
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.gapro_match_loss_backward(ctx.handle, stream, *args, total_gt, cls_logits.data_ptr(),
+                                                        conf_logits.data_ptr(), box_preds.data_ptr(), prob.data_ptr(),
+                                                        feats.data_ptr(), coords.data_ptr(), weight.data_ptr(),
+                                                        voxel_scale, ws.data_ptr(), ws_bytes, grad_out.data_ptr(),
+                                                        ptr(g_cls), ptr(g_mask), ptr(g_conf), ptr(g_box)))
+        masks = [g_mask[first:first + Q * n_cols].view(Q, n_cols) if need[4 + k] else None
+                 for k, (first, n_cols) in enumerate(grad_spans)]
+        return (None, g_cls, g_conf, g_box, *masks)
+
+
+def matched_losses(cls_logits, mask_logits, conf_logits, box_preds, prob_labels, batch_offsets, levelset_feats,
+                   levelset_coords, gt_dict, *, empty_weight=None, voxel_scale=50, check=True):
+    """The seven main losses of ``Criterion.single_layer_loss`` (ISBNet/isbnet/model/criterion.py:235-331, called at
+    :414) for a whole batch: a dict with the reference's keys ``dice_loss``, ``bce_loss``, ``cls_loss``, ``iou_loss``,
+    ``box_loss``, ``giou_loss``, ``levelset_loss`` (device scalars, selections of ONE ``f32[7]`` of one autograd node)
+    and ``kl_loss``, a constant zero.  Two kernels forward; ``sum(w[k] * losses[k]).backward()`` runs one kernel, which
+    reads the upstream ``f32[7]`` on the device, and gives gradients for ``cls_logits``, every ``mask_logits[b]``,
+    ``conf_logits`` and ``box_preds`` (zeros in the rows no instance matched; ``None`` for a skipped sample's logits).
+
+    The arguments are ``single_layer_loss``'s with the four label lists taken as ``gt_dict``, what ``hungarian_match``
+    returns: ``prob_labels`` ``f32[N]``, ``batch_offsets`` ``B + 1`` host integers with ``mask_logits[b]`` of
+    ``batch_offsets[b + 1] - batch_offsets[b]`` columns, ``levelset_feats`` ``f32[N, F]`` (1 <= F <= 8),
+    ``levelset_coords`` ``f32[N, 3]``.  ``empty_weight`` is ``Criterion.empty_weight`` (``f32[C]``; ``None``: ones with
+    the last entry 0.1).  A sample whose ``mask_logits[b]`` or ``row_indices[b]`` is ``None`` is skipped as in the
+    reference: nothing is added for it, and it counts in the division by B.  A batch of skipped samples returns zeros
+    without a launch of the library.
+
+    Float64 from the float32 inputs, rounded once; no floating-point atomics, so two calls give equal
+    bytes.  Mismatched shapes, dtypes or devices, row indices that are empty, on the device, out of ``[0, Q)`` or listed
+    twice, offsets out of order and a ``voxel_scale`` that is not finite are ``ValueError``s before a device is touched.
+    A class label outside ``[0, C)`` is refused by the device: with ``check=True`` the status is read behind the kernels
+    (the call's one synchronisation) and a ``GaproError`` raised; with ``check=False`` the call only enqueues, the seven
+    losses are NaN and the backward writes zeros."""
+    who = "matched_losses"
+    kept, rows_host, off, cls_dtype = _check_loss_args(who, cls_logits, mask_logits, conf_logits, box_preds,
+                                                       prob_labels, batch_offsets, levelset_feats, levelset_coords,
+                                                       gt_dict, empty_weight, voxel_scale)
+    dev = cls_logits.device
+    if not kept:
+        zeros = torch.zeros(_lib.MATCH_LOSS_N + 1, dtype=torch.float32, device=dev)
+        return {name: zeros[k] for k, name in enumerate(LOSS_NAMES + ("kl_loss",))}
+    if not cls_logits.is_cuda:
+        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    weight = (_default_empty_weight(dev, int(cls_logits.shape[2])) if empty_weight is None else empty_weight).detach()
+    plan = {"kept": kept, "rows": rows_host, "off": off, "cls_dtype": cls_dtype, "gt": gt_dict,
+            "prob": prob_labels.detach(), "feats": levelset_feats.detach(), "coords": levelset_coords.detach(),
+            "weight": weight, "voxel_scale": float(voxel_scale), "check": bool(check)}
+    out = _MatchedLosses.apply(plan, cls_logits, conf_logits, box_preds, *[mask_logits[b] for b in kept])
+    losses = dict(zip(LOSS_NAMES, out.unbind(0)))  # one node between the dict and the function
+    losses["kl_loss"] = torch.zeros((), dtype=torch.float32, device=dev)
+    return losses

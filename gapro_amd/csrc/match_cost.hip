@@ -15,9 +15,10 @@
 // layout above fixes (inside a wave ascending chunks, inside a chunk the MFMA's k order; then lanes 16 apart by a butterfly;
 // then waves 0 .. 3), one rounding to float32, then NaN / +-inf -> 100000.  No floating-point atomics, no workgroup waits
 // for another.  Tails in Q, I and S are zeros in the operands; a lane outside the matrix forms no address.
-// A NaN propagates as in the reference, whose min / max / clamp hand a NaN on: nan_min / nan_max / clamp0 below.
+// A NaN propagates as in the reference, whose min / max / clamp hand a NaN on: nan_min / nan_max / clamp0 (match_math.h).
 #include "common.h"
 #include "launch_util.h"
+#include "match_math.h"
 #include "mfma64.h"
 #include "wave_reduce.h"
 
@@ -87,10 +88,6 @@ __host__ __device__ inline size_t match_ws(void* base, int B, int Q, long long t
   return (size_t)(p - (char*)base);
 }
 
-__device__ inline long long cls_at(const void* cls, int type, int i) {
-  return type == GAPRO_LABEL_I32 ? (long long)((const int*)cls)[i] : ((const long long*)cls)[i];
-}
-
 // ---- check ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_match_check(void* base, MatchDims d) {
   MatchWs w;
@@ -128,10 +125,6 @@ __global__ __launch_bounds__(kThreads) void k_match_check(void* base, MatchDims 
 }
 
 // ---- cost ----------------------------------------------------------------------------------------------------------
-__device__ inline double nan_min(double a, double b) { return (a < b || a != a) ? a : b; }  // torch.min: a NaN wins
-__device__ inline double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
-__device__ inline double clamp0(double v) { return v < 0.0 ? 0.0 : v; }                     // clamp(min=0) keeps a NaN
-
 // model_utils.py:385-413 for one pair, in float64
 __device__ inline double giou_of(const float* __restrict__ p, const float* __restrict__ g) {
   double inter = 1.0, v1 = 1.0, v2 = 1.0, bound = 1.0;

@@ -981,6 +981,81 @@ int gapro_match_cost(gapro_ctx* ctx, void* stream, const gapro_match_task* h_tas
                      float* h_cost_pinned /* NULL or cost_floats: async copy behind the kernels */,
                      int32_t* d_status, int32_t* h_status_pinned);
 
+/* ------------------------------------------------------------------------------------------
+ * Matched losses (csrc/match_loss.hip).  Replaces the loop of ISBNet's Criterion.single_layer_loss
+ * (isbnet/model/criterion.py:235-331): the seven main losses of a whole batch in two launches, their gradients in one.
+ * Sample b has n_queries queries, n_gt matched rows (h_rows[row_offset + r] = the query of row r, distinct, in
+ * [0, n_queries)), n_cols columns which are [col_offset, col_offset + n_cols) of d_prob_labels (f32[n_points]),
+ * d_levelset_feats (f32[n_points, n_feats], 1 <= n_feats <= GAPRO_MATCH_LOSS_MAX_FEATS) and d_levelset_coords
+ * (f32[n_points, 3]).  A task with n_gt == 0 is a skipped sample: it adds nothing, not even a class term, but counts in
+ * the division by batch_size.  The rule continues the matcher's: float64 from the float32 inputs, every sum a float64
+ * sum in a fixed order, one rounding.  With x the matched rows of the logits, t = d_inst_labels, w the sample's slice of
+ * d_prob_labels, n = n_gt, e = exp(-|x|), sig = (x >= 0 ? 1 : e) / (1 + e), sp = max(x, 0) + log1p(e), per sample:
+ *   dice     = sum_r [1 - (2 sum_s sig t + 1) / (sum_s sig + sum_s t + 1)] / (n + 1e-6)                  (:23-43)
+ *   bce      = (sum_{r,s} w_s (sp - x t)) / (sum_s w_s) / (n + 1e-6); a zero weight sum gives NaN         (:287-288)
+ *   iou      = sum_r (conf_r - inter_r / (union_r + 1e-6))^2 / n, inter = sum_s [x >= 0] t,
+ *              union = sum_s [x >= 0] + sum_s t - inter; no gradient through the IoU                      (:10-20, 293-297)
+ *   cls      = sum_q W[tgt_q] (lse_q - z[q, tgt_q]) / sum_q W[tgt_q] over ALL queries, tgt_q the matched row's class
+ *              or n_classes - 1, W = d_empty_weight (f32[n_classes])                                     (:299-310)
+ *   box      = (voxel_scale / 50) sum |box_pred - box_label| / n                                          (:312-315)
+ *   giou     = sum_r (1 - GIoU_r) / n, the clamps at 0 and the two + 1e-6 of model_utils.py:277-306; min / max / clamp
+ *              hand a NaN on
+ *   levelset = sum_r L_r / (n + 1e-4): column s belongs to box r iff coords >= (float)(lo - 0.005f) and
+ *              coords <= (float)(hi + 0.005f) on all three axes, a FLOAT32 comparison (a NaN is outside); with n_r the
+ *              member count, v = sig(x[r, s]), A = sum v, mu_f = (sum v f_sf) / max(A, 1e-5):
+ *              L_r = (1 / n_r) sum_s v sum_f (f_sf - mu_f)^2, a box with n_r = 0 left out                 (:193-233)
+ * d_losses f32[GAPRO_MATCH_LOSS_N] = the samples' values added in sample order and divided by batch_size, in the order
+ * dice, bce, cls, iou, box, giou, levelset.  The IoU predicate is the exact x >= 0 (the reference's float32
+ * sigmoid(x) >= 0.5 also admits negative x of magnitude below about 6e-8).
+ * gapro_match_loss_backward: the exact derivatives of these expressions, weighted by d_grad_losses (f32[7], read on the
+ * device), in float64, rounded once: L1 with sign(0) = 0, the clamps and min / max with torch's subgradients (a clamp
+ * passes at equality, min / max share a tie), the max(A, 1e-5) branch with its own d mu / d v, sig - t in the
+ * cancellation-free form; nothing overflows at |x| = 100.  A NULL gradient pointer is not written.  d_grad_mask_logits
+ * holds the kept samples' packed f32[n_queries, n_cols] blocks one after the other in sample order; every row of a kept
+ * sample is written (zeros for an unmatched query), and every row of d_grad_cls_logits / _conf_logits / _box_preds
+ * (zeros for a skipped sample).  It reads the workspace and the inputs as the forward call left them.
+ * No floating-point atomics: two calls give equal bytes.  The forward call uploads one table (tasks, row indices, the
+ * per-query table query -> row or -1, the zeroed status), launches two kernels and, when given, copies d_status to
+ * h_status_pinned behind them; both calls only enqueue.
+ * d_status i32[GAPRO_MATCH_STATUS_WORDS] = {status, the lowest sample of the refusal or -1, flags, 0}.  Refused by the
+ * device: flags & 1, a class label outside [0, n_classes): GAPRO_ERR_BAD_ARG, all seven losses NaN, and the backward
+ * call writes zeros.  Refused before anything is launched (GAPRO_ERR_BAD_ARG): a null or non-positive argument,
+ * n_feats outside its range, ld_logits < n_cols, columns that leave [0, n_points), a row_offset that is not the sum of
+ * the earlier n_gt, a row index outside [0, n_queries) or listed twice, every sample skipped, a voxel_scale that is not
+ * finite, batch_size > GAPRO_SPP_GT_MAX_SAMPLES; GAPRO_ERR_WORKSPACE: a workspace smaller than
+ * gapro_match_loss_workspace_bytes (0 for sizes the call refuses; total_gt = the sum of n_gt).
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_MATCH_LOSS_N 7
+#define GAPRO_MATCH_LOSS_MAX_FEATS 8
+typedef struct {            /* one per sample; n_gt == 0: skipped */
+  const float* d_mask_logits;   /* f32[n_queries, n_cols], row stride ld_logits */
+  int64_t      ld_logits;
+  const float* d_inst_labels;   /* f32[n_gt, n_cols], packed */
+  const void*  d_cls_labels;    /* GAPRO_LABEL_I32 / _I64 [n_gt] */
+  const float* d_box_labels;    /* f32[n_gt, 6] */
+  int32_t      n_gt, n_cols;
+  int64_t      col_offset;      /* the sample's first column in d_prob_labels, d_levelset_feats, d_levelset_coords */
+  int64_t      row_offset;      /* the sum of n_gt over the samples before this one */
+} gapro_match_loss_task;
+size_t gapro_match_loss_workspace_bytes(int32_t batch_size, int32_t n_queries, int64_t total_gt);
+int gapro_match_loss_forward(gapro_ctx* ctx, void* stream, const gapro_match_loss_task* h_tasks,
+                             const int32_t* h_rows /* [total_gt] */, int32_t batch_size, int32_t n_queries,
+                             int32_t n_classes, int32_t cls_type, int32_t n_feats,
+                             const float* d_cls_logits /* [B,Q,C] */, const float* d_conf_logits /* [B,Q] */,
+                             const float* d_box_preds /* [B,Q,6] */, const float* d_prob_labels,
+                             const float* d_levelset_feats, const float* d_levelset_coords, int64_t n_points,
+                             const float* d_empty_weight /* [C] */, double voxel_scale, void* d_workspace,
+                             size_t workspace_bytes, float* d_losses /* [7] */, int32_t* d_status,
+                             int32_t* h_status_pinned /* NULL: no copy */);
+int gapro_match_loss_backward(gapro_ctx* ctx, void* stream, int32_t batch_size, int32_t n_queries, int32_t n_classes,
+                              int32_t cls_type, int32_t n_feats, int64_t total_gt, const float* d_cls_logits,
+                              const float* d_conf_logits, const float* d_box_preds, const float* d_prob_labels,
+                              const float* d_levelset_feats, const float* d_levelset_coords,
+                              const float* d_empty_weight, double voxel_scale, const void* d_workspace,
+                              size_t workspace_bytes, const float* d_grad_losses /* [7] */,
+                              float* d_grad_cls_logits /* [B,Q,C] or NULL */, float* d_grad_mask_logits,
+                              float* d_grad_conf_logits /* [B,Q] or NULL */, float* d_grad_box_preds /* [B,Q,6] or NULL */);
+
 /* Rectangular linear sum assignment on the host (csrc/lsap.cc; no device, no ctx): the scipy.optimize call of
  * matcher.py:201-204.  cost is f32[n_rows, n_cols] with row stride ld; dup >= 1 solves the problem whose column j, j in
  * [0, dup n_cols), is cost[:, j % n_cols] -- the reference's final_cost.repeat(1, dup_gt) without the repeated matrix.
