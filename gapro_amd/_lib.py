@@ -195,6 +195,11 @@ class MatchLossTask(C.Structure):
 
 MATCH_LOSS_N = 7          # GAPRO_MATCH_LOSS_N: dice, bce, cls, iou, box, giou, levelset
 MATCH_LOSS_MAX_FEATS = 8  # GAPRO_MATCH_LOSS_MAX_FEATS
+POINT_LOSS_N = 4                                      # GAPRO_POINT_LOSS_N: sem, corners, giou, conf
+POINT_LOSS_MIN_CLASSES, POINT_LOSS_MAX_CLASSES = 2, 64  # GAPRO_POINT_LOSS_MIN_CLASSES / _MAX_CLASSES
+POINT_LOSS_MAX_POINTS = (1 << 31) - 1                 # n_points of one call
+POINT_LOSS_RUN = 1024                                 # GAPRO_POINT_LOSS_RUN: points of one workgroup
+POINT_LOSS_FOLD = 256                                 # GAPRO_POINT_LOSS_FOLD: records the finishing kernel folds in one pass
 
 
 class FitOptions(C.Structure):
@@ -281,6 +286,11 @@ SIGNATURES = {
     "gapro_match_loss_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                             _P, _P, _P, _P, _P, _P, _P, C.c_double, _P, C.c_size_t, _P, _P, _P, _P,
                                             _P]),
+    "gapro_point_loss_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
+    "gapro_point_loss_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P,
+                                           _P, _P, _P, _P, C.c_int64, C.c_double, _P, C.c_size_t, _P, _P, _P]),
+    "gapro_point_loss_backward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P,
+                                            _P, _P, _P, _P, C.c_int64, C.c_double, _P, C.c_size_t, _P, _P, _P, _P]),
     "gapro_lsap_solve": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _P, _P]),
     "gapro_schedule_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "gapro_schedule_free": (None, [_P]),

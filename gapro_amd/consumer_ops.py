@@ -900,3 +900,291 @@ def matched_losses(cls_logits, mask_logits, conf_logits, box_preds, prob_labels,
     losses = dict(zip(LOSS_NAMES, out.unbind(0)))  # one node between the dict and the function
     losses["kl_loss"] = torch.zeros((), dtype=torch.float32, device=dev)
     return losses
+
+
+# ---- the point-wise losses (gapro_amd/csrc/point_loss.hip) -----------------------------------------------
+POINT_LOSS_NAMES = ("pw_sem_loss", "pw_corners_loss", "pw_giou_loss", "pw_conf_loss")
+_class_weights = {}  # (device, the weights) -> f32[C] on the device
+
+
+def _is_number(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float))
+
+
+def _semantic_weight_arg(who, semantic_weight, n_classes, dev):
+    """``None``, a float32 tensor of shape [C] or a sequence of C numbers (what ``Criterion`` holds) -> ``None`` or the
+    tensor on ``dev``; a sequence is uploaded once per device and kept."""
+    if semantic_weight is None:
+        return None
+    if isinstance(semantic_weight, torch.Tensor):
+        if semantic_weight.dtype != torch.float32 or tuple(semantic_weight.shape) != (n_classes,):
+            raise ValueError("%s: semantic_weight must be a float32 tensor of shape [%d]" % (who, n_classes))
+        if semantic_weight.device != dev:
+            raise ValueError("%s: tensors on %s and on %s; one device is expected" % (who, dev, semantic_weight.device))
+        return semantic_weight.detach()
+    try:
+        vals = tuple(float(v) for v in semantic_weight)
+    except (TypeError, ValueError):
+        raise ValueError("%s: semantic_weight must be None, a float32 tensor or a sequence of numbers" % who) from None
+    if not vals:
+        return None  # the reference tests the list's truth
+    if len(vals) != n_classes:
+        raise ValueError("%s: %d semantic weights for %d classes" % (who, len(vals), n_classes))
+    key = (dev, vals)
+    if key not in _class_weights:
+        _class_weights[key] = torch.tensor(vals, dtype=torch.float32).to(dev)
+    return _class_weights[key]
+
+
+def _check_point_args(who, semantic_scores, corners_offset, box_conf, semantic_labels, instance_labels,
+                      corners_offset_labels, coords_float, ignore_label, voxel_scale):
+    """What is refused before a device is touched; returns N and C."""
+    if not isinstance(semantic_scores, torch.Tensor) or semantic_scores.dim() != 2 \
+            or semantic_scores.dtype != torch.float32:
+        raise ValueError("%s: semantic_scores must be a float32 tensor of shape [N, C]" % who)
+    N, n_classes = (int(v) for v in semantic_scores.shape)
+    if not _lib.POINT_LOSS_MIN_CLASSES <= n_classes <= _lib.POINT_LOSS_MAX_CLASSES:
+        raise ValueError("%s: %d classes; %d to %d are expected"
+                         % (who, n_classes, _lib.POINT_LOSS_MIN_CLASSES, _lib.POINT_LOSS_MAX_CLASSES))
+    if N > _lib.POINT_LOSS_MAX_POINTS:
+        raise ValueError("%s: %d points are beyond the library's bound of %d" % (who, N, _lib.POINT_LOSS_MAX_POINTS))
+    for name, t, width in (("corners_offset", corners_offset, 6), ("corners_offset_labels", corners_offset_labels, 6),
+                           ("coords_float", coords_float, 3)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (N, width):
+            raise ValueError("%s: %s must be a float32 tensor of shape [%d, %d]" % (who, name, N, width))
+    if not isinstance(box_conf, torch.Tensor) or box_conf.dtype != torch.float32 \
+            or tuple(box_conf.shape) not in ((N,), (N, 1)):
+        raise ValueError("%s: box_conf must be a float32 tensor of shape [%d] or [%d, 1]" % (who, N, N))
+    for name, t in (("semantic_labels", semantic_labels), ("instance_labels", instance_labels)):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != (N,):
+            raise ValueError("%s: %s must be an int32 or int64 tensor of shape [%d]" % (who, name, N))
+    if isinstance(ignore_label, bool) or not isinstance(ignore_label, int) or not -2 ** 63 <= ignore_label < 2 ** 63:
+        raise ValueError("%s: ignore_label must be an int" % who)
+    if not _is_number(voxel_scale) or voxel_scale != voxel_scale or abs(voxel_scale) == float("inf"):
+        raise ValueError("%s: voxel_scale must be a finite number" % who)
+    dev = semantic_scores.device
+    for t in (corners_offset, box_conf, semantic_labels, instance_labels, corners_offset_labels, coords_float):
+        if t.device != dev:
+            raise ValueError("%s: tensors on %s and on %s; one device is expected" % (who, dev, t.device))
+    return N, n_classes
+
+
+class _PointWiseLosses(torch.autograd.Function):
+    """The one autograd node of ``point_wise_losses``: ``f32[4]`` forward, one kernel backward."""
+
+    @staticmethod
+    def forward(fctx, plan, semantic_scores, corners_offset, box_conf):
+        who = "point_wise_losses"
+        ctx, stream = _ctx_stream(semantic_scores)
+        lib, dev = ctx.lib, semantic_scores.device
+        N, n_classes = (int(v) for v in semantic_scores.shape)
+        z = semantic_scores
+        if z.stride(1) != 1 or z.stride(0) < n_classes:
+            z = z.contiguous()
+        corners, conf = corners_offset.contiguous(), box_conf.contiguous()
+        sem, inst, labels, coords, weight = (None if plan[k] is None else plan[k].contiguous()
+                                             for k in ("sem", "inst", "labels", "coords", "weight"))
+        with torch.cuda.device(dev):
+            ws_bytes = int(lib.gapro_point_loss_workspace_bytes(N, n_classes))
+            if ws_bytes == 0:
+                raise ValueError("%s: %d points and %d classes are beyond the library's bounds" % (who, N, n_classes))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            out = torch.empty(_lib.POINT_LOSS_N, dtype=torch.float32, device=dev)
+            d_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, device=dev)
+            h_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, pin_memory=True) if plan["check"] else None
+            args = (N, n_classes, z.data_ptr(), int(z.stride(0)), sem.data_ptr(), _LABEL_CODES[sem.dtype],
+                    inst.data_ptr(), _LABEL_CODES[inst.dtype], corners.data_ptr(), conf.data_ptr(), labels.data_ptr(),
+                    coords.data_ptr(), weight.data_ptr() if weight is not None else None, plan["ignore_label"],
+                    plan["voxel_scale"], ws.data_ptr(), ws_bytes)
+            ctx.check(lib.gapro_point_loss_forward(ctx.handle, stream, *args, out.data_ptr(), d_status.data_ptr(),
+                                                   h_status.data_ptr() if h_status is not None else None))
+            if h_status is not None:
+                torch.cuda.current_stream(dev).synchronize()  # the call's one host read, asked for by check=True
+                status, bad = int(h_status[0]), int(h_status[1])
+                if status != 0:
+                    raise GaproError(status, "%s: point %d: a semantic label that is neither ignore_label nor in "
+                                             "[0, %d)" % (who, bad, n_classes))
+        fctx.save_for_backward(z, corners, conf)
+        fctx.held = (sem, inst, labels, coords, weight, ws, args)  # alive until the backward has run
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad_out):
+        z, corners, conf = fctx.saved_tensors
+        args = fctx.held[-1]
+        ctx, stream = _ctx_stream(z)
+        dev = z.device
+        need = fctx.needs_input_grad
+        grad_out = grad_out.to(dtype=torch.float32).contiguous()
+        g_z = torch.empty((args[0], args[1]), dtype=torch.float32, device=dev) if need[1] else None
+        g_corners = torch.empty_like(corners) if need[2] else None
+        g_conf = torch.empty_like(conf) if need[3] else None
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.gapro_point_loss_backward(ctx.handle, stream, *args, grad_out.data_ptr(), ptr(g_z),
+                                                        ptr(g_corners), ptr(g_conf)))
+        return None, g_z, g_corners, g_conf
+
+
+def point_wise_losses(semantic_scores, corners_offset, box_conf, semantic_labels, instance_labels,
+                      corners_offset_labels, coords_float, *, semantic_weight=None, ignore_label=-100, voxel_scale=50,
+                      check=True):
+    """The four point-wise losses of ``Criterion.cal_point_wise_loss`` (ISBNet/isbnet/model/criterion.py:136-191, called
+    at :357) over all N voxels of a batch, in its argument order: a dict with the reference's keys ``pw_sem_loss``,
+    ``pw_corners_loss``, ``pw_giou_loss``, ``pw_conf_loss`` (device scalars, selections of ONE ``f32[4]`` of one
+    autograd node).  Two kernels forward and no host read: the reference's six boolean-mask gathers and its
+    ``total_pos_inds == 0`` test are gone.  ``sum(w[k] * losses[k]).backward()`` runs one kernel, which reads the
+    upstream ``f32[4]`` on the device and writes whole gradients for ``semantic_scores``, ``corners_offset`` and
+    ``box_conf`` (zeros where a label is ignored).
+
+    ``semantic_scores`` is ``f32[N, C]`` with 2 <= C <= 64 (rows of any stride are read in place; other layouts are
+    copied), ``corners_offset`` and ``corners_offset_labels`` ``f32[N, 6]``, ``box_conf`` ``f32[N]`` or ``f32[N, 1]``,
+    the two label arrays int32 or int64 ``[N]`` (each its own type), ``coords_float`` ``f32[N, 3]``;
+    ``semantic_weight`` is ``None``, ``f32[C]`` or a sequence of C numbers.
+
+    Float64 from the float32 inputs, rounded once; no floating-point atomics, so two calls give equal
+    bytes.  When no instance label differs from ``ignore_label`` the last three losses are exactly 0 with zero gradients
+    (the reference's ``0 * corners_offset.sum()`` would be NaN for non-finite inputs); when every semantic label is
+    ignored ``pw_sem_loss`` is NaN and its gradient zero, as ``F.cross_entropy``.  ``N == 0`` returns that NaN and three
+    zeros without a launch.  Mismatched shapes, dtypes or devices, C outside its range, an ``ignore_label`` that is not
+    an int and a ``voxel_scale`` that is not finite are ``ValueError``s before a device is touched.  A semantic label
+    that is neither ``ignore_label`` nor in ``[0, C)`` is refused by the device: with ``check=True`` the status is read
+    behind the kernels (the call's one synchronisation) and a ``GaproError`` names the lowest such point; with
+    ``check=False`` the call only enqueues, the four losses are NaN and the backward writes zeros."""
+    who = "point_wise_losses"
+    N, n_classes = _check_point_args(who, semantic_scores, corners_offset, box_conf, semantic_labels, instance_labels,
+                                     corners_offset_labels, coords_float, ignore_label, voxel_scale)
+    dev = semantic_scores.device
+    weight = _semantic_weight_arg(who, semantic_weight, n_classes, dev)
+    if N == 0:
+        out = torch.tensor([float("nan"), 0.0, 0.0, 0.0], dtype=torch.float32).to(dev)
+        return dict(zip(POINT_LOSS_NAMES, out.unbind(0)))
+    if not semantic_scores.is_cuda:
+        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    plan = {"sem": semantic_labels, "inst": instance_labels, "labels": corners_offset_labels.detach(),
+            "coords": coords_float.detach(), "weight": weight, "ignore_label": int(ignore_label),
+            "voxel_scale": float(voxel_scale), "check": bool(check)}
+    out = _PointWiseLosses.apply(plan, semantic_scores, corners_offset, box_conf)
+    return dict(zip(POINT_LOSS_NAMES, out.unbind(0)))  # one node between the dict and the function
+
+
+# ---- the whole criterion (DESIGN.md 4.7): a composition, no kernel of its own ------------------------------------------
+LOSS_WEIGHT = {"dice_loss": 1, "bce_loss": 1, "cls_loss": 0.5, "iou_loss": 0.5, "box_loss": 0.5, "giou_loss": 0.5,
+               "levelset_loss": 0.5, "kl_loss": 0.1}  # Criterion.loss_weight (criterion.py:125-134)
+_BATCH_KEYS = ("semantic_labels", "instance_labels")
+_PW_BATCH_KEYS = ("coords_float", "corners_offset_labels")
+_PW_MODEL_KEYS = ("semantic_scores", "corners_offset", "box_conf")
+_MAIN_MODEL_KEYS = ("cls_logits", "mask_logits", "conf_logits", "box_preds", "dc_inst_mask_arr", "dc_prob_labels",
+                    "dc_batch_offsets", "dc_rgb_feats", "dc_coords_float", "dc_mu_labels", "dc_var_labels", "mu_pred",
+                    "logvar_pred")
+_empty_weights = {}  # (device, instance_classes, eos_coef, the semantic weights) -> Criterion.empty_weight
+
+
+def _empty_weight_of(dev, instance_classes, eos_coef, semantic_weight):
+    """``Criterion.__init__``'s ``empty_weight`` (criterion.py:107-111): ones, ``eos_coef`` last, and the semantic
+    weights shifted by ``label_shift = 1`` when given."""
+    key = (dev, instance_classes, eos_coef, semantic_weight)
+    if key not in _empty_weights:
+        w = torch.ones(instance_classes + 1, dtype=torch.float32)
+        w[-1] = eos_coef
+        if semantic_weight:
+            for i in range(1, instance_classes + 1):
+                w[i - 1] = semantic_weight[i]
+        _empty_weights[key] = w.to(dev)
+    return _empty_weights[key]
+
+
+def criterion_losses(batch_inputs, model_outputs, *, instance_classes=18, semantic_weight=None, ignore_label=-100,
+                     eos_coef=0.1, semantic_only=True, trainall=False, voxel_scale=50, loss_weight=None, dup_gt=4,
+                     check=True):
+    """What ``Criterion.forward`` (ISBNet/isbnet/model/criterion.py:333-465) means, with the constructor's arguments as
+    keywords: it reads the same keys of ``batch_inputs`` and ``model_outputs``, takes the same branches and returns the
+    same keys in the same insertion order.  (As released, ``forward`` passes ``cls_logits.shape[:1]`` as
+    ``batch_size`` and stops with a ``TypeError``; this is the call with the int.)
+
+    1. ``model_outputs is None``: ``{"Placeholder": 0}``, a leaf with ``requires_grad``.
+    2. ``semantic_only or trainall``: ``point_wise_losses``; with ``semantic_only`` they are returned here, unscaled.
+    3. Every key containing ``"pw"`` is multiplied by 0.25.
+    4. ``hungarian_match(..., dup_gt=dup_gt)``, then ``matched_losses`` with ``Criterion.empty_weight`` (ones,
+       ``eos_coef`` last, ``semantic_weight[i]`` at ``i - 1`` when given), each value times ``loss_weight`` (default
+       ``LOSS_WEIGHT``, the reference's eight values).
+    5. ``kl_loss = kl_to_gp_loss(mu_pred, logvar_pred, dc_mu_labels, dc_var_labels, weight=loss_weight["kl_loss"])``.
+
+    Pure composition: no kernel and no arithmetic rule of its own.  ``semantic_weight`` is ``None`` or a sequence of
+    numbers, one per semantic class.  ``dc_batch_offsets`` may be host integers or a tensor; a DEVICE tensor costs one
+    host read.  ``check=True`` adds the one status read of each of the two loss calls (``hungarian_match`` always has
+    one).  A missing key, a ``loss_weight`` without exactly the eight keys or with a value that is not finite, and an
+    ``instance_classes`` or ``dup_gt`` that is not a positive int are ``ValueError``s before a device is touched, as is
+    everything the composed calls refuse."""
+    who = "criterion_losses"
+    if not isinstance(batch_inputs, dict):
+        raise ValueError("%s: batch_inputs must be a dict" % who)
+    if model_outputs is not None and not isinstance(model_outputs, dict):
+        raise ValueError("%s: model_outputs must be a dict or None" % who)
+    if isinstance(instance_classes, bool) or not isinstance(instance_classes, int) or instance_classes < 1:
+        raise ValueError("%s: instance_classes must be a positive int" % who)
+    if isinstance(dup_gt, bool) or not isinstance(dup_gt, int) or dup_gt < 1:
+        raise ValueError("%s: dup_gt must be a positive int" % who)
+    if not _is_number(eos_coef) or eos_coef != eos_coef or abs(eos_coef) == float("inf"):
+        raise ValueError("%s: eos_coef must be a finite number" % who)
+    weights = dict(LOSS_WEIGHT) if loss_weight is None else loss_weight
+    if not isinstance(weights, dict) or list(weights) != list(LOSS_WEIGHT) \
+            or any(not _is_number(v) or v != v or abs(v) == float("inf") for v in weights.values()):
+        raise ValueError("%s: loss_weight must be a dict of finite numbers with the keys %s, in this order"
+                         % (who, ", ".join(LOSS_WEIGHT)))
+    if semantic_weight is not None:
+        try:
+            semantic_weight = tuple(float(v) for v in semantic_weight) or None
+        except (TypeError, ValueError):
+            raise ValueError("%s: semantic_weight must be None or a sequence of numbers" % who) from None
+    pointwise, main = bool(semantic_only or trainall), not semantic_only
+    need = [(batch_inputs, "batch_inputs", _BATCH_KEYS)]
+    if model_outputs is not None:
+        if pointwise:
+            need += [(batch_inputs, "batch_inputs", _PW_BATCH_KEYS), (model_outputs, "model_outputs", _PW_MODEL_KEYS)]
+        if main:
+            need.append((model_outputs, "model_outputs", _MAIN_MODEL_KEYS))
+    for d, name, keys in need:
+        for k in keys:
+            if k not in d:
+                raise ValueError("%s: %s lacks %r" % (who, name, k))
+    semantic_labels, instance_labels = batch_inputs["semantic_labels"], batch_inputs["instance_labels"]
+    if not isinstance(semantic_labels, torch.Tensor) or not isinstance(instance_labels, torch.Tensor):
+        raise ValueError("%s: semantic_labels and instance_labels must be tensors" % who)
+    if main and model_outputs is not None and semantic_weight is not None and len(semantic_weight) <= instance_classes:
+        raise ValueError("%s: %d semantic weights; empty_weight reads the entries 1 to %d"
+                         % (who, len(semantic_weight), instance_classes))
+    dev = semantic_labels.device
+    loss_dict = {}
+    if model_outputs is None:
+        loss_dict["Placeholder"] = torch.tensor(0.0, requires_grad=True, device=dev, dtype=torch.float32)
+        return loss_dict
+    if pointwise:
+        loss_dict.update(point_wise_losses(
+            model_outputs["semantic_scores"], model_outputs["corners_offset"], model_outputs["box_conf"],
+            semantic_labels, instance_labels, batch_inputs["corners_offset_labels"], batch_inputs["coords_float"],
+            semantic_weight=semantic_weight, ignore_label=ignore_label, voxel_scale=voxel_scale, check=check))
+        if semantic_only:
+            return loss_dict
+    for k in loss_dict:
+        if "pw" in k:
+            loss_dict[k] = loss_dict[k] * 0.25
+    cls_logits, mask_logits = model_outputs["cls_logits"], model_outputs["mask_logits"]
+    conf_logits, box_preds = model_outputs["conf_logits"], model_outputs["box_preds"]
+    gt_dict, _ = hungarian_match(cls_logits, mask_logits, conf_logits, box_preds, model_outputs["dc_inst_mask_arr"],
+                                 dup_gt=dup_gt)
+    offsets = model_outputs["dc_batch_offsets"]
+    if isinstance(offsets, torch.Tensor) and offsets.device.type != "cpu":
+        offsets = offsets.tolist()  # the one host read of a device tensor
+    main_losses = matched_losses(cls_logits, mask_logits, conf_logits, box_preds, model_outputs["dc_prob_labels"],
+                                 offsets, model_outputs["dc_rgb_feats"], model_outputs["dc_coords_float"], gt_dict,
+                                 empty_weight=_empty_weight_of(cls_logits.device, instance_classes, float(eos_coef),
+                                                               semantic_weight),
+                                 voxel_scale=voxel_scale, check=check)
+    for k, v in weights.items():
+        loss_dict[k] = main_losses[k] * v
+    loss_dict["kl_loss"] = kl_to_gp_loss(model_outputs["mu_pred"], model_outputs["logvar_pred"],
+                                         model_outputs["dc_mu_labels"], model_outputs["dc_var_labels"],
+                                         weight=weights["kl_loss"])
+    return loss_dict

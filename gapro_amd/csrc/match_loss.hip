@@ -123,45 +123,6 @@ __device__ inline bool inside(const BoxTest& bt, const float* __restrict__ c) { 
   return in;
 }
 
-// model_utils.py:277-306 for one pair in float64: 1 - GIoU, and with `grad` its derivative by the predicted box
-__device__ inline double giou_loss_of(const float* __restrict__ p, const float* __restrict__ g, double* grad) {
-  double iw[3], pw[3], bw[3];
-  double inter = 1.0, pv = 1.0, gv = 1.0, bound = 1.0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double a0 = p[k], a1 = p[k + 3], b0 = g[k], b1 = g[k + 3];
-    iw[k] = clamp0(nan_min(a1, b1) - nan_max(a0, b0));
-    pw[k] = clamp0(a1 - a0);
-    bw[k] = clamp0(nan_max(a1, b1) - nan_min(a0, b0));
-    inter *= iw[k];
-    pv *= pw[k];
-    gv *= clamp0(b1 - b0);
-    bound *= bw[k];
-  }
-  const double uni = gv + pv - inter;
-  const double giou = inter / (uni + 1e-6) - (bound - uni) / (bound + 1e-6);
-  if (grad) {
-    // d giou by inter, by the predicted volume and by the bounding volume (uni = gv + pv - inter)
-    const double d_uni = -inter / ((uni + 1e-6) * (uni + 1e-6)) + 1.0 / (bound + 1e-6);
-    const double g_inter = 1.0 / (uni + 1e-6) - d_uni, g_pv = d_uni;
-    const double g_bound = -(uni + 1e-6) / ((bound + 1e-6) * (bound + 1e-6));
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
-      const double a0 = p[k], a1 = p[k + 3], b0 = g[k], b1 = g[k + 3];
-      // torch: clamp(min=0) passes the gradient where its argument is >= 0; min / max share it at a tie
-      const double ci = (nan_min(a1, b1) - nan_max(a0, b0)) >= 0.0 ? g_inter * iw[k1] * iw[k2] : 0.0;
-      const double cp = (a1 - a0) >= 0.0 ? g_pv * pw[k1] * pw[k2] : 0.0;
-      const double cb = (nan_max(a1, b1) - nan_min(a0, b0)) >= 0.0 ? g_bound * bw[k1] * bw[k2] : 0.0;
-      const double up_a = a1 < b1 ? 1.0 : (a1 == b1 ? 0.5 : 0.0), lo_a = a0 > b0 ? 1.0 : (a0 == b0 ? 0.5 : 0.0);
-      const double ub_a = a1 > b1 ? 1.0 : (a1 == b1 ? 0.5 : 0.0), lb_a = a0 < b0 ? 1.0 : (a0 == b0 ? 0.5 : 0.0);
-      grad[k + 3] = -(ci * up_a + cp + cb * ub_a);
-      grad[k] = ci * lo_a + cp + cb * lb_a;
-    }
-  }
-  return 1.0 - giou;
-}
-
 struct Sig {
   double sig, e;
 };

@@ -1056,6 +1056,66 @@ int gapro_match_loss_backward(gapro_ctx* ctx, void* stream, int32_t batch_size, 
                               float* d_grad_cls_logits /* [B,Q,C] or NULL */, float* d_grad_mask_logits,
                               float* d_grad_conf_logits /* [B,Q] or NULL */, float* d_grad_box_preds /* [B,Q,6] or NULL */);
 
+/* ------------------------------------------------------------------------------------------
+ * Point-wise losses (csrc/point_loss.hip).  Replaces ISBNet's Criterion.cal_point_wise_loss
+ * (isbnet/model/criterion.py:136-191, called at :357): the four losses over all n_points voxels of a batch in two
+ * launches, their gradients in one, with no host read.  The rule continues the matched losses': float64 from the float32
+ * inputs, every sum a float64 sum in a fixed order, one rounding, no floating-point atomics.  With z = d_semantic_scores
+ * (f32[n_points, n_classes], row stride ld_scores), y = d_semantic_labels, W = d_semantic_weight (f32[n_classes]; NULL:
+ * ones), c = d_corners_offset and l = d_corners_offset_labels (f32[n_points, 6]), x = d_coords_float (f32[n_points, 3]),
+ * P = {i : d_instance_labels[i] != ignore_label}, n = |P|:
+ *   sem     = sum_{y_i != ignore} W[y_i] (lse_i - z[i, y_i]) / sum_{y_i != ignore} W[y_i], lse the max-shifted
+ *             log-sum-exp; NaN when every label is ignored, as F.cross_entropy                            (:154-156)
+ *   corners = (voxel_scale / 50) sum_P sum_k |c_ik - l_ik| / n                                            (:173-175, 187)
+ *   giou    = sum_P (1 - GIoU(a_i, b_i)) / n, a_i = c_i + [x_i, x_i], b_i = l_i + [x_i, x_i] (the reference forms a and b
+ *             in float32; here the add is float64 as everything else), the three clamps at 0 and the two + 1e-6 of
+ *             model_utils.py:416-444; min / max / clamp hand a NaN on                                     (:177-181)
+ *   conf    = sum_P (box_conf_i - IoU(a_i, b_i))^2 / n, no gradient through the IoU                       (:183-184)
+ * d_losses f32[GAPRO_POINT_LOSS_N] in this order.  With n == 0 the last three are exactly 0 and their gradients exactly
+ * zero; THE ONE DEVIATION: the reference's 0 * corners_offset.sum() is NaN for non-finite inputs, this call's 0 is not.
+ * An instance label is only compared with ignore_label.
+ * gapro_point_loss_backward: the exact derivatives of these expressions, weighted by d_grad_losses (f32[4], read on the
+ * device), in float64, rounded once, with the conventions of gapro_match_loss_backward: L1 with sign(0) = 0, a clamp
+ * passes at equality, min / max share a tie, softmax minus one-hot is expm1(z - lse) at the target; nothing overflows at
+ * |z| = 100.  A NULL gradient pointer is not written; the others are written whole by the kernel (no memset):
+ * d_grad_semantic_scores f32[n_points, n_classes] packed, a row zero where the label is ignored (so all zeros when every
+ * label is ignored, as torch's backward); d_grad_corners_offset f32[n_points, 6], the L1 plus the GIoU term, and
+ * d_grad_box_conf f32[n_points], both zero outside P.  It reads the workspace and the inputs as the forward call left
+ * them.
+ * Kernels: `partial`, ceil(n_points / GAPRO_POINT_LOSS_RUN) workgroups of 256 threads, one record each; `finish`, one
+ * workgroup, thread t folding the records t, t + GAPRO_POINT_LOSS_FOLD, ..; `backward` on `partial`'s grid.  Both calls
+ * only enqueue; the forward call copies d_status to h_status_pinned behind its kernels when given.
+ * d_status i32[GAPRO_MATCH_STATUS_WORDS] = {status, the lowest point of the refusal or -1, flags, 0}.  Refused by the
+ * device: flags & 1, a semantic label that is neither ignore_label nor in [0, n_classes): GAPRO_ERR_BAD_ARG, all four
+ * losses NaN, and the backward call writes zeros.  Refused before anything is launched (GAPRO_ERR_BAD_ARG): a null
+ * argument, n_points outside [1, 2^31 - 1], n_classes outside [GAPRO_POINT_LOSS_MIN_CLASSES,
+ * GAPRO_POINT_LOSS_MAX_CLASSES], ld_scores < n_classes, an unknown label type, a voxel_scale that is not finite;
+ * GAPRO_ERR_WORKSPACE: a workspace smaller than gapro_point_loss_workspace_bytes (0 for sizes the call refuses).
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_POINT_LOSS_N 4
+#define GAPRO_POINT_LOSS_MIN_CLASSES 2
+#define GAPRO_POINT_LOSS_MAX_CLASSES 64
+#define GAPRO_POINT_LOSS_RUN 1024   /* points of one workgroup of `partial` and `backward` */
+#define GAPRO_POINT_LOSS_FOLD 256   /* records `finish` folds in one pass */
+size_t gapro_point_loss_workspace_bytes(int64_t n_points, int32_t n_classes);
+int gapro_point_loss_forward(gapro_ctx* ctx, void* stream, int64_t n_points, int32_t n_classes,
+                             const float* d_semantic_scores, int64_t ld_scores, const void* d_semantic_labels,
+                             int32_t semantic_type, const void* d_instance_labels, int32_t instance_type,
+                             const float* d_corners_offset, const float* d_box_conf,
+                             const float* d_corners_offset_labels, const float* d_coords_float,
+                             const float* d_semantic_weight /* [C] or NULL */, int64_t ignore_label, double voxel_scale,
+                             void* d_workspace, size_t workspace_bytes, float* d_losses /* [4] */, int32_t* d_status,
+                             int32_t* h_status_pinned /* NULL: no copy */);
+int gapro_point_loss_backward(gapro_ctx* ctx, void* stream, int64_t n_points, int32_t n_classes,
+                              const float* d_semantic_scores, int64_t ld_scores, const void* d_semantic_labels,
+                              int32_t semantic_type, const void* d_instance_labels, int32_t instance_type,
+                              const float* d_corners_offset, const float* d_box_conf,
+                              const float* d_corners_offset_labels, const float* d_coords_float,
+                              const float* d_semantic_weight, int64_t ignore_label, double voxel_scale,
+                              const void* d_workspace, size_t workspace_bytes, const float* d_grad_losses /* [4] */,
+                              float* d_grad_semantic_scores /* [N,C] or NULL */,
+                              float* d_grad_corners_offset /* [N,6] or NULL */, float* d_grad_box_conf /* [N] or NULL */);
+
 /* Rectangular linear sum assignment on the host (csrc/lsap.cc; no device, no ctx): the scipy.optimize call of
  * matcher.py:201-204.  cost is f32[n_rows, n_cols] with row stride ld; dup >= 1 solves the problem whose column j, j in
  * [0, dup n_cols), is cost[:, j % n_cols] -- the reference's final_cost.repeat(1, dup_gt) without the repeated matrix.
