@@ -559,9 +559,10 @@ int gapro_point_refine_vote(gapro_ctx* ctx, void* stream_, int32_t n_scenes,
     if (t.n_spps <= 0 || !t.sem_spp || !t.inst_spp || !t.prob_spp || !t.mu_spp || !t.var_spp)
       return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_vote: scene %d: bad argument", i);
   }
+  // equal boxes: both labels of a segment would argue for one box, two candidates where rule 3 counts one
   for (int k = 0; k < n_models; ++k)
     if (h_models[k].scene < 0 || h_models[k].scene >= n_scenes || h_model_boxes[2 * k] < 0 ||
-        h_model_boxes[2 * k + 1] < 0)
+        h_model_boxes[2 * k + 1] < 0 || h_model_boxes[2 * k] == h_model_boxes[2 * k + 1])
       return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_point_refine_vote: model %d: scene %d, boxes %d, %d", k,
                         (int)h_models[k].scene, (int)h_model_boxes[2 * k], (int)h_model_boxes[2 * k + 1]);
   if (const char* why = check_blocks(n_blocks, h_blocks, n_segs, h_segs, n_rows, n_rows2, n_scenes, n_models))

@@ -733,6 +733,8 @@ int gapro_point_refine_compete(gapro_ctx* ctx, void* stream, int32_t n_scenes, c
  * h_block_spp i32[n_blocks]: the scene-local superpoint of every block, inside [0, scene.n_spps); no two blocks may
  * share one.  d_block_out i32[3 * n_blocks] (NULL = not wanted): the model of f*, X and the votes for X; -1, -1, 0 for
  * rule 5.  Block and segment rules, copies and refusals as for gapro_point_refine_expand; also refused: a negative box,
+ * a model whose two boxes are equal (both labels of its segments would argue for one box, two candidates where rule 3
+ * counts the voters of one label, and the means of rule 4 would be taken over more rows than they are divided by),
  * a block of more than 2048 segments (the candidates' counters live in LDS).  Only thread 0 of a workgroup writes, to
  * its own block's entries.  n_blocks == 0 or n_scenes == 0 is a no-op.  Enqueue only. */
 typedef struct {

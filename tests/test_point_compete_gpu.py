@@ -13,6 +13,8 @@ import sys
 import numpy as np
 import pytest
 
+from point_refine_cases import contract_reference as _contract_reference
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,15 +40,6 @@ def _same(got, want, what):
 
 
 # ---------------------------------------------------------------------------------------------- the kernels alone
-def _first_maximum(p):
-    """The rule of the issue for one row: best = 0.0f; for k in order: if best < p[k] (strict, float32) take k."""
-    best, took = np.float32(0), -1
-    for k, v in enumerate(p):
-        if best < np.float32(v):
-            best, took = np.float32(v), k
-    return took
-
-
 def _contract_case():
     """Two scenes, hand-made predict outputs.  Block sizes 1, 2, 63, 64, 65, 257, 1025 x segment counts 1, 2, 3, 8, the
     p_new patterns cycling over the blocks; models 16 (scene 0) and 17 (scene 1) have status -5."""
@@ -133,30 +126,6 @@ def _contract_case():
     return dict(spec=spec, blocks=np.array(blocks, np.int64), segs=np.array(segs, np.int64), R=R, R2=R2, pn=pn, lab=lab,
                 mu=mu, var=var, status=status, pairs=pairs, model_scene=model_scene, n_pts=n_pts, row_point=row_point,
                 failed=failed)
-
-
-def _contract_reference(c, start):
-    """NumPy: d_rows, and the five arrays of both scenes (from their `start` values) and row_model after compete."""
-    rows = np.full(c["R2"], -7, np.int32)
-    outs = [[a.copy() for a in sc] for sc in start]
-    row_model = np.full(c["R"], -1, np.int32)
-    for r0, n, si, s0, ns in c["blocks"]:
-        sg = c["segs"][s0:s0 + ns]
-        for o, _ in sg:
-            rows[o:o + n] = np.arange(r0, r0 + n)
-        live = [(o, m) for o, m in sg if c["status"][m] == 0]
-        for j in range(n):
-            k = _first_maximum([c["pn"][o + j] for o, _ in live])
-            i = c["row_point"][r0 + j]
-            if k < 0 or i < 0 or i >= c["n_pts"][si]:
-                continue
-            o, m = live[k]
-            second = c["lab"][o + j] != 0
-            sem, ins, prob, mu, var = outs[si]
-            sem[i], ins[i] = c["pairs"][m][2 if second else 0], c["pairs"][m][3 if second else 1]
-            prob[i], mu[i], var[i] = c["pn"][o + j], c["mu"][o + j], c["var"][o + j]
-            row_model[r0 + j] = m
-    return rows, outs, row_model
 
 
 def test_expand_and_compete_contract():

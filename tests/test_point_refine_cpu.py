@@ -207,3 +207,54 @@ def test_point_refine_abi():
     z = np.zeros(4, np.int32)
     assert lib.gapro_schedule_merge_ex(None, None, None, None, None, None, None, 0, 18, _p(z), _p(z), _p(z), _p(z), _p(z),
                                        _p(z)) == -1
+
+
+def test_vote_refuses_a_model_whose_two_boxes_are_equal():
+    """Equal boxes make both labels of a segment argue for one box: rule 3 of the vote keys a candidate by the voters of ONE
+    label while rule 4 sums mu / var over both, so the means would cover more rows than they are divided by.  The call
+    refuses such a model with GAPRO_ERR_BAD_ARG in its loop over the models, which runs before the block checks and
+    before the first copy or launch.  Without a device there is no context and the call returns before that loop, so the
+    return code alone proves nothing here: the order is read off the source, with tables that every other check of the
+    call accepts (tests/test_point_refine_edges_gpu.py holds the refusal with a context, the message and the untouched
+    tables)."""
+    import os
+    import re
+
+    import point_refine_cases as pc
+
+    c = pc.vote_edge_case()
+    boxes = c["boxes"].copy()
+    assert (boxes[:, 0] != boxes[:, 1]).all() and (boxes >= 0).all()
+    boxes[17, 1] = boxes[17, 0]
+    nb, ng, nm = len(c["blocks"]), len(c["segs"]), len(boxes)
+    # valid-looking scene and block arguments: the restated host checks pass, the superpoints are inside their scenes
+    assert pc.check_blocks(c["blocks"], c["segs"], c["R"], c["R2"], 2, nm) is None
+    assert (c["block_spp"] < np.asarray(c["n_spps"])[c["blocks"][:, 2]]).all() and c["blocks"][:, 4].max() <= 2048
+    blocks, segs, models = pc.block_table(c["blocks"]), pc.segment_table(c["segs"]), pc.model_table(c["pairs"], 0)
+    tabs = [np.zeros(max(c["n_spps"]), np.int32) for _ in range(5)]
+    scenes = (_lib.PointRefineVoteScene * 2)()
+    for q, s in zip(scenes, c["n_spps"]):
+        q.sem_spp, q.inst_spp, q.prob_spp, q.mu_spp, q.var_spp = (t.ctypes.data for t in tabs)
+        q.n_spps = s
+    lib = _lib.load()
+    sp = C.cast(scenes, C.c_void_p)
+    rows = [_p(c["pn"]), _p(c["lab"]), _p(c["mu"]), _p(c["var"])]
+    bspp = np.ascontiguousarray(c["block_spp"])
+    for bx in (boxes, c["boxes"]):
+        bx = np.ascontiguousarray(bx)
+        assert lib.gapro_point_refine_vote(None, None, 2, sp, sp, nm, _p(models), _p(models), _p(bx), _p(bx), nb, _p(blocks),
+                                           _p(blocks), _p(bspp), _p(bspp), ng, _p(segs), _p(segs), c["R"], c["R2"], *rows,
+                                           None, None) == -1
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "gapro_amd", "csrc", "point_refine.hip")) as f:
+        text = f.read()
+    body = text[text.index("int gapro_point_refine_vote("):]
+    test = body.index("h_model_boxes[2 * k] == h_model_boxes[2 * k + 1]")
+    loop = body.rindex("for (int k = 0; k < n_models; ++k)", 0, test)
+    fail = body.index("gapro_fail(ctx, GAPRO_ERR_BAD_ARG", test)
+    assert re.search(r'"gapro_point_refine_vote: model %d:', body[fail:fail + 200])  # the message names the model
+    assert loop < test < fail < body.index("check_blocks(") < body.index("hipMemcpyAsync") < body.index("hipLaunchKernelGGL")
+    assert body[loop:fail].count(";") == 2  # the loop header only: nothing between the test and the refusal
+    with open(os.path.join(root, "include", "gapro_hip.h")) as f:
+        header = " ".join(f.read().split())
+    assert "also refused: a negative box, * a model whose two boxes are equal" in header
