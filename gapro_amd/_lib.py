@@ -166,6 +166,39 @@ class SppGtHeader(C.Structure):
 SPP_GT_MAX_SAMPLES = 1024             # GAPRO_SPP_GT_MAX_SAMPLES: samples of one call
 SPP_GT_MAX_BATCH_SPPS = (1 << 31) - 1  # GAPRO_SPP_GT_MAX_BATCH_SPPS: batch_size * n_spps of one call
 SPP_GT_GRID_CAP = 512                 # GAPRO_SPP_GT_GRID_CAP: workgroups (of 256 threads) of a pass over the points
+class ProposalsInputs(C.Structure):
+    """gapro_proposals_inputs: the sizes and device pointers of one scene (a host struct, read when the call enqueues)."""
+    _fields_ = [("n_queries", C.c_int64), ("n_voxels", C.c_int64), ("n_points", C.c_int64), ("n_spps", C.c_int32),
+                ("n_mask_cols", C.c_int32), ("cls_logits", C.c_void_p), ("conf_logits", C.c_void_p),
+                ("box_preds", C.c_void_p), ("mask_logits", C.c_void_p), ("voxel_spps", C.c_void_p),
+                ("v2p_map", C.c_void_p), ("spps", C.c_void_p), ("semantic_preds", C.c_void_p),
+                ("cand_scores", C.c_void_p), ("cand_classes", C.c_void_p), ("mask_type", C.c_int32),
+                ("voxel_spps_i64", C.c_int32), ("v2p_i64", C.c_int32), ("spps_i64", C.c_int32),
+                ("semantic_i64", C.c_int32), ("reserved", C.c_int32)]
+
+
+PROPOSALS_MAX_PRE_TOPK, PROPOSALS_MAX_SEM2INS = 1024, 8
+PROPOSALS_FULL, PROPOSALS_NMS, PROPOSALS_RLE = 0, 1, 2
+PROPOSALS_NMS_MATRIX, PROPOSALS_NMS_STANDARD = 0, 1
+PROPOSALS_MASK_F32, PROPOSALS_MASK_U8 = 0, 1
+
+
+class ProposalsParams(C.Structure):
+    """gapro_proposals_params."""
+    _fields_ = [("mode", C.c_int32), ("instance_classes", C.c_int32), ("pre_topk", C.c_int32),
+                ("type_nms", C.c_int32), ("topk", C.c_int32), ("npoint_thresh", C.c_int32),
+                ("label_shift", C.c_int32), ("n_sem2ins", C.c_int32), ("logit_thresh", C.c_float),
+                ("final_score_thresh", C.c_float), ("nms_threshold", C.c_float), ("reserved", C.c_int32),
+                ("sem2ins_classes", C.c_int32 * PROPOSALS_MAX_SEM2INS)]
+
+
+class ProposalsHeader(C.Structure):
+    """gapro_proposals_header: what gapro_proposals_count reports; n_rows int32 run counts follow it."""
+    _fields_ = [("status", C.c_int32), ("flags", C.c_int32), ("n_rows", C.c_int32), ("n_sem2ins", C.c_int32),
+                ("total_runs", C.c_int64), ("n_candidates", C.c_int32), ("n_after_npoints", C.c_int32),
+                ("n_after_nms", C.c_int32), ("n_after_refine", C.c_int32)]
+
+
 SPP_GT_HALF, SPP_GT_STRICT = 0, 1     # the rule of gapro_spp_gt_fill: 2 c >= n, 2 c > n
 GAPRO_ERR_SPP_RANGE = -6
 GAPRO_EVAL_MAX_THRESHOLDS = 32
@@ -277,6 +310,11 @@ SIGNATURES = {
     "gapro_spp_gt_fill": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P,
                                     C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, C.c_int32, _P, C.c_size_t, _P,
                                     C.c_int64, _P, _P, _P, C.c_int64, _P]),
+    "gapro_proposals_workspace_bytes": (C.c_size_t, [_P, _P]),
+    "gapro_proposals_header_bytes": (C.c_size_t, [_P, _P]),
+    "gapro_proposals_count": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P]),
+    "gapro_proposals_fill": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64,
+                                       _P, _P]),
     "gapro_match_cost_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
     "gapro_match_cost": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                    C.c_size_t, _P, C.c_int64, _P, _P, _P]),
@@ -474,6 +512,7 @@ def load() -> C.CDLL:
                                             "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex",
                                             "gapro_schedule_export_testers", "gapro_spp_vote",
                                             "gapro_fit_launch_plan", "gapro_inst_", "gapro_spp_gt_", "gapro_match_",
+                                            "gapro_proposals_",
                                             "gapro_lsap_")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)

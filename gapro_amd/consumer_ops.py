@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1188,3 +1189,239 @@ def criterion_losses(batch_inputs, model_outputs, *, instance_classes=18, semant
                                          model_outputs["dc_mu_labels"], model_outputs["dc_var_labels"],
                                          weight=weights["kl_loss"])
     return loss_dict
+
+
+# ---- predicted instances: the inference post-processing (csrc/proposals.hip) ------------------------------------------
+_NMS_TYPES = {"matrix": _lib.PROPOSALS_NMS_MATRIX, "standard": _lib.PROPOSALS_NMS_STANDARD}
+_LABEL_SHIFTS = {"scannetv2": 1, "s3dis": 3}
+_PROPOSAL_CAUSES = ((1, "a non-finite cls_logits, conf_logits or score entry"),
+                    (2, "a non-finite mask_logits entry in the row of a candidate"),
+                    (4, "a v2p_map entry outside the voxels"),
+                    (8, "a voxel_spps entry outside the columns of mask_logits"),
+                    (16, "a superpoint id outside [0, n_spps)"))
+ProposalArrays = namedtuple("ProposalArrays", "conf label_id box query run_offsets runs masks header n_runs")
+
+
+def _index_arg(t, name, who, n=None):
+    """A 1-D integer device tensor as contiguous int32 / int64, and whether it is int64."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype not in _SPP_DTYPES:
+        raise ValueError("%s: %s must be a 1-D integer tensor" % (who, name))
+    if n is not None and int(t.shape[0]) != n:
+        raise ValueError("%s: %s has %d entries, expected %d" % (who, name, int(t.shape[0]), n))
+    if not t.is_cuda:
+        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    if t.dtype not in (torch.int32, torch.int64):
+        t = t.to(torch.int32)
+    return t.contiguous(), int(t.dtype == torch.int64)
+
+
+def _f32_arg(t, name, who, shape):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: %s must be a float32 tensor of shape %s" % (who, name, tuple(shape)))
+    if not t.is_cuda:
+        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    return t.contiguous()
+
+
+def _proposals_run(who, anchor, inputs, params, keep, n_points, want_masks=False, want_rows=True):
+    """gapro_proposals_count, the call's one host read of its header, gapro_proposals_fill.  ``keep`` holds the tensors
+    the structs point to.  Returns ProposalArrays of device tensors (``None`` where the mode has none)."""
+    ctx, stream = _ctx_stream(anchor)
+    lib, dev = ctx.lib, anchor.device
+    pin, ppar = C.byref(inputs), C.byref(params)
+    with torch.cuda.device(dev):
+        ws_bytes, hdr_bytes = int(lib.gapro_proposals_workspace_bytes(pin, ppar)), int(
+            lib.gapro_proposals_header_bytes(pin, ppar))
+        if ws_bytes == 0:
+            raise ValueError("%s: the sizes or parameters are beyond the library's bounds" % who)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        d_hdr = torch.empty(hdr_bytes, dtype=torch.uint8, device=dev)
+        h_hdr = torch.empty(hdr_bytes, dtype=torch.uint8, pin_memory=True)
+        ctx.check(lib.gapro_proposals_count(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, d_hdr.data_ptr(),
+                                            h_hdr.data_ptr()))
+        torch.cuda.current_stream(dev).synchronize()  # the call's one host read
+        raw = h_hdr.numpy().tobytes()
+        hdr = _lib.ProposalsHeader.from_buffer_copy(raw)
+        if hdr.status != 0:
+            why = next(text for bit, text in _PROPOSAL_CAUSES if hdr.flags & bit)
+            raise GaproError(hdr.status, "%s: %s" % (who, why))
+        rows, runs = int(hdr.n_rows), int(hdr.total_runs)
+        nms_only = params.mode == _lib.PROPOSALS_NMS
+        conf = torch.empty(rows, dtype=torch.float32, device=dev) if want_rows else None
+        label = torch.empty(rows, dtype=torch.int32, device=dev) if want_rows else None
+        box = torch.empty((rows, 6), dtype=torch.float32, device=dev) if want_rows else None
+        query = torch.empty(rows, dtype=torch.int32, device=dev) if want_rows else None
+        run_off = None if nms_only else torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+        d_runs = None if nms_only else torch.empty(2 * runs, dtype=torch.int64, device=dev)
+        masks = torch.empty((rows, n_points), dtype=torch.uint8, device=dev) if want_masks else None
+        if rows > 0:
+            ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None  # noqa: E731
+            ctx.check(lib.gapro_proposals_fill(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, ptr(conf),
+                                               ptr(label), ptr(box), ptr(query), rows, ptr(run_off), ptr(d_runs), runs,
+                                               ptr(masks), None))
+    del keep
+    n_runs = np.frombuffer(raw, dtype=np.int32, count=rows, offset=C.sizeof(_lib.ProposalsHeader))
+    return ProposalArrays(conf, label, box, query, run_off, d_runs, masks, hdr, n_runs)
+
+
+def _counts_of(run_off, runs):
+    """The rows' ``counts`` arrays (views of one host copy) from two host arrays."""
+    return [runs[2 * int(run_off[r]):2 * int(run_off[r + 1])] for r in range(len(run_off) - 1)]
+
+
+def get_instance(scan_id, cls_logits, mask_logits, conf_logits, box_preds, v2p_map, semantic_scores_preds, spps,
+                 logit_thresh=0.0, score_thresh=0.1, npoint_thresh=100, *, instance_classes, test_cfg=None,
+                 type_nms="matrix", topk=100, nms_threshold=0.2, sem2ins_classes=(), dataset_name="scannetv2",
+                 voxel_spps=None, n_spps=None, pre_topk=300, return_arrays=False, return_masks=False):
+    """``ISBNet.get_instance`` (ISBNet/isbnet/model/isbnet.py:887-1005) with the ``nms``, ``custom_scatter_mean``,
+    ``superpoint_align`` and ``rle_encode_gpu_batch`` it calls, as one chain of integer kernels (include/gapro_hip.h,
+    "Predicted instances"): the list of ``{"scan_id", "label_id", "conf", "pred_mask": {"length": N,
+    "counts": int64 array}}``, the ``sem2ins_classes`` rows first (``conf`` 1.0), then the kept proposals -- in
+    descending updated score for matrix NMS, in descending score for standard NMS; equal values in the order of the
+    flat index ``query * instance_classes + class``.  The reference leaves that order to ``torch.topk`` and an unstable
+    ``argsort``.
+
+    ``mask_logits`` is ``f32[Q, V]``, or ``f32[Q, S_v]`` with ``voxel_spps`` (``int[V]`` in ``[0, S_v)``): the form the
+    reference holds before isbnet.py:610 expands it, and the one to pass.  ``semantic_scores_preds`` (``int[V]``) is
+    read with ``sem2ins_classes`` only and may be ``None`` without.  ``score_thresh`` is accepted and unused, as in the
+    reference.  ``test_cfg`` (an object with ``type_nms``, ``topk``, ``nms_threshold``) overrides the three keywords.
+    ``n_spps=None`` costs a host read of ``spps.max()``.  ``return_arrays`` gives the device tensors (``ProposalArrays``;
+    ``masks`` u8[K, N] with ``return_masks``) instead of the list.  Non-finite logits a candidate reads and indices out
+    of range are a ``GaproError``; the reference's case of ``spps`` holding only ``ignore_label`` is not built."""
+    who = "get_instance"
+    if test_cfg is not None:
+        type_nms = getattr(test_cfg, "type_nms", type_nms)
+        topk = getattr(test_cfg, "topk", topk)
+        nms_threshold = getattr(test_cfg, "nms_threshold", nms_threshold)
+    if type_nms not in _NMS_TYPES:
+        raise RuntimeError("Invalid nms type")
+    if dataset_name not in _LABEL_SHIFTS:
+        raise Exception("Invalid dataset name")
+    C_ = int(instance_classes)
+    if not isinstance(cls_logits, torch.Tensor) or cls_logits.dim() != 2 or int(cls_logits.shape[1]) != C_ + 1:
+        raise ValueError("%s: cls_logits must be f32[Q, instance_classes + 1]" % who)
+    Q = int(cls_logits.shape[0])
+    if Q < 1 or C_ < 1:
+        raise ValueError("%s: no queries or no classes" % who)
+    if int(npoint_thresh) < 1:
+        raise ValueError("%s: npoint_thresh must be at least 1" % who)
+    if not 1 <= int(pre_topk) <= _lib.PROPOSALS_MAX_PRE_TOPK:
+        raise ValueError("%s: pre_topk must lie in [1, %d]" % (who, _lib.PROPOSALS_MAX_PRE_TOPK))
+    if int(topk) < -1:
+        raise ValueError("%s: topk must be -1 or a count" % who)
+    sem = [int(i) for i in sem2ins_classes]
+    if len(sem) > _lib.PROPOSALS_MAX_SEM2INS:
+        raise ValueError("%s: at most %d sem2ins classes" % (who, _lib.PROPOSALS_MAX_SEM2INS))
+    cls_logits = _f32_arg(cls_logits, "cls_logits", who, (Q, C_ + 1))
+    conf_logits = _f32_arg(conf_logits.reshape(-1) if isinstance(conf_logits, torch.Tensor) else conf_logits,
+                           "conf_logits", who, (Q,))
+    box_preds = _f32_arg(box_preds, "box_preds", who, (Q, 6))
+    v2p, v2p_i64 = _index_arg(v2p_map, "v2p_map", who)
+    N = int(v2p.shape[0])
+    sp, sp_i64 = _index_arg(spps, "spps", who, N)
+    if N < 1:
+        raise ValueError("%s: no points" % who)
+    if not isinstance(mask_logits, torch.Tensor) or mask_logits.dim() != 2 or int(mask_logits.shape[0]) != Q:
+        raise ValueError("%s: mask_logits must be f32[Q, columns]" % who)
+    cols = int(mask_logits.shape[1])
+    mask_logits = _f32_arg(mask_logits, "mask_logits", who, (Q, cols))
+    vs, vs_i64 = (None, 0) if voxel_spps is None else _index_arg(voxel_spps, "voxel_spps", who)
+    V = cols if vs is None else int(vs.shape[0])
+    if V < 1 or cols < 1:
+        raise ValueError("%s: no voxels" % who)
+    sm, sm_i64 = (None, 0)
+    if sem:
+        sm, sm_i64 = _index_arg(semantic_scores_preds, "semantic_scores_preds", who, V)
+    if n_spps is not None and (isinstance(n_spps, bool) or not isinstance(n_spps, int) or n_spps < 1):
+        raise ValueError("%s: n_spps must be a positive int" % who)
+    if n_spps is None:
+        n_spps = max(int(sp.max()) + 1, 1)  # a host read; a negative id is refused by the device below
+    inputs = _lib.ProposalsInputs(
+        n_queries=Q, n_voxels=V, n_points=N, n_spps=n_spps, n_mask_cols=0 if vs is None else cols,
+        cls_logits=cls_logits.data_ptr(), conf_logits=conf_logits.data_ptr(), box_preds=box_preds.data_ptr(),
+        mask_logits=mask_logits.data_ptr(), voxel_spps=None if vs is None else vs.data_ptr(), v2p_map=v2p.data_ptr(),
+        spps=sp.data_ptr(), semantic_preds=None if sm is None else sm.data_ptr(), mask_type=_lib.PROPOSALS_MASK_F32,
+        voxel_spps_i64=vs_i64, v2p_i64=v2p_i64, spps_i64=sp_i64, semantic_i64=sm_i64)
+    params = _lib.ProposalsParams(
+        mode=_lib.PROPOSALS_FULL, instance_classes=C_, pre_topk=int(pre_topk), type_nms=_NMS_TYPES[type_nms],
+        topk=int(topk), npoint_thresh=int(npoint_thresh), label_shift=_LABEL_SHIFTS[dataset_name], n_sem2ins=len(sem),
+        logit_thresh=float(logit_thresh), final_score_thresh=0.1, nms_threshold=float(nms_threshold))
+    for i, c in enumerate(sem):
+        params.sem2ins_classes[i] = c
+    out = _proposals_run(who, cls_logits, inputs, params, (cls_logits, conf_logits, box_preds, mask_logits, vs, v2p, sp,
+                                                           sm), N, want_masks=return_masks)
+    if return_arrays:
+        return out
+    rows = int(out.header.n_rows)
+    if rows == 0:
+        return []
+    small = torch.cat([out.conf.view(torch.int32).to(torch.int64), out.label_id.to(torch.int64), out.run_offsets])
+    small = small.cpu().numpy()  # the small arrays: one copy
+    runs = out.runs.cpu().numpy()  # the runs: the other
+    conf = small[:rows].astype(np.int32).view(np.float32)
+    label, run_off = small[rows:2 * rows], small[2 * rows:]
+    counts = _counts_of(run_off, runs)
+    n_sem = int(out.header.n_sem2ins)
+    return [{"scan_id": scan_id, "label_id": int(label[r]) if r < n_sem else label[r],
+             "conf": 1.0 if r < n_sem else conf[r], "pred_mask": {"length": N, "counts": counts[r]}}
+            for r in range(rows)]
+
+
+def mask_nms(proposals_pred, categories, scores, boxes, test_cfg):
+    """The reference's ``nms`` (ISBNet/isbnet/model/model_utils.py:163-169) for a caller that holds bool masks
+    ``[n, V]``: stages 3-4 of ``get_instance`` on the masks packed by the same kernel.  Returns the reference's 4-tuple
+    ``(masks, categories, scores, boxes)`` of the kept proposals in the order ``get_instance`` defines (matrix: descending
+    updated score; standard: descending score; equal values by row).  ``test_cfg`` has ``type_nms``, ``topk`` and
+    ``nms_threshold``.  At most 1024 proposals."""
+    who = "mask_nms"
+    type_nms = getattr(test_cfg, "type_nms", "matrix")
+    if type_nms not in _NMS_TYPES:
+        raise RuntimeError("Invalid nms type")
+    if not isinstance(proposals_pred, torch.Tensor) or proposals_pred.dim() != 2:
+        raise ValueError("%s: proposals_pred must be a [n, V] mask tensor" % who)
+    n, V = int(proposals_pred.shape[0]), int(proposals_pred.shape[1])
+    if n == 0:
+        return proposals_pred, categories, scores, boxes
+    if n > _lib.PROPOSALS_MAX_PRE_TOPK or V < 1:
+        raise ValueError("%s: %d proposals over %d voxels are beyond the library's bounds" % (who, n, V))
+    if not proposals_pred.is_cuda:
+        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    masks = (proposals_pred if proposals_pred.dtype in (torch.bool, torch.uint8) else proposals_pred != 0).contiguous()
+    sc = _f32_arg(scores, "scores", who, (n,))
+    cat = categories.to(torch.int32).contiguous()
+    if tuple(cat.shape) != (n,):
+        raise ValueError("%s: categories must have one entry a proposal" % who)
+    inputs = _lib.ProposalsInputs(n_queries=n, n_voxels=V, n_points=0, mask_logits=masks.data_ptr(),
+                                  cand_scores=sc.data_ptr(), cand_classes=cat.data_ptr(),
+                                  mask_type=_lib.PROPOSALS_MASK_U8)
+    params = _lib.ProposalsParams(mode=_lib.PROPOSALS_NMS, type_nms=_NMS_TYPES[type_nms],
+                                  topk=int(getattr(test_cfg, "topk", -1)), npoint_thresh=1, final_score_thresh=0.1,
+                                  nms_threshold=float(getattr(test_cfg, "nms_threshold", 0.2)))
+    out = _proposals_run(who, sc, inputs, params, (masks, sc, cat), 0)
+    idx = out.query.to(torch.int64)
+    return proposals_pred[idx], categories[idx], out.conf, boxes[idx]
+
+
+def rle_encode_gpu_batch(masks):
+    """``rle_encode_gpu_batch`` (ISBNet/isbnet/util/rle.py:47-69) without its loop: the list of ``{"length": N,
+    "counts": int64 array}`` of a device bool ``[K, N]``, from one read of the counts and one copy of the runs (a read
+    and a copy per 1032 rows beyond that many)."""
+    who = "rle_encode_gpu_batch"
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 2 or masks.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("%s: masks must be a bool [K, N] tensor" % who)
+    if not masks.is_cuda:
+        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    K, N = int(masks.shape[0]), int(masks.shape[1])
+    if N < 1:
+        raise ValueError("%s: no points" % who)
+    step, rles = _lib.PROPOSALS_MAX_PRE_TOPK + _lib.PROPOSALS_MAX_SEM2INS, []
+    for k0 in range(0, K, step):
+        part = masks[k0:k0 + step].contiguous()
+        inputs = _lib.ProposalsInputs(n_queries=int(part.shape[0]), n_voxels=0, n_points=N, mask_logits=part.data_ptr(),
+                                      mask_type=_lib.PROPOSALS_MASK_U8)
+        params = _lib.ProposalsParams(mode=_lib.PROPOSALS_RLE)
+        out = _proposals_run(who, part, inputs, params, (part,), N, want_rows=False)
+        offs = np.concatenate([[0], np.cumsum(out.n_runs, dtype=np.int64)])  # the counts came with the header
+        runs = out.runs.cpu().numpy()
+        rles += [{"length": N, "counts": c} for c in _counts_of(offs, runs)]
+    return rles

@@ -934,6 +934,142 @@ int gapro_spp_gt_fill(gapro_ctx* ctx, void* stream, int64_t n_points, int64_t n_
                       void* d_cls, float* d_box, int64_t* d_ids, int64_t n_rows, gapro_spp_gt_header* d_header);
 
 /* ------------------------------------------------------------------------------------------
+ * Predicted instances: the consumer's inference post-processing (csrc/proposals.hip).  Replaces ISBNet.get_instance
+ * (isbnet/model/isbnet.py:887-1005) with the nms it calls (model_utils.py:77-169), custom_scatter_mean (:600-613),
+ * superpoint_align (:447-470) and rle_encode_gpu_batch (isbnet/util/rle.py:47-69): float products of bit masks, a host
+ * loop per surviving proposal and a blocking copy per instance.  Two calls with one host read between them, as
+ * gapro_spp_gt_*: gapro_proposals_count runs stages 1-6 and counts the runs, the caller allocates, gapro_proposals_fill
+ * writes.  One scene a call.
+ * gapro_proposals_inputs (GAPRO_PROPOSALS_FULL; Q = n_queries, C = instance_classes, V = n_voxels, N = n_points):
+ *   cls_logits f32[Q, C + 1], conf_logits f32[Q], box_preds f32[Q, 6] (NULL: the boxes are zeros)
+ *   mask_logits     f32[Q, V] with n_mask_cols == 0, or f32[Q, n_mask_cols] with voxel_spps i32 / i64 [V] in
+ *                   [0, n_mask_cols): bit (q, v) reads column voxel_spps[v] (what the reference expands at isbnet.py:610)
+ *   v2p_map         i32 / i64 [N] in [0, V);  spps i32 / i64 [N] in [0, n_spps)
+ *   semantic_preds  i32 / i64 [V], with n_sem2ins > 0 only
+ *   the *_i64 members say which of the two integer types a pointer has
+ * Stages.  Every floating-point term is evaluated in float64 from the float32 inputs and rounded to float32 once, where
+ * the stage says so; everything else is integer.
+ *   1 scores      score[q, c] = float32(sqrt(softmax(cls_logits[q, :])[c] * clamp(conf[q], 0, 1))), c < C; the softmax is
+ *                 exp(x - max) over the sum of these terms in ascending c.  The candidates are the min(pre_topk, Q C)
+ *                 largest by float32 value, descending; equal values by ascending flat index q C + c (this tie rule is
+ *                 the library's own: the reference's torch.topk has none).
+ *   2 mask bits   bit (q, v) = mask_logits >= logit_thresh, a float32 comparison; 64-bit words along v (the ballot of a
+ *                 wavefront that loaded 64 consecutive values), the bits beyond V zero; npoints[q] = the row's popcount.
+ *                 A candidate stays if npoints >= npoint_thresh; the order is kept.
+ *   3 inter       inter[a, b] = sum_w popcount(A_w & B_w), exact, no atomics; iou = float32(inter) / float32(n_a + n_b -
+ *                 inter), one float32 division.  For V < 2^24 this is the reference's float32 einsum and division to the
+ *                 bit; beyond, the integer form is the definition.
+ *   4 nms         MATRIX: d_ij = iou_ij for i < j of one class, else 0; c_i = max_k d_ki; coef_j = min_i exp(-2 d_ij^2) /
+ *                 exp(-2 c_i^2); new_j = float32(score_j coef_j), float64 inside.  Kept: the min(topk, n) largest new
+ *                 (ties: the earlier sorted position), or with topk == -1 those with new >= final_score_thresh (float32);
+ *                 written in descending new, ties by position.  STANDARD: the reference's greedy loop: a kept pivot
+ *                 removes every later candidate of its class with iou > nms_threshold (float32, the stage-3 value);
+ *                 scores and order unchanged.  One workgroup, a suppressed bitmap in LDS, no host.
+ *   5 refine      c(k, s) = points p with spps[p] == s whose voxel v2p_map[p] has bit k; n(s) = points of s;
+ *                 m(k, p) = [2 c(k, spps[p]) >= n(spps[p])] -- the GAPRO_SPP_GT_HALF rule, equal to the reference's
+ *                 float32 scatter_mean >= 0.5 by the proof given there.  A row stays if sum_p m(k, p) >= npoint_thresh.
+ *   6 sem2ins     for each i of sem2ins_classes a row whose voxel bits are semantic_preds[v] == i, through stage 5's rule,
+ *                 with no NMS and no point count.  These rows come first: conf 1.0, label_id i + 1, query -1, a zero box.
+ *                 The reference's case "every spps entry is ignore_label" is not built: such ids are refused.
+ *   7 runs        per row the transitions of m(k, .) with a zero before and after: 1-based starts, each followed by its
+ *                 length, int64: the `counts` of rle_encode_gpu_batch, byte for byte.
+ * label_id of an ordinary row = class + label_shift (1 for scannetv2, 3 for s3dis).
+ * GAPRO_PROPOSALS_NMS: stages 3-4 alone for a caller that holds masks (the reference's `nms`): mask_logits is u8[Q, V]
+ * (GAPRO_PROPOSALS_MASK_U8, bit = non-zero) or f32[Q, V], Q <= GAPRO_PROPOSALS_MAX_PRE_TOPK; cand_scores f32[Q] and
+ * cand_classes i32[Q] replace stage 1: every row is a candidate, sorted by (score descending, row ascending); no
+ * npoints filter; an empty union has iou 0.  The rows out name their masks by `query`; no runs.
+ * GAPRO_PROPOSALS_RLE: stage 7 alone: mask_logits is u8[Q, N], Q <= GAPRO_PROPOSALS_MAX_PRE_TOPK +
+ * GAPRO_PROPOSALS_MAX_SEM2INS; every row is kept.
+ * gapro_proposals_count writes d_header (and its page-locked host copy when h_header_pinned is given): the struct below
+ * followed by int32 n_runs of every row out; gapro_proposals_header_bytes(...) in all, sized for the most rows the call
+ * can give (pre_topk, or topk where matrix NMS cuts to it, plus n_sem2ins).  gapro_proposals_fill reads what the count left in the workspace -- same inputs, nothing in between -- and
+ * writes (NULL = not wanted)
+ *   d_conf f32[n_rows], d_label_id i32[n_rows], d_box f32[n_rows, 6] (bit copies of box_preds), d_query i32[n_rows]
+ *   d_run_offsets i64[n_rows + 1] in runs; d_runs i64[2 total_runs]: row r owns d_runs[2 off[r], 2 off[r + 1])
+ *   d_masks u8[n_rows, N]: m(k, .), on request
+ * cap_rows / cap_runs are the lengths the caller allocated; smaller ones than the header's: GAPRO_ERR_WORKSPACE in
+ * d_header->status (when given), nothing written.
+ * Refusals of the data, header.status of gapro_proposals_count; flags names every cause met.  In this order of
+ * precedence:
+ *   GAPRO_ERR_NOT_FINITE  flags & 1: a non-finite cls_logits or conf_logits entry (every score takes part in stage 1), or
+ *                         cand_scores entry
+ *   GAPRO_ERR_NOT_FINITE  flags & 2: a non-finite mask_logits entry read for the row of a stage-1 candidate
+ *   GAPRO_ERR_BAD_ARG     flags & 4: a v2p_map entry outside [0, V)
+ *   GAPRO_ERR_BAD_ARG     flags & 8: a voxel_spps entry outside [0, n_mask_cols)
+ *   GAPRO_ERR_SPP_RANGE   flags & 16: a spps id outside [0, n_spps)
+ * With a non-zero status n_rows is 0 and gapro_proposals_fill writes nothing.  Refused before anything is launched
+ * (GAPRO_ERR_BAD_ARG): a null or non-positive argument, npoint_thresh < 1, pre_topk outside [1,
+ * GAPRO_PROPOSALS_MAX_PRE_TOPK], Q C > 2^20, V or N > 2^31 - 1, an unknown mode, NMS type or mask type, topk < -1,
+ * n_sem2ins outside [0, GAPRO_PROPOSALS_MAX_SEM2INS], a threshold that is not finite, (pre_topk + n_sem2ins) n_spps >
+ * 2^31 - 1; GAPRO_ERR_WORKSPACE: a workspace smaller than gapro_proposals_workspace_bytes (0 for sizes the calls
+ * refuse).  The two structs are host memory, read while the call enqueues.  Both calls only enqueue: a scene costs one
+ * host read.  Integer atomics only, so the results are the same bits for every run.  The passes over the scores, voxels,
+ * points and pairs run at most GAPRO_PROPOSALS_GRID_CAP workgroups of 256 threads; the passes per row (stages 5 and 7)
+ * at most 1024 workgroups a row, one per chunk of at least 1024 points.
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_PROPOSALS_MAX_PRE_TOPK 1024
+#define GAPRO_PROPOSALS_MAX_SEM2INS 8
+#define GAPRO_PROPOSALS_GRID_CAP 2048
+enum { GAPRO_PROPOSALS_FULL = 0, GAPRO_PROPOSALS_NMS = 1, GAPRO_PROPOSALS_RLE = 2 };
+enum { GAPRO_PROPOSALS_NMS_MATRIX = 0, GAPRO_PROPOSALS_NMS_STANDARD = 1 };
+enum { GAPRO_PROPOSALS_MASK_F32 = 0, GAPRO_PROPOSALS_MASK_U8 = 1 };
+typedef struct {
+  int64_t n_queries, n_voxels, n_points;
+  int32_t n_spps;
+  int32_t n_mask_cols;      /* 0: mask_logits has a column per voxel */
+  const float* cls_logits;
+  const float* conf_logits;
+  const float* box_preds;
+  const void* mask_logits;
+  const void* voxel_spps;
+  const void* v2p_map;
+  const void* spps;
+  const void* semantic_preds;
+  const float* cand_scores;     /* GAPRO_PROPOSALS_NMS */
+  const int32_t* cand_classes;  /* GAPRO_PROPOSALS_NMS */
+  int32_t mask_type;
+  int32_t voxel_spps_i64, v2p_i64, spps_i64, semantic_i64;
+  int32_t reserved;
+} gapro_proposals_inputs; /* 136 bytes */
+typedef struct {
+  int32_t mode;
+  int32_t instance_classes;
+  int32_t pre_topk;         /* 300 in the reference */
+  int32_t type_nms;
+  int32_t topk;             /* -1: none */
+  int32_t npoint_thresh;
+  int32_t label_shift;
+  int32_t n_sem2ins;
+  float logit_thresh;
+  float final_score_thresh; /* 0.1 in the reference */
+  float nms_threshold;
+  int32_t reserved;
+  int32_t sem2ins_classes[GAPRO_PROPOSALS_MAX_SEM2INS];
+} gapro_proposals_params; /* 80 bytes */
+typedef struct {
+  int32_t status;
+  int32_t flags;            /* 1: score input, 2: mask value, 4: v2p_map, 8: voxel_spps, 16: spps */
+  int32_t n_rows;
+  int32_t n_sem2ins;        /* the first rows */
+  int64_t total_runs;
+  int32_t n_candidates;     /* after stage 1 */
+  int32_t n_after_npoints;  /* after stage 2 */
+  int32_t n_after_nms;      /* after stage 4 */
+  int32_t n_after_refine;   /* after stage 5 */
+} gapro_proposals_header; /* 40 bytes; n_rows x int32_t n_runs follow */
+#define GAPRO_PROPOSALS_HEADER_BYTES(max_rows) (40 + 4 * (size_t)(max_rows))
+
+size_t gapro_proposals_workspace_bytes(const gapro_proposals_inputs* in, const gapro_proposals_params* params);
+size_t gapro_proposals_header_bytes(const gapro_proposals_inputs* in, const gapro_proposals_params* params);
+int gapro_proposals_count(gapro_ctx* ctx, void* stream, const gapro_proposals_inputs* in,
+                          const gapro_proposals_params* params, void* d_workspace, size_t workspace_bytes,
+                          gapro_proposals_header* d_header, gapro_proposals_header* h_header_pinned);
+int gapro_proposals_fill(gapro_ctx* ctx, void* stream, const gapro_proposals_inputs* in,
+                         const gapro_proposals_params* params, void* d_workspace, size_t workspace_bytes, float* d_conf,
+                         int32_t* d_label_id, float* d_box, int32_t* d_query, int64_t cap_rows, int64_t* d_run_offsets,
+                         int64_t* d_runs, int64_t cap_runs, uint8_t* d_masks, gapro_proposals_header* d_header);
+
+/* ------------------------------------------------------------------------------------------
  * Cost matrices of the consumer's Hungarian matcher (csrc/match_cost.hip).  Replaces the per-sample expression chain of
  * ISBNet's HungarianMatcher.get_match (isbnet/model/matcher.py:144-199): one call enqueues the cost matrices of every
  * sample of a batch.  Sample b has n_queries queries, n_inst kept instances, n_cols columns (superpoints or subsampled
