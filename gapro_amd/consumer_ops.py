@@ -15,11 +15,147 @@ from . import _lib
 from ._lib import Context, GaproError
 
 
-def _ctx_stream(t):
-    if not t.is_cuda:
+# ---- the argument vocabulary: what every family refuses "before a device is touched", said once ---------------------
+# A family raises its ValueErrors first and the RuntimeError for host tensors (_need_device) once they have passed.
+_F32, _INT = (torch.float32,), (torch.int32, torch.int64)
+_KINDS = {_F32: "a float32", _INT: "an int32 or int64"}
+_INDEX_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
+
+
+def _need_device(*tensors):
+    """The module's one refusal of host tensors; ``None`` stands for an argument that was not given."""
+    if not all(t is None or t.is_cuda for t in tensors):
         raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+
+
+def _tensor_arg(who, name, t, shape, dtypes=_F32, nonempty=False, text=None):
+    """``t`` must be a tensor of one of ``dtypes`` and of ``shape``, in which a str names a dimension of any size
+    (``(N, "F")`` reads ``[5, F]`` in the message; ``text`` words the shape otherwise)."""
+    ok = isinstance(t, torch.Tensor) and t.dtype in dtypes
+    if ok:
+        have = t.shape
+        if have != shape:  # the wrong shape, or a named dimension (a plain loop: these checks run per sample and step)
+            ok = len(have) == len(shape)
+            for h, want in zip(have, shape):
+                ok = ok and (h == want or want.__class__ is str)
+        ok = ok and not (nonempty and 0 in have)
+    if not ok:
+        raise ValueError("%s: %s must be %s tensor of shape %s"
+                         % (who, name, "a non-empty float32" if nonempty else _KINDS[dtypes],
+                            text or "[%s]" % ", ".join(str(v) for v in shape)))
+
+
+def _one_device(who, dev, tensors):
+    for t in tensors:
+        if t.device != dev:
+            raise ValueError("%s: tensors on %s and on %s; one device is expected" % (who, dev, t.device))
+
+
+def _is_int(v, types=int):
+    return isinstance(v, types) and not isinstance(v, bool)
+
+
+def _is_finite(v):
+    return _is_int(v, (int, float)) and v == v and abs(v) != float("inf")
+
+
+def _finite_arg(who, name, v):
+    if not _is_finite(v):
+        raise ValueError("%s: %s must be a finite number" % (who, name))
+
+
+def _positive_int_arg(who, name, v, types=int):
+    if not _is_int(v, types) or v < 1:
+        raise ValueError("%s: %s must be a positive int" % (who, name))
+
+
+def _index_check(who, name, t):
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype not in _INDEX_DTYPES:
+        raise ValueError("%s: %s must be a 1-D integer tensor" % (who, name))
+
+
+def _as_index(t):
+    """An integer tensor as the kernels read it: contiguous int32 / int64, and whether it is int64."""
+    if t.dtype not in _INT:
+        t = t.to(torch.int32)
+    return t.contiguous(), int(t.dtype == torch.int64)
+
+
+def _index_arg(t, name, who, n=None):
+    """A 1-D integer device tensor as contiguous int32 / int64, and whether it is int64."""
+    _index_check(who, name, t)
+    if n is not None and int(t.shape[0]) != n:
+        raise ValueError("%s: %s has %d entries, expected %d" % (who, name, int(t.shape[0]), n))
+    _need_device(t)
+    return _as_index(t)
+
+
+def _n_spps_arg(who, n_spps, spps):
+    """The bound of the superpoint ids: the caller's positive int, or ``max(spps) + 1`` of the device tensor."""
+    if n_spps is not None:
+        _positive_int_arg(who, "n_spps", n_spps)
+    _need_device(spps)
+    if n_spps is None:
+        n_spps = max(int(spps.max()) + 1, 1)  # a host read; a negative id is refused by the device below
+    return n_spps
+
+
+def _ptr(t):
+    """The address of a tensor for the C ABI; NULL for one that is absent or empty."""
+    return t.data_ptr() if t is not None and t.numel() > 0 else None
+
+
+def _row_contiguous(x):
+    """A 2-D tensor whose rows the kernels can read in place (unit column stride, rows of any stride), else a copy."""
+    return x if x.stride(1) == 1 and x.stride(0) >= x.shape[1] else x.contiguous()
+
+
+def _ctx_stream(t):
+    _need_device(t)
     ctx = Context.get(t.device.index or 0)
     return ctx, C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+# ---- the launch scaffold: workspace, status / header pair, the call's one host read ----------------------------------
+def _workspace(who, nbytes, dev, beyond=None):
+    """The bytes the library asked for as a device tensor.  0 bytes is the library's word for sizes beyond its bounds:
+    a family that has such bounds names the sizes in ``beyond``."""
+    if nbytes == 0 and beyond:
+        raise ValueError("%s: %s beyond the library's bounds" % (who, beyond))
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _status_pair(dev, count, dtype=torch.uint8, read=True):
+    """A status / header buffer on the device and its page-locked twin (``None`` for a call that will not read it)."""
+    return (torch.empty(count, dtype=dtype, device=dev),
+            torch.empty(count, dtype=dtype, pin_memory=True) if read else None)
+
+
+def _host_read(dev, h_buf, header=None):
+    """The call's one host read: synchronise the current stream, then decode the page-locked buffer as the ``header``
+    struct and the raw bytes behind it, or as status words."""
+    torch.cuda.current_stream(dev).synchronize()
+    if header is None:
+        return h_buf.tolist()
+    raw = h_buf.numpy().tobytes()
+    return header.from_buffer_copy(raw), raw
+
+
+def _refuse(who, status, flags, causes):
+    """A non-zero status as the ``GaproError`` of the first cause whose bit is set."""
+    if status != 0:
+        raise GaproError(status, "%s: %s" % (who, next(text for bit, text in causes if flags & bit)))
+
+
+_constants = {}  # (device, the values) -> the float32 tensor on the device
+
+
+def _device_constant(dev, values):
+    """A tuple of numbers as a float32 tensor on ``dev``: uploaded once per device and kept."""
+    key = (dev, values)
+    if key not in _constants:
+        _constants[key] = torch.tensor(values, dtype=torch.float32).to(dev)
+    return _constants[key]
 
 
 def pool_labels_to_superpoints(prob_labels, mu_labels, var_labels, spps, n_out=None):
@@ -140,9 +276,7 @@ def _label_code(t, what):
 
 def _check_info_args(coords_float, instance_labels, semantic_labels, who):
     """What is refused before a device is touched."""
-    if not isinstance(coords_float, torch.Tensor) or coords_float.dim() != 2 or coords_float.shape[1] != 3 \
-            or coords_float.dtype != torch.float32:
-        raise ValueError("%s: coords_float must be a float32 tensor of shape [V, 3]" % who)
+    _tensor_arg(who, "coords_float", coords_float, ("V", 3))
     _label_code(instance_labels, who + ": instance_labels")
     _label_code(semantic_labels, who + ": semantic_labels")
     v = int(coords_float.shape[0])
@@ -151,8 +285,7 @@ def _check_info_args(coords_float, instance_labels, semantic_labels, who):
                          % (who, v, int(instance_labels.shape[0]), int(semantic_labels.shape[0])))
     if v == 0:
         raise ValueError("%s: no points" % who)
-    if not (coords_float.is_cuda and instance_labels.is_cuda and semantic_labels.is_cuda):
-        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    _need_device(coords_float, instance_labels, semantic_labels)
 
 
 def _refusal(who, hdr):
@@ -180,10 +313,9 @@ def _inst_prep(who, labels, coords=None, sem=None, label_shift=0, crop=True):
     cap = ID_TABLE
     with torch.cuda.device(dev):
         while True:
-            ws_bytes = int(lib.gapro_inst_prep_workspace_bytes(cap))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            d_hdr = torch.empty(C.sizeof(_lib.InstPrepHeader), dtype=torch.uint8, device=dev)
-            h_hdr = torch.empty(C.sizeof(_lib.InstPrepHeader), dtype=torch.uint8, pin_memory=True)
+            ws = _workspace(who, int(lib.gapro_inst_prep_workspace_bytes(cap)), dev)
+            ws_bytes = ws.numel()
+            d_hdr, h_hdr = _status_pair(dev, C.sizeof(_lib.InstPrepHeader))
             outs = None
             if info:
                 outs = (torch.empty(cap, dtype=torch.int64, device=dev),
@@ -198,8 +330,7 @@ def _inst_prep(who, labels, coords=None, sem=None, label_shift=0, crop=True):
             else:
                 ctx.check(lib.gapro_inst_crop(ctx.handle, stream, n, labels.data_ptr(), _LABEL_CODES[labels.dtype], cap,
                                               ws.data_ptr(), ws_bytes, d_hdr.data_ptr(), h_hdr.data_ptr()))
-            torch.cuda.current_stream(dev).synchronize()  # the call's one host read
-            hdr = _lib.InstPrepHeader.from_buffer_copy(h_hdr.numpy().tobytes())
+            hdr, _ = _host_read(dev, h_hdr, _lib.InstPrepHeader)
             if hdr.status == _lib.GAPRO_ERR_WORKSPACE and cap <= hdr.max_id < _lib.INST_PREP_MAX_IDS:
                 cap = hdr.max_id + 1
                 continue
@@ -250,7 +381,6 @@ def prepare_instance_labels(coords_float, instance_labels, semantic_labels, labe
 
 
 # ---- ground-truth instance masks per sample (gapro_amd/csrc/spp_gt.hip) ----------------------------------
-_SPP_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
 _GT_CAUSES = ((1, "batch offsets that decrease or leave [0, n_points]"),
               (2, "a subsample index outside the labels"),
               (4, "an instance label that is not ignore_label and is negative, at or beyond len(instance_cls), or no "
@@ -279,7 +409,7 @@ def _check_gt_args(who, instance_labels, instance_cls, instance_box, batch_size)
     """What both functions refuse before a device is touched; returns the label and class codes."""
     code = _label_code(instance_labels, who + ": instance_labels")
     cls_code = _label_code(instance_cls, who + ": instance_cls")
-    if isinstance(batch_size, bool) or not isinstance(batch_size, int):
+    if not _is_int(batch_size):
         raise ValueError("%s: batch_size must be an int" % who)
     if not 1 <= batch_size <= _lib.SPP_GT_MAX_SAMPLES:
         raise ValueError("%s: batch_size %d outside [1, %d]" % (who, batch_size, _lib.SPP_GT_MAX_SAMPLES))
@@ -297,43 +427,27 @@ def _check_gt_args(who, instance_labels, instance_cls, instance_box, batch_size)
 
 def _gt_run(who, labels, gather, spps, n_spps, cls, box, offsets, batch_size, ignore_label, rule, return_ids):
     """gapro_spp_gt_count, the call's one host read of its header, gapro_spp_gt_fill; the per-sample views."""
-    if not (labels.is_cuda and cls.is_cuda and box.is_cuda and (gather is None or gather.is_cuda)
-            and (spps is None or spps.is_cuda)):
-        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    _need_device(labels, cls, box, gather, spps)
     ctx, stream = _ctx_stream(labels)
     lib, dev = ctx.lib, labels.device
     labels, cls, box = labels.contiguous(), cls.contiguous(), box.contiguous()
     off = offsets.to(device=dev, dtype=torch.int64).contiguous()
     if gather is not None:
         gather = gather.to(dtype=torch.int64).contiguous()
-    spp_i64 = 0
-    if spps is not None:
-        if spps.dtype not in (torch.int32, torch.int64):
-            spps = spps.to(torch.int32)
-        spps = spps.contiguous()
-        spp_i64 = int(spps.dtype == torch.int64)
+    spps, spp_i64 = (None, 0) if spps is None else _as_index(spps)
     n = int(gather.shape[0]) if gather is not None else int(labels.shape[0])
     n_cls = int(cls.shape[0])
-    hdr_bytes = C.sizeof(_lib.SppGtHeader) + 8 * batch_size
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.gapro_spp_gt_workspace_bytes(n, batch_size, n_cls, n_spps))
-        if ws_bytes == 0:
-            raise ValueError("%s: %d points, batch_size %d and %d superpoint ids are beyond the library's bounds"
-                             % (who, n, batch_size, n_spps))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        d_hdr = torch.empty(hdr_bytes, dtype=torch.uint8, device=dev)
-        h_hdr = torch.empty(hdr_bytes, dtype=torch.uint8, pin_memory=True)
-        common = (n, int(labels.shape[0]), labels.data_ptr(), _LABEL_CODES[labels.dtype],
-                  gather.data_ptr() if gather is not None else None, spps.data_ptr() if spps is not None else None,
+        ws = _workspace(who, int(lib.gapro_spp_gt_workspace_bytes(n, batch_size, n_cls, n_spps)), dev,
+                        "%d points, batch_size %d and %d superpoint ids are" % (n, batch_size, n_spps))
+        ws_bytes = ws.numel()
+        d_hdr, h_hdr = _status_pair(dev, C.sizeof(_lib.SppGtHeader) + 8 * batch_size)
+        common = (n, int(labels.shape[0]), labels.data_ptr(), _LABEL_CODES[labels.dtype], _ptr(gather), _ptr(spps),
                   spp_i64, n_spps, cls.data_ptr(), _LABEL_CODES[cls.dtype], n_cls)
         ctx.check(lib.gapro_spp_gt_count(ctx.handle, stream, *common, off.data_ptr(), batch_size, int(ignore_label),
                                          ws.data_ptr(), ws_bytes, d_hdr.data_ptr(), h_hdr.data_ptr()))
-        torch.cuda.current_stream(dev).synchronize()  # the call's one host read
-        raw = h_hdr.numpy().tobytes()
-        hdr = _lib.SppGtHeader.from_buffer_copy(raw)
-        if hdr.status != 0:
-            why = next(text for bit, text in _GT_CAUSES if hdr.flags & bit)
-            raise GaproError(hdr.status, "%s: sample %d: %s" % (who, hdr.bad_sample, why))
+        hdr, raw = _host_read(dev, h_hdr, _lib.SppGtHeader)
+        _refuse("%s: sample %d" % (who, hdr.bad_sample), hdr.status, hdr.flags, _GT_CAUSES)
         counts = (C.c_int32 * (2 * batch_size)).from_buffer_copy(raw, C.sizeof(_lib.SppGtHeader))
         if hdr.total_rows == 0:
             return [None] * batch_size
@@ -344,8 +458,7 @@ def _gt_run(who, labels, gather, spps, n_spps, cls, box, offsets, batch_size, ig
         out_ids = torch.empty(rows, dtype=torch.int64, device=dev) if return_ids else None
         ctx.check(lib.gapro_spp_gt_fill(ctx.handle, stream, *common, box.data_ptr(), off.data_ptr(), batch_size,
                                         int(ignore_label), rule, ws.data_ptr(), ws_bytes, mask.data_ptr(), cells,
-                                        out_cls.data_ptr(), out_box.data_ptr(),
-                                        out_ids.data_ptr() if return_ids else None, rows, None))
+                                        out_cls.data_ptr(), out_box.data_ptr(), _ptr(out_ids), rows, None))
     out, r0, c0 = [], 0, 0
     for b in range(batch_size):
         ni, ns = int(counts[2 * b]), int(counts[2 * b + 1])
@@ -386,17 +499,11 @@ def get_spp_gt(instance_labels, spps, instance_cls, instance_box, batch_offsets,
         raise ValueError("get_spp_gt: pool=False makes every point its own column, which is get_subsample_gt (with "
                          "subsample_idxs = arange): call get_subsample_gt")
     _check_gt_args(who, instance_labels, instance_cls, instance_box, batch_size)
-    if not isinstance(spps, torch.Tensor) or spps.dim() != 1 or spps.dtype not in _SPP_DTYPES:
-        raise ValueError("%s: spps must be a 1-D integer tensor" % who)
+    _index_check(who, "spps", spps)
     if int(spps.shape[0]) != int(instance_labels.shape[0]):
         raise ValueError("%s: %d labels, %d superpoint ids" % (who, int(instance_labels.shape[0]), int(spps.shape[0])))
     off = _offsets_arg(batch_offsets, batch_size, who)
-    if n_spps is not None and (isinstance(n_spps, bool) or not isinstance(n_spps, int) or n_spps < 1):
-        raise ValueError("%s: n_spps must be a positive int" % who)
-    if not spps.is_cuda:
-        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
-    if n_spps is None:
-        n_spps = max(int(spps.max()) + 1, 1)  # a host read; a negative id is refused by the device below
+    n_spps = _n_spps_arg(who, n_spps, spps)
     return _gt_run(who, instance_labels, None, spps, n_spps, instance_cls, instance_box, off, batch_size, ignore_label,
                    _lib.SPP_GT_STRICT if strict else _lib.SPP_GT_HALF, return_ids)
 
@@ -408,9 +515,7 @@ def get_subsample_gt(instance_labels, subsample_idxs, instance_cls, instance_box
     ``[subsample_batch_offsets[b], subsample_batch_offsets[b + 1])``.  Same return, refusals and single host read."""
     who = "get_subsample_gt"
     _check_gt_args(who, instance_labels, instance_cls, instance_box, batch_size)
-    if not isinstance(subsample_idxs, torch.Tensor) or subsample_idxs.dim() != 1 \
-            or subsample_idxs.dtype not in _SPP_DTYPES:
-        raise ValueError("%s: subsample_idxs must be a 1-D integer tensor" % who)
+    _index_check(who, "subsample_idxs", subsample_idxs)
     if int(subsample_idxs.shape[0]) == 0:
         raise ValueError("%s: no points" % who)
     off = _offsets_arg(subsample_batch_offsets, batch_size, who)
@@ -435,57 +540,63 @@ def _weights_arg(weights, who):
                          % who) from None
     if len(vals) != 5 or (isinstance(weights, dict) and len(weights) != 5):
         raise ValueError("%s: weights must be five numbers (class, dice, bce, conf, giou) or a dict with these keys" % who)
-    if any(v != v or v < 0.0 or v == float("inf") for v in vals):
+    if any(not _is_finite(v) or v < 0.0 for v in vals):
         raise ValueError("%s: a weight is negative or not finite" % who)
     return _lib.MatchWeights(*vals)
 
 
-def _check_match_args(who, cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mask_arr):
-    """What is refused before a device is touched; returns the samples that have instances and the class dtype."""
-    if not isinstance(cls_logits, torch.Tensor) or cls_logits.dim() != 3 or cls_logits.dtype != torch.float32 \
-            or 0 in cls_logits.shape:
-        raise ValueError("%s: cls_logits must be a non-empty float32 tensor of shape [B, Q, C]" % who)
-    B, Q, _ = (int(v) for v in cls_logits.shape)
-    dev = cls_logits.device
-    if not isinstance(conf_logits, torch.Tensor) or conf_logits.dtype != torch.float32 \
-            or tuple(conf_logits.shape) != (B, Q):
-        raise ValueError("%s: conf_logits must be a float32 tensor of shape [%d, %d]" % (who, B, Q))
-    if not isinstance(box_preds, torch.Tensor) or box_preds.dtype != torch.float32 \
-            or tuple(box_preds.shape) != (B, Q, 6):
-        raise ValueError("%s: box_preds must be a float32 tensor of shape [%d, %d, 6]" % (who, B, Q))
+def _heads_arg(who, cls_logits, conf_logits, box_preds, **lists):
+    """The prediction heads the matcher and the matched losses take, and the per-sample ``lists`` beside them; returns
+    B, Q and C."""
+    _tensor_arg(who, "cls_logits", cls_logits, ("B", "Q", "C"), nonempty=True)
+    B, Q, n_classes = (int(v) for v in cls_logits.shape)
+    _tensor_arg(who, "conf_logits", conf_logits, (B, Q))
+    _tensor_arg(who, "box_preds", box_preds, (B, Q, 6))
     if B > _lib.SPP_GT_MAX_SAMPLES:
         raise ValueError("%s: batch size %d beyond %d" % (who, B, _lib.SPP_GT_MAX_SAMPLES))
-    for name, seq in (("mask_logits", mask_logits), ("dc_inst_mask_arr", dc_inst_mask_arr)):
+    for name, seq in lists.items():
         if not isinstance(seq, (list, tuple)) or len(seq) != B:
             raise ValueError("%s: %s must be a list of %d entries, one per sample" % (who, name, B))
+    return B, Q, n_classes
+
+
+def _sample_labels_arg(who, cls_name, cls, box_name, box, n, cls_dtype):
+    """A sample's class and box labels, ``n`` rows each, the classes of the dtype of every earlier sample's."""
+    _tensor_arg(who, cls_name, cls, (n,), _INT)
+    if cls_dtype not in (None, cls.dtype):
+        raise ValueError("%s: %s is %s, an earlier sample's %s" % (who, cls_name, cls.dtype, cls_dtype))
+    _tensor_arg(who, box_name, box, (n, 6))
+    return cls.dtype
+
+
+def _sample_logits_arg(who, x, Q, n_cols, column):
+    """A sample's mask logits: one row per query and one column per ``column``."""
+    _tensor_arg(who, "mask_logits", x, ("Q", "S"))
+    if x.shape != (Q, n_cols) or n_cols == 0:
+        raise ValueError("%s: mask_logits is %s, [%d, %d] is expected: one row per query and one column per %s"
+                         % (who, tuple(x.shape), Q, n_cols, column))
+
+
+def _check_match_args(who, cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mask_arr):
+    """What is refused before a device is touched; returns the samples that have instances and the class dtype."""
+    _, Q, _ = _heads_arg(who, cls_logits, conf_logits, box_preds, mask_logits=mask_logits,
+                         dc_inst_mask_arr=dc_inst_mask_arr)
     tensors = [conf_logits, box_preds]
     kept, cls_dtype = [], None
     for b, entry in enumerate(dc_inst_mask_arr):
         if entry is None:
             continue
+        who_b = "%s: sample %d" % (who, b)
         if not isinstance(entry, dict) or any(not isinstance(entry.get(k), torch.Tensor) for k in ("mask", "cls", "box")):
-            raise ValueError("%s: sample %d: a dict with the tensors mask, cls and box, or None, is expected" % (who, b))
+            raise ValueError("%s: a dict with the tensors mask, cls and box, or None, is expected" % who_b)
         mask, cls, box, x = entry["mask"], entry["cls"], entry["box"], mask_logits[b]
-        if mask.dim() != 2 or mask.dtype != torch.float32 or 0 in mask.shape:
-            raise ValueError("%s: sample %d: mask must be a non-empty float32 tensor of shape [I, S]" % (who, b))
+        _tensor_arg(who_b, "mask", mask, ("I", "S"), nonempty=True)
         n_inst, n_cols = (int(v) for v in mask.shape)
-        if cls.dtype not in (torch.int32, torch.int64) or tuple(cls.shape) != (n_inst,):
-            raise ValueError("%s: sample %d: cls must be an int32 or int64 tensor of shape [%d]" % (who, b, n_inst))
-        if cls_dtype not in (None, cls.dtype):
-            raise ValueError("%s: sample %d: cls is %s, an earlier sample's %s" % (who, b, cls.dtype, cls_dtype))
-        cls_dtype = cls.dtype
-        if box.dtype != torch.float32 or tuple(box.shape) != (n_inst, 6):
-            raise ValueError("%s: sample %d: box must be a float32 tensor of shape [%d, 6]" % (who, b, n_inst))
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
-            raise ValueError("%s: sample %d: mask_logits must be a float32 tensor of shape [Q, S]" % (who, b))
-        if int(x.shape[0]) != Q or int(x.shape[1]) != n_cols:
-            raise ValueError("%s: sample %d: mask_logits is %s, [%d, %d] is expected: one row per query and one column "
-                             "per column of the mask" % (who, b, tuple(x.shape), Q, n_cols))
+        cls_dtype = _sample_labels_arg(who_b, "cls", cls, "box", box, n_inst, cls_dtype)
+        _sample_logits_arg(who_b, x, Q, n_cols, "column of the mask")
         tensors += [mask, cls, box, x]
         kept.append(b)
-    for t in tensors:
-        if t.device != dev:
-            raise ValueError("%s: tensors on %s and on %s; one device is expected" % (who, dev, t.device))
+    _one_device(who, cls_logits.device, tensors)
     return kept, cls_dtype
 
 
@@ -499,9 +610,7 @@ def _match_run(who, cls_logits, mask_logits, conf_logits, box_preds, entries, ke
     tasks = (_lib.MatchTask * B)()
     keep, offsets, total, total_inst, total_cols = [], {}, 0, 0, 0
     for b in kept:
-        e, x = entries[b], mask_logits[b]
-        if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
-            x = x.contiguous()
+        e, x = entries[b], _row_contiguous(mask_logits[b])
         mask, cls, box = e["mask"].contiguous(), e["cls"].contiguous(), e["box"].contiguous()
         keep += [x, mask, cls, box]  # alive until the call has been enqueued and synchronised
         n_inst, n_cols = (int(v) for v in mask.shape)
@@ -512,26 +621,18 @@ def _match_run(who, cls_logits, mask_logits, conf_logits, box_preds, entries, ke
         total_inst += n_inst
         total_cols += n_cols
     with torch.cuda.device(dev):
-        ws_bytes = int(lib.gapro_match_cost_workspace_bytes(B, Q, total_inst, total_cols))
-        if ws_bytes == 0:
-            raise ValueError("%s: %d samples, %d queries and %d instances are beyond the library's bounds"
-                             % (who, B, Q, total_inst))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = _workspace(who, int(lib.gapro_match_cost_workspace_bytes(B, Q, total_inst, total_cols)), dev,
+                        "%d samples, %d queries and %d instances are" % (B, Q, total_inst))
         cost = torch.empty(total, dtype=torch.float32, device=dev)
-        d_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, device=dev)
-        h_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, pin_memory=True)
+        d_status, h_status = _status_pair(dev, _lib.MATCH_STATUS_WORDS, torch.int32)
         h_cost = torch.empty(total, dtype=torch.float32, pin_memory=True) if pinned else None
         ctx.check(lib.gapro_match_cost(ctx.handle, stream, C.cast(tasks, C.c_void_p), B, Q, n_classes,
                                        _LABEL_CODES[cls_dtype], cls_logits.data_ptr(), conf_logits.data_ptr(),
                                        box_preds.data_ptr(), C.byref(weights) if weights is not None else None,
-                                       ws.data_ptr(), ws_bytes, cost.data_ptr(), total,
-                                       h_cost.data_ptr() if pinned else None, d_status.data_ptr(),
-                                       h_status.data_ptr()))
-        torch.cuda.current_stream(dev).synchronize()  # the call's one host read
-    status, bad, flags = (int(v) for v in h_status[:3])
-    if status != 0:
-        why = next(text for bit, text in _MATCH_CAUSES if flags & bit)
-        raise GaproError(status, "%s: sample %d: %s" % (who, bad, why))
+                                       ws.data_ptr(), ws.numel(), cost.data_ptr(), total, _ptr(h_cost),
+                                       d_status.data_ptr(), h_status.data_ptr()))
+        status, bad, flags = _host_read(dev, h_status)[:3]
+    _refuse("%s: sample %d" % (who, bad), status, flags, _MATCH_CAUSES)
     views = [None] * B
     host = [None] * B
     for b, (off, n_inst) in offsets.items():
@@ -569,13 +670,10 @@ def linear_sum_assignment(cost, dup=1):
     ``(rows, cols)`` as int64 arrays, rows ascending.  ``dup > 1`` solves ``np.tile(cost, (1, dup))`` without building
     it and returns the ORIGINAL column ``j % cost.shape[1]`` of every pair.  Among equal-cost optima the choice is the
     solver's own (include/gapro_hip.h) and the same for every run.  A non-finite entry is a ``GaproError``."""
-    import numpy as np
-
     who = "linear_sum_assignment"
     if not isinstance(cost, np.ndarray) or cost.ndim != 2 or cost.dtype != np.float32:
         raise ValueError("%s: a two-dimensional float32 NumPy array is expected" % who)
-    if isinstance(dup, bool) or not isinstance(dup, (int, np.integer)) or dup < 1:
-        raise ValueError("%s: dup must be a positive int" % who)
+    _positive_int_arg(who, "dup", dup, (int, np.integer))
     n_rows, n_cols = cost.shape
     if n_rows == 0 or n_cols == 0:
         raise ValueError("%s: an empty matrix" % who)
@@ -624,12 +722,9 @@ def hungarian_match(cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mas
     result does not depend on their number), and one upload carries all matched columns to the gathers.  A batch of
     ``None``s returns without a launch.  Among equal-cost optima the assignment is the solver's own, not necessarily
     SciPy's."""
-    import numpy as np
-
     who = "hungarian_match"
     kept, cls_dtype = _check_match_args(who, cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mask_arr)
-    if isinstance(dup_gt, bool) or not isinstance(dup_gt, int) or dup_gt < 1:
-        raise ValueError("%s: dup_gt must be a positive int" % who)
+    _positive_int_arg(who, "dup_gt", dup_gt)
     B = len(dc_inst_mask_arr)
     gt, aux = ({k: [None] * B for k in _GT_KEYS} for _ in range(2))
     if not kept:
@@ -659,62 +754,27 @@ def hungarian_match(cls_logits, mask_logits, conf_logits, box_preds, dc_inst_mas
 
 # ---- the matched losses (gapro_amd/csrc/match_loss.hip) -------------------------------------------------
 LOSS_NAMES = ("dice_loss", "bce_loss", "cls_loss", "iou_loss", "box_loss", "giou_loss", "levelset_loss")
-_default_weights = {}  # (device, C) -> ones with the last entry 0.1
-
-
-def _default_empty_weight(dev, n_classes):
-    key = (dev, n_classes)
-    if key not in _default_weights:
-        w = torch.ones(n_classes, dtype=torch.float32)
-        w[-1] = 0.1
-        _default_weights[key] = w.to(dev)
-    return _default_weights[key]
 
 
 def _check_loss_args(who, cls_logits, mask_logits, conf_logits, box_preds, prob_labels, batch_offsets, levelset_feats,
                      levelset_coords, gt_dict, empty_weight, voxel_scale):
     """What is refused before a device is touched; returns the kept samples, their host row indices (int32 NumPy), the
     offsets as ints and the class dtype."""
-    import numpy as np
-
-    if not isinstance(cls_logits, torch.Tensor) or cls_logits.dim() != 3 or cls_logits.dtype != torch.float32 \
-            or 0 in cls_logits.shape:
-        raise ValueError("%s: cls_logits must be a non-empty float32 tensor of shape [B, Q, C]" % who)
-    B, Q, n_classes = (int(v) for v in cls_logits.shape)
-    dev = cls_logits.device
-    if not isinstance(conf_logits, torch.Tensor) or conf_logits.dtype != torch.float32 \
-            or tuple(conf_logits.shape) != (B, Q):
-        raise ValueError("%s: conf_logits must be a float32 tensor of shape [%d, %d]" % (who, B, Q))
-    if not isinstance(box_preds, torch.Tensor) or box_preds.dtype != torch.float32 \
-            or tuple(box_preds.shape) != (B, Q, 6):
-        raise ValueError("%s: box_preds must be a float32 tensor of shape [%d, %d, 6]" % (who, B, Q))
-    if B > _lib.SPP_GT_MAX_SAMPLES:
-        raise ValueError("%s: batch size %d beyond %d" % (who, B, _lib.SPP_GT_MAX_SAMPLES))
-    if not isinstance(mask_logits, (list, tuple)) or len(mask_logits) != B:
-        raise ValueError("%s: mask_logits must be a list of %d entries, one per sample" % (who, B))
+    B, Q, n_classes = _heads_arg(who, cls_logits, conf_logits, box_preds, mask_logits=mask_logits)
     if not isinstance(gt_dict, dict) or any(not isinstance(gt_dict.get(k), (list, tuple)) or len(gt_dict[k]) != B
                                             for k in _GT_KEYS):
         raise ValueError("%s: gt_dict must hold the lists %s of %d entries, as hungarian_match returns them"
                          % (who, ", ".join(_GT_KEYS), B))
-    if not isinstance(prob_labels, torch.Tensor) or prob_labels.dim() != 1 or prob_labels.dtype != torch.float32 \
-            or int(prob_labels.shape[0]) == 0:
-        raise ValueError("%s: prob_labels must be a non-empty float32 tensor of shape [N]" % who)
+    _tensor_arg(who, "prob_labels", prob_labels, ("N",), nonempty=True)
     N = int(prob_labels.shape[0])
-    if not isinstance(levelset_feats, torch.Tensor) or levelset_feats.dim() != 2 \
-            or levelset_feats.dtype != torch.float32 or int(levelset_feats.shape[0]) != N:
-        raise ValueError("%s: levelset_feats must be a float32 tensor of shape [%d, F]" % (who, N))
+    _tensor_arg(who, "levelset_feats", levelset_feats, (N, "F"))
     if not 1 <= int(levelset_feats.shape[1]) <= _lib.MATCH_LOSS_MAX_FEATS:
         raise ValueError("%s: %d level-set features; 1 to %d are expected"
                          % (who, int(levelset_feats.shape[1]), _lib.MATCH_LOSS_MAX_FEATS))
-    if not isinstance(levelset_coords, torch.Tensor) or levelset_coords.dtype != torch.float32 \
-            or tuple(levelset_coords.shape) != (N, 3):
-        raise ValueError("%s: levelset_coords must be a float32 tensor of shape [%d, 3]" % (who, N))
-    if empty_weight is not None and (not isinstance(empty_weight, torch.Tensor) or empty_weight.dtype != torch.float32
-                                     or tuple(empty_weight.shape) != (n_classes,)):
-        raise ValueError("%s: empty_weight must be a float32 tensor of shape [%d]" % (who, n_classes))
-    if isinstance(voxel_scale, bool) or not isinstance(voxel_scale, (int, float)) \
-            or voxel_scale != voxel_scale or abs(voxel_scale) == float("inf"):
-        raise ValueError("%s: voxel_scale must be a finite number" % who)
+    _tensor_arg(who, "levelset_coords", levelset_coords, (N, 3))
+    if empty_weight is not None:
+        _tensor_arg(who, "empty_weight", empty_weight, (n_classes,))
+    _finite_arg(who, "voxel_scale", voxel_scale)
     if isinstance(batch_offsets, torch.Tensor):
         if batch_offsets.device.type != "cpu":
             raise ValueError("%s: batch_offsets must be on the host (a sequence, a NumPy array or a CPU tensor)" % who)
@@ -737,43 +797,29 @@ def _check_loss_args(who, cls_logits, mask_logits, conf_logits, box_preds, prob_
         x, rows = mask_logits[b], gt_dict["row_indices"][b]
         if x is None or rows is None:
             continue
+        who_b = "%s: sample %d" % (who, b)
         if isinstance(rows, torch.Tensor):
             if rows.device.type != "cpu":
-                raise ValueError("%s: sample %d: row_indices must be on the host (NumPy or a CPU tensor)" % (who, b))
+                raise ValueError("%s: row_indices must be on the host (NumPy or a CPU tensor)" % who_b)
             rows = rows.numpy()
         if not isinstance(rows, np.ndarray) or rows.ndim != 1 or rows.dtype.kind not in "iu":
-            raise ValueError("%s: sample %d: row_indices must be a 1-D integer NumPy array or CPU tensor" % (who, b))
+            raise ValueError("%s: row_indices must be a 1-D integer NumPy array or CPU tensor" % who_b)
         n_gt = int(rows.shape[0])
         if n_gt == 0:
-            raise ValueError("%s: sample %d: row_indices is empty; a sample without a match is None" % (who, b))
+            raise ValueError("%s: row_indices is empty; a sample without a match is None" % who_b)
         if int(rows.min()) < 0 or int(rows.max()) >= Q:
-            raise ValueError("%s: sample %d: a row index outside [0, %d)" % (who, b, Q))
+            raise ValueError("%s: a row index outside [0, %d)" % (who_b, Q))
         if len(np.unique(rows)) != n_gt:
-            raise ValueError("%s: sample %d: a row index is listed twice" % (who, b))
-        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
-            raise ValueError("%s: sample %d: mask_logits must be a float32 tensor of shape [Q, S]" % (who, b))
+            raise ValueError("%s: a row index is listed twice" % who_b)
         n_cols = off[b + 1] - off[b]
-        if int(x.shape[0]) != Q or int(x.shape[1]) != n_cols or n_cols == 0:
-            raise ValueError("%s: sample %d: mask_logits is %s, [%d, %d] is expected: one row per query and one column "
-                             "per point of batch_offsets, at least one" % (who, b, tuple(x.shape), Q, n_cols))
+        _sample_logits_arg(who_b, x, Q, n_cols, "point of batch_offsets, at least one")
         inst, cls, box = (gt_dict[k][b] for k in ("inst_labels", "cls_labels", "box_labels"))
-        if not isinstance(inst, torch.Tensor) or inst.dtype != torch.float32 or tuple(inst.shape) != (n_gt, n_cols):
-            raise ValueError("%s: sample %d: inst_labels must be a float32 tensor of shape [%d, %d]"
-                             % (who, b, n_gt, n_cols))
-        if not isinstance(cls, torch.Tensor) or cls.dtype not in (torch.int32, torch.int64) \
-                or tuple(cls.shape) != (n_gt,):
-            raise ValueError("%s: sample %d: cls_labels must be an int32 or int64 tensor of shape [%d]" % (who, b, n_gt))
-        if cls_dtype not in (None, cls.dtype):
-            raise ValueError("%s: sample %d: cls_labels is %s, an earlier sample's %s" % (who, b, cls.dtype, cls_dtype))
-        cls_dtype = cls.dtype
-        if not isinstance(box, torch.Tensor) or box.dtype != torch.float32 or tuple(box.shape) != (n_gt, 6):
-            raise ValueError("%s: sample %d: box_labels must be a float32 tensor of shape [%d, 6]" % (who, b, n_gt))
+        _tensor_arg(who_b, "inst_labels", inst, (n_gt, n_cols))
+        cls_dtype = _sample_labels_arg(who_b, "cls_labels", cls, "box_labels", box, n_gt, cls_dtype)
         tensors += [x, inst, cls, box]
         kept.append(b)
         rows_host[b] = rows.astype(np.int32)
-    for t in tensors:
-        if t.device != dev:
-            raise ValueError("%s: tensors on %s and on %s; one device is expected" % (who, dev, t.device))
+    _one_device(who, cls_logits.device, tensors)
     return kept, rows_host, off, cls_dtype
 
 
@@ -782,8 +828,6 @@ class _MatchedLosses(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, plan, cls_logits, conf_logits, box_preds, *mask_logits):
-        import numpy as np
-
         who = "matched_losses"
         ctx, stream = _ctx_stream(cls_logits)
         lib, dev = ctx.lib, cls_logits.device
@@ -793,8 +837,7 @@ class _MatchedLosses(torch.autograd.Function):
         tasks = (_lib.MatchLossTask * B)()
         keep, xs, total_gt, grad_spans, grad_floats = [], [], 0, [], 0
         for b, x in zip(plan["kept"], mask_logits):
-            if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
-                x = x.contiguous()
+            x = _row_contiguous(x)
             inst, cls, box = (gt[k][b].contiguous() for k in ("inst_labels", "cls_labels", "box_labels"))
             keep += [inst, cls, box]  # alive until the backward has run
             xs.append(x)
@@ -808,25 +851,20 @@ class _MatchedLosses(torch.autograd.Function):
         prob, feats, coords = (plan[k].contiguous() for k in ("prob", "feats", "coords"))
         weight = plan["weight"].contiguous()
         with torch.cuda.device(dev):
-            ws_bytes = int(lib.gapro_match_loss_workspace_bytes(B, Q, total_gt))
-            if ws_bytes == 0:
-                raise ValueError("%s: %d samples, %d queries and %d matched rows are beyond the library's bounds"
-                                 % (who, B, Q, total_gt))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _workspace(who, int(lib.gapro_match_loss_workspace_bytes(B, Q, total_gt)), dev,
+                            "%d samples, %d queries and %d matched rows are" % (B, Q, total_gt))
+            ws_bytes = ws.numel()
             out = torch.empty(_lib.MATCH_LOSS_N, dtype=torch.float32, device=dev)
-            d_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, device=dev)
-            h_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, pin_memory=True) if plan["check"] else None
+            d_status, h_status = _status_pair(dev, _lib.MATCH_STATUS_WORDS, torch.int32, read=plan["check"])
             args = (B, Q, n_classes, _LABEL_CODES[plan["cls_dtype"]], int(feats.shape[1]))
             ctx.check(lib.gapro_match_loss_forward(ctx.handle, stream, C.cast(tasks, C.c_void_p), rows.ctypes.data,
                                                    *args, cls_logits.data_ptr(), conf_logits.data_ptr(),
                                                    box_preds.data_ptr(), prob.data_ptr(), feats.data_ptr(),
                                                    coords.data_ptr(), int(prob.shape[0]), weight.data_ptr(),
                                                    plan["voxel_scale"], ws.data_ptr(), ws_bytes, out.data_ptr(),
-                                                   d_status.data_ptr(),
-                                                   h_status.data_ptr() if h_status is not None else None))
-            if h_status is not None:
-                torch.cuda.current_stream(dev).synchronize()  # the call's one host read, asked for by check=True
-                status, bad, flags = (int(v) for v in h_status[:3])
+                                                   d_status.data_ptr(), _ptr(h_status)))
+            if h_status is not None:  # the call's one host read, asked for by check=True
+                status, bad = _host_read(dev, h_status)[:2]
                 if status != 0:
                     raise GaproError(status, "%s: sample %d: a class label outside [0, n_classes)" % (who, bad))
         fctx.save_for_backward(cls_logits, conf_logits, box_preds, *xs)
@@ -848,13 +886,12 @@ class _MatchedLosses(torch.autograd.Function):
         g_conf = torch.empty_like(conf_logits) if need[2] else None
         g_box = torch.empty_like(box_preds) if need[3] else None
         g_mask = torch.empty(grad_floats, dtype=torch.float32, device=dev) if any(need[4:]) else None
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         with torch.cuda.device(dev):
             ctx.check(ctx.lib.gapro_match_loss_backward(ctx.handle, stream, *args, total_gt, cls_logits.data_ptr(),
                                                         conf_logits.data_ptr(), box_preds.data_ptr(), prob.data_ptr(),
                                                         feats.data_ptr(), coords.data_ptr(), weight.data_ptr(),
                                                         voxel_scale, ws.data_ptr(), ws_bytes, grad_out.data_ptr(),
-                                                        ptr(g_cls), ptr(g_mask), ptr(g_conf), ptr(g_box)))
+                                                        _ptr(g_cls), _ptr(g_mask), _ptr(g_conf), _ptr(g_box)))
         masks = [g_mask[first:first + Q * n_cols].view(Q, n_cols) if need[4 + k] else None
                  for k, (first, n_cols) in enumerate(grad_spans)]
         return (None, g_cls, g_conf, g_box, *masks)
@@ -891,9 +928,10 @@ def matched_losses(cls_logits, mask_logits, conf_logits, box_preds, prob_labels,
     if not kept:
         zeros = torch.zeros(_lib.MATCH_LOSS_N + 1, dtype=torch.float32, device=dev)
         return {name: zeros[k] for k, name in enumerate(LOSS_NAMES + ("kl_loss",))}
-    if not cls_logits.is_cuda:
-        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
-    weight = (_default_empty_weight(dev, int(cls_logits.shape[2])) if empty_weight is None else empty_weight).detach()
+    _need_device(cls_logits)
+    if empty_weight is None:
+        empty_weight = _empty_weight_of(dev, int(cls_logits.shape[2]) - 1, 0.1, None)
+    weight = empty_weight.detach()
     plan = {"kept": kept, "rows": rows_host, "off": off, "cls_dtype": cls_dtype, "gt": gt_dict,
             "prob": prob_labels.detach(), "feats": levelset_feats.detach(), "coords": levelset_coords.detach(),
             "weight": weight, "voxel_scale": float(voxel_scale), "check": bool(check)}
@@ -905,11 +943,6 @@ def matched_losses(cls_logits, mask_logits, conf_logits, box_preds, prob_labels,
 
 # ---- the point-wise losses (gapro_amd/csrc/point_loss.hip) -----------------------------------------------
 POINT_LOSS_NAMES = ("pw_sem_loss", "pw_corners_loss", "pw_giou_loss", "pw_conf_loss")
-_class_weights = {}  # (device, the weights) -> f32[C] on the device
-
-
-def _is_number(v):
-    return not isinstance(v, bool) and isinstance(v, (int, float))
 
 
 def _semantic_weight_arg(who, semantic_weight, n_classes, dev):
@@ -918,10 +951,8 @@ def _semantic_weight_arg(who, semantic_weight, n_classes, dev):
     if semantic_weight is None:
         return None
     if isinstance(semantic_weight, torch.Tensor):
-        if semantic_weight.dtype != torch.float32 or tuple(semantic_weight.shape) != (n_classes,):
-            raise ValueError("%s: semantic_weight must be a float32 tensor of shape [%d]" % (who, n_classes))
-        if semantic_weight.device != dev:
-            raise ValueError("%s: tensors on %s and on %s; one device is expected" % (who, dev, semantic_weight.device))
+        _tensor_arg(who, "semantic_weight", semantic_weight, (n_classes,))
+        _one_device(who, dev, [semantic_weight])
         return semantic_weight.detach()
     try:
         vals = tuple(float(v) for v in semantic_weight)
@@ -931,18 +962,13 @@ def _semantic_weight_arg(who, semantic_weight, n_classes, dev):
         return None  # the reference tests the list's truth
     if len(vals) != n_classes:
         raise ValueError("%s: %d semantic weights for %d classes" % (who, len(vals), n_classes))
-    key = (dev, vals)
-    if key not in _class_weights:
-        _class_weights[key] = torch.tensor(vals, dtype=torch.float32).to(dev)
-    return _class_weights[key]
+    return _device_constant(dev, vals)
 
 
 def _check_point_args(who, semantic_scores, corners_offset, box_conf, semantic_labels, instance_labels,
                       corners_offset_labels, coords_float, ignore_label, voxel_scale):
     """What is refused before a device is touched; returns N and C."""
-    if not isinstance(semantic_scores, torch.Tensor) or semantic_scores.dim() != 2 \
-            or semantic_scores.dtype != torch.float32:
-        raise ValueError("%s: semantic_scores must be a float32 tensor of shape [N, C]" % who)
+    _tensor_arg(who, "semantic_scores", semantic_scores, ("N", "C"))
     N, n_classes = (int(v) for v in semantic_scores.shape)
     if not _lib.POINT_LOSS_MIN_CLASSES <= n_classes <= _lib.POINT_LOSS_MAX_CLASSES:
         raise ValueError("%s: %d classes; %d to %d are expected"
@@ -951,22 +977,17 @@ def _check_point_args(who, semantic_scores, corners_offset, box_conf, semantic_l
         raise ValueError("%s: %d points are beyond the library's bound of %d" % (who, N, _lib.POINT_LOSS_MAX_POINTS))
     for name, t, width in (("corners_offset", corners_offset, 6), ("corners_offset_labels", corners_offset_labels, 6),
                            ("coords_float", coords_float, 3)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (N, width):
-            raise ValueError("%s: %s must be a float32 tensor of shape [%d, %d]" % (who, name, N, width))
+        _tensor_arg(who, name, t, (N, width))
     if not isinstance(box_conf, torch.Tensor) or box_conf.dtype != torch.float32 \
             or tuple(box_conf.shape) not in ((N,), (N, 1)):
         raise ValueError("%s: box_conf must be a float32 tensor of shape [%d] or [%d, 1]" % (who, N, N))
     for name, t in (("semantic_labels", semantic_labels), ("instance_labels", instance_labels)):
-        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.int64) or tuple(t.shape) != (N,):
-            raise ValueError("%s: %s must be an int32 or int64 tensor of shape [%d]" % (who, name, N))
-    if isinstance(ignore_label, bool) or not isinstance(ignore_label, int) or not -2 ** 63 <= ignore_label < 2 ** 63:
+        _tensor_arg(who, name, t, (N,), _INT)
+    if not _is_int(ignore_label) or not -2 ** 63 <= ignore_label < 2 ** 63:
         raise ValueError("%s: ignore_label must be an int" % who)
-    if not _is_number(voxel_scale) or voxel_scale != voxel_scale or abs(voxel_scale) == float("inf"):
-        raise ValueError("%s: voxel_scale must be a finite number" % who)
-    dev = semantic_scores.device
-    for t in (corners_offset, box_conf, semantic_labels, instance_labels, corners_offset_labels, coords_float):
-        if t.device != dev:
-            raise ValueError("%s: tensors on %s and on %s; one device is expected" % (who, dev, t.device))
+    _finite_arg(who, "voxel_scale", voxel_scale)
+    _one_device(who, semantic_scores.device, (corners_offset, box_conf, semantic_labels, instance_labels,
+                                              corners_offset_labels, coords_float))
     return N, n_classes
 
 
@@ -979,29 +1000,23 @@ class _PointWiseLosses(torch.autograd.Function):
         ctx, stream = _ctx_stream(semantic_scores)
         lib, dev = ctx.lib, semantic_scores.device
         N, n_classes = (int(v) for v in semantic_scores.shape)
-        z = semantic_scores
-        if z.stride(1) != 1 or z.stride(0) < n_classes:
-            z = z.contiguous()
+        z = _row_contiguous(semantic_scores)
         corners, conf = corners_offset.contiguous(), box_conf.contiguous()
         sem, inst, labels, coords, weight = (None if plan[k] is None else plan[k].contiguous()
                                              for k in ("sem", "inst", "labels", "coords", "weight"))
         with torch.cuda.device(dev):
-            ws_bytes = int(lib.gapro_point_loss_workspace_bytes(N, n_classes))
-            if ws_bytes == 0:
-                raise ValueError("%s: %d points and %d classes are beyond the library's bounds" % (who, N, n_classes))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            ws = _workspace(who, int(lib.gapro_point_loss_workspace_bytes(N, n_classes)), dev,
+                            "%d points and %d classes are" % (N, n_classes))
             out = torch.empty(_lib.POINT_LOSS_N, dtype=torch.float32, device=dev)
-            d_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, device=dev)
-            h_status = torch.empty(_lib.MATCH_STATUS_WORDS, dtype=torch.int32, pin_memory=True) if plan["check"] else None
+            d_status, h_status = _status_pair(dev, _lib.MATCH_STATUS_WORDS, torch.int32, read=plan["check"])
             args = (N, n_classes, z.data_ptr(), int(z.stride(0)), sem.data_ptr(), _LABEL_CODES[sem.dtype],
                     inst.data_ptr(), _LABEL_CODES[inst.dtype], corners.data_ptr(), conf.data_ptr(), labels.data_ptr(),
-                    coords.data_ptr(), weight.data_ptr() if weight is not None else None, plan["ignore_label"],
-                    plan["voxel_scale"], ws.data_ptr(), ws_bytes)
+                    coords.data_ptr(), _ptr(weight), plan["ignore_label"], plan["voxel_scale"], ws.data_ptr(),
+                    ws.numel())
             ctx.check(lib.gapro_point_loss_forward(ctx.handle, stream, *args, out.data_ptr(), d_status.data_ptr(),
-                                                   h_status.data_ptr() if h_status is not None else None))
-            if h_status is not None:
-                torch.cuda.current_stream(dev).synchronize()  # the call's one host read, asked for by check=True
-                status, bad = int(h_status[0]), int(h_status[1])
+                                                   _ptr(h_status)))
+            if h_status is not None:  # the call's one host read, asked for by check=True
+                status, bad = _host_read(dev, h_status)[:2]
                 if status != 0:
                     raise GaproError(status, "%s: point %d: a semantic label that is neither ignore_label nor in "
                                              "[0, %d)" % (who, bad, n_classes))
@@ -1021,10 +1036,9 @@ class _PointWiseLosses(torch.autograd.Function):
         g_z = torch.empty((args[0], args[1]), dtype=torch.float32, device=dev) if need[1] else None
         g_corners = torch.empty_like(corners) if need[2] else None
         g_conf = torch.empty_like(conf) if need[3] else None
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         with torch.cuda.device(dev):
-            ctx.check(ctx.lib.gapro_point_loss_backward(ctx.handle, stream, *args, grad_out.data_ptr(), ptr(g_z),
-                                                        ptr(g_corners), ptr(g_conf)))
+            ctx.check(ctx.lib.gapro_point_loss_backward(ctx.handle, stream, *args, grad_out.data_ptr(), _ptr(g_z),
+                                                        _ptr(g_corners), _ptr(g_conf)))
         return None, g_z, g_corners, g_conf
 
 
@@ -1061,8 +1075,7 @@ def point_wise_losses(semantic_scores, corners_offset, box_conf, semantic_labels
     if N == 0:
         out = torch.tensor([float("nan"), 0.0, 0.0, 0.0], dtype=torch.float32).to(dev)
         return dict(zip(POINT_LOSS_NAMES, out.unbind(0)))
-    if not semantic_scores.is_cuda:
-        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    _need_device(semantic_scores)
     plan = {"sem": semantic_labels, "inst": instance_labels, "labels": corners_offset_labels.detach(),
             "coords": coords_float.detach(), "weight": weight, "ignore_label": int(ignore_label),
             "voxel_scale": float(voxel_scale), "check": bool(check)}
@@ -1079,21 +1092,14 @@ _PW_MODEL_KEYS = ("semantic_scores", "corners_offset", "box_conf")
 _MAIN_MODEL_KEYS = ("cls_logits", "mask_logits", "conf_logits", "box_preds", "dc_inst_mask_arr", "dc_prob_labels",
                     "dc_batch_offsets", "dc_rgb_feats", "dc_coords_float", "dc_mu_labels", "dc_var_labels", "mu_pred",
                     "logvar_pred")
-_empty_weights = {}  # (device, instance_classes, eos_coef, the semantic weights) -> Criterion.empty_weight
 
 
 def _empty_weight_of(dev, instance_classes, eos_coef, semantic_weight):
     """``Criterion.__init__``'s ``empty_weight`` (criterion.py:107-111): ones, ``eos_coef`` last, and the semantic
     weights shifted by ``label_shift = 1`` when given."""
-    key = (dev, instance_classes, eos_coef, semantic_weight)
-    if key not in _empty_weights:
-        w = torch.ones(instance_classes + 1, dtype=torch.float32)
-        w[-1] = eos_coef
-        if semantic_weight:
-            for i in range(1, instance_classes + 1):
-                w[i - 1] = semantic_weight[i]
-        _empty_weights[key] = w.to(dev)
-    return _empty_weights[key]
+    classes = range(1, instance_classes + 1)
+    return _device_constant(dev, tuple(float(semantic_weight[i]) if semantic_weight else 1.0 for i in classes)
+                            + (float(eos_coef),))
 
 
 def criterion_losses(batch_inputs, model_outputs, *, instance_classes=18, semantic_weight=None, ignore_label=-100,
@@ -1123,15 +1129,12 @@ def criterion_losses(batch_inputs, model_outputs, *, instance_classes=18, semant
         raise ValueError("%s: batch_inputs must be a dict" % who)
     if model_outputs is not None and not isinstance(model_outputs, dict):
         raise ValueError("%s: model_outputs must be a dict or None" % who)
-    if isinstance(instance_classes, bool) or not isinstance(instance_classes, int) or instance_classes < 1:
-        raise ValueError("%s: instance_classes must be a positive int" % who)
-    if isinstance(dup_gt, bool) or not isinstance(dup_gt, int) or dup_gt < 1:
-        raise ValueError("%s: dup_gt must be a positive int" % who)
-    if not _is_number(eos_coef) or eos_coef != eos_coef or abs(eos_coef) == float("inf"):
-        raise ValueError("%s: eos_coef must be a finite number" % who)
+    _positive_int_arg(who, "instance_classes", instance_classes)
+    _positive_int_arg(who, "dup_gt", dup_gt)
+    _finite_arg(who, "eos_coef", eos_coef)
     weights = dict(LOSS_WEIGHT) if loss_weight is None else loss_weight
     if not isinstance(weights, dict) or list(weights) != list(LOSS_WEIGHT) \
-            or any(not _is_number(v) or v != v or abs(v) == float("inf") for v in weights.values()):
+            or any(not _is_finite(v) for v in weights.values()):
         raise ValueError("%s: loss_weight must be a dict of finite numbers with the keys %s, in this order"
                          % (who, ", ".join(LOSS_WEIGHT)))
     if semantic_weight is not None:
@@ -1202,24 +1205,10 @@ _PROPOSAL_CAUSES = ((1, "a non-finite cls_logits, conf_logits or score entry"),
 ProposalArrays = namedtuple("ProposalArrays", "conf label_id box query run_offsets runs masks header n_runs")
 
 
-def _index_arg(t, name, who, n=None):
-    """A 1-D integer device tensor as contiguous int32 / int64, and whether it is int64."""
-    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype not in _SPP_DTYPES:
-        raise ValueError("%s: %s must be a 1-D integer tensor" % (who, name))
-    if n is not None and int(t.shape[0]) != n:
-        raise ValueError("%s: %s has %d entries, expected %d" % (who, name, int(t.shape[0]), n))
-    if not t.is_cuda:
-        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
-    if t.dtype not in (torch.int32, torch.int64):
-        t = t.to(torch.int32)
-    return t.contiguous(), int(t.dtype == torch.int64)
-
-
 def _f32_arg(t, name, who, shape):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
-        raise ValueError("%s: %s must be a float32 tensor of shape %s" % (who, name, tuple(shape)))
-    if not t.is_cuda:
-        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    """This family refuses a host tensor argument by argument, not behind all its ValueErrors."""
+    _tensor_arg(who, name, t, shape, text=tuple(shape))
+    _need_device(t)
     return t.contiguous()
 
 
@@ -1232,19 +1221,12 @@ def _proposals_run(who, anchor, inputs, params, keep, n_points, want_masks=False
     with torch.cuda.device(dev):
         ws_bytes, hdr_bytes = int(lib.gapro_proposals_workspace_bytes(pin, ppar)), int(
             lib.gapro_proposals_header_bytes(pin, ppar))
-        if ws_bytes == 0:
-            raise ValueError("%s: the sizes or parameters are beyond the library's bounds" % who)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        d_hdr = torch.empty(hdr_bytes, dtype=torch.uint8, device=dev)
-        h_hdr = torch.empty(hdr_bytes, dtype=torch.uint8, pin_memory=True)
+        ws = _workspace(who, ws_bytes, dev, "the sizes or parameters are")
+        d_hdr, h_hdr = _status_pair(dev, hdr_bytes)
         ctx.check(lib.gapro_proposals_count(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, d_hdr.data_ptr(),
                                             h_hdr.data_ptr()))
-        torch.cuda.current_stream(dev).synchronize()  # the call's one host read
-        raw = h_hdr.numpy().tobytes()
-        hdr = _lib.ProposalsHeader.from_buffer_copy(raw)
-        if hdr.status != 0:
-            why = next(text for bit, text in _PROPOSAL_CAUSES if hdr.flags & bit)
-            raise GaproError(hdr.status, "%s: %s" % (who, why))
+        hdr, raw = _host_read(dev, h_hdr, _lib.ProposalsHeader)
+        _refuse(who, hdr.status, hdr.flags, _PROPOSAL_CAUSES)
         rows, runs = int(hdr.n_rows), int(hdr.total_runs)
         nms_only = params.mode == _lib.PROPOSALS_NMS
         conf = torch.empty(rows, dtype=torch.float32, device=dev) if want_rows else None
@@ -1255,10 +1237,9 @@ def _proposals_run(who, anchor, inputs, params, keep, n_points, want_masks=False
         d_runs = None if nms_only else torch.empty(2 * runs, dtype=torch.int64, device=dev)
         masks = torch.empty((rows, n_points), dtype=torch.uint8, device=dev) if want_masks else None
         if rows > 0:
-            ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None  # noqa: E731
-            ctx.check(lib.gapro_proposals_fill(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, ptr(conf),
-                                               ptr(label), ptr(box), ptr(query), rows, ptr(run_off), ptr(d_runs), runs,
-                                               ptr(masks), None))
+            ctx.check(lib.gapro_proposals_fill(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, _ptr(conf),
+                                               _ptr(label), _ptr(box), _ptr(query), rows, _ptr(run_off), _ptr(d_runs),
+                                               runs, _ptr(masks), None))
     del keep
     n_runs = np.frombuffer(raw, dtype=np.int32, count=rows, offset=C.sizeof(_lib.ProposalsHeader))
     return ProposalArrays(conf, label, box, query, run_off, d_runs, masks, hdr, n_runs)
@@ -1332,10 +1313,7 @@ def get_instance(scan_id, cls_logits, mask_logits, conf_logits, box_preds, v2p_m
     sm, sm_i64 = (None, 0)
     if sem:
         sm, sm_i64 = _index_arg(semantic_scores_preds, "semantic_scores_preds", who, V)
-    if n_spps is not None and (isinstance(n_spps, bool) or not isinstance(n_spps, int) or n_spps < 1):
-        raise ValueError("%s: n_spps must be a positive int" % who)
-    if n_spps is None:
-        n_spps = max(int(sp.max()) + 1, 1)  # a host read; a negative id is refused by the device below
+    n_spps = _n_spps_arg(who, n_spps, sp)
     inputs = _lib.ProposalsInputs(
         n_queries=Q, n_voxels=V, n_points=N, n_spps=n_spps, n_mask_cols=0 if vs is None else cols,
         cls_logits=cls_logits.data_ptr(), conf_logits=conf_logits.data_ptr(), box_preds=box_preds.data_ptr(),
@@ -1384,8 +1362,7 @@ def mask_nms(proposals_pred, categories, scores, boxes, test_cfg):
         return proposals_pred, categories, scores, boxes
     if n > _lib.PROPOSALS_MAX_PRE_TOPK or V < 1:
         raise ValueError("%s: %d proposals over %d voxels are beyond the library's bounds" % (who, n, V))
-    if not proposals_pred.is_cuda:
-        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    _need_device(proposals_pred)
     masks = (proposals_pred if proposals_pred.dtype in (torch.bool, torch.uint8) else proposals_pred != 0).contiguous()
     sc = _f32_arg(scores, "scores", who, (n,))
     cat = categories.to(torch.int32).contiguous()
@@ -1409,8 +1386,7 @@ def rle_encode_gpu_batch(masks):
     who = "rle_encode_gpu_batch"
     if not isinstance(masks, torch.Tensor) or masks.dim() != 2 or masks.dtype not in (torch.bool, torch.uint8):
         raise ValueError("%s: masks must be a bool [K, N] tensor" % who)
-    if not masks.is_cuda:
-        raise RuntimeError("gapro_amd.consumer_ops works on HIP device tensors; there is no CPU fallback")
+    _need_device(masks)
     K, N = int(masks.shape[0]), int(masks.shape[1])
     if N < 1:
         raise ValueError("%s: no points" % who)

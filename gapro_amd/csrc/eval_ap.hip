@@ -385,7 +385,7 @@ int gapro_eval_ap_keys(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const ga
   if (n_scenes < 1 || n_scenes > 65535 || !h_scenes || !d_scenes || n_total_points < 0 || !d_workspace || !d_n_keys ||
       !d_status || (n_total_points > 0 && (!d_sem_gt || !d_inst_gt)))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_ap_keys: bad argument");
-  if (!with_gt_type(sem_gt_dtype, [](auto) {}) || !with_gt_type(inst_gt_dtype, [](auto) {}))
+  if (!with_label_type(sem_gt_dtype, [](auto) {}) || !with_label_type(inst_gt_dtype, [](auto) {}))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_ap_keys: unsupported label dtype code");
   long long n_max, ps_max, fin_max;
   size_t rows_at;
@@ -399,8 +399,8 @@ int gapro_eval_ap_keys(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const ga
   hipLaunchKernelGGL(k_ap_init, dim3(grid_for(kApWords + ps_max, 1, 64), n_scenes), dim3(kThreads), 0, stream,
                      d_scenes, d_workspace);
   if (n_max > 0)
-    with_gt_type(sem_gt_dtype, [&](auto sgt) {
-      with_gt_type(inst_gt_dtype, [&](auto igt) {
+    with_label_type(sem_gt_dtype, [&](auto sgt) {
+      with_label_type(inst_gt_dtype, [&](auto igt) {
         using TGS = std::remove_const_t<std::remove_pointer_t<decltype(sgt)>>;
         using TGI = std::remove_const_t<std::remove_pointer_t<decltype(igt)>>;
         hipLaunchKernelGGL((k_ap_mark<TGS, TGI>), dim3(grid_for(n_max, 8, 128), n_scenes), dim3(kThreads), 0,
@@ -429,7 +429,7 @@ static int ap_tables_rows(const char* fn, gapro_ctx* ctx, void* stream_, int32_t
       !d_key_code || !d_key_n || !d_ps_n || !d_ps_label || !d_ps_void || !d_ps_sum || !d_pair || !d_status ||
       (n_total_points > 0 && (!d_sem_gt || !d_inst_gt || !d_sem_ps || !d_inst_ps)))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "%s: bad argument", fn);
-  if (!with_gt_type(sem_gt_dtype, [](auto) {}) || !with_gt_type(inst_gt_dtype, [](auto) {}) ||
+  if (!with_label_type(sem_gt_dtype, [](auto) {}) || !with_label_type(inst_gt_dtype, [](auto) {}) ||
       !with_ps_type(sem_ps_dtype, [](auto) {}) || !with_ps_type(inst_ps_dtype, [](auto) {}))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "%s: unsupported label dtype code", fn);
   Rows rows = {};
@@ -461,8 +461,8 @@ static int ap_tables_rows(const char* fn, gapro_ctx* ctx, void* stream_, int32_t
   if (K > 0)  // kFirstNone in every byte; row 0's first points are gapro_eval_ap_keys'
     GAPRO_HIP_CHECK(ctx, hipMemsetAsync(rows.first, 0xff, (size_t)K * rows.n_ids * sizeof(unsigned long long), stream));
   if (n_max > 0)
-    with_gt_type(sem_gt_dtype, [&](auto sgt) {
-      with_gt_type(inst_gt_dtype, [&](auto igt) {
+    with_label_type(sem_gt_dtype, [&](auto sgt) {
+      with_label_type(inst_gt_dtype, [&](auto igt) {
         with_ps_type(sem_ps_dtype, [&](auto sps) {
           with_ps_type(inst_ps_dtype, [&](auto ips) {
             using TGS = std::remove_const_t<std::remove_pointer_t<decltype(sgt)>>;

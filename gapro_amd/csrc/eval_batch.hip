@@ -267,7 +267,7 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapr
       !d_kept || !d_status ||
       (n_total_points > 0 && (!d_sem_gt || !d_sem_ps || (pairs && (!d_inst_gt || !d_inst_ps)))))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_batch: bad argument");
-  if (!with_gt_type(sem_gt_dtype, [](auto) {}) || !with_gt_type(inst_gt_dtype, [](auto) {}) ||
+  if (!with_label_type(sem_gt_dtype, [](auto) {}) || !with_label_type(inst_gt_dtype, [](auto) {}) ||
       !with_ps_type(sem_ps_dtype, [](auto) {}) || !with_ps_type(inst_ps_dtype, [](auto) {}))
     return gapro_fail(ctx, GAPRO_ERR_BAD_ARG, "gapro_eval_batch: unsupported label dtype code");
   Thresholds thr = {};
@@ -304,8 +304,8 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapr
   hipLaunchKernelGGL(k_evb_init, dim3(grid_for(words_max, 4, 256), n_scenes), dim3(kThreads), 0, stream, d_scenes,
                      d_workspace, B);
   if (n_max > 0)
-    with_gt_type(sem_gt_dtype, [&](auto sgt) {
-      with_gt_type(inst_gt_dtype, [&](auto igt) {
+    with_label_type(sem_gt_dtype, [&](auto sgt) {
+      with_label_type(inst_gt_dtype, [&](auto igt) {
         with_ps_type(sem_ps_dtype, [&](auto sps) {
           with_ps_type(inst_ps_dtype, [&](auto ips) {
             using TGS = std::remove_const_t<std::remove_pointer_t<decltype(sgt)>>;
@@ -329,7 +329,7 @@ int gapro_eval_batch(gapro_ctx* ctx, void* stream_, int32_t n_scenes, const gapr
   if (d_max_iou && d_gt_cls) {
     hipLaunchKernelGGL(k_evb_ps_count, dim3(grid_for((long long)B * ps_max, 1, 64), n_scenes), dim3(kThreads), 0,
                        stream, d_scenes, d_workspace, B);
-    with_gt_type(sem_gt_dtype, [&](auto sgt) {
+    with_label_type(sem_gt_dtype, [&](auto sgt) {
       with_ps_type(sem_ps_dtype, [&](auto sps) {
         using TGS = std::remove_const_t<std::remove_pointer_t<decltype(sgt)>>;
         using TPS = std::remove_const_t<std::remove_pointer_t<decltype(sps)>>;

@@ -2,6 +2,7 @@
 // one template instance per GAPRO_LABEL_* code.
 #pragma once
 #include "common.h"
+#include "label_types.h"
 
 #include <cstdint>
 
@@ -30,16 +31,8 @@ __device__ inline int prob_bin(const Thresholds& thr, int K, float pr) {
   return b;
 }
 
-// dtype code -> template instance
-template <class F>
-bool with_gt_type(int code, F&& f) {
-  switch (code) {
-    case GAPRO_LABEL_F64: f((const double*)nullptr); return true;
-    case GAPRO_LABEL_I32: f((const int32_t*)nullptr); return true;
-    case GAPRO_LABEL_I64: f((const int64_t*)nullptr); return true;
-    default: return false;
-  }
-}
+// dtype code -> template instance: the ground truth goes through with_label_type (label_types.h); the pseudo labels
+// are integers
 template <class F>
 bool with_ps_type(int code, F&& f) {
   switch (code) {

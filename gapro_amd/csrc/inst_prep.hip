@@ -12,6 +12,7 @@
 // kernel returns at once and neither the labels nor the outputs are touched.
 #include "common.h"
 #include "exact_sum.h"
+#include "label_types.h"
 #include "launch_util.h"
 #include "wave_reduce.h"
 
@@ -358,16 +359,6 @@ __global__ __launch_bounds__(kThreads) void k_prep_offsets(long long n, const fl
       corner_off[6 * i + k] = id >= 0 ? box[6 * id + k] - x : -100.0f;
       corner_off[6 * i + 3 + k] = id >= 0 ? box[6 * id + 3 + k] - x : -100.0f;
     }
-  }
-}
-
-template <class F>
-bool with_label_type(int code, F&& f) {
-  switch (code) {
-    case GAPRO_LABEL_F64: f((double*)nullptr); return true;
-    case GAPRO_LABEL_I32: f((int32_t*)nullptr); return true;
-    case GAPRO_LABEL_I64: f((int64_t*)nullptr); return true;
-    default: return false;
   }
 }
 

@@ -22,6 +22,7 @@
 // Integer atomics only, so every result is the same bits for every grid and every run.  The kernel boundaries on the
 // stream are the only ordering.  A refusal is a status word written by `filter`: every later kernel returns at once.
 #include "common.h"
+#include "label_types.h"
 #include "launch_util.h"
 #include "wave_reduce.h"
 
@@ -146,10 +147,6 @@ struct PrPar {  // gapro_proposals_params as the kernels read it
   float logit_thresh, final_score_thresh, nms_threshold;
   int sem[kMaxSem];
 };
-
-__device__ inline long long idx_at(const void* a, int is_i64, long long i) {
-  return is_i64 ? ((const long long*)a)[i] : (long long)((const int*)a)[i];
-}
 
 // float32 as an unsigned integer of the same order (-0.0 below +0.0; the scores here are never -0.0)
 __device__ inline unsigned order_bits(float f) {

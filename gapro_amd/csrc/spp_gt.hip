@@ -17,6 +17,7 @@
 // the kernel boundaries on the stream are the only ordering.  A refusal is a status word written by `pack`: every kernel
 // of the fill returns at once and no output is touched.
 #include "common.h"
+#include "label_types.h"
 #include "launch_util.h"
 #include "wave_reduce.h"
 
@@ -119,10 +120,6 @@ __device__ inline int inst_id<double>(double v, long long ignore, int I) {
   if (!(v >= 0.0) || v >= (double)I) return -2;
   const int id = (int)v;
   return (double)id == v ? id : -2;
-}
-
-__device__ inline long long spp_at(const void* spps, int is_i64, long long i) {
-  return is_i64 ? ((const long long*)spps)[i] : (long long)((const int*)spps)[i];
 }
 
 __device__ inline bool cls_kept(const void* cls, int type, int id) {  // instance_cls[id] >= 0
@@ -255,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void k_gt_mark(void* base, GtDims d, GtIn
           ibit = 1u << (id & 31);
         }
         if (in.spps) {
-          const long long s = spp_at(in.spps, in.spp_is_i64, src);
+          const long long s = idx_at(in.spps, in.spp_is_i64, src);
           if (s < 0 || s >= d.S) {
             flags |= kFlagSpp;
             bad[3] = min(bad[3], b);
@@ -408,7 +405,7 @@ __device__ inline long long cell_of(const GtWs& w, const GtDims& d, const GtIn& 
   const long long src = in.gather ? in.gather[p] : p;
   long long col;
   if (in.spps) {
-    const long long s = spp_at(in.spps, in.spp_is_i64, src);
+    const long long s = idx_at(in.spps, in.spp_is_i64, src);
     col = rank_of(w.spp_bits, w.spp_pre, (size_t)b * d.ws() + (size_t)(s >> 5), (int)s);
     *col_key = w.col_off[b] + col;
   } else {
@@ -492,16 +489,6 @@ __global__ __launch_bounds__(kThreads) void k_gt_gather(void* base, GtDims d, Gt
     }
     if (box_out)
       for (int k = 0; k < 6; ++k) box_out[6 * row + k] = box_in[6 * (size_t)id + k];
-  }
-}
-
-template <class F>
-bool with_label_type(int code, F&& f) {
-  switch (code) {
-    case GAPRO_LABEL_F64: f((double*)nullptr); return true;
-    case GAPRO_LABEL_I32: f((int32_t*)nullptr); return true;
-    case GAPRO_LABEL_I64: f((int64_t*)nullptr); return true;
-    default: return false;
   }
 }
 
