@@ -20,7 +20,8 @@ _EXPORTS = {
     "scannet_planes": ("get_wall_boxes",),
     "consumer_ops": ("get_instance_info", "prepare_instance_labels", "get_spp_gt", "get_subsample_gt", "match_cost",
                      "linear_sum_assignment", "hungarian_match", "point_wise_losses", "criterion_losses",
-                     "get_instance", "mask_nms", "rle_encode_gpu_batch"),
+                     "get_instance", "mask_nms", "rle_encode_gpu_batch", "furthestsampling_batchflat",
+                     "ballquery_batchflat", "furthest_point_sample", "ball_query", "sample_queries"),
 }
 __all__ = [n for names in _EXPORTS.values() for n in names]
 

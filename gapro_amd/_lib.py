@@ -228,7 +228,11 @@ class MatchLossTask(C.Structure):
 
 MATCH_LOSS_N = 7          # GAPRO_MATCH_LOSS_N: dice, bce, cls, iou, box, giou, levelset
 MATCH_LOSS_MAX_FEATS = 8  # GAPRO_MATCH_LOSS_MAX_FEATS
-POINT_LOSS_N = 4                                      # GAPRO_POINT_LOSS_N: sem, corners, giou, conf
+QS_STATUS_WORDS = 4  # GAPRO_QS_STATUS_WORDS: status, flags (1: offsets, 2: a sample without points, 4: not finite), 0, 0
+FPS_SKIP_ORIGIN, QS_LOCAL_INDEX = 1, 2                # the flags of gapro_fps_batch / gapro_ball_query_batch
+FPS_PATHS = ("resident", "streamed", "global")        # GAPRO_FPS_RESIDENT, _STREAMED, _GLOBAL
+QS_MAX_SAMPLES, BALL_QUERY_MAX_NSAMPLE = 4096, 4096
+POINT_LOSS_N = 4                                     # GAPRO_POINT_LOSS_N: sem, corners, giou, conf
 POINT_LOSS_MIN_CLASSES, POINT_LOSS_MAX_CLASSES = 2, 64  # GAPRO_POINT_LOSS_MIN_CLASSES / _MAX_CLASSES
 POINT_LOSS_MAX_POINTS = (1 << 31) - 1                 # n_points of one call
 POINT_LOSS_RUN = 1024                                 # GAPRO_POINT_LOSS_RUN: points of one workgroup
@@ -329,6 +333,12 @@ SIGNATURES = {
                                            _P, _P, _P, _P, C.c_int64, C.c_double, _P, C.c_size_t, _P, _P, _P]),
     "gapro_point_loss_backward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P,
                                             _P, _P, _P, _P, C.c_int64, C.c_double, _P, C.c_size_t, _P, _P, _P, _P]),
+    "gapro_fps_plan": (C.c_int, [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gapro_fps_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gapro_fps_batch": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int32,
+                                  _P, C.c_size_t, _P, _P, _P, _P]),
+    "gapro_ball_query_batch": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32,
+                                         C.c_double, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "gapro_lsap_solve": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _P, _P]),
     "gapro_schedule_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "gapro_schedule_free": (None, [_P]),
@@ -512,7 +522,7 @@ def load() -> C.CDLL:
                                             "gapro_trainset_", "gapro_point_refine_", "gapro_schedule_merge_ex",
                                             "gapro_schedule_export_testers", "gapro_spp_vote",
                                             "gapro_fit_launch_plan", "gapro_inst_", "gapro_spp_gt_", "gapro_match_",
-                                            "gapro_proposals_",
+                                            "gapro_proposals_", "gapro_fps_", "gapro_ball_query_",
                                             "gapro_lsap_")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)

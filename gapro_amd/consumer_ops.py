@@ -1401,3 +1401,234 @@ def rle_encode_gpu_batch(masks):
         runs = out.runs.cpu().numpy()
         rles += [{"length": N, "counts": c} for c in _counts_of(offs, runs)]
     return rles
+
+
+# ---- query sampling: the Point Aggregator's index work (csrc/query_sample.hip) -------------------------
+_QS_CAUSES = ((1, "offsets that decrease or leave [0, the number of points] / [0, the number of outputs]"),
+              (2, "a sample with outputs and no points (its outputs are -1)"),
+              (4, "a coordinate that is not finite"))
+_uniform = {}  # (device, entries, step) -> int32 step, 2 step, .., entries * step on the device
+
+
+def fps_plan(n_max):
+    """``gapro_fps_plan`` without a device: ``(path, xyz_capacity, capacity)`` for a sample of ``n_max`` points -- the
+    path is "resident" (coordinates and running minima in registers, up to ``xyz_capacity`` points), "streamed" (the
+    minima in registers, up to ``capacity``) or "global" (the minima in device memory).  The results are the same."""
+    if not _is_int(n_max) or n_max < 0:
+        raise ValueError("fps_plan: n_max must be a non-negative int")
+    xyz_cap, cap = C.c_int64(0), C.c_int64(0)
+    path = _lib.load().gapro_fps_plan(int(n_max), C.byref(xyz_cap), C.byref(cap))
+    if path < 0:
+        raise ValueError("fps_plan: %d points are beyond the library's bounds" % n_max)
+    return _lib.FPS_PATHS[path], int(xyz_cap.value), int(cap.value)
+
+
+def _uniform_offsets(dev, entries, step):
+    """``step * (i + 1)`` for ``i < entries`` as an int32 device tensor: made once per device and shape, no host read."""
+    key = (dev, entries, step)
+    if key not in _uniform:
+        if entries * step > 2 ** 31 - 1:
+            raise ValueError("%d samples of %d entries are beyond the library's bounds" % (entries, step))
+        _uniform[key] = torch.arange(step, step * entries + 1, step, dtype=torch.int32, device=dev) if step > 0 \
+            else torch.zeros(entries, dtype=torch.int32, device=dev)
+    return _uniform[key]
+
+
+def _samples_arg(who, offset, new_offset, n_sample, m_known=None):
+    """The two offset tables of a batch-flat call as the kernels read them, and the number of outputs: ``new_offset``
+    as given (its last entry is the number of outputs: the call's host read unless ``m_known``) or ``n_sample * (i +
+    1)``, which needs no read."""
+    _index_check(who, "offset", offset)
+    n_samples = int(offset.shape[0])
+    if not 1 <= n_samples <= _lib.QS_MAX_SAMPLES:
+        raise ValueError("%s: %d offsets outside [1, %d]" % (who, n_samples, _lib.QS_MAX_SAMPLES))
+    if (new_offset is None) == (n_sample is None):
+        raise ValueError("%s: one of new_offset and n_sample= is expected" % who)
+    if n_sample is not None:
+        if not _is_int(n_sample) or n_sample < 0:
+            raise ValueError("%s: n_sample must be a non-negative int" % who)
+        _need_device(offset)
+        return offset, _uniform_offsets(offset.device, n_samples, n_sample), n_samples * n_sample
+    _index_check(who, "new_offset", new_offset)
+    if int(new_offset.shape[0]) != n_samples:
+        raise ValueError("%s: %d offsets, %d new offsets" % (who, n_samples, int(new_offset.shape[0])))
+    _need_device(offset, new_offset)
+    m = m_known if m_known is not None else max(int(new_offset[-1]), 0)  # the host read, as the reference's
+    return offset, new_offset, m
+
+
+def _qs_status(who, dev, h_status):
+    if h_status is not None:  # the call's host read of its status, asked for by check=True
+        status, flags = _host_read(dev, h_status)[:2]
+        _refuse(who, status, flags, _QS_CAUSES)
+
+
+def _fps_run(who, xyz, offset, new_offset, m, flags, check, return_dist):
+    ctx, stream = _ctx_stream(xyz)
+    lib, dev = ctx.lib, xyz.device
+    xyz = xyz.detach().contiguous()
+    n = int(xyz.shape[0])
+    off, off_i64 = _as_index(offset)
+    new_off, new_i64 = _as_index(new_offset)
+    _one_device(who, dev, (off, new_off))
+    with torch.cuda.device(dev):
+        ws = _workspace(who, int(lib.gapro_fps_workspace_bytes(n)), dev, "%d points are" % n)
+        idx = torch.empty(m, dtype=torch.int32, device=dev)
+        dist = torch.empty(n, dtype=torch.float32, device=dev) if return_dist else None
+        d_status, h_status = _status_pair(dev, _lib.QS_STATUS_WORDS, torch.int32, read=check)
+        ctx.check(lib.gapro_fps_batch(ctx.handle, stream, n, _ptr(xyz), int(off.shape[0]), off.data_ptr(), off_i64,
+                                      new_off.data_ptr(), new_i64, m, flags, ws.data_ptr(), ws.numel(), _ptr(idx),
+                                      _ptr(dist), d_status.data_ptr(), _ptr(h_status)))
+        _qs_status(who, dev, h_status)
+    return idx, dist
+
+
+def _ball_run(who, radius, nsample, xyz, new_xyz, offset, new_offset, flags, check, return_counts):
+    ctx, stream = _ctx_stream(xyz)
+    lib, dev = ctx.lib, xyz.device
+    xyz, new_xyz = xyz.detach().contiguous(), new_xyz.detach().contiguous()
+    n, m = int(xyz.shape[0]), int(new_xyz.shape[0])
+    off, off_i64 = _as_index(offset)
+    new_off, new_i64 = _as_index(new_offset)
+    _one_device(who, dev, (new_xyz, off, new_off))
+    if n > 2 ** 31 - 1 or m * nsample > 2 ** 31 - 1:
+        raise ValueError("%s: %d points and %d x %d indices are beyond the library's bounds" % (who, n, m, nsample))
+    with torch.cuda.device(dev):
+        idx = torch.empty((m, nsample), dtype=torch.int32, device=dev)
+        counts = torch.empty(m, dtype=torch.int32, device=dev) if return_counts else None
+        d_status, h_status = _status_pair(dev, _lib.QS_STATUS_WORDS, torch.int32, read=check)
+        ctx.check(lib.gapro_ball_query_batch(ctx.handle, stream, n, _ptr(xyz), m, _ptr(new_xyz), int(off.shape[0]),
+                                             off.data_ptr(), off_i64, new_off.data_ptr(), new_i64, float(radius),
+                                             nsample, flags, _ptr(idx), _ptr(counts), d_status.data_ptr(),
+                                             _ptr(h_status)))
+        _qs_status(who, dev, h_status)
+    return idx, counts
+
+
+def _ball_args(who, radius, nsample):
+    _finite_arg(who, "radius", radius)
+    _positive_int_arg(who, "nsample", nsample)
+    if nsample > _lib.BALL_QUERY_MAX_NSAMPLE:
+        raise ValueError("%s: nsample beyond %d" % (who, _lib.BALL_QUERY_MAX_NSAMPLE))
+
+
+def furthestsampling_batchflat(xyz, offset, new_offset=None, *, n_sample=None, check=True, return_dist=False):
+    """``isbnet.ops.furthestsampling_batchflat`` (called at ISBNet/isbnet/model/aggregator.py:69): ``int32[m]`` indices
+    into ``xyz`` (``f32[n, 3]``), the furthest point sampling of every sample in one launch.  Sample ``i`` owns the points
+    ``offset[i - 1] .. offset[i]`` and the outputs ``new_offset[i - 1] .. new_offset[i]`` (``offset[-1] = 0``; the
+    reference's tables with a leading 0 have an empty first sample and are read by the same rule).
+
+    The definition: a sample's first output is its first point; each later one the point with the
+    largest running minimum of the float32 squared distances ``((dx*dx + dy*dy) + dz*dz)``, every operation rounded on
+    its own, to the outputs before it; AMONG EQUAL MAXIMA THE LOWEST INDEX wins (the reference leaves that to its block
+    size).  More outputs than points repeat indices.
+
+    ``new_offset`` costs one host read of its last entry, as in the reference; ``n_sample=`` stands for the table
+    ``n_sample * (i + 1)`` over the entries of ``offset`` (so ``offset`` WITHOUT a leading 0) and reads nothing.  With
+    ``check=True`` the status is read behind the kernel: offsets that decrease or leave their range, a sample with
+    outputs and no points (its outputs are -1) and a non-finite coordinate are a ``GaproError``; with ``check=False``
+    the call only enqueues, and in all three cases every index written is inside its sample's range or -1.
+    ``return_dist`` adds ``f32[n]``: every point's running minimum as the last iteration left it (over all outputs of
+    its sample but the last).  No autograd: these are indices."""
+    who = "furthestsampling_batchflat"
+    _tensor_arg(who, "xyz", xyz, ("n", 3))
+    off, new_off, m = _samples_arg(who, offset, new_offset, n_sample)
+    _need_device(xyz)
+    idx, dist = _fps_run(who, xyz, off, new_off, m, 0, check, return_dist)
+    return (idx, dist) if return_dist else idx
+
+
+def ballquery_batchflat(radius, nsample, xyz, new_xyz, offset, new_offset=None, *, n_sample=None, check=True,
+                        return_counts=False):
+    """``isbnet.ops.ballquery_batchflat`` (aggregator.py:75-77): ``int32[m, nsample]`` indices into ``xyz``, per query
+    of ``new_xyz`` (``f32[m, 3]``; ``None`` means ``xyz``, with ``offset`` for its samples) the first ``nsample`` points
+    of the query's own sample, in ascending index, with ``d2 < r2`` -- the float32 distance of
+    ``furthestsampling_batchflat``, ``r2 = float32(radius) * float32(radius)``, strictly: a point at exactly the radius
+    is no hit.  The remaining slots repeat the first hit.  A QUERY WITHOUT A HIT HAS A ROW OF ZEROS, index 0 of the
+    whole table, as the reference's zero-initialised output.  A point of a neighbouring sample is never returned.
+    The query's sample comes from ``new_offset`` (or ``n_sample=``) by the rule of ``furthestsampling_batchflat``;
+    neither costs a host read here.  ``return_counts`` adds ``int32[m]``, the hits of each query, at most ``nsample``.
+    ``check=True`` reads the status (offsets that decrease or leave their range; a query beyond the last offset)."""
+    who = "ballquery_batchflat"
+    _ball_args(who, radius, nsample)
+    _tensor_arg(who, "xyz", xyz, ("n", 3))
+    if new_xyz is None:
+        new_xyz = xyz
+        if new_offset is None and n_sample is None:
+            new_offset = offset
+    _tensor_arg(who, "new_xyz", new_xyz, ("m", 3))
+    off, new_off, m = _samples_arg(who, offset, new_offset, n_sample, m_known=int(new_xyz.shape[0]))
+    _need_device(xyz, new_xyz)
+    if n_sample is not None and m != int(new_xyz.shape[0]):
+        raise ValueError("%s: %d queries, %d samples of n_sample=%d" % (who, int(new_xyz.shape[0]),
+                                                                       int(off.shape[0]), n_sample))
+    idx, counts = _ball_run(who, radius, nsample, xyz, new_xyz, off, new_off, 0, check, return_counts)
+    return (idx, counts) if return_counts else idx
+
+
+def _batched_arg(who, name, t):
+    _tensor_arg(who, name, t, ("B", "N", 3))
+    B, N = int(t.shape[0]), int(t.shape[1])
+    if not 1 <= B <= _lib.QS_MAX_SAMPLES:
+        raise ValueError("%s: batch size %d outside [1, %d]" % (who, B, _lib.QS_MAX_SAMPLES))
+    return B, N
+
+
+def furthest_point_sample(xyz, npoint, *, check=False):
+    """pointnet2's ``furthest_point_sample`` (aggregator.py:170): ``int32[B, npoint]`` indices into each sample of
+    ``xyz`` (``f32[B, N, 3]``), by the kernel and the definition of ``furthestsampling_batchflat`` with pointnet2's
+    near-origin skip: a point with ``x*x + y*y + z*z <= 1e-3f`` is never a candidate (it can still be the first output,
+    which is point 0); without a candidate point 0 is the answer.  No host read unless ``check``."""
+    who = "furthest_point_sample"
+    B, N = _batched_arg(who, "xyz", xyz)
+    if not _is_int(npoint) or npoint < 0:
+        raise ValueError("%s: npoint must be a non-negative int" % who)
+    if N == 0 and npoint > 0:
+        raise ValueError("%s: no points" % who)
+    _need_device(xyz)
+    dev = xyz.device
+    idx, _ = _fps_run(who, xyz.reshape(B * N, 3), _uniform_offsets(dev, B, N), _uniform_offsets(dev, B, npoint),
+                      B * npoint, _lib.FPS_SKIP_ORIGIN | _lib.QS_LOCAL_INDEX, check, False)
+    return idx.view(B, npoint)
+
+
+def ball_query(radius, nsample, xyz, new_xyz, *, return_counts=False):
+    """pointnet2's ``ball_query`` (aggregator.py:115, 176): ``int32[B, M, nsample]`` indices into each sample of ``xyz``
+    (``f32[B, N, 3]``) per query of ``new_xyz`` (``f32[B, M, 3]``), by the kernel and the definition of
+    ``ballquery_batchflat``; a query without a hit has a row of zeros.  No host read."""
+    who = "ball_query"
+    _ball_args(who, radius, nsample)
+    B, N = _batched_arg(who, "xyz", xyz)
+    _tensor_arg(who, "new_xyz", new_xyz, (B, "M", 3))
+    M = int(new_xyz.shape[1])
+    _need_device(xyz, new_xyz)
+    dev = xyz.device
+    idx, counts = _ball_run(who, radius, nsample, xyz.reshape(B * N, 3), new_xyz.reshape(B * M, 3),
+                            _uniform_offsets(dev, B, N), _uniform_offsets(dev, B, M), _lib.QS_LOCAL_INDEX, False,
+                            return_counts)
+    idx = idx.view(B, M, nsample)
+    return (idx, counts.view(B, M)) if return_counts else idx
+
+
+def sample_queries(locs, batch_offsets, batch_size, n_sample, radius, n_neighbor, n_neighbor_post, *, check=False):
+    """The index work of ``LocalAggregator.forward_batchflat`` (aggregator.py:63-115) in one call with no host read:
+    ``(fps_inds int32[B * n_sample], neighbor_inds int32[B * n_sample, n_neighbor], neighbor_inds_post int32[B,
+    n_sample, n_neighbor_post])`` -- the furthest point sampling of ``n_sample`` points per sample, the batch-flat ball
+    query of radius ``radius`` around them, and the batched ball query of radius ``2 * radius`` among them (indices
+    into the sample's ``n_sample`` queries).  ``locs`` is ``f32[n, 3]``; ``batch_offsets`` the reference's ``B + 1``
+    entries with the leading 0 (an int32 / int64 tensor or a sequence).  The gathers and the MLPs stay torch.
+    ``check=True`` reads the status of the first two calls (two host reads)."""
+    who = "sample_queries"
+    _tensor_arg(who, "locs", locs, ("n", 3))
+    _positive_int_arg(who, "batch_size", batch_size)
+    _positive_int_arg(who, "n_sample", n_sample)
+    _ball_args(who, radius, n_neighbor)
+    _ball_args(who, radius, n_neighbor_post)
+    off = _offsets_arg(batch_offsets, batch_size, who)
+    _need_device(locs)
+    off = off.to(locs.device)[1:]
+    fps_inds = furthestsampling_batchflat(locs, off, n_sample=n_sample, check=check)
+    fps_locs = locs.detach().index_select(0, fps_inds.clamp(min=0).to(torch.int64))  # -1: a sample without points
+    neighbor_inds = ballquery_batchflat(radius, n_neighbor, locs, fps_locs, off, n_sample=n_sample, check=check)
+    fps_locs = fps_locs.view(batch_size, n_sample, 3)
+    return fps_inds, neighbor_inds, ball_query(2 * radius, n_neighbor_post, fps_locs, fps_locs)

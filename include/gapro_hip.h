@@ -1268,6 +1268,72 @@ int gapro_lsap_solve(int32_t n_rows, int32_t n_cols, const float* cost, int64_t 
                      int32_t* n_out, int32_t* rows /* [min(n_rows, dup*n_cols)] */, int32_t* cols);
 
 /* ------------------------------------------------------------------------------------------
+ * Query sampling (csrc/query_sample.hip).  Replaces the CUDA-only extensions behind ISBNet's Point
+ * Aggregator (isbnet/model/aggregator.py:63-115, 154-205): isbnet.ops.furthestsampling_batchflat and
+ * ballquery_batchflat, pointnet2's furthest_point_sample and ball_query.  The batched forms are the batch-flat kernels
+ * with uniform offsets and GAPRO_QS_LOCAL_INDEX.
+ * Samples: d_offset and d_new_offset are int32 / int64 device arrays of n_samples entries (*_i64 = 1: int64).  Sample b
+ * owns the points [offset[b - 1], offset[b]) of d_xyz f32[n_points, 3] and the outputs / queries [new_offset[b - 1],
+ * new_offset[b]), with offset[-1] = new_offset[-1] = 0; a leading 0 is an empty first sample.  Outputs beyond the last
+ * entry of d_new_offset are not written.
+ * Every squared distance is ((dx*dx + dy*dy) + dz*dz) in float32, each operation rounded on its own (no contraction).
+ * gapro_fps_batch: one workgroup of GAPRO_FPS_THREADS threads serves a sample, for all of its outputs, and never waits
+ *   for another workgroup; one launch per path below that n_points admits (a workgroup whose sample is of another path
+ *   returns at once), each over all samples.  d_idx i32[m_total]: the first
+ *   output of a sample is its first point; each later one the point with the largest running minimum of the squared
+ *   distances to the outputs before it (the minimum starts at 1e10f; a NaN distance leaves it), AMONG EQUAL MAXIMA THE
+ *   LOWEST INDEX.  More outputs than points repeat indices: once every minimum is 0 the first point wins.  Indices count
+ *   from the start of d_xyz, with GAPRO_QS_LOCAL_INDEX from the sample's first point.  GAPRO_FPS_SKIP_ORIGIN (pointnet2's
+ *   flavour): a point with x*x + y*y + z*z <= 1e-3f, evaluated as the distances are, is never a candidate and its
+ *   minimum is never updated; without a candidate the sample's first point is the answer.  d_dist f32[n_points] or NULL:
+ *   every point's running minimum as the last iteration left it, i.e. over all outputs of its sample but the last.
+ *   The minima of a sample stay in registers up to *capacity points (gapro_fps_plan), its coordinates too up to
+ *   *xyz_capacity; a larger sample keeps the minima in the workspace, gapro_fps_workspace_bytes(n_points) bytes.  The
+ *   results do not depend on the path.  gapro_fps_plan returns the path of a sample of n_max points.
+ * gapro_ball_query_batch: one wave a query.  d_idx i32[m_total, nsample]: the first nsample points of the query's own
+ *   sample, in ascending index, with d2 < r2, r2 = (float)radius * (float)radius -- strictly: a point at exactly the
+ *   radius is no hit; the remaining slots repeat the first hit; A QUERY WITHOUT A HIT HAS A ROW OF ZEROS (index 0 of the
+ *   whole table, as the reference's zero-initialised output).  A NaN distance is no hit.  d_counts i32[m_total] or
+ *   NULL: the hits, at most nsample.  Every row is written whole.
+ * d_status i32[GAPRO_QS_STATUS_WORDS] = {status, flags, 0, 0}, cleared by the call, copied to h_status_pinned behind the
+ * kernel when given.  Both calls only enqueue.  Raised by the device:
+ *   GAPRO_ERR_BAD_ARG     GAPRO_QS_FLAG_OFFSETS: offsets that decrease or leave [0, n_points] / [0, m_total], or a query
+ *                         beyond the last new_offset.  Such a sample writes no index (its queries: rows of zeros)
+ *   GAPRO_ERR_BAD_ARG     GAPRO_QS_FLAG_EMPTY: fps, a sample with outputs and no points: its outputs are -1
+ *   GAPRO_ERR_NOT_FINITE  GAPRO_QS_FLAG_NOT_FINITE: fps, a coordinate that is not finite; the indices stay inside the
+ *                         sample's range.  A bad argument wins over it
+ * Nothing is read or written out of range in any of these cases.  Refused before anything is launched
+ * (GAPRO_ERR_BAD_ARG): a null argument, n_points or m_total outside [0, 2^31 - 1], n_samples outside [1,
+ * GAPRO_QS_MAX_SAMPLES], an unknown flag, nsample outside [1, GAPRO_BALL_QUERY_MAX_NSAMPLE], m_total * nsample beyond
+ * 2^31 - 1, a radius that is not finite; GAPRO_ERR_WORKSPACE: a workspace smaller than gapro_fps_workspace_bytes.
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_FPS_THREADS 1024
+#define GAPRO_FPS_RESIDENT 0   /* gapro_fps_plan: coordinates and minima in registers */
+#define GAPRO_FPS_STREAMED 1   /* the minima in registers, the coordinates read from L2 every iteration */
+#define GAPRO_FPS_GLOBAL 2     /* the minima in the workspace */
+#define GAPRO_FPS_SKIP_ORIGIN 1
+#define GAPRO_QS_LOCAL_INDEX 2
+#define GAPRO_QS_MAX_SAMPLES 4096
+#define GAPRO_QS_STATUS_WORDS 4
+#define GAPRO_QS_FLAG_OFFSETS 1
+#define GAPRO_QS_FLAG_EMPTY 2
+#define GAPRO_QS_FLAG_NOT_FINITE 4
+#define GAPRO_BALL_QUERY_MAX_NSAMPLE 4096
+int gapro_fps_plan(int64_t n_max, int64_t* xyz_capacity /* or NULL */, int64_t* capacity /* or NULL */);
+size_t gapro_fps_workspace_bytes(int64_t n_points);
+int gapro_fps_batch(gapro_ctx* ctx, void* stream, int64_t n_points, const float* d_xyz, int32_t n_samples,
+                    const void* d_offset, int32_t offset_i64, const void* d_new_offset, int32_t new_offset_i64,
+                    int64_t m_total, int32_t flags, void* d_workspace, size_t workspace_bytes,
+                    int32_t* d_idx /* [m_total] */, float* d_dist /* [n_points] or NULL */, int32_t* d_status,
+                    int32_t* h_status_pinned /* NULL: no copy */);
+int gapro_ball_query_batch(gapro_ctx* ctx, void* stream, int64_t n_points, const float* d_xyz, int64_t m_total,
+                           const float* d_new_xyz, int32_t n_samples, const void* d_offset, int32_t offset_i64,
+                           const void* d_new_offset, int32_t new_offset_i64, double radius, int32_t nsample,
+                           int32_t flags, int32_t* d_idx /* [m_total, nsample] */,
+                           int32_t* d_counts /* [m_total] or NULL */, int32_t* d_status,
+                           int32_t* h_status_pinned /* NULL: no copy */);
+
+/* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
  * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
  * to superpoint means (:64-69) or by keeping the npoint_nearest points of each side nearest to the centroid of the
