@@ -21,7 +21,8 @@ _EXPORTS = {
     "consumer_ops": ("get_instance_info", "prepare_instance_labels", "get_spp_gt", "get_subsample_gt", "match_cost",
                      "linear_sum_assignment", "hungarian_match", "point_wise_losses", "criterion_losses",
                      "get_instance", "mask_nms", "rle_encode_gpu_batch", "furthestsampling_batchflat",
-                     "ballquery_batchflat", "furthest_point_sample", "ball_query", "sample_queries"),
+                     "ballquery_batchflat", "furthest_point_sample", "ball_query", "sample_queries",
+                     "voxelization_idx", "voxelization"),
 }
 __all__ = [n for names in _EXPORTS.values() for n in names]
 

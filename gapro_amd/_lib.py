@@ -232,6 +232,15 @@ QS_STATUS_WORDS = 4  # GAPRO_QS_STATUS_WORDS: status, flags (1: offsets, 2: a sa
 FPS_SKIP_ORIGIN, QS_LOCAL_INDEX = 1, 2                # the flags of gapro_fps_batch / gapro_ball_query_batch
 FPS_PATHS = ("resident", "streamed", "global")        # GAPRO_FPS_RESIDENT, _STREAMED, _GLOBAL
 QS_MAX_SAMPLES, BALL_QUERY_MAX_NSAMPLE = 4096, 4096
+VOXELIZE_MAX_ACTIVE = 4096    # GAPRO_VOXELIZE_MAX_ACTIVE: points of one voxel in modes 3 and 4
+VOXELIZE_STATUS_WORDS = 4     # GAPRO_VOXELIZE_STATUS_WORDS: status, flags, 0, 0 (the header: n_voxels, max_active)
+
+
+class VoxelizeHeader(C.Structure):
+    """gapro_voxelize_header: what gapro_voxelize_count / gapro_voxelize_host_count report."""
+    _fields_ = [("status", C.c_int32), ("flags", C.c_int32), ("n_voxels", C.c_int32), ("max_active", C.c_int32)]
+
+
 POINT_LOSS_N = 4                                     # GAPRO_POINT_LOSS_N: sem, corners, giou, conf
 POINT_LOSS_MIN_CLASSES, POINT_LOSS_MAX_CLASSES = 2, 64  # GAPRO_POINT_LOSS_MIN_CLASSES / _MAX_CLASSES
 POINT_LOSS_MAX_POINTS = (1 << 31) - 1                 # n_points of one call
@@ -340,6 +349,22 @@ SIGNATURES = {
     "gapro_ball_query_batch": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_int32,
                                          C.c_double, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "gapro_lsap_solve": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.POINTER(C.c_int32), _P, _P]),
+    "gapro_voxelize_table_shape": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "gapro_voxelize_plan": (C.c_int64, [C.c_int64]),
+    "gapro_voxelize_hash": (C.c_uint64, [_P, C.c_int32]),
+    "gapro_voxelize_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gapro_voxelize_count": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, _P, C.c_size_t, _P, _P, _P]),
+    "gapro_voxelize_fill": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int64, C.c_int64, _P,
+                                      C.c_size_t, _P, _P, _P, _P, _P]),
+    "gapro_voxelize_host_count": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, C.POINTER(VoxelizeHeader),
+                                            C.POINTER(C.c_void_p)]),
+    "gapro_voxelize_host_fill": (C.c_int, [_P, _P, _P, _P, _P]),
+    "gapro_voxelize_host_free": (None, [_P]),
+    "gapro_voxel_pool_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gapro_voxel_pool_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int32,
+                                           C.c_int32, _P, C.c_size_t, _P, _P, _P]),
+    "gapro_voxel_pool_backward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int32, _P,
+                                            _P, _P]),
     "gapro_schedule_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "gapro_schedule_free": (None, [_P]),
     "gapro_schedule_get_counts": (C.c_int, [_P, C.POINTER(ScheduleCounts)]),
@@ -523,7 +548,7 @@ def load() -> C.CDLL:
                                             "gapro_schedule_export_testers", "gapro_spp_vote",
                                             "gapro_fit_launch_plan", "gapro_inst_", "gapro_spp_gt_", "gapro_match_",
                                             "gapro_proposals_", "gapro_fps_", "gapro_ball_query_",
-                                            "gapro_lsap_")):
+                                            "gapro_lsap_", "gapro_voxelize_", "gapro_voxel_pool_")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

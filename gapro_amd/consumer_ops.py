@@ -1,7 +1,8 @@
 """Consumer-side label ops on the GPU: the first thing ISBNet / SPFormer do with
 the pseudo labels this package generates.  Same semantics as the reference lines cited per function; the work is
 done by gapro_amd/csrc/consumer.hip behind the C ABI; the losses are ``torch.autograd.Function``s whose backward
-uses the gradients the forward launch already produced.  There is no CPU path.
+uses the gradients the forward launch already produced.  There is no CPU path, with one exception:
+``voxelization_idx`` on CPU tensors takes the library's host path (csrc/voxelize_host.cc), for DataLoader workers.
 """
 from __future__ import annotations
 
@@ -1632,3 +1633,209 @@ def sample_queries(locs, batch_offsets, batch_size, n_sample, radius, n_neighbor
     neighbor_inds = ballquery_batchflat(radius, n_neighbor, locs, fps_locs, off, n_sample=n_sample, check=check)
     fps_locs = fps_locs.view(batch_size, n_sample, 3)
     return fps_inds, neighbor_inds, ball_query(2 * radius, n_neighbor_post, fps_locs, fps_locs)
+
+
+# ---- voxelisation: the first tensors of a consumer's step (csrc/voxelize.hip, csrc/voxelize_host.cc) ---
+_VOX_CAUSES = ((1, "a negative batch index"),
+               (2, "mode 0 and a voxel that holds two points"),
+               (4, "a table that is not the count's"))
+_POOL_CAUSES = ((1, "a count outside [0, max_active]"),
+                (2, "a point index outside [0, n_points)"),
+                (4, "a point listed twice"))
+
+
+def voxelize_plan(n_points):
+    """``gapro_voxelize_plan`` without a device: the slots of the device path's table for ``n_points`` points (a power
+    of two); the slot a row starts its probes at is ``voxelize_hash(row) & (slots - 1)``."""
+    if not _is_int(n_points) or not 1 <= n_points <= 2 ** 31 - 1:
+        raise ValueError("voxelize_plan: n_points must be an int in [1, 2^31 - 1]")
+    return int(_lib.load().gapro_voxelize_plan(n_points))
+
+
+def voxelize_hash(coords):
+    """``gapro_voxelize_hash`` of every row of an int64 ``[n, 3]`` / ``[n, 4]`` array: ``uint64[n]`` (a host loop: for
+    tests and tools)."""
+    rows = np.ascontiguousarray(coords, dtype=np.int64)
+    if rows.ndim != 2 or rows.shape[1] not in (3, 4):
+        raise ValueError("voxelize_hash: coords must be an int64 array of shape [n, 3] or [n, 4]")
+    fn, cols, base = _lib.load().gapro_voxelize_hash, rows.shape[1], rows.ctypes.data
+    return np.array([fn(base + 8 * cols * i, cols) for i in range(rows.shape[0])], dtype=np.uint64)
+
+
+def voxel_table_shape(mode, n_voxels, max_active):
+    """The header arithmetic of ``voxelization_idx`` (``gapro_voxelize_table_shape``; nothing is allocated): the width
+    of ``output_map`` for a header that reports ``n_voxels`` and ``max_active``, ``max_active + 1`` in modes 3 and 4 and 2
+    otherwise.  A ``ValueError`` for what the call refuses from its header: ``max_active`` beyond
+    ``GAPRO_VOXELIZE_MAX_ACTIVE`` (modes 3, 4), ``n_voxels * width`` beyond 2^31 - 1, two points in a voxel in mode 0."""
+    who = "voxelization_idx"
+    if not _is_int(mode) or not 0 <= mode <= 4:
+        raise ValueError("%s: mode must be an int in 0..4" % who)
+    width = C.c_int64(0)
+    if _lib.load().gapro_voxelize_table_shape(mode, int(n_voxels), int(max_active), C.byref(width)) != _lib.GAPRO_OK:
+        raise ValueError("%s: %d voxels of at most %d points in mode %d: beyond the library's bounds (%d points a voxel, "
+                         "2^31 - 1 table entries, one point a voxel in mode 0)"
+                         % (who, n_voxels, max_active, mode, _lib.VOXELIZE_MAX_ACTIVE))
+    return int(width.value)
+
+
+def _vox_header(who, hdr, mode):
+    _refuse(who, hdr.status, hdr.flags, _VOX_CAUSES)
+    return int(hdr.n_voxels), voxel_table_shape(mode, hdr.n_voxels, hdr.max_active)
+
+
+def voxelization_idx(coords, batchsize, mode=4):
+    """``isbnet.ops.voxelization_idx`` / ``pointgroup_ops.voxelization_idx`` (ISBNet/isbnet/data/custom.py:296,
+    SPFormer/spformer/dataset/scannetv2.py:363): ``(output_coords int64[M, cols], input_map int32[N], output_map
+    int32[M, width])`` of ``coords``, int64 ``[N, 3]`` or ``[N, 4]`` with the batch index in column 0.
+
+    The definition: a voxel is a distinct row over all columns and all 64 bits; VOXELS ARE NUMBERED BY
+    THE INDEX OF THEIR FIRST POINT, ascending (the reference's hash map in insertion order, not ``torch.unique``'s
+    sorted order); ``input_map`` is the voxel of each point, ``output_coords`` the row of each voxel's first point.
+    Modes 3 and 4: ``width = max_active + 1`` and a row of ``output_map`` is ``[count, its points ascending, zeros]``;
+    mode 1: ``[1, first point]``; mode 2: ``[1, last point]`` (the code of the reference, not its comment); mode 0: as
+    mode 1, and two points in a voxel are refused.  ``batchsize`` only sizes a vector in the reference: a positive int,
+    otherwise ignored.  ``N = 0`` returns empty tensors of shapes ``(0, cols)``, ``(0,)`` and ``(0, 2)``.
+
+    CPU tensors take the host path (``gapro_voxelize_host_*``: an ordinary hash map, no device in the process -- what a
+    DataLoader worker calls) and return CPU tensors; device tensors take the device path (count, ONE host read of the
+    header, fill) and return device tensors.  Both give the same bits.  A ``GaproError``: a negative batch index, mode 0
+    on a duplicate.  A ``ValueError``: a bad argument, and what the header refuses (``voxel_table_shape``)."""
+    who = "voxelization_idx"
+    if not isinstance(coords, torch.Tensor) or coords.dtype != torch.int64 or coords.dim() != 2 or \
+            coords.shape[1] not in (3, 4):
+        raise ValueError("%s: coords must be an int64 tensor of shape [N, 3] or [N, 4]" % who)
+    _positive_int_arg(who, "batchsize", batchsize)
+    if not _is_int(mode) or not 0 <= mode <= 4:
+        raise ValueError("%s: mode must be an int in 0..4" % who)
+    n, cols = int(coords.shape[0]), int(coords.shape[1])
+    if n > 2 ** 31 - 1:
+        raise ValueError("%s: %d points are beyond the library's bounds" % (who, n))
+    dev = coords.device
+    if n == 0:
+        return (torch.empty((0, cols), dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                torch.empty((0, 2), dtype=torch.int32, device=dev))
+    coords = coords.detach().contiguous()
+    if not coords.is_cuda:
+        lib = _lib.load()
+        input_map = torch.empty(n, dtype=torch.int32)
+        hdr, handle = _lib.VoxelizeHeader(), C.c_void_p()
+        rc = lib.gapro_voxelize_host_count(coords.data_ptr(), n, cols, mode, input_map.data_ptr(), C.byref(hdr),
+                                           C.byref(handle))
+        try:
+            if rc != _lib.GAPRO_OK:
+                raise GaproError(rc, who)
+            M, width = _vox_header(who, hdr, mode)
+            out_coords = torch.empty((M, cols), dtype=torch.int64)
+            out_map = torch.empty((M, width), dtype=torch.int32)
+            rc = lib.gapro_voxelize_host_fill(handle, coords.data_ptr(), input_map.data_ptr(), out_coords.data_ptr(),
+                                              out_map.data_ptr())
+            if rc != _lib.GAPRO_OK:
+                raise GaproError(rc, who)
+        finally:
+            lib.gapro_voxelize_host_free(handle)
+        return out_coords, input_map, out_map
+    ctx, stream = _ctx_stream(coords)
+    lib = ctx.lib
+    with torch.cuda.device(dev):
+        ws = _workspace(who, int(lib.gapro_voxelize_workspace_bytes(n)), dev, "%d points are" % n)
+        input_map = torch.empty(n, dtype=torch.int32, device=dev)
+        d_hdr, h_hdr = _status_pair(dev, C.sizeof(_lib.VoxelizeHeader))
+        ctx.check(lib.gapro_voxelize_count(ctx.handle, stream, n, cols, coords.data_ptr(), mode, ws.data_ptr(),
+                                           ws.numel(), input_map.data_ptr(), d_hdr.data_ptr(), h_hdr.data_ptr()))
+        hdr, _ = _host_read(dev, h_hdr, _lib.VoxelizeHeader)  # the call's one host read
+        M, width = _vox_header(who, hdr, mode)
+        out_coords = torch.empty((M, cols), dtype=torch.int64, device=dev)
+        out_map = torch.empty((M, width), dtype=torch.int32, device=dev)
+        d_status, _ = _status_pair(dev, _lib.VOXELIZE_STATUS_WORDS, torch.int32, read=False)
+        ctx.check(lib.gapro_voxelize_fill(ctx.handle, stream, n, cols, coords.data_ptr(), mode, M, hdr.max_active,
+                                          ws.data_ptr(), ws.numel(), input_map.data_ptr(), out_coords.data_ptr(),
+                                          out_map.data_ptr(), d_status.data_ptr(), None))
+    return out_coords, input_map, out_map
+
+
+class Voxelization(torch.autograd.Function):
+    """``isbnet.ops.functions.Voxelization``: see ``voxelization``, which checks the arguments first."""
+
+    @staticmethod
+    def forward(fctx, feats, map_rule, mode=4, check=True):
+        who = "voxelization"
+        N, Cn = int(feats.shape[0]), int(feats.shape[1])
+        M, A = int(map_rule.shape[0]), int(map_rule.shape[1]) - 1
+        dev = feats.device
+        feats, map_rule = feats.detach().contiguous(), map_rule.contiguous()
+        fctx.plan = (map_rule, mode, N, Cn, M, A)
+        out = torch.empty((M, Cn), dtype=torch.float32, device=dev)
+        if M == 0:
+            return out
+        if N == 0:  # every listed index is out of range; the rows pool to zeros as flagged rows do
+            return out.zero_()
+        ctx, stream = _ctx_stream(feats)
+        lib = ctx.lib
+        with torch.cuda.device(dev):
+            ws = _workspace(who, int(lib.gapro_voxel_pool_workspace_bytes(N)), dev) if check else None
+            d_status, h_status = _status_pair(dev, _lib.VOXELIZE_STATUS_WORDS, torch.int32, read=check)
+            ctx.check(lib.gapro_voxel_pool_forward(ctx.handle, stream, N, Cn, feats.data_ptr(), M, A,
+                                                   map_rule.data_ptr(), mode, int(check), _ptr(ws),
+                                                   ws.numel() if check else 0, out.data_ptr(), d_status.data_ptr(),
+                                                   _ptr(h_status)))
+            if h_status is not None:  # the call's host read of its status, asked for by check=True
+                status, flags = _host_read(dev, h_status)[:2]
+                _refuse(who, status, flags, _POOL_CAUSES)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad_out):
+        map_rule, mode, N, Cn, M, A = fctx.plan
+        dev = grad_out.device
+        if M == 0 or N == 0:
+            return torch.zeros((N, Cn), dtype=torch.float32, device=dev), None, None, None
+        grad_out = grad_out.contiguous()
+        ctx, stream = _ctx_stream(grad_out)
+        with torch.cuda.device(dev):
+            d_feats = torch.empty((N, Cn), dtype=torch.float32, device=dev)
+            d_status, _ = _status_pair(dev, _lib.VOXELIZE_STATUS_WORDS, torch.int32, read=False)
+            ctx.check(ctx.lib.gapro_voxel_pool_backward(ctx.handle, stream, N, Cn, grad_out.data_ptr(), M, A,
+                                                        map_rule.data_ptr(), mode, d_feats.data_ptr(),
+                                                        d_status.data_ptr(), None))
+        return d_feats, None, None, None
+
+
+def voxelization(feats, map_rule, mode=4, *, check=True, n_points=None):
+    """``isbnet.ops.voxelization`` / ``pointgroup_ops.voxelization`` (ISBNet/isbnet/model/isbnet.py:265, 478, 672;
+    SPFormer/spformer/model/spformer.py:115-120): ``f32[M, C]``, the rows of ``feats`` (``f32[N, C]``) pooled into voxel
+    rows through ``map_rule`` (``int32[M, A + 1]``, the ``output_map`` of ``voxelization_idx`` or any table of that
+    shape), both on the device; a ``torch.autograd.Function`` (``Voxelization``).
+
+    Forward, for row ``v`` with ``n = map_rule[v, 0]``: ``mult = 1.0f / n`` when ``mode == 4`` and ``n > 0``, else 1;
+    ``out[v, c] = ((0 + fl(mult * x_1)) + fl(mult * x_2)) + ...`` IN THE ROW'S ORDER, in float32, product and sum each
+    rounded on their own -- the order of the reference's atomic adds into a zeroed buffer.  Not "sum, then divide", not
+    a fused multiply-add; a single ``-0.0`` input gives ``+0.0``.  A row with ``n = 0`` is zeros.  Every mode runs this
+    kernel; modes other than 4 sum the rows as given.
+    Backward: ``d_feats[p, c] = fl(mult * d_out[v, c])`` for every point ``p`` listed in row ``v``, 0 for every unlisted
+    point: the array is cleared and the rows stored, with no floating-point atomics.  THE CONTRACT: this equals the
+    reference for every table in which a point is listed at most once, which holds for every table
+    ``voxelization_idx`` produces; a point listed twice receives one of its rows' gradients, not their sum.
+
+    ``check=True`` reads a status word behind the forward kernel (the call's one host read): a count outside ``[0,
+    A]``, a point index outside ``[0, N)`` and a point listed twice are a ``GaproError``.  With ``check=False`` the call
+    only enqueues; a flagged row pools to zeros, a flagged entry is skipped, nothing is touched out of range.  The
+    backward never reads.  ``n_points=`` states the number of points the table was built for: a ``ValueError`` when
+    ``feats`` has another number of rows.  Only float32 is built."""
+    who = "voxelization"
+    _tensor_arg(who, "feats", feats, ("N", "C"))
+    if not isinstance(map_rule, torch.Tensor) or map_rule.dtype != torch.int32 or map_rule.dim() != 2:
+        raise ValueError("%s: map_rule must be an int32 tensor of shape [M, A + 1]" % who)
+    if int(feats.shape[1]) < 1 or int(map_rule.shape[1]) < 2:
+        raise ValueError("%s: feats needs a channel and map_rule a count and an index column" % who)
+    if not _is_int(mode) or not 0 <= mode <= 4:
+        raise ValueError("%s: mode must be an int in 0..4" % who)
+    if not isinstance(check, bool):
+        raise ValueError("%s: check must be a bool" % who)
+    if n_points is not None and (not _is_int(n_points) or n_points != int(feats.shape[0])):
+        raise ValueError("%s: feats has %d rows, n_points=%r" % (who, int(feats.shape[0]), n_points))
+    if int(map_rule.shape[0]) * int(map_rule.shape[1]) > 2 ** 31 - 1 or int(feats.shape[0]) > 2 ** 31 - 1:
+        raise ValueError("%s: a table or a point count beyond the library's bounds" % who)
+    _need_device(feats, map_rule)
+    _one_device(who, feats.device, (map_rule,))
+    return Voxelization.apply(feats, map_rule, mode, check)

@@ -1334,6 +1334,101 @@ int gapro_ball_query_batch(gapro_ctx* ctx, void* stream, int64_t n_points, const
                            int32_t* h_status_pinned /* NULL: no copy */);
 
 /* ------------------------------------------------------------------------------------------
+ * Voxelisation (csrc/voxelize.hip, csrc/voxelize_host.cc).  Replaces the CUDA-only extension behind
+ * isbnet.ops / pointgroup_ops voxelization_idx and voxelization (src/voxelize/voxelize.cpp, voxelize.cu).
+ * The definition.  coords is int64[n_points, cols], cols 3 or 4 (4: the batch index in column 0).  A voxel is a
+ * distinct row, over all columns and all 64 bits of each value.  VOXELS ARE NUMBERED BY THE INDEX OF THEIR FIRST POINT
+ * IN ASCENDING ORDER
+ * (the insertion order of the reference's hash map, not a sorted order).
+ *   input_map     i32[n_points]            the voxel of each point
+ *   output_coords i64[n_voxels, cols]      the row of each voxel's first point
+ *   output_map    i32[n_voxels, width]     modes 3, 4: width = max_active + 1, a row is {count, its point indices in
+ *                                          ascending order, zeros}; mode 1: {1, first point}; mode 2: {1, last point};
+ *                                          mode 0: as mode 1, refused when a voxel holds two points (width 2 for 0..2)
+ * max_active is the largest number of points in a voxel (every mode reports it; modes 3 and 4 refuse one beyond
+ * GAPRO_VOXELIZE_MAX_ACTIVE).  gapro_voxelize_table_shape is the header arithmetic both paths share: *width for the
+ * mode, GAPRO_ERR_BAD_ARG for a mode outside 0..4, n_voxels or max_active < 1, max_active > 1 in mode 0, max_active
+ * beyond the cap in modes 3 and 4, or n_voxels * width beyond 2^31 - 1.
+ * Device path, count / one header read / fill.  gapro_voxelize_count writes d_input_map and d_header
+ * (gapro_voxelize_header, cleared by the call, copied to h_header_pinned behind the kernels when given);
+ * gapro_voxelize_fill takes n_voxels and max_active as the caller read them, the SAME workspace
+ * (gapro_voxelize_workspace_bytes(n_points) bytes; 0 for sizes the calls refuse) and writes d_output_coords and
+ * d_output_map whole.  Both only enqueue.  The count: an open-addressing table of gapro_voxelize_plan slots (a power of
+ * two, at least 2 n_points up to 2^31), a slot claimed by compare-and-swap and lowered to its voxel's first point by an
+ * integer atomic minimum, an exclusive scan of the "first" flags, integer atomic counts.  The fill: points claim row
+ * slots by the count's atomics, then every row is put in ascending order by rank counting (rows up to 8 entries by 8
+ * lanes, up to 64 by a wave, longer ones by a workgroup through LDS).  Integer atomics only; every probe loop is
+ * bounded by the table; no workgroup waits for another; the results do not depend on the schedule.
+ * Raised by the device (header.status / header.flags; fill: d_status i32[GAPRO_VOXELIZE_STATUS_WORDS]):
+ *   GAPRO_ERR_BAD_ARG  GAPRO_VOXELIZE_FLAG_BATCH: a negative batch index (4 columns); the point joins no voxel
+ *   GAPRO_ERR_BAD_ARG  GAPRO_VOXELIZE_FLAG_DUPLICATE: mode 0 and a voxel of two points
+ *   GAPRO_ERR_BAD_ARG  GAPRO_VOXELIZE_FLAG_TABLE: fill, n_voxels / max_active that are not the count's
+ * Nothing is read or written out of range in any of these cases.  Refused before anything is launched
+ * (GAPRO_ERR_BAD_ARG): a null argument, n_points outside [1, 2^31 - 1], cols other than 3 or 4, a mode outside 0..4,
+ * what gapro_voxelize_table_shape refuses; GAPRO_ERR_WORKSPACE: a workspace smaller than
+ * gapro_voxelize_workspace_bytes.  gapro_voxelize_hash is the table's hash of a row (the slot is hash & (slots - 1)).
+ * Host path (no device in the process: a DataLoader worker): gapro_voxelize_host_count fills input_map and the header
+ * and returns a handle, gapro_voxelize_host_fill writes the two tables from it, gapro_voxelize_host_free releases it.
+ * An ordinary hash map in insertion order: an independent second implementation of the definition above.
+ * Pooling.  feats f32[n_points, n_channels], map_rule i32[n_voxels, max_active + 1] (any table of that shape).
+ * gapro_voxel_pool_forward: for row v with n = map_rule[v, 0], mult = 1.0f / (float)n when mode == 4 and n > 0, else
+ *   1.0f; out[v, c] = (((+0 + fl(mult * x_1)) + fl(mult * x_2)) + ...) in the row's order, in float32, the product and
+ *   the sum each rounded on their own (no contraction): the order of the reference's atomic adds from a zeroed buffer.
+ *   A row with n = 0 is zeros; every mode runs this kernel.
+ * gapro_voxel_pool_backward: d_feats[p, c] = fl(mult * d_out[v, c]) for every point p listed in row v, 0 for every
+ *   unlisted point: the array is cleared, then plain stores by row -- no floating-point atomics.  This equals the
+ *   reference for every table that lists a point at most once (every table gapro_voxelize_fill writes).
+ * d_status i32[GAPRO_VOXELIZE_STATUS_WORDS] = {status, flags, 0, 0}, cleared by the call, copied to h_status_pinned
+ * when given.  GAPRO_ERR_BAD_ARG with GAPRO_VOXEL_POOL_FLAG_COUNT (a count outside [0, max_active]: the row pools to zeros
+ * and receives no gradient), _INDEX (a point index outside [0, n_points): the entry is skipped), _TWICE (forward with
+ * check != 0 only: a point listed twice, found with an int32 mark per point in the workspace,
+ * gapro_voxel_pool_workspace_bytes(n_points) bytes, and integer atomics).  Refused before anything is launched: a null
+ * argument, n_points, n_voxels or n_channels outside [1, 2^31 - 1], max_active < 1, n_voxels * (max_active + 1) beyond
+ * 2^31 - 1 (the products with n_channels are 64-bit); GAPRO_ERR_WORKSPACE: check and a workspace that is too small.
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_VOXELIZE_MAX_ACTIVE 4096
+#define GAPRO_VOXELIZE_STATUS_WORDS 4
+#define GAPRO_VOXELIZE_FLAG_BATCH 1
+#define GAPRO_VOXELIZE_FLAG_DUPLICATE 2
+#define GAPRO_VOXELIZE_FLAG_TABLE 4
+#define GAPRO_VOXEL_POOL_FLAG_COUNT 1
+#define GAPRO_VOXEL_POOL_FLAG_INDEX 2
+#define GAPRO_VOXEL_POOL_FLAG_TWICE 4
+typedef struct gapro_voxelize_header {
+  int32_t status;      /* gapro_status raised on the device */
+  int32_t flags;       /* GAPRO_VOXELIZE_FLAG_* */
+  int32_t n_voxels;    /* M */
+  int32_t max_active;  /* the largest number of points in a voxel, whatever the mode */
+} gapro_voxelize_header;
+int gapro_voxelize_table_shape(int32_t mode, int64_t n_voxels, int64_t max_active, int64_t* width /* or NULL */);
+int64_t gapro_voxelize_plan(int64_t n_points);  /* slots of the device table; 0: n_points outside [1, 2^31 - 1] */
+uint64_t gapro_voxelize_hash(const int64_t* row, int32_t cols);
+size_t gapro_voxelize_workspace_bytes(int64_t n_points);
+int gapro_voxelize_count(gapro_ctx* ctx, void* stream, int64_t n_points, int32_t cols, const int64_t* d_coords,
+                         int32_t mode, void* d_workspace, size_t workspace_bytes, int32_t* d_input_map /* [n_points] */,
+                         gapro_voxelize_header* d_header, gapro_voxelize_header* h_header_pinned /* NULL: no copy */);
+int gapro_voxelize_fill(gapro_ctx* ctx, void* stream, int64_t n_points, int32_t cols, const int64_t* d_coords,
+                        int32_t mode, int64_t n_voxels, int64_t max_active, const void* d_workspace,
+                        size_t workspace_bytes, const int32_t* d_input_map, int64_t* d_output_coords /* [M, cols] */,
+                        int32_t* d_output_map /* [M, width] */, int32_t* d_status,
+                        int32_t* h_status_pinned /* NULL: no copy */);
+int gapro_voxelize_host_count(const int64_t* coords, int64_t n_points, int32_t cols, int32_t mode,
+                              int32_t* input_map /* [n_points] */, gapro_voxelize_header* header, void** handle);
+int gapro_voxelize_host_fill(const void* handle, const int64_t* coords, const int32_t* input_map,
+                             int64_t* output_coords /* [M, cols] */, int32_t* output_map /* [M, width] */);
+void gapro_voxelize_host_free(void* handle);
+size_t gapro_voxel_pool_workspace_bytes(int64_t n_points);
+int gapro_voxel_pool_forward(gapro_ctx* ctx, void* stream, int64_t n_points, int32_t n_channels, const float* d_feats,
+                             int64_t n_voxels, int64_t max_active, const int32_t* d_map_rule, int32_t mode,
+                             int32_t check, void* d_workspace /* check: the marks */, size_t workspace_bytes,
+                             float* d_out /* [M, C] */, int32_t* d_status,
+                             int32_t* h_status_pinned /* NULL: no copy */);
+int gapro_voxel_pool_backward(gapro_ctx* ctx, void* stream, int64_t n_points, int32_t n_channels,
+                              const float* d_grad_out /* [M, C] */, int64_t n_voxels, int64_t max_active,
+                              const int32_t* d_map_rule, int32_t mode, float* d_grad_feats /* [N, C] */,
+                              int32_t* d_status, int32_t* h_status_pinned /* NULL: no copy */);
+
+/* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
  * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
  * to superpoint means (:64-69) or by keeping the npoint_nearest points of each side nearest to the centroid of the
