@@ -22,7 +22,8 @@ _EXPORTS = {
                      "linear_sum_assignment", "hungarian_match", "point_wise_losses", "criterion_losses",
                      "get_instance", "mask_nms", "rle_encode_gpu_batch", "furthestsampling_batchflat",
                      "ballquery_batchflat", "furthest_point_sample", "ball_query", "sample_queries",
-                     "voxelization_idx", "voxelization"),
+                     "voxelization_idx", "voxelization", "spformer_match", "spformer_layer_losses",
+                     "spformer_criterion"),
 }
 __all__ = [n for names in _EXPORTS.values() for n in names]
 

@@ -228,6 +228,25 @@ class MatchLossTask(C.Structure):
 
 MATCH_LOSS_N = 7          # GAPRO_MATCH_LOSS_N: dice, bce, cls, iou, box, giou, levelset
 MATCH_LOSS_MAX_FEATS = 8  # GAPRO_MATCH_LOSS_MAX_FEATS
+
+
+class SpfLossTask(C.Structure):
+    """gapro_spf_loss_task: one (head, sample) of gapro_spf_loss_forward."""
+    _fields_ = [("d_labels", C.c_void_p), ("d_scores", C.c_void_p), ("d_mask_logits", C.c_void_p),
+                ("ld_logits", C.c_int64), ("d_gt_masks", C.c_void_p), ("d_gt_labels", C.c_void_p),
+                ("d_gt_boxes", C.c_void_p), ("n_gt", C.c_int32), ("n_inst", C.c_int32), ("n_cols", C.c_int32),
+                ("reserved", C.c_int32), ("col_offset", C.c_int64), ("row_offset", C.c_int64)]
+
+
+class SpfLossDims(C.Structure):
+    """gapro_spf_loss_dims: the sizes and switches of gapro_spf_loss_forward / _backward."""
+    _fields_ = [("n_heads", C.c_int32), ("batch_size", C.c_int32), ("n_queries", C.c_int32), ("n_classes", C.c_int32),
+                ("cls_type", C.c_int32), ("n_feats", C.c_int32), ("min_points", C.c_int32), ("flags", C.c_int32),
+                ("non_object_weight", C.c_double)]
+
+
+SPF_LOSS_N = 5                                   # GAPRO_SPF_LOSS_N: cls, mask_bce, mask_dice, score, levelset
+SPF_WEIGHTED_BCE, SPF_DICE_DIV_MAIN = 1, 2       # GAPRO_SPF_WEIGHTED_BCE, GAPRO_SPF_DICE_DIV_MAIN
 QS_STATUS_WORDS = 4  # GAPRO_QS_STATUS_WORDS: status, flags (1: offsets, 2: a sample without points, 4: not finite), 0, 0
 FPS_SKIP_ORIGIN, QS_LOCAL_INDEX = 1, 2                # the flags of gapro_fps_batch / gapro_ball_query_batch
 FPS_PATHS = ("resident", "streamed", "global")        # GAPRO_FPS_RESIDENT, _STREAMED, _GLOBAL
@@ -337,6 +356,9 @@ SIGNATURES = {
     "gapro_match_loss_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                             _P, _P, _P, _P, _P, _P, _P, C.c_double, _P, C.c_size_t, _P, _P, _P, _P,
                                             _P]),
+    "gapro_spf_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "gapro_spf_loss_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.c_size_t, _P, _P, _P]),
+    "gapro_spf_loss_backward": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
     "gapro_point_loss_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32]),
     "gapro_point_loss_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P,
                                            _P, _P, _P, _P, C.c_int64, C.c_double, _P, C.c_size_t, _P, _P, _P]),

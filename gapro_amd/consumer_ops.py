@@ -151,11 +151,11 @@ def _refuse(who, status, flags, causes):
 _constants = {}  # (device, the values) -> the float32 tensor on the device
 
 
-def _device_constant(dev, values):
-    """A tuple of numbers as a float32 tensor on ``dev``: uploaded once per device and kept."""
-    key = (dev, values)
+def _device_constant(dev, values, dtype=torch.float32):
+    """A tuple of numbers as a float32 (or ``dtype``) tensor on ``dev``: uploaded once per device and kept."""
+    key = (dev, values) if dtype == torch.float32 else (dev, values, dtype)
     if key not in _constants:
-        _constants[key] = torch.tensor(values, dtype=torch.float32).to(dev)
+        _constants[key] = torch.tensor(values, dtype=dtype).to(dev)
     return _constants[key]
 
 
@@ -1839,3 +1839,427 @@ def voxelization(feats, map_rule, mode=4, *, check=True, n_points=None):
     _need_device(feats, map_rule)
     _one_device(who, feats.device, (map_rule,))
     return Voxelization.apply(feats, map_rule, mode, check)
+
+
+# ---- SPFormer's criterion (gapro_amd/csrc/spf_loss.hip, match_cost.hip, lsap.cc) ------------------------
+SPF_LOSS_NAMES = ("cls_loss", "mask_bce_loss", "mask_dice_loss", "score_loss", "levelset_loss")  # the table's columns
+_SPF_OUT_NAMES = ("cls_loss", "score_loss", "mask_bce_loss", "mask_dice_loss", "levelset_loss")  # loss_out's order
+_SPF_CAUSES = ((1, "a GT label outside [0, num_class)"), (2, "a GT mask value that is neither 0 nor 1"))
+_SPF_PRED_KEYS = ("labels", "scores", "masks", "sp_coords", "sp_rgb_feats", "batch_offsets", "sp_prob_labels",
+                  "sp_mu_labels", "sp_var_labels", "sp_mu_preds", "sp_logvar_preds")
+_SPF_MASK_DTYPES = (torch.float32, torch.bool, torch.uint8, torch.int32, torch.int64)
+_spf_zeros = {}  # device -> the float32 zeros that stand in for the confidences and boxes SPFormer's matcher lacks
+
+
+def _spf_zero_buffer(dev, n):
+    if dev not in _spf_zeros or _spf_zeros[dev].numel() < n:
+        _spf_zeros[dev] = torch.zeros(n, dtype=torch.float32, device=dev)
+    return _spf_zeros[dev]
+
+
+def _spf_insts_arg(who, insts):
+    """The GT of every sample, duck-typed (an object or a dict with ``gt_labels``, ``gt_spmasks``, ``gt_boxes``):
+    ``None`` for a sample without an instance (the reference's ``len(inst) == 0``), else ``(labels, masks, boxes)`` as
+    given; returns them, the tensors and the labels' dtype."""
+    if not isinstance(insts, (list, tuple)) or not insts:
+        raise ValueError("%s: insts must be a non-empty list, one entry per sample" % who)
+    out, tensors, cls_dtype = [], [], None
+    for b, inst in enumerate(insts):
+        who_b = "%s: sample %d" % (who, b)
+        try:
+            cls, mask, box = ((inst[k] for k in ("gt_labels", "gt_spmasks", "gt_boxes")) if isinstance(inst, dict)
+                              else (inst.gt_labels, inst.gt_spmasks, inst.gt_boxes))
+            n = len(cls) if isinstance(inst, dict) else len(inst)
+        except (AttributeError, KeyError, TypeError):
+            raise ValueError("%s: an object or dict with gt_labels, gt_spmasks, gt_boxes and a length is expected"
+                             % who_b) from None
+        if n == 0:
+            out.append(None)
+            continue
+        if not isinstance(mask, torch.Tensor) or mask.dim() != 2 or mask.dtype not in _SPF_MASK_DTYPES \
+                or mask.shape[0] != n or mask.shape[1] == 0:
+            raise ValueError("%s: gt_spmasks must be a float32, bool or integer tensor of shape [%d, S]" % (who_b, n))
+        cls_dtype = _sample_labels_arg(who_b, "gt_labels", cls, "gt_boxes", box, n, cls_dtype)
+        out.append((cls, mask, box))
+        tensors += [cls, mask, box]
+    return out, tensors, cls_dtype
+
+
+def _spf_heads_arg(who, pred_labels, pred_masks, B, pred_scores=None):
+    """One head's tensors or lists over heads, as lists over heads; returns them with L1, Q, C and the tensors."""
+    single = isinstance(pred_labels, torch.Tensor)
+    labels = [pred_labels] if single else pred_labels
+    masks = [pred_masks] if single else pred_masks
+    scores = None if pred_scores is None else ([pred_scores] if single else pred_scores)
+    if not isinstance(labels, (list, tuple)) or not labels:
+        raise ValueError("%s: pred_labels must be a tensor or a non-empty list of tensors, one per head" % who)
+    L1 = len(labels)
+    for name, seq in (("pred_masks", masks), ("pred_scores", scores)):
+        if seq is not None and (not isinstance(seq, (list, tuple)) or len(seq) != L1):
+            raise ValueError("%s: %s must follow pred_labels: one head's, or a list of %d heads" % (who, name, L1))
+    _tensor_arg(who, "pred_labels", labels[0], (B, "Q", "C"), nonempty=True)
+    _, Q, n_classes = (int(v) for v in labels[0].shape)
+    if n_classes < 2:
+        raise ValueError("%s: pred_labels needs a class beside \"no object\"" % who)
+    if L1 * B > _lib.SPP_GT_MAX_SAMPLES:
+        raise ValueError("%s: %d heads of %d samples; heads * samples beyond %d" % (who, L1, B, _lib.SPP_GT_MAX_SAMPLES))
+    tensors = []
+    for h in range(L1):
+        who_h = "%s: head %d" % (who, h)
+        _tensor_arg(who_h, "pred_labels", labels[h], (B, Q, n_classes))
+        if not isinstance(masks[h], (list, tuple)) or len(masks[h]) != B:
+            raise ValueError("%s: pred_masks must be a list of %d tensors, one per sample" % (who_h, B))
+        for x in masks[h]:
+            _tensor_arg(who_h, "pred_masks", x, (Q, "S"))
+        tensors += [labels[h], *masks[h]]
+        if scores is not None:
+            s = scores[h]
+            if not isinstance(s, torch.Tensor) or s.dtype != torch.float32 or tuple(s.shape) not in ((B, Q), (B, Q, 1)):
+                raise ValueError("%s: pred_scores must be a float32 tensor of shape [%d, %d, 1] or [%d, %d]"
+                                 % (who_h, B, Q, B, Q))
+            tensors.append(s)
+    return single, labels, masks, scores, L1, Q, n_classes, tensors
+
+
+def _spf_widths_arg(who, masks, gts, Q):
+    """The number of columns of every sample: every head's mask logits and the sample's GT masks agree on it."""
+    widths = [int(x.shape[1]) for x in masks[0]]
+    for h, head in enumerate(masks):
+        for b, x in enumerate(head):
+            want = int(gts[b][1].shape[1]) if gts[b] is not None else widths[b]
+            if int(x.shape[1]) != want or (want == 0 and gts[b] is not None):
+                raise ValueError("%s: head %d, sample %d: pred_masks is %s, [%d, %d] is expected: one row per query and "
+                                 "one column per superpoint" % (who, h, b, tuple(x.shape), Q, want))
+    return [int(gts[b][1].shape[1]) if gts[b] is not None else widths[b] for b in range(len(widths))]
+
+
+def _three_weights_arg(who, cost_weight):
+    try:
+        vals = [float(v) for v in cost_weight]
+    except (TypeError, ValueError):
+        vals = []
+    if len(vals) != 3 or any(not _is_finite(v) or v < 0.0 for v in vals):
+        raise ValueError("%s: cost_weight must be three finite, non-negative numbers (class, mask BCE, dice)" % who)
+    return vals
+
+
+def spformer_match(pred_labels, pred_masks, insts, cost_weight=(1.0, 1.0, 1.0)):
+    """SPFormer's ``HungarianMatcher.forward`` (SPFormer/spformer/model/loss.py:198-222) for every prediction head of a
+    step at once: per head and sample the reference's ``(rows, cols)`` pair of int64 CPU tensors, ``([], [])`` as two
+    empty tensors for a sample without an instance.  ``pred_labels`` is one head's ``f32[B, Q, C]`` and ``pred_masks``
+    its list of ``f32[Q, S_b]`` (the result is then a list over the samples), or both are lists over the heads (a list
+    over the heads of such lists).  ``insts`` holds per sample any object with ``gt_labels`` (int32 / int64 ``[n]``),
+    ``gt_spmasks`` (``[n, S_b]`` of 0 / 1: float32, bool or integer), ``gt_boxes`` (``f32[n, 6]``) and ``len()``, or a
+    dict with these keys.  ``cost_weight`` is the reference's: class, mask BCE, dice.
+
+    All heads x samples are the "samples" of ONE ``gapro_match_cost`` call (the cost terms are the ISBNet matcher's
+    class, BCE and dice terms; its confidence and GIoU terms get the weight 0 and a buffer of zeros, and a weight of 0
+    times a finite term adds an exact zero, so nothing of ``gt_boxes`` reaches the cost).  The costs go to page-locked
+    memory behind the kernels, one stream synchronisation covers them all, and the assignments are solved by the
+    library on the host.  The matched pairs stay on the host: ``spformer_layer_losses`` uploads them inside its one
+    table.  A cost that is NaN or infinite becomes 100000, which the reference does not do (SciPy refuses such a
+    matrix).  No autograd.  Mismatched shapes, dtypes or devices, and more than ``1024`` heads x samples, are
+    ``ValueError``s before a device is touched; a label outside ``[0, C)`` or a mask value other than 0 / 1 is a
+    ``GaproError``."""
+    who = "spformer_match"
+    gts, tensors, cls_dtype = _spf_insts_arg(who, insts)
+    B = len(gts)
+    single, labels, masks, _, L1, Q, n_classes, head_tensors = _spf_heads_arg(who, pred_labels, pred_masks, B)
+    _spf_widths_arg(who, masks, gts, Q)
+    cw = _three_weights_arg(who, cost_weight)
+    dev = labels[0].device
+    _one_device(who, dev, tensors + head_tensors)
+    empty = (torch.empty(0, dtype=torch.int64), torch.empty(0, dtype=torch.int64))
+    out = [[empty] * B for _ in range(L1)]
+    kept = [h * B + b for h in range(L1) for b in range(B) if gts[b] is not None]
+    if kept:
+        _need_device(labels[0])
+        T = L1 * B
+        zeros = _spf_zero_buffer(dev, max(T * Q, max(len(g[0]) for g in gts if g is not None)) * 6)
+        entries = [None if g is None else {"mask": g[1] if g[1].dtype == torch.float32 else g[1].float(), "cls": g[0],
+                                           "box": zeros[:len(g[0]) * 6].view(-1, 6)} for g in gts]
+        stacked = labels[0].detach() if L1 == 1 else torch.cat([z.detach() for z in labels])
+        _, host = _match_run(who, stacked, [x.detach() for head in masks for x in head], zeros[:T * Q].view(T, Q),
+                             zeros[:T * Q * 6].view(T, Q, 6), entries * L1, kept, cls_dtype,
+                             _lib.MatchWeights(cw[0], cw[2], cw[1], 0.0, 0.0), True)
+        for k, (r, c) in zip(kept, _solve_all([(host[k], 1) for k in kept])):
+            out[k // B][k % B] = (torch.from_numpy(r), torch.from_numpy(c))
+    return out[0] if single else out
+
+
+def _spf_indices_arg(who, indices, single, L1, gts, Q):
+    """The matched pairs as int32 NumPy arrays per (head, sample); ``None`` for a skipped sample."""
+    indices = [indices] if single else indices
+    B = len(gts)
+    if not isinstance(indices, (list, tuple)) or len(indices) != L1 \
+            or any(not isinstance(head, (list, tuple)) or len(head) != B for head in indices):
+        raise ValueError("%s: indices must hold, per head, one (rows, cols) pair per sample, as spformer_match returns "
+                         "them" % who)
+    out = []
+    for h, head in enumerate(indices):
+        for b, pair in enumerate(head):
+            who_b = "%s: head %d, sample %d" % (who, h, b)
+            try:
+                rows, cols = pair
+                if any(isinstance(v, torch.Tensor) and v.device.type != "cpu" for v in pair):
+                    raise TypeError
+                rows, cols = np.asarray(rows), np.asarray(cols)
+                if rows.size == 0 and cols.size == 0:
+                    rows = cols = np.empty(0, dtype=np.int64)
+                if rows.ndim != 1 or rows.shape != cols.shape or rows.dtype.kind not in "iu" or cols.dtype.kind not in "iu":
+                    raise TypeError
+            except (TypeError, ValueError):
+                raise ValueError("%s: a (rows, cols) pair of 1-D integer host arrays of one length is expected"
+                                 % who_b) from None
+            if gts[b] is None:
+                if rows.size:
+                    raise ValueError("%s: matched pairs for a sample without an instance" % who_b)
+                out.append(None)
+                continue
+            n_inst = len(gts[b][0])
+            if rows.size == 0:
+                raise ValueError("%s: no matched pair for a sample with instances" % who_b)
+            if int(rows.min()) < 0 or int(rows.max()) >= Q or len(np.unique(rows)) != rows.size:
+                raise ValueError("%s: the rows must be distinct and inside [0, %d)" % (who_b, Q))
+            if int(cols.min()) < 0 or int(cols.max()) >= n_inst:
+                raise ValueError("%s: a column outside [0, %d)" % (who_b, n_inst))
+            out.append((rows.astype(np.int32), cols.astype(np.int32)))
+    return out
+
+
+def _spf_offsets_arg(who, batch_offsets, widths, n_points):
+    """The first column of every sample.  ``None`` (and a device tensor, which is not read): the samples' columns follow
+    each other from 0, the one layout the reference's ``[b_s:b_e]`` slices allow; host integers are checked against it."""
+    off = [0]
+    for wd in widths:
+        off.append(off[-1] + wd)
+    if isinstance(batch_offsets, torch.Tensor):
+        batch_offsets = batch_offsets.tolist() if batch_offsets.device.type == "cpu" else None
+    if batch_offsets is not None:
+        try:
+            given = [int(v) for v in batch_offsets]
+            if any(g != v for g, v in zip(given, batch_offsets)):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError("%s: batch_offsets must be integers" % who) from None
+        if len(given) != len(off) or any(b - a != wd for a, b, wd in zip(given, given[1:], widths)) or given[0] < 0:
+            raise ValueError("%s: batch_offsets must hold batch_size + 1 integers whose steps are the samples' numbers of "
+                             "mask columns" % who)
+        off = given
+    if off[-1] > n_points:
+        raise ValueError("%s: the samples have %d columns, sp_prob_labels %d entries" % (who, off[-1], n_points))
+    return off
+
+
+class _SpfLayerLosses(torch.autograd.Function):
+    """The one autograd node of ``spformer_layer_losses``: ``f32[L1, 5]`` forward, one kernel backward."""
+
+    @staticmethod
+    def forward(fctx, plan, *heads):
+        who = "spformer_layer_losses"
+        L1, B, Q, n_classes = plan["L1"], plan["B"], plan["Q"], plan["C"]
+        labels = [z.contiguous() for z in heads[:L1]]
+        scores = [s.contiguous() for s in heads[L1:2 * L1]]
+        masks = iter(heads[2 * L1:])
+        ctx, stream = _ctx_stream(labels[0])
+        lib, dev = ctx.lib, labels[0].device
+        gts, off, pairs = plan["gts"], plan["off"], plan["pairs"]
+        T = L1 * B
+        tasks = (_lib.SpfLossTask * T)()
+        xs, rows, cols, total_gt, grad_spans, grad_floats = [], [], [], 0, [], 0
+        for h in range(L1):
+            for b in range(B):
+                z_ptr, s_ptr = labels[h].data_ptr() + 4 * b * Q * n_classes, scores[h].data_ptr() + 4 * b * Q
+                if gts[b] is None:
+                    tasks[h * B + b] = _lib.SpfLossTask(z_ptr, s_ptr, None, 0, None, None, None, 0, 0, 0, 0, 0, total_gt)
+                    continue
+                x = _row_contiguous(next(masks))
+                xs.append(x)
+                cls, mask, box = gts[b]
+                r, c = pairs[h * B + b]
+                n_inst, n_cols = (int(v) for v in mask.shape)
+                tasks[h * B + b] = _lib.SpfLossTask(z_ptr, s_ptr, x.data_ptr(), int(x.stride(0)), mask.data_ptr(),
+                                                    cls.data_ptr(), box.data_ptr(), len(r), n_inst, n_cols, 0, off[b],
+                                                    total_gt)
+                rows.append(r)
+                cols.append(c)
+                total_gt += len(r)
+                grad_spans.append((grad_floats, n_cols))
+                grad_floats += Q * n_cols
+        rows = np.ascontiguousarray(np.concatenate(rows), dtype=np.int32) if rows else np.zeros(1, dtype=np.int32)
+        cols = np.ascontiguousarray(np.concatenate(cols), dtype=np.int32) if cols else np.zeros(1, dtype=np.int32)
+        prob, feats, coords = plan["prob"], plan["feats"], plan["coords"]
+        dims = _lib.SpfLossDims(L1, B, Q, n_classes, _LABEL_CODES[plan["cls_dtype"]], int(feats.shape[1]),
+                                plan["min_points"], plan["flags"], plan["non_object_weight"])
+        with torch.cuda.device(dev):
+            ws = _workspace(who, int(lib.gapro_spf_loss_workspace_bytes(L1, B, Q, total_gt)), dev,
+                            "%d heads, %d samples and %d queries are" % (L1, B, Q))
+            out = torch.empty((L1, _lib.SPF_LOSS_N), dtype=torch.float32, device=dev)
+            d_status, h_status = _status_pair(dev, _lib.MATCH_STATUS_WORDS, torch.int32, read=plan["check"])
+            ctx.check(lib.gapro_spf_loss_forward(ctx.handle, stream, C.byref(dims), C.cast(tasks, C.c_void_p),
+                                                 rows.ctypes.data, cols.ctypes.data, prob.data_ptr(), feats.data_ptr(),
+                                                 coords.data_ptr(), int(prob.shape[0]), ws.data_ptr(), ws.numel(),
+                                                 out.data_ptr(), d_status.data_ptr(), _ptr(h_status)))
+            if h_status is not None:  # the call's one host read, asked for by check=True
+                status, bad, flags = _host_read(dev, h_status)[:3]
+                _refuse("%s: head %d, sample %d" % (who, bad // B, bad % B), status, flags, _SPF_CAUSES)
+        fctx.save_for_backward(*labels, *scores, *xs)
+        fctx.held = (gts, prob, feats, coords, ws, dims, total_gt, grad_spans, grad_floats,
+                     [s.shape for s in heads[L1:2 * L1]])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad_out):
+        _, prob, feats, coords, ws, dims, total_gt, grad_spans, grad_floats, score_shapes = fctx.held
+        L1, B, Q, n_classes = dims.n_heads, dims.batch_size, dims.n_queries, dims.n_classes
+        saved = fctx.saved_tensors
+        ctx, stream = _ctx_stream(saved[0])
+        dev = saved[0].device
+        need = fctx.needs_input_grad[1:]
+        grad_out = grad_out.to(dtype=torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            g_labels = torch.empty((L1, B, Q, n_classes), dtype=torch.float32, device=dev) if any(need[:L1]) else None
+            g_scores = torch.empty((L1, B, Q), dtype=torch.float32, device=dev) if any(need[L1:2 * L1]) else None
+            g_mask = torch.empty(grad_floats, dtype=torch.float32, device=dev) \
+                if grad_floats and any(need[2 * L1:]) else None
+            ctx.check(ctx.lib.gapro_spf_loss_backward(ctx.handle, stream, C.byref(dims), total_gt, prob.data_ptr(),
+                                                      feats.data_ptr(), coords.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      grad_out.data_ptr(), _ptr(g_labels), _ptr(g_scores),
+                                                      _ptr(g_mask)))
+        grads = [g_labels[h] if need[h] else None for h in range(L1)]
+        grads += [g_scores[h].view(score_shapes[h]) if need[L1 + h] else None for h in range(L1)]
+        grads += [g_mask[first:first + Q * n_cols].view(Q, n_cols) if need[2 * L1 + k] else None
+                  for k, (first, n_cols) in enumerate(grad_spans)]
+        return (None, *grads)
+
+
+def spformer_layer_losses(pred_labels, pred_scores, pred_masks, insts, indices, sp_coords, sp_rgb_feats,
+                          sp_prob_labels, batch_offsets=None, *, non_object_weight=0.1, num_class=None,
+                          weighted_bce=False, dice_div_main=False, min_points=100, check=True):
+    """The five losses of every prediction head of SPFormer's ``Criterion`` (SPFormer/spformer/model/loss.py:415-499 for
+    the main head, :263-349 for an aux head) in two kernels: ``f32[L1, 5]`` with the columns ``SPF_LOSS_NAMES`` (cls,
+    mask_bce, mask_dice, score, levelset), one autograd node; its backward is one kernel, which reads the upstream
+    ``f32[L1, 5]`` on the device and writes every element of every head's label, score and mask-logit gradients.
+
+    ``pred_labels`` / ``pred_scores`` / ``pred_masks`` are one head's ``f32[B, Q, C]``, ``f32[B, Q, 1]`` (or ``[B, Q]``)
+    and list of ``f32[Q, S_b]``, or lists over the heads with THE MAIN HEAD LAST (``aux_outputs[i]`` is head ``i``).
+    ``insts`` and ``indices`` are ``spformer_match``'s argument and result.  ``sp_coords`` ``f32[N, 3]``,
+    ``sp_rgb_feats`` ``f32[N, F]`` (1 <= F <= 8) and ``sp_prob_labels`` ``f32[N]`` hold the samples' superpoints one
+    after the other; ``batch_offsets`` is ``None``, ``B + 1`` host integers (checked against the masks' widths) or a
+    device tensor, which is NOT read: the samples' columns then follow each other from 0.
+
+    The rule is include/gapro_hip.h's ("SPFormer's criterion"): float64 from the float32 inputs, one
+    rounding, no floating-point atomics.  Two quirks of the released code are reproduced by default:
+    ``mask_bce`` is the plain mean BCE (``reduce="none"`` is the legacy boolean and selects the mean), times
+    ``sum(w) / sum(w)``, which is 1, or NaN for a weight sum that is 0 or not finite; ``weighted_bce=True`` gives the
+    ``sp_prob_labels``-weighted mean the code means.  ``mask_dice`` of the main head is not divided by B while the aux
+    heads' is; ``dice_div_main=True`` divides it too.  ``min_points`` is the reference's 100: a box with fewer columns
+    inside takes no part in the level-set term.  A sample without an instance adds its Q "no object" rows to the class
+    loss and nothing else; a batch of such samples is legitimate.
+
+    Shapes, dtypes, devices, offsets, pairs out of range and ``F`` outside 1 .. 8 are ``ValueError``s before a device
+    is touched.  A GT label outside ``[0, num_class)`` or a matched mask value other than 0 / 1 is refused by the device:
+    with ``check=True`` the status is read behind the kernels (the call's one synchronisation) and a ``GaproError``
+    raised; with ``check=False`` the call only enqueues, every loss is NaN and the backward writes zeros."""
+    who = "spformer_layer_losses"
+    gts, tensors, cls_dtype = _spf_insts_arg(who, insts)
+    B = len(gts)
+    single, labels, masks, scores, L1, Q, n_classes, head_tensors = _spf_heads_arg(who, pred_labels, pred_masks, B,
+                                                                                   pred_scores)
+    if pred_scores is None:
+        raise ValueError("%s: pred_scores is missing" % who)
+    widths = _spf_widths_arg(who, masks, gts, Q)
+    pairs = _spf_indices_arg(who, indices, single, L1, gts, Q)
+    _tensor_arg(who, "sp_prob_labels", sp_prob_labels, ("N",), nonempty=True)
+    N = int(sp_prob_labels.shape[0])
+    _tensor_arg(who, "sp_rgb_feats", sp_rgb_feats, (N, "F"))
+    if not 1 <= int(sp_rgb_feats.shape[1]) <= _lib.MATCH_LOSS_MAX_FEATS:
+        raise ValueError("%s: %d level-set features; 1 to %d are expected"
+                         % (who, int(sp_rgb_feats.shape[1]), _lib.MATCH_LOSS_MAX_FEATS))
+    _tensor_arg(who, "sp_coords", sp_coords, (N, 3))
+    off = _spf_offsets_arg(who, batch_offsets, widths, N)
+    _finite_arg(who, "non_object_weight", non_object_weight)
+    _positive_int_arg(who, "min_points", min_points)
+    if num_class is not None and (not _is_int(num_class) or num_class != n_classes - 1):
+        raise ValueError("%s: num_class=%r, pred_labels has %d classes (num_class + 1 is expected)"
+                         % (who, num_class, n_classes))
+    for name, v in (("weighted_bce", weighted_bce), ("dice_div_main", dice_div_main), ("check", check)):
+        if not isinstance(v, bool):
+            raise ValueError("%s: %s must be a bool" % (who, name))
+    dev = labels[0].device
+    _one_device(who, dev, tensors + head_tensors + [sp_prob_labels, sp_rgb_feats, sp_coords])
+    _need_device(labels[0])
+    kept = [b for b in range(B) if gts[b] is not None]
+    dev_gts = [None if g is None else (g[0].contiguous(), (g[1] if g[1].dtype == torch.float32 else g[1].float())
+                                       .contiguous(), g[2].contiguous()) for g in gts]
+    plan = {"L1": L1, "B": B, "Q": Q, "C": n_classes, "gts": dev_gts, "off": off, "pairs": pairs,
+            "cls_dtype": cls_dtype or torch.int64, "prob": sp_prob_labels.detach().contiguous(),
+            "feats": sp_rgb_feats.detach().contiguous(), "coords": sp_coords.detach().contiguous(),
+            "min_points": int(min_points), "non_object_weight": float(non_object_weight), "check": check,
+            "flags": (_lib.SPF_WEIGHTED_BCE if weighted_bce else 0) | (_lib.SPF_DICE_DIV_MAIN if dice_div_main else 0)}
+    return _SpfLayerLosses.apply(plan, *labels, *scores, *[masks[h][b] for h in range(L1) for b in kept])
+
+
+def spformer_criterion(pred, insts, *, loss_weight=(1.0, 1.0, 1.0, 1.0, 0.5), cost_weight=(1.0, 1.0, 1.0),
+                       non_object_weight=0.1, num_class=18, weighted_bce=False, dice_div_main=False, min_points=100,
+                       check=True, as_floats=False):
+    """SPFormer's ``Criterion.forward`` (SPFormer/spformer/model/loss.py:393-556) with the constructor's arguments as
+    keywords: it reads the same keys of ``pred`` (``labels``, ``scores``, ``masks``, ``sp_coords``, ``sp_rgb_feats``,
+    ``batch_offsets``, ``sp_prob_labels``, ``sp_mu_labels``, ``sp_var_labels``, ``sp_mu_preds``, ``sp_logvar_preds`` and,
+    when present, ``aux_outputs``: a list of dicts with ``labels``, ``scores``, ``masks``) and returns ``(loss,
+    loss_out)``.  ``loss_out`` has the reference's keys in its order: ``cls_loss``, ``score_loss``, ``mask_bce_loss``,
+    ``mask_dice_loss``, ``levelset_loss``, ``kl_loss``, then ``layer_{i}_`` + the first five for each aux head, then
+    ``loss``; its values are detached 0-dim device tensors, or with ``as_floats=True`` Python floats from ONE host copy
+    of the whole table (the reference's ``.item()``s, about 35 of them at the released configuration).
+
+    Pure composition: ``spformer_match`` over all heads, ``spformer_layer_losses`` (``loss_weight`` is cls, mask BCE,
+    dice, score, level set, applied to every head), and ``kl_to_gp_loss(..., weight=0.1)``.  As released the main head's
+    dice loss is not divided by the batch size and the mask BCE is unweighted; see ``spformer_layer_losses`` for the two
+    switches.  A ``batch_offsets`` on the device is not read.  With ``check=False`` the only host synchronisation of
+    the call is the matcher's.  A missing key, a ``loss_weight`` that is not five finite numbers and everything the
+    composed calls refuse are ``ValueError``s before a device is touched."""
+    who = "spformer_criterion"
+    if not isinstance(pred, dict):
+        raise ValueError("%s: pred must be a dict" % who)
+    for k in _SPF_PRED_KEYS:
+        if k not in pred:
+            raise ValueError("%s: pred lacks %r" % (who, k))
+    aux = pred.get("aux_outputs", [])
+    if not isinstance(aux, (list, tuple)) or any(not isinstance(a, dict) or any(k not in a for k in _SPF_PRED_KEYS[:3])
+                                                 for a in aux):
+        raise ValueError("%s: aux_outputs must be a list of dicts with labels, scores and masks" % who)
+    try:
+        lw = tuple(float(v) for v in loss_weight)
+    except (TypeError, ValueError):
+        lw = ()
+    if len(lw) != 5 or any(not _is_finite(v) for v in lw):
+        raise ValueError("%s: loss_weight must be five finite numbers (cls, mask BCE, dice, score, level set)" % who)
+    _positive_int_arg(who, "num_class", num_class)
+    if not isinstance(as_floats, bool):
+        raise ValueError("%s: as_floats must be a bool" % who)
+    heads = list(aux) + [pred]  # the main head last
+    labels, scores, masks = ([h[k] for h in heads] for k in ("labels", "scores", "masks"))
+    if isinstance(labels[0], torch.Tensor) and labels[0].dim() == 3 and int(labels[0].shape[2]) != num_class + 1:
+        raise ValueError("%s: num_class=%r, pred_labels has %d classes (num_class + 1 is expected)"
+                         % (who, num_class, int(labels[0].shape[2])))
+    indices = spformer_match(labels, masks, insts, cost_weight)
+    table = spformer_layer_losses(labels, scores, masks, insts, indices, pred["sp_coords"], pred["sp_rgb_feats"],
+                                  pred["sp_prob_labels"], pred["batch_offsets"], non_object_weight=non_object_weight,
+                                  num_class=num_class, weighted_bce=weighted_bce, dice_div_main=dice_div_main,
+                                  min_points=min_points, check=check)
+    dev = table.device
+    kl = kl_to_gp_loss(pred["sp_mu_preds"], pred["sp_logvar_preds"], pred["sp_mu_labels"], pred["sp_var_labels"],
+                       weight=0.1)
+    # the total in float64 from the float32 losses, rounded once: the rule of the kernels, kept to the last addition
+    loss = ((table.double() * _device_constant(dev, lw, torch.float64)).sum() + kl.double()).float()
+    flat = torch.cat([table.detach().reshape(-1), kl.detach().reshape(1), loss.detach().reshape(1)])
+    values = flat.tolist() if as_floats else flat.unbind(0)  # as_floats: the one host copy
+    L1 = len(heads)
+    order = [SPF_LOSS_NAMES.index(k) for k in _SPF_OUT_NAMES]
+    loss_out = {k: values[(L1 - 1) * 5 + j] for k, j in zip(_SPF_OUT_NAMES, order)}
+    loss_out["kl_loss"] = values[L1 * 5]
+    for i in range(L1 - 1):
+        loss_out.update({"layer_%d_%s" % (i, k): values[i * 5 + j] for k, j in zip(_SPF_OUT_NAMES, order)})
+    loss_out["loss"] = values[L1 * 5 + 1]
+    return loss, loss_out

@@ -18,6 +18,7 @@
 // outside the row forms no address.  min / max / clamp hand a NaN on, as torch's.
 #include "common.h"
 #include "launch_util.h"
+#include "loss_rows.h"
 #include "match_math.h"
 #include "wave_reduce.h"
 
@@ -27,7 +28,7 @@
 
 namespace {
 
-constexpr int kThreads = 256, kWaves = 4;
+constexpr int kThreads = kLossThreads, kWaves = kLossWaves;
 constexpr int kMaxF = GAPRO_MATCH_LOSS_MAX_FEATS;
 constexpr int kNoSample = 0x7fffffff;
 constexpr int kRowRec = 24, kQueryRec = 4, kSampleRec = 12;  // doubles
@@ -85,50 +86,6 @@ __host__ __device__ inline size_t loss_ws(void* base, int B, int Q, long long to
   w->rrec = (double*)p; p += (size_t)total_gt * kRowRec * 8;
   w->srec = (double*)p; p += (size_t)B * kSampleRec * 8;
   return (size_t)(p - (char*)base);
-}
-
-// every thread's partial -> the workgroup's sum in every thread: the butterfly, then the waves in their order
-__device__ inline double block_sum(double v, double* slot /* [kWaves] in LDS, this quantity's own */) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = slot[0];
-#pragma unroll
-  for (int k = 1; k < kWaves; ++k) s += slot[k];
-  return s;
-}
-__device__ inline int block_sum(int v, int* slot) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return slot[0] + slot[1] + slot[2] + slot[3];
-}
-
-struct BoxTest {  // criterion.py:196-198 in float32: the padded faces of one label box
-  float lo[3], hi[3];
-};
-__device__ inline BoxTest box_test(const float* __restrict__ g) {
-  BoxTest bt;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    bt.lo[k] = g[k] - 0.005f;
-    bt.hi[k] = g[k + 3] + 0.005f;
-  }
-  return bt;
-}
-__device__ inline bool inside(const BoxTest& bt, const float* __restrict__ c) {  // a NaN coordinate is outside
-  bool in = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) in = in && c[k] >= bt.lo[k] && c[k] <= bt.hi[k];
-  return in;
-}
-
-struct Sig {
-  double sig, e;
-};
-__device__ inline Sig sigmoid_of(double x) {
-  const double e = exp(-fabs(x));  // in (0, 1]: no overflow on either side
-  return {(x >= 0.0 ? 1.0 : e) / (1.0 + e), e};
 }
 
 // ---- rows ----------------------------------------------------------------------------------------------------------

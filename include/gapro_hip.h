@@ -1195,6 +1195,82 @@ int gapro_match_loss_backward(gapro_ctx* ctx, void* stream, int32_t batch_size, 
                               float* d_grad_conf_logits /* [B,Q] or NULL */, float* d_grad_box_preds /* [B,Q,6] or NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ * SPFormer's criterion (csrc/spf_loss.hip).  Replaces the per-sample loops of SPFormer's Criterion.forward and
+ * get_layer_loss (SPFormer/spformer/model/loss.py:415-499, 263-349) for ALL prediction heads at once: the five losses
+ * of every head in two launches, their gradients in one.  There are n_heads heads (the main head LAST, aux head i at
+ * index i), batch_size samples, n_queries queries and n_classes = num_class + 1 classes, the last one "no object".
+ * Task h * batch_size + b is head h of sample b: its class logits f32[n_queries, n_classes] and scores f32[n_queries],
+ * its mask logits, and the sample's GT (n_inst instances: masks f32[n_inst, n_cols] of 0 / 1, labels, boxes).  Its
+ * n_gt matched pairs are h_rows / h_cols[row_offset + r]: the query and the GT instance of row r (queries distinct and
+ * in [0, n_queries), instances in [0, n_inst)).  n_gt == 0 is a skipped sample: only its class terms count.  The
+ * sample's columns are [col_offset, col_offset + n_cols) of d_sp_prob (f32[n_points]), d_sp_feats
+ * (f32[n_points, n_feats]) and d_sp_coords (f32[n_points, 3]).
+ * The rule is the matched losses': float64 from the float32 inputs, every sum a float64 sum in a fixed order, one
+ * rounding.  With x the matched rows of the logits, t the matched GT masks, w the sample's slice of d_sp_prob, n = n_gt,
+ * S = n_cols, B = batch_size, e = exp(-|x|), sig = (x >= 0 ? 1 : e) / (1 + e), sp = max(x, 0) + log1p(e), per head:
+ *   cls      = sum_{b,q} W[tgt] (lse - z[tgt]) / sum_{b,q} W[tgt] over all B Q queries, tgt the matched instance's label
+ *              or num_class, W = 1 but non_object_weight for num_class; not divided by B                  (:419-428)
+ *   bce      = sum_b bce_b / B.  As released (:464-466; `reduce="none"` is the legacy boolean and selects the mean):
+ *              bce_b = [sum_{r,s} (sp - x t) / (n S)] * (sum_s w / sum_s w), the factor being 1, or NaN for a weight sum
+ *              that is 0, infinite or NaN.  GAPRO_SPF_WEIGHTED_BCE: bce_b = sum_{r,s} w_s (sp - x t) / (sum_s w) / n
+ *   dice     = sum_b [sum_r (1 - (2 sum_s sig t + 1) / (sum_s sig + sum_s t + 1)) / n]; divided by B for the aux heads
+ *              (:331) and, as released, NOT for the main head (:469-488) unless GAPRO_SPF_DICE_DIV_MAIN
+ *   score    = sum_b [sum_{kept r} (score_r - iou_r)^2 / n_kept] / B with inter = sum_s [x >= 0] t,
+ *              union = sum_s [x >= 0] + sum_s t - inter, iou = inter / (union + 1e-6); a row is kept iff iou > 0.5,
+ *              decided as the integer predicate 2 inter > union; a sample without a kept row adds nothing; no gradient
+ *              through the IoU                                                                            (:455-462)
+ *   levelset = sum_b [sum_r L_r / (n + 1e-4)] / B with the matched losses' L_r (float32 membership test, n_r members,
+ *              mu_f = (sum v f) / max(A, 1e-5)); a box takes part iff n_r >= min_points (>= 1)              (:351-391)
+ * d_losses f32[n_heads, GAPRO_SPF_LOSS_N] in the order cls, bce, dice, score, levelset.  A batch whose samples are all
+ * skipped is legitimate: its class loss, and zeros.  gapro_spf_loss_backward: the exact float64 derivatives, weighted by
+ * d_grad_losses (f32[n_heads, 5], read on the device), rounded once, with the kink conventions of the matched losses.
+ * It writes EVERY element of d_grad_labels (f32[n_heads, B, Q, n_classes]), d_grad_scores (f32[n_heads, B, Q]) and
+ * d_grad_masks (the packed f32[n_queries, n_cols] blocks of the tasks with n_gt > 0, in task order), zeros included; a
+ * NULL pointer is not written.  No floating-point atomics: two calls give equal bytes, and a head's values do not
+ * depend on the other heads of the call.  The forward call uploads one table (tasks, rows, columns, query -> row or -1,
+ * the zeroed status), launches two kernels and, when given, copies d_status to h_status_pinned; both calls only enqueue.
+ * d_status i32[GAPRO_MATCH_STATUS_WORDS] = {status, the lowest task of the refusal or -1, flags, 0}.  Refused by the
+ * device (GAPRO_ERR_BAD_ARG, every loss NaN, the backward writes zeros): flags & 1, a matched label outside
+ * [0, num_class); flags & 2, a matched mask value that is neither 0 nor 1.  Refused before anything is launched
+ * (GAPRO_ERR_BAD_ARG): a null or non-positive argument, n_feats outside [1, GAPRO_MATCH_LOSS_MAX_FEATS], n_classes < 2,
+ * a non_object_weight that is not finite, ld_logits < n_cols, columns that leave [0, n_points), a row_offset that is
+ * not the sum of the earlier n_gt, a row or column index out of range or a row listed twice, n_heads * batch_size >
+ * GAPRO_SPP_GT_MAX_SAMPLES; GAPRO_ERR_WORKSPACE: a workspace smaller than gapro_spf_loss_workspace_bytes (0 for sizes
+ * the call refuses; total_gt = the sum of n_gt over all tasks, which may be 0).
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_SPF_LOSS_N 5
+#define GAPRO_SPF_WEIGHTED_BCE 1
+#define GAPRO_SPF_DICE_DIV_MAIN 2
+typedef struct {            /* one per (head, sample); n_gt == 0: skipped */
+  const float* d_labels;        /* f32[n_queries, n_classes] */
+  const float* d_scores;        /* f32[n_queries] */
+  const float* d_mask_logits;   /* f32[n_queries, n_cols], row stride ld_logits */
+  int64_t      ld_logits;
+  const float* d_gt_masks;      /* f32[n_inst, n_cols], packed */
+  const void*  d_gt_labels;     /* GAPRO_LABEL_I32 / _I64 [n_inst] */
+  const float* d_gt_boxes;      /* f32[n_inst, 6] */
+  int32_t      n_gt, n_inst, n_cols, reserved;
+  int64_t      col_offset;      /* the sample's first column in d_sp_prob, d_sp_feats, d_sp_coords */
+  int64_t      row_offset;      /* the sum of n_gt over the tasks before this one */
+} gapro_spf_loss_task;
+typedef struct {
+  int32_t n_heads, batch_size, n_queries, n_classes, cls_type, n_feats, min_points, flags;
+  double  non_object_weight;
+} gapro_spf_loss_dims;
+size_t gapro_spf_loss_workspace_bytes(int32_t n_heads, int32_t batch_size, int32_t n_queries, int64_t total_gt);
+int gapro_spf_loss_forward(gapro_ctx* ctx, void* stream, const gapro_spf_loss_dims* dims,
+                           const gapro_spf_loss_task* h_tasks /* [n_heads * batch_size] */,
+                           const int32_t* h_rows /* [total_gt] */, const int32_t* h_cols /* [total_gt] */,
+                           const float* d_sp_prob, const float* d_sp_feats, const float* d_sp_coords, int64_t n_points,
+                           void* d_workspace, size_t workspace_bytes, float* d_losses /* [n_heads, 5] */,
+                           int32_t* d_status, int32_t* h_status_pinned /* NULL: no copy */);
+int gapro_spf_loss_backward(gapro_ctx* ctx, void* stream, const gapro_spf_loss_dims* dims, int64_t total_gt,
+                            const float* d_sp_prob, const float* d_sp_feats, const float* d_sp_coords,
+                            const void* d_workspace, size_t workspace_bytes,
+                            const float* d_grad_losses /* [n_heads, 5] */, float* d_grad_labels, float* d_grad_scores,
+                            float* d_grad_masks);
+
+/* ------------------------------------------------------------------------------------------
  * Point-wise losses (csrc/point_loss.hip).  Replaces ISBNet's Criterion.cal_point_wise_loss
  * (isbnet/model/criterion.py:136-191, called at :357): the four losses over all n_points voxels of a batch in two
  * launches, their gradients in one, with no host read.  The rule continues the matched losses': float64 from the float32
