@@ -199,6 +199,25 @@ class ProposalsHeader(C.Structure):
                 ("n_after_nms", C.c_int32), ("n_after_refine", C.c_int32)]
 
 
+class SpfPredictInputs(C.Structure):
+    """gapro_spf_predict_inputs: the sizes and device pointers of one scene (a host struct, read when the call enqueues)."""
+    _fields_ = [("n_queries", C.c_int64), ("n_spps", C.c_int64), ("n_points", C.c_int64), ("labels", C.c_void_p),
+                ("pred_scores", C.c_void_p), ("masks", C.c_void_p), ("superpoints", C.c_void_p),
+                ("coords_float", C.c_void_p), ("superpoints_i64", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SpfPredictParams(C.Structure):
+    """gapro_spf_predict_params."""
+    _fields_ = [("num_class", C.c_int32), ("topk_insts", C.c_int32), ("npoint_thr", C.c_int32),
+                ("score_thr", C.c_float)]
+
+
+class SpfPredictHeader(C.Structure):
+    """gapro_spf_predict_header: what gapro_spf_predict_count reports; n_rows int32 run counts follow it."""
+    _fields_ = [("status", C.c_int32), ("flags", C.c_int32), ("n_candidates", C.c_int32), ("n_after_score", C.c_int32),
+                ("n_rows", C.c_int32), ("reserved", C.c_int32), ("total_runs", C.c_int64)]
+
+
 SPP_GT_HALF, SPP_GT_STRICT = 0, 1     # the rule of gapro_spp_gt_fill: 2 c >= n, 2 c > n
 GAPRO_ERR_SPP_RANGE = -6
 GAPRO_EVAL_MAX_THRESHOLDS = 32
@@ -347,6 +366,11 @@ SIGNATURES = {
     "gapro_proposals_count": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P]),
     "gapro_proposals_fill": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64,
                                        _P, _P]),
+    "gapro_spf_predict_workspace_bytes": (C.c_size_t, [_P, _P]),
+    "gapro_spf_predict_header_bytes": (C.c_size_t, [_P, _P]),
+    "gapro_spf_predict_count": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P]),
+    "gapro_spf_predict_fill": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64,
+                                         _P, _P]),
     "gapro_match_cost_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
     "gapro_match_cost": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                    C.c_size_t, _P, C.c_int64, _P, _P, _P]),
@@ -570,7 +594,7 @@ def load() -> C.CDLL:
                                             "gapro_schedule_export_testers", "gapro_spp_vote",
                                             "gapro_fit_launch_plan", "gapro_inst_", "gapro_spp_gt_", "gapro_match_",
                                             "gapro_proposals_", "gapro_fps_", "gapro_ball_query_",
-                                            "gapro_lsap_", "gapro_voxelize_", "gapro_voxel_pool_")):
+                                            "gapro_lsap_", "gapro_voxelize_", "gapro_voxel_pool_", "gapro_spf_predict_")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

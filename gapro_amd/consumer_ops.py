@@ -2263,3 +2263,122 @@ def spformer_criterion(pred, insts, *, loss_weight=(1.0, 1.0, 1.0, 1.0, 0.5), co
         loss_out.update({"layer_%d_%s" % (i, k): values[i * 5 + j] for k, j in zip(_SPF_OUT_NAMES, order)})
     loss_out["loss"] = values[L1 * 5 + 1]
     return loss, loss_out
+
+
+# ---- SPFormer's predicted instances: its inference post-processing (csrc/spf_predict.hip) --------------
+_SPF_PREDICT_CAUSES = ((1, "a non-finite labels or scores entry"),
+                       (2, "a non-finite masks entry in the row of a candidate"),
+                       (4, "a non-finite coords_float entry"),
+                       (8, "a superpoint id outside the columns of masks"))
+SpfInstanceArrays = namedtuple("SpfInstanceArrays", "conf label_id box query run_offsets runs masks header n_runs")
+
+
+def spformer_instances(scan_id, pred_labels, pred_scores, pred_masks, superpoints, coords_float, *, num_class,
+                       topk_insts, score_thr, npoint_thr, return_arrays=False, return_masks=False):
+    """``SPFormer.predict_by_feat`` (SPFormer/spformer/model/spformer.py:180-242) on the tensors of one scene:
+    ``pred_labels f32[Q, num_class + 1]``, ``pred_scores f32[Q]`` or ``[Q, 1]``, ``pred_masks f32[Q, S]`` (logits over
+    the superpoints), ``superpoints int[N]`` in ``[0, S)``, ``coords_float f32[N, 3]``.  One chain of integer kernels
+    (include/gapro_hip.h, "SPFormer's predicted instances") with one host read and at most two copies
+    behind it; the reference's ``[topk_insts, N]`` expansion is never built.  Returns the list of ``{"scan_id",
+    "label_id" (np.int64), "conf" (np.float32), "pred_mask": {"length": N, "counts": int64 array}, "box"
+    (np.float32[6]: min xyz, max xyz of the instance's points)}`` in descending ``conf``, equal values in the order of
+    the class scores (descending, then the flat index ``query * num_class + class``).  The reference's own order is
+    undefined: it is what ``torch.topk(sorted=False)`` returns.
+
+    ``return_arrays`` gives the device tensors (``SpfInstanceArrays``; ``masks`` u8[K', N] with ``return_masks``)
+    instead of the list.  Non-finite inputs and superpoint ids out of range are a ``GaproError`` naming the cause."""
+    who = "spformer_instances"
+    _positive_int_arg(who, "num_class", num_class)
+    if not _is_int(topk_insts) or not 1 <= topk_insts <= _lib.PROPOSALS_MAX_PRE_TOPK:
+        raise ValueError("%s: topk_insts must be an int in [1, %d]" % (who, _lib.PROPOSALS_MAX_PRE_TOPK))
+    _finite_arg(who, "score_thr", score_thr)
+    if not _is_int(npoint_thr) or npoint_thr < 0:
+        raise ValueError("%s: npoint_thr must be a non-negative int" % who)
+    if not isinstance(pred_labels, torch.Tensor) or pred_labels.dim() != 2 or int(pred_labels.shape[1]) != num_class + 1:
+        raise ValueError("%s: pred_labels must be f32[Q, num_class + 1]" % who)
+    Q = int(pred_labels.shape[0])
+    if Q < 1:
+        raise ValueError("%s: no queries" % who)
+    labels = _f32_arg(pred_labels, "pred_labels", who, (Q, num_class + 1))
+    if isinstance(pred_scores, torch.Tensor) and pred_scores.dim() == 2 and int(pred_scores.shape[1]) == 1:
+        pred_scores = pred_scores.reshape(-1)
+    scores = _f32_arg(pred_scores, "pred_scores", who, (Q,))
+    if not isinstance(pred_masks, torch.Tensor) or pred_masks.dim() != 2 or int(pred_masks.shape[0]) != Q:
+        raise ValueError("%s: pred_masks must be f32[Q, superpoints]" % who)
+    S = int(pred_masks.shape[1])
+    masks = _f32_arg(pred_masks, "pred_masks", who, (Q, S))
+    sp, sp_i64 = _index_arg(superpoints, "superpoints", who)
+    N = int(sp.shape[0])
+    coords = _f32_arg(coords_float, "coords_float", who, (N, 3))
+    if S < 1 or N < 1:
+        raise ValueError("%s: no superpoints or no points" % who)
+    keep = (labels, scores, masks, sp, coords)
+    _one_device(who, labels.device, keep)
+    inputs = _lib.SpfPredictInputs(n_queries=Q, n_spps=S, n_points=N, labels=labels.data_ptr(),
+                                   pred_scores=scores.data_ptr(), masks=masks.data_ptr(), superpoints=sp.data_ptr(),
+                                   coords_float=coords.data_ptr(), superpoints_i64=sp_i64)
+    params = _lib.SpfPredictParams(num_class=num_class, topk_insts=topk_insts, npoint_thr=npoint_thr,
+                                   score_thr=float(score_thr))
+    ctx, stream = _ctx_stream(labels)
+    lib, dev = ctx.lib, labels.device
+    pin, ppar = C.byref(inputs), C.byref(params)
+    with torch.cuda.device(dev):
+        ws_bytes, hdr_bytes = int(lib.gapro_spf_predict_workspace_bytes(pin, ppar)), int(
+            lib.gapro_spf_predict_header_bytes(pin, ppar))
+        ws = _workspace(who, ws_bytes, dev, "the sizes or parameters are")
+        d_hdr, h_hdr = _status_pair(dev, hdr_bytes)
+        ctx.check(lib.gapro_spf_predict_count(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, d_hdr.data_ptr(),
+                                              h_hdr.data_ptr()))
+        hdr, raw = _host_read(dev, h_hdr, _lib.SpfPredictHeader)
+        _refuse(who, hdr.status, hdr.flags, _SPF_PREDICT_CAUSES)
+        rows, runs = int(hdr.n_rows), int(hdr.total_runs)
+        conf = torch.empty(rows, dtype=torch.float32, device=dev)
+        label = torch.empty(rows, dtype=torch.int32, device=dev)
+        box = torch.empty((rows, 6), dtype=torch.float32, device=dev)
+        query = torch.empty(rows, dtype=torch.int32, device=dev)
+        run_off = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+        d_runs = torch.empty(2 * runs, dtype=torch.int64, device=dev)
+        out_masks = torch.empty((rows, N), dtype=torch.uint8, device=dev) if return_masks else None
+        if rows > 0:
+            ctx.check(lib.gapro_spf_predict_fill(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, _ptr(conf),
+                                                 _ptr(label), _ptr(box), _ptr(query), rows, _ptr(run_off),
+                                                 _ptr(d_runs), runs, _ptr(out_masks), None))
+    del keep
+    n_runs = np.frombuffer(raw, dtype=np.int32, count=rows, offset=C.sizeof(_lib.SpfPredictHeader))
+    out = SpfInstanceArrays(conf, label, box, query, run_off, d_runs, out_masks, hdr, n_runs)
+    if return_arrays:
+        return out
+    if rows == 0:
+        return []
+    small = torch.cat([conf.view(torch.int32), label, box.view(torch.int32).reshape(-1)]).cpu().numpy()  # one copy
+    host_runs = d_runs.cpu().numpy()  # the runs: the other
+    conf_h, label_h = small[:rows].view(np.float32), small[rows:2 * rows].astype(np.int64)
+    box_h = small[2 * rows:].view(np.float32).reshape(rows, 6)
+    counts = _counts_of(np.concatenate([[0], np.cumsum(n_runs, dtype=np.int64)]), host_runs)  # came with the header
+    return [{"scan_id": scan_id, "label_id": label_h[r], "conf": conf_h[r],
+             "pred_mask": {"length": N, "counts": counts[r]}, "box": box_h[r].copy()} for r in range(rows)]
+
+
+def spformer_predict(scan_ids, out, superpoints, insts, coords_float, *, num_class=18, test_cfg=None, topk_insts=100,
+                     score_thr=0.0, npoint_thr=100):
+    """``SPFormer.predict_by_feat`` with its positional signature (SPFormer/spformer/model/spformer.py:180): reads
+    sample 0 of ``out["labels"]``, ``out["scores"]`` and ``out["masks"]`` as the reference does ("only batch 1 when
+    test") and returns ``dict(scan_id=scan_ids[0], pred_instances=[...], gt_instances=insts[0].gt_instances)``; the
+    instances and their order are ``spformer_instances``'.  ``test_cfg`` (an object with ``topk_insts``, ``score_thr``,
+    ``npoint_thr``) overrides the three keywords."""
+    who = "spformer_predict"
+    if test_cfg is not None:
+        topk_insts = getattr(test_cfg, "topk_insts", topk_insts)
+        score_thr = getattr(test_cfg, "score_thr", score_thr)
+        npoint_thr = getattr(test_cfg, "npoint_thr", npoint_thr)
+    if not isinstance(out, dict) or any(k not in out for k in ("labels", "scores", "masks")):
+        raise ValueError("%s: out must be a dict with labels, scores and masks" % who)
+    if len(scan_ids) < 1 or len(insts) < 1:
+        raise ValueError("%s: no scene" % who)
+    for k in ("labels", "scores", "masks"):
+        if len(out[k]) < 1:
+            raise ValueError("%s: out[%r] holds no sample" % (who, k))
+    pred = spformer_instances(scan_ids[0], out["labels"][0], out["scores"][0], out["masks"][0], superpoints,
+                              coords_float, num_class=num_class, topk_insts=topk_insts, score_thr=score_thr,
+                              npoint_thr=npoint_thr)
+    return dict(scan_id=scan_ids[0], pred_instances=pred, gt_instances=insts[0].gt_instances)

@@ -1070,6 +1070,102 @@ int gapro_proposals_fill(gapro_ctx* ctx, void* stream, const gapro_proposals_inp
                          int64_t* d_runs, int64_t cap_runs, uint8_t* d_masks, gapro_proposals_header* d_header);
 
 /* ------------------------------------------------------------------------------------------
+ * SPFormer's predicted instances: the second consumer's inference post-processing (csrc/spf_predict.hip).  Replaces
+ * SPFormer.predict_by_feat (SPFormer/spformer/model/spformer.py:180-242) with the rle_encode_gpu_batch it calls: a
+ * [K, N] int32 expansion of the superpoint masks, three boolean compactions of it, and per instance a nonzero, a boolean
+ * gather of the coordinates and two blocking copies.  Two calls with one host read between them, as gapro_proposals_*.
+ * One scene a call.  Q = n_queries, C = num_class, S = n_spps (the columns of the mask logits), N = n_points,
+ * K = min(topk_insts, Q C).
+ * gapro_spf_predict_inputs:
+ *   labels f32[Q, C + 1], pred_scores f32[Q] (the raw linear output: it may be negative), masks f32[Q, S]
+ *   superpoints i32 / i64 [N] in [0, S) (superpoints_i64 says which), coords_float f32[N, 3]
+ * Steps.  Every floating-point term is evaluated in float64 from the float32 inputs and rounded to float32 once;
+ * everything else is integer or a bit copy (the rule of "Predicted instances" above).
+ *   1 scores   s[q, c] = float32(softmax(labels[q, :])[c] * pred_scores[q]), c < C; the softmax runs over all C + 1
+ *              columns as exp(x - max) over the sum of these terms in ascending c; the last column is dropped and the
+ *              rest are not renormalised.  A -0.0 is stored as +0.0.  The candidates are the K largest s by float32
+ *              value, descending; equal values by ascending flat index q C + c (the tie rule, radix select and sort of
+ *              "Predicted instances" stage 1; the reference's torch.topk(sorted=False) has no rule).
+ *   2 bits     bit (q, j) = masks[q, j] > 0, a strict float32 comparison: a logit of +0.0 or -0.0 is not set.  64 bits
+ *              to a word by the ballot of a wavefront that loaded 64 consecutive values; the tail of the last word is
+ *              zero.  For a candidate's row: cnt = the set bits, sum = the float64 sum of 1 / (1 + exp(-x)) over the set
+ *              entries, in an order the kernel fixes (a lane adds its words in ascending order, the 64 lanes fold by the
+ *              xor butterfly 32 .. 1, the four waves add in ascending order), so two runs give the same bytes.
+ *              conf = float32(softmax64 * pred_scores * sum / (cnt + 1e-6)), one float64 expression rounded once (the
+ *              softmax term as in step 1, before its rounding); cnt = 0 gives conf = 0; a -0.0 is stored as +0.0.
+ *   3 tables   per superpoint j, once a call: n(j) = its points; lo(j), hi(j) = the component-wise min and max of
+ *              coords_float over them.  Integer atomics only: the float min / max go through the order-preserving
+ *              integer image of the float32 bits (sign set: all bits flipped; else the sign bit set), so -0.0 < +0.0.
+ *   4 rows     for candidate k with query q_k: npoints[k] = sum_j bit(q_k, j) n(j), int64; box[k] = the min of lo(j) and
+ *              the max of hi(j) over the set j with n(j) > 0.  A row is kept if conf > score_thr (float32, strict) and
+ *              then npoints > npoint_thr (strict).  No [K, N] array exists.
+ *   5 order    the kept rows in descending conf; equal values in candidate order.  (The reference's own order is whatever
+ *              torch.topk(sorted=False) returned.)
+ *   6 runs     per kept row the transitions of m(k, p) = bit(q_k, superpoints[p]) along p with a zero before and after:
+ *              1-based starts, each followed by its length, int64: the `counts` of rle_encode_gpu_batch, byte for byte.
+ * gapro_spf_predict_count runs all of it up to the run counts and writes d_header (and its page-locked host copy when
+ * h_header_pinned is given): the struct below followed by int32 n_runs of every row out,
+ * gapro_spf_predict_header_bytes(...) in all, sized for K rows.  gapro_spf_predict_fill reads what the count left in the
+ * workspace -- same inputs, nothing in between -- and writes (NULL = not wanted, but for d_run_offsets)
+ *   d_conf f32[n_rows], d_label_id i32[n_rows] = c + 1, d_box f32[n_rows, 6] (min xyz, max xyz), d_query i32[n_rows]
+ *   d_run_offsets i64[n_rows + 1] in runs; d_runs i64[2 total_runs]: row r owns d_runs[2 off[r], 2 off[r + 1])
+ *   d_masks u8[n_rows, N]: m(k, .), on request
+ * cap_rows / cap_runs are the lengths the caller allocated; smaller ones than the header's: GAPRO_ERR_WORKSPACE in
+ * d_header->status (when given), nothing written.
+ * Refusals of the data, header.status of gapro_spf_predict_count; flags names every cause met.  In this order of
+ * precedence:
+ *   GAPRO_ERR_NOT_FINITE  flags & 1: a non-finite labels or pred_scores entry (every score takes part in step 1)
+ *   GAPRO_ERR_NOT_FINITE  flags & 2: a non-finite masks entry in the row of a candidate
+ *   GAPRO_ERR_NOT_FINITE  flags & 4: a non-finite coords_float entry
+ *   GAPRO_ERR_SPP_RANGE   flags & 8: a superpoints id outside [0, S)
+ * With a non-zero status the stage counts and n_rows are 0 and gapro_spf_predict_fill writes nothing.  Refused before
+ * anything is launched (GAPRO_ERR_BAD_ARG): a null or non-positive argument, topk_insts outside [1,
+ * GAPRO_PROPOSALS_MAX_PRE_TOPK], Q C > 2^20, S or N > 2^31 - 1, npoint_thr < 0 (so that a kept row always has a point
+ * and a box), a score_thr that is not finite; GAPRO_ERR_WORKSPACE: a workspace smaller than
+ * gapro_spf_predict_workspace_bytes (0 for sizes the calls refuse).  The two structs are host memory, read while the
+ * call enqueues.  Both calls only enqueue: a scene costs one host read.  The passes over the queries and points run at
+ * most GAPRO_PROPOSALS_GRID_CAP workgroups of 256 threads, step 2 and 4 a workgroup per candidate, step 6 at most 1024
+ * workgroups a row, one per chunk of at least 1024 points.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int64_t n_queries, n_spps, n_points;
+  const float* labels;
+  const float* pred_scores;
+  const float* masks;
+  const void* superpoints;
+  const float* coords_float;
+  int32_t superpoints_i64;
+  int32_t reserved;
+} gapro_spf_predict_inputs; /* 72 bytes */
+typedef struct {
+  int32_t num_class;
+  int32_t topk_insts;       /* 100 in the released configuration */
+  int32_t npoint_thr;       /* 100 */
+  float score_thr;          /* 0.0 */
+} gapro_spf_predict_params; /* 16 bytes */
+typedef struct {
+  int32_t status;
+  int32_t flags;            /* 1: labels / pred_scores, 2: mask value, 4: coords_float, 8: superpoints */
+  int32_t n_candidates;     /* after step 1 */
+  int32_t n_after_score;    /* rows with conf > score_thr */
+  int32_t n_rows;           /* of them, rows with npoints > npoint_thr */
+  int32_t reserved;
+  int64_t total_runs;
+} gapro_spf_predict_header; /* 32 bytes; n_rows x int32_t n_runs follow */
+#define GAPRO_SPF_PREDICT_HEADER_BYTES(max_rows) (32 + 4 * (size_t)(max_rows))
+
+size_t gapro_spf_predict_workspace_bytes(const gapro_spf_predict_inputs* in, const gapro_spf_predict_params* params);
+size_t gapro_spf_predict_header_bytes(const gapro_spf_predict_inputs* in, const gapro_spf_predict_params* params);
+int gapro_spf_predict_count(gapro_ctx* ctx, void* stream, const gapro_spf_predict_inputs* in,
+                            const gapro_spf_predict_params* params, void* d_workspace, size_t workspace_bytes,
+                            gapro_spf_predict_header* d_header, gapro_spf_predict_header* h_header_pinned);
+int gapro_spf_predict_fill(gapro_ctx* ctx, void* stream, const gapro_spf_predict_inputs* in,
+                           const gapro_spf_predict_params* params, void* d_workspace, size_t workspace_bytes,
+                           float* d_conf, int32_t* d_label_id, float* d_box, int32_t* d_query, int64_t cap_rows,
+                           int64_t* d_run_offsets, int64_t* d_runs, int64_t cap_runs, uint8_t* d_masks,
+                           gapro_spf_predict_header* d_header);
+
+/* ------------------------------------------------------------------------------------------
  * Cost matrices of the consumer's Hungarian matcher (csrc/match_cost.hip).  Replaces the per-sample expression chain of
  * ISBNet's HungarianMatcher.get_match (isbnet/model/matcher.py:144-199): one call enqueues the cost matrices of every
  * sample of a batch.  Sample b has n_queries queries, n_inst kept instances, n_cols columns (superpoints or subsampled
