@@ -23,7 +23,9 @@ _EXPORTS = {
                      "get_instance", "mask_nms", "rle_encode_gpu_batch", "furthestsampling_batchflat",
                      "ballquery_batchflat", "furthest_point_sample", "ball_query", "sample_queries",
                      "voxelization_idx", "voxelization", "spformer_match", "spformer_layer_losses",
-                     "spformer_criterion", "spformer_instances", "spformer_predict"),
+                     "spformer_criterion", "spformer_instances", "spformer_predict", "superpoint_plan",
+                     "superpoint_pool", "scatter_mean", "scatter_max", "custom_scatter_mean", "isbnet_spp_pool",
+                     "spformer_pool"),
 }
 __all__ = [n for names in _EXPORTS.values() for n in names]
 

@@ -274,6 +274,19 @@ VOXELIZE_MAX_ACTIVE = 4096    # GAPRO_VOXELIZE_MAX_ACTIVE: points of one voxel i
 VOXELIZE_STATUS_WORDS = 4     # GAPRO_VOXELIZE_STATUS_WORDS: status, flags, 0, 0 (the header: n_voxels, max_active)
 
 
+SPP_SORT_TILE, SPP_MAX_SEGMENTS, SPP_MAX_BATCHES, SPP_STATUS_WORDS = 4096, 1 << 24, 65536, 4   # GAPRO_SPP_*
+SPP_FLAG_INDEX, SPP_FLAG_MAP, SPP_MEAN, SPP_MAX = 1, 2, 0, 1
+
+
+class SppPlan(C.Structure):
+    """gapro_spp_plan: the sizes and device pointers of a superpoint pooling plan (a host struct, read when a call
+    enqueues)."""
+    _fields_ = [("n_points", C.c_int64), ("n_spps", C.c_int64), ("n_rows", C.c_int64), ("d_index", C.c_void_p),
+                ("d_point_map", C.c_void_p), ("index_i64", C.c_int32), ("map_i64", C.c_int32),
+                ("d_seg_off", C.c_void_p), ("d_seg_pts", C.c_void_p), ("d_counts", C.c_void_p),
+                ("d_row_off", C.c_void_p), ("d_row_pts", C.c_void_p), ("d_seg_rows", C.c_void_p)]
+
+
 class VoxelizeHeader(C.Structure):
     """gapro_voxelize_header: what gapro_voxelize_count / gapro_voxelize_host_count report."""
     _fields_ = [("status", C.c_int32), ("flags", C.c_int32), ("n_voxels", C.c_int32), ("max_active", C.c_int32)]
@@ -411,6 +424,10 @@ SIGNATURES = {
                                            C.c_int32, _P, C.c_size_t, _P, _P, _P]),
     "gapro_voxel_pool_backward": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, _P, C.c_int32, _P,
                                             _P, _P]),
+    "gapro_spp_plan_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gapro_spp_plan_build": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int32, _P, _P, C.c_size_t, _P, _P]),
+    "gapro_spp_pool_forward": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "gapro_spp_pool_backward": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "gapro_schedule_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "gapro_schedule_free": (None, [_P]),
     "gapro_schedule_get_counts": (C.c_int, [_P, C.POINTER(ScheduleCounts)]),
@@ -594,7 +611,8 @@ def load() -> C.CDLL:
                                             "gapro_schedule_export_testers", "gapro_spp_vote",
                                             "gapro_fit_launch_plan", "gapro_inst_", "gapro_spp_gt_", "gapro_match_",
                                             "gapro_proposals_", "gapro_fps_", "gapro_ball_query_",
-                                            "gapro_lsap_", "gapro_voxelize_", "gapro_voxel_pool_", "gapro_spf_predict_")):
+                                            "gapro_lsap_", "gapro_voxelize_", "gapro_voxel_pool_", "gapro_spf_predict_",
+                                            "gapro_spp_plan_", "gapro_spp_pool_")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

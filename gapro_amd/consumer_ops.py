@@ -1841,6 +1841,313 @@ def voxelization(feats, map_rule, mode=4, *, check=True, n_points=None):
     return Voxelization.apply(feats, map_rule, mode, check)
 
 
+# ---- superpoint pooling: torch_scatter's scatter_mean / scatter_max with grad (csrc/spp_pool.hip) ------
+_SPP_CAUSES = ((_lib.SPP_FLAG_INDEX, "a superpoint index outside [0, n_spps)"),
+               (_lib.SPP_FLAG_MAP, "a point_map value outside [0, n_rows)"))
+_SPP_REDUCE = {"mean": _lib.SPP_MEAN, "max": _lib.SPP_MAX}
+
+
+class SuperpointPlan:
+    """What ``superpoint_plan`` built: ``n_points``, ``n_spps``, ``n_rows`` (0 without a point map), ``counts``
+    int32 ``[S]``, the CSR by superpoint ``seg_off`` int32 ``[S + 1]`` / ``seg_pts`` int32 ``[N]``, with a point map
+    the CSR by source row ``row_off`` / ``row_pts`` and ``seg_rows``, and ``spp_batch_offsets`` int64 ``[B + 1]`` (or
+    ``None``).  It keeps the index tensors it was built from: they must not be written while it is in use."""
+    __slots__ = ("n_points", "n_spps", "n_rows", "index", "point_map", "counts", "seg_off", "seg_pts", "row_off",
+                 "row_pts", "seg_rows", "spp_batch_offsets", "device", "_struct")
+
+    def struct(self):
+        return C.byref(self._struct)
+
+
+def _empty_plan(dev, S, R, B):
+    plan = SuperpointPlan()
+    z = lambda n, dt=torch.int32: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
+    plan.n_points, plan.n_spps, plan.n_rows, plan.device = 0, S, R, dev
+    plan.index = plan.point_map = plan._struct = None
+    plan.counts, plan.seg_off, plan.seg_pts = z(S), z(S + 1), z(0)
+    plan.row_off, plan.row_pts, plan.seg_rows = (z(R + 1), z(0), z(0)) if R else (None, None, None)
+    plan.spp_batch_offsets = z(B + 1, torch.int64) if B else None
+    return plan
+
+
+def superpoint_plan(superpoints, *, n_spps=None, point_map=None, n_rows=None, batch_offsets=None, check=True):
+    """The plan of a step's superpoint pooling (``gapro_spp_plan_build``), built once and shared by
+    every tensor that ``superpoint_pool`` pools: a ``SuperpointPlan``.
+
+    ``superpoints`` is a 1-D integer device tensor ``[N]`` with values in ``[0, n_spps)``; ``n_spps=None`` reads
+    ``max(superpoints) + 1`` from the device (one host read).  ``point_map`` (1-D integer ``[N]``, values in ``[0,
+    n_rows)``, ``n_rows`` needed) makes point ``p`` read row ``point_map[p]`` of the pooled tensor -- the fused form of
+    ``x[v2p_map]`` followed by the scatter.  ``batch_offsets`` (1-D integer ``[B + 1]``, the point offsets of the
+    samples) adds ``spp_batch_offsets``: per sample the number of non-empty superpoints whose first point lies in it,
+    which is ISBNet's loop of ``torch.unique`` (isbnet.py:736-742) when no id is shared between samples, without a host
+    read.  ``check=True`` reads the status word (the call's host read): an index outside ``[0, n_spps)`` or a map value
+    outside ``[0, n_rows)`` is a ``GaproError``; with ``check=False`` the call only enqueues and such a point is left
+    out of every superpoint.  Bounds: ``n_spps`` and ``n_rows`` up to 2^24, ``N`` up to 2^31 - 1."""
+    who = "superpoint_plan"
+    _index_check(who, "superpoints", superpoints)
+    N = int(superpoints.shape[0])
+    if point_map is not None:
+        _index_check(who, "point_map", point_map)
+        if int(point_map.shape[0]) != N:
+            raise ValueError("%s: point_map has %d entries, expected %d" % (who, int(point_map.shape[0]), N))
+        _positive_int_arg(who, "n_rows", n_rows)
+    elif n_rows is not None:
+        raise ValueError("%s: n_rows is the row count of point_map's target and needs point_map" % who)
+    if batch_offsets is not None:
+        _index_check(who, "batch_offsets", batch_offsets)
+        if int(batch_offsets.shape[0]) < 2:
+            raise ValueError("%s: batch_offsets needs at least two entries" % who)
+    if not isinstance(check, bool):
+        raise ValueError("%s: check must be a bool" % who)
+    if n_spps is None and N == 0:
+        raise ValueError("%s: n_spps is needed for an empty superpoints tensor" % who)
+    B = int(batch_offsets.shape[0]) - 1 if batch_offsets is not None else 0
+    R = int(n_rows) if point_map is not None else 0
+    if n_spps is not None:
+        _positive_int_arg(who, "n_spps", n_spps)
+    if N > 2 ** 31 - 1 or R > _lib.SPP_MAX_SEGMENTS or B > _lib.SPP_MAX_BATCHES or \
+            (n_spps is not None and n_spps > _lib.SPP_MAX_SEGMENTS):
+        raise ValueError("%s: %d points, %r superpoints, %d rows, %d samples: beyond the library's bounds (2^31 - 1 "
+                         "points, 2^24 superpoints and rows, 65536 samples)" % (who, N, n_spps, R, B))
+    _need_device(superpoints, point_map, batch_offsets)
+    dev = superpoints.device
+    _one_device(who, dev, [t for t in (point_map, batch_offsets) if t is not None])
+    S = _n_spps_arg(who, n_spps, superpoints)
+    if S > _lib.SPP_MAX_SEGMENTS:
+        raise ValueError("%s: %d superpoints are beyond the library's bounds (2^24)" % (who, S))
+    if N == 0:
+        return _empty_plan(dev, S, R, B)
+    ctx, stream = _ctx_stream(superpoints)
+    lib = ctx.lib
+    plan = SuperpointPlan()
+    plan.n_points, plan.n_spps, plan.n_rows, plan.device = N, S, R, dev
+    plan.index, index_i64 = _as_index(superpoints.detach())
+    plan.point_map, map_i64 = _as_index(point_map.detach()) if R else (None, 0)
+    with torch.cuda.device(dev):
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)  # noqa: E731
+        plan.counts, plan.seg_off, plan.seg_pts = i32(S), i32(S + 1), i32(N)
+        plan.row_off, plan.row_pts, plan.seg_rows = (i32(R + 1), i32(N), i32(N)) if R else (None, None, None)
+        plan.spp_batch_offsets = torch.empty(B + 1, dtype=torch.int64, device=dev) if B else None
+        offsets, offsets_i64 = _as_index(batch_offsets.detach()) if B else (None, 0)
+        plan._struct = _lib.SppPlan(N, S, R, _ptr(plan.index), _ptr(plan.point_map), index_i64, map_i64,
+                                    _ptr(plan.seg_off), _ptr(plan.seg_pts), _ptr(plan.counts), _ptr(plan.row_off),
+                                    _ptr(plan.row_pts), _ptr(plan.seg_rows))
+        ws = _workspace(who, int(lib.gapro_spp_plan_workspace_bytes(N, B)), dev, "%d points are" % N)
+        d_status, h_status = _status_pair(dev, _lib.SPP_STATUS_WORDS, torch.int32, read=check)
+        ctx.check(lib.gapro_spp_plan_build(ctx.handle, stream, plan.struct(), B, _ptr(offsets), offsets_i64,
+                                           _ptr(plan.spp_batch_offsets), ws.data_ptr(), ws.numel(),
+                                           d_status.data_ptr(), _ptr(h_status)))
+        if h_status is not None:  # the call's host read of its status, asked for by check=True
+            status, flags = _host_read(dev, h_status)[:2]
+            _refuse(who, status, flags, _SPP_CAUSES)
+    return plan
+
+
+class _SuperpointPool(torch.autograd.Function):
+    """Both reductions of ``superpoint_pool``, which checks the arguments first: ``(out, arg)``, ``arg`` None for the
+    mean."""
+
+    @staticmethod
+    def forward(fctx, x, plan, reduce, mapped):
+        Cn, S, dev = int(x.shape[1]), plan.n_spps, x.device
+        fctx.plan, fctx.reduce, fctx.mapped, fctx.shape = plan, reduce, mapped, tuple(x.shape)
+        out = torch.empty((S, Cn), dtype=torch.float32, device=dev)
+        arg = torch.empty((S, Cn), dtype=torch.int64, device=dev) if reduce == _lib.SPP_MAX else None
+        if plan.n_points == 0:
+            out.zero_()
+            if arg is not None:
+                arg.zero_()  # N = 0: the fill value
+        else:
+            x = _row_contiguous(x.detach())
+            ctx, stream = _ctx_stream(x)
+            with torch.cuda.device(dev):
+                ctx.check(ctx.lib.gapro_spp_pool_forward(ctx.handle, stream, plan.struct(), x.data_ptr(),
+                                                         int(x.shape[0]), int(x.stride(0)), Cn, reduce, int(mapped),
+                                                         out.data_ptr(), _ptr(arg)))
+        if arg is not None:
+            fctx.mark_non_differentiable(arg)
+            fctx.save_for_backward(arg)
+        return out, arg
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad_out, _grad_arg=None):
+        plan, reduce, mapped = fctx.plan, fctx.reduce, fctx.mapped
+        dev = grad_out.device
+        if plan.n_points == 0 or 0 in fctx.shape:
+            return torch.zeros(fctx.shape, dtype=torch.float32, device=dev), None, None, None
+        arg = fctx.saved_tensors[0] if reduce == _lib.SPP_MAX else None
+        grad_out = grad_out.contiguous()
+        ctx, stream = _ctx_stream(grad_out)
+        with torch.cuda.device(dev):
+            d_x = torch.empty(fctx.shape, dtype=torch.float32, device=dev)
+            ctx.check(ctx.lib.gapro_spp_pool_backward(ctx.handle, stream, plan.struct(), grad_out.data_ptr(),
+                                                      fctx.shape[1], reduce, int(mapped), _ptr(arg), d_x.data_ptr()))
+        return d_x, None, None, None
+
+
+def superpoint_pool(x, plan, reduce="mean", *, return_arg=False, through_map=None):
+    """``torch_scatter.scatter_mean`` / ``scatter_max`` of ``x`` (float32 ``[R, C]`` or ``[R]``, on the plan's device)
+    to the superpoints of ``plan``: float32 ``[S, C]`` (``[S]``), differentiable in ``x``; with ``return_arg=True``
+    (max only) also ``arg`` int64 of the same shape.
+
+    The definition.  A superpoint's points are taken IN ASCENDING POINT INDEX.  ``mean``: ``((+0 +
+    x_1) + x_2) + ...`` in float32, each sum rounded on its own, then a true division by ``float32(n)``; an empty
+    superpoint is ``+0.0``.  ``max``: the first value, replaced by a later one only if it is greater -- the lowest point
+    wins ties, a NaN never replaces and a leading NaN stays; an empty superpoint is ``+0.0`` with ``arg = N``.  The
+    gradient of the mean is ``fl(g / float32(n))`` per point, of the max ``g`` at ``arg``; through a point map the
+    points of a row are added in ascending point order from ``+0``.  Everything is bit for bit reproducible: there are
+    no floating-point atomics.
+
+    ``through_map`` (default: whether the plan has a point map) says whether ``x`` has the map's ``n_rows`` rows and is
+    read through it, or one row a point -- a plan with a map serves both."""
+    who = "superpoint_pool"
+    if not isinstance(plan, SuperpointPlan):
+        raise ValueError("%s: plan must come from superpoint_plan" % who)
+    if reduce not in _SPP_REDUCE:
+        raise ValueError("%s: reduce must be 'mean' or 'max'; other reductions are not built" % who)
+    if not isinstance(return_arg, bool) or (return_arg and reduce != "max"):
+        raise ValueError("%s: return_arg must be a bool, and True only with reduce='max'" % who)
+    if through_map is None:
+        through_map = plan.n_rows > 0
+    if not isinstance(through_map, bool) or (through_map and plan.n_rows == 0):
+        raise ValueError("%s: through_map must be a bool, and True only for a plan with a point_map" % who)
+    rows = plan.n_rows if through_map else plan.n_points
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() not in (1, 2) or \
+            int(x.shape[0]) != rows or (x.dim() == 2 and int(x.shape[1]) < 1):
+        raise ValueError("%s: x must be a float32 tensor of shape [%d] or [%d, C], C >= 1" % (who, rows, rows))
+    _need_device(x)
+    _one_device(who, plan.device, (x,))
+    flat = x.dim() == 1
+    out, arg = _SuperpointPool.apply(x[:, None] if flat else x, plan, _SPP_REDUCE[reduce], through_map)
+    if flat:
+        out, arg = out[:, 0], (arg[:, 0] if arg is not None else None)
+    return (out, arg) if return_arg else out
+
+
+def _scatter_args(who, src, index, dim, dim_size):
+    if not isinstance(src, torch.Tensor) or src.dim() not in (1, 2):
+        raise ValueError("%s: src must be a 1-D or 2-D tensor; other ranks are not built" % who)
+    if not _is_int(dim) or not (dim == 0 or (dim == -1 and src.dim() == 1)):
+        raise ValueError("%s: dim=%r is not built; only dim=0, and dim=-1 of a 1-D src" % (who, dim))
+    if not isinstance(index, torch.Tensor) or index.dtype not in _INDEX_DTYPES:
+        raise ValueError("%s: index must be an integer tensor" % who)
+    if index.dim() == 2 and src.dim() == 2 and index.shape == src.shape and \
+            (index.stride(1) == 0 or index.shape[1] == 1):
+        index = index[:, 0]  # the reference's index[:, None].expand_as(src)
+    if index.dim() != 1 or index.shape[0] != src.shape[0]:
+        raise ValueError("%s: index must be 1-D of src's length, or that vector expanded along dim 1; a general "
+                         "element-wise index is not built" % who)
+    if dim_size is not None:
+        _positive_int_arg(who, "dim_size", dim_size)
+    return index
+
+
+def scatter_mean(src, index, dim=0, dim_size=None):
+    """``torch_scatter.scatter_mean(src, index, dim=0, dim_size=dim_size)`` for a float32 device ``src`` of shape ``[N]``
+    or ``[N, C]`` and a 1-D ``index`` (or its ``[:, None].expand_as(src)`` form), differentiable in ``src``, by
+    ``superpoint_pool``'s definition.  Anything else is a ``ValueError`` that names what is not built.  ``dim_size=None``
+    reads ``max(index) + 1`` from the device; an index out of range is a ``GaproError``."""
+    who = "scatter_mean"
+    index = _scatter_args(who, src, index, dim, dim_size)
+    if src.dtype != torch.float32:
+        raise ValueError("%s: only a float32 src is built" % who)
+    return superpoint_pool(src, superpoint_plan(index, n_spps=dim_size), "mean")
+
+
+def scatter_max(src, index, dim=0, dim_size=None):
+    """``torch_scatter.scatter_max``: ``(out, arg)``; see ``scatter_mean`` for what is built and ``superpoint_pool`` for
+    the definition (``arg`` int64: the lowest point index among equal maxima, ``N`` for an empty segment)."""
+    who = "scatter_max"
+    index = _scatter_args(who, src, index, dim, dim_size)
+    if src.dtype != torch.float32:
+        raise ValueError("%s: only a float32 src is built" % who)
+    return superpoint_pool(src, superpoint_plan(index, n_spps=dim_size), "max", return_arg=True)
+
+
+def _pool_cast(x, plan, output_type=None, **kw):
+    """A pool of a float32 / half / bfloat16 tensor, computed in float32 and cast to ``output_type`` or back."""
+    out = superpoint_pool(x if x.dtype == torch.float32 else x.to(torch.float32), plan, "mean", **kw)
+    want = x.dtype if output_type is None else output_type
+    return out if want == torch.float32 else out.to(want)
+
+
+_SPP_FLOATS = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def custom_scatter_mean(input_feats, indices, dim=0, pool=True, output_type=None):
+    """``custom_scatter_mean`` of ISBNet (isbnet/model/model_utils.py:600-613): ``scatter_mean`` of ``input_feats``
+    (float32, half or bfloat16) computed in float32 and cast back to the input's dtype or to ``output_type``;
+    ``pool=False`` returns the input."""
+    who = "custom_scatter_mean"
+    if not pool:
+        return input_feats
+    if not isinstance(input_feats, torch.Tensor) or input_feats.dtype not in _SPP_FLOATS:
+        raise ValueError("%s: input_feats must be a float32, half or bfloat16 tensor" % who)
+    if output_type is not None and not isinstance(output_type, torch.dtype):
+        raise ValueError("%s: output_type must be a torch.dtype" % who)
+    indices = _scatter_args(who, input_feats, indices, dim, None)
+    return _pool_cast(input_feats, superpoint_plan(indices), output_type)
+
+
+def isbnet_spp_pool(voxel_coords_float, voxel_output_feats, voxel_box_preds, voxel_spps, voxel_batch_offsets, *,
+                    n_spps=None, use_spp_pool=True, check=False):
+    """``ISBNet.spp_pool`` (isbnet/model/isbnet.py:735-748): ``(spp_coords_float, spp_output_feats, spp_box_preds,
+    spp_batch_offsets)`` from ONE plan and three pools.  ``spp_batch_offsets`` (int64 ``[B + 1]``, on the device) comes
+    from the plan instead of ``B`` blocking ``torch.unique`` calls.  With ``n_spps`` given the call makes no host read
+    (``check=True`` adds the read of the status word); ``use_spp_pool=False`` returns the three tensors as they are."""
+    who = "isbnet_spp_pool"
+    feats = (voxel_coords_float, voxel_output_feats, voxel_box_preds)
+    for name, t in zip(("voxel_coords_float", "voxel_output_feats", "voxel_box_preds"), feats):
+        if not isinstance(t, torch.Tensor) or t.dtype not in _SPP_FLOATS or t.dim() not in (1, 2):
+            raise ValueError("%s: %s must be a 1-D or 2-D float32, half or bfloat16 tensor" % (who, name))
+    if not isinstance(use_spp_pool, bool):
+        raise ValueError("%s: use_spp_pool must be a bool" % who)
+    _index_check(who, "voxel_spps", voxel_spps)
+    for name, t in zip(("voxel_coords_float", "voxel_output_feats", "voxel_box_preds"), feats):
+        if int(t.shape[0]) != int(voxel_spps.shape[0]):
+            raise ValueError("%s: %s has %d rows, voxel_spps %d entries" % (who, name, int(t.shape[0]),
+                                                                           int(voxel_spps.shape[0])))
+    plan = superpoint_plan(voxel_spps, n_spps=n_spps, batch_offsets=voxel_batch_offsets, check=check)
+    _need_device(*feats)
+    if not use_spp_pool:
+        return voxel_coords_float, voxel_output_feats, voxel_box_preds, plan.spp_batch_offsets
+    return tuple(_pool_cast(t, plan) for t in feats) + (plan.spp_batch_offsets,)
+
+
+def spformer_pool(x, coords_float, rgb_feats, superpoints, v2p_map, prob_labels=None, mu_labels=None, var_labels=None,
+                  *, pool="mean", n_spps=None, check=False):
+    """Lines 251-280 of SPFormer's ``extract_feat`` (spformer/model/spformer.py): the gathers ``x[v2p_map]``,
+    ``coords_float[v2p_map]``, ``rgb_feats[v2p_map]`` fused into their ``scatter_mean`` / ``scatter_max`` through the
+    plan's point map, and the three per-point label channels pooled by the same plan.  ``x`` (the backbone's
+    ``features``), ``coords_float`` and ``rgb_feats`` are per voxel, the labels per point.  Returns the reference's
+    3-tuple, or its 6-tuple when ``prob_labels`` is given; the gradient reaches ``x`` only.  With ``n_spps`` given the
+    call makes no host read (``check=True`` adds the read of the status word)."""
+    who = "spformer_pool"
+    _tensor_arg(who, "x", x, ("R", "C"))
+    R = int(x.shape[0])
+    _tensor_arg(who, "coords_float", coords_float, (R, "D"))
+    _tensor_arg(who, "rgb_feats", rgb_feats, (R, "D"))
+    if pool not in _SPP_REDUCE:
+        raise ValueError("%s: pool must be 'mean' or 'max'" % who)
+    labels = (prob_labels, mu_labels, var_labels)
+    if any(t is None for t in labels) and prob_labels is not None:
+        raise ValueError("%s: prob_labels comes with mu_labels and var_labels" % who)
+    _index_check(who, "superpoints", superpoints)
+    N = int(superpoints.shape[0])
+    if prob_labels is not None:
+        for name, t in zip(("prob_labels", "mu_labels", "var_labels"), labels):
+            _tensor_arg(who, name, t, (N,))
+    if R < 1 or int(x.shape[1]) < 1:
+        raise ValueError("%s: x needs a row and a channel" % who)
+    plan = superpoint_plan(superpoints, n_spps=n_spps, point_map=v2p_map, n_rows=R, check=check)
+    outs = [superpoint_pool(x, plan, pool), superpoint_pool(coords_float.detach(), plan, pool),
+            superpoint_pool(rgb_feats.detach(), plan, pool)]
+    if prob_labels is not None:
+        outs += [superpoint_pool(t.detach(), plan, pool, through_map=False) for t in labels]
+    return tuple(outs)
+
+
 # ---- SPFormer's criterion (gapro_amd/csrc/spf_loss.hip, match_cost.hip, lsap.cc; DESIGN.md 4.11) ------------------------
 SPF_LOSS_NAMES = ("cls_loss", "mask_bce_loss", "mask_dice_loss", "score_loss", "levelset_loss")  # the table's columns
 _SPF_OUT_NAMES = ("cls_loss", "score_loss", "mask_bce_loss", "mask_dice_loss", "levelset_loss")  # loss_out's order

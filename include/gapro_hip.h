@@ -1601,6 +1601,87 @@ int gapro_voxel_pool_backward(gapro_ctx* ctx, void* stream, int64_t n_points, in
                               int32_t* d_status, int32_t* h_status_pinned /* NULL: no copy */);
 
 /* ------------------------------------------------------------------------------------------
+ * Superpoint pooling (csrc/spp_pool.hip).  Replaces torch_scatter's scatter_mean / scatter_max where
+ * the consumers pool backbone features to superpoints (SPFormer spformer.py:251-280, ISBNet isbnet.py:735-748 and
+ * model_utils.py:600-613), with their gradients.
+ * The definition.  src is f32[R, C] (rows of any stride >= C), index is i32/i64[N] with values in [0, S), point_map is
+ * an optional i32/i64[N] with values in [0, R): point p reads row point_map[p] of src; without it R == N and point p
+ * reads row p.  Segment s is the set of points with index[p] == s IN ASCENDING p, n_s its length.
+ *   mean      out[s, c] = fl(sum / fl(n_s)), sum = ((+0 + x_1) + x_2) + ... over the segment in ascending p, every
+ *             operation rounded to float32 on its own (no contraction), a true division and not a multiplication by a
+ *             reciprocal.  n_s = 0 gives +0.0; a lone -0.0 gives +0.0.  This is scatter_mean (scatter_add_, the count
+ *             clamped to 1, true_divide_) with its atomics arriving in point order.
+ *   max       best starts as the segment's first value and arg as that point; a later value replaces it only if
+ *             v > best in float32: the lowest point index wins ties (+0.0 against -0.0 included), a NaN never replaces
+ *             anything and a leading NaN is never replaced.  n_s = 0 gives +0.0 and arg = N.  arg is i64[S, C] and
+ *             holds POINT indices.
+ *   backward  mean: d_point[p, c] = fl(g[index[p], c] / fl(n)); max: d_point[p, c] = g[s, c] if arg[s, c] == p, else 0.
+ *             Without point_map d_src = d_point; with it d_src[r, c] is the sum of d_point[p, c] over the points with
+ *             point_map[p] == r in ascending p, in float32 from +0, and a row that no point reads gets 0.  The
+ *             gradient array is written whole by plain stores.  No floating-point atomics anywhere.
+ * The plan (gapro_spp_plan: sizes and device pointers, a host struct read when a call enqueues; the caller owns every
+ * array and keeps index and point_map unchanged while the plan is in use).  gapro_spp_plan_build writes
+ *   seg_off i32[S + 1], seg_pts i32[N]   the CSR by superpoint, each segment in ascending point order; the points left
+ *                                        out (below) follow the last segment in ascending order
+ *   counts  i32[S]
+ *   row_off i32[R + 1], row_pts i32[N]   with point_map: the CSR by source row, by the same routine
+ *   seg_rows i32[N]                      with point_map: point_map[seg_pts[k]]; -1 behind the last segment
+ * by a stable LSD radix sort of the point indices by key: 8-bit digits, ceil(bits(S) / 8) passes (the key S is the
+ * sentinel of a point left out), per pass a histogram per tile of GAPRO_SPP_SORT_TILE points, an exclusive scan of the
+ * bin-major histogram in three launches (no look-back, no spin-wait) and a stable scatter (ballot ranks within a wave,
+ * a per-wave bin scan in LDS); the offsets by bisection.  Integer atomics only, the output does not depend on the
+ * schedule, and the cost is linear in N whatever the segments' lengths.
+ * With n_batches > 0, d_batch_offsets (i32/i64[n_batches + 1], the point offsets of the samples) gives
+ * d_spp_batch_offsets i64[n_batches + 1]: entry b + 1 minus entry b is the number of non-empty segments whose first
+ * point lies in sample b -- the reference's loop of torch.unique when no id is shared between samples.
+ * d_status i32[GAPRO_SPP_STATUS_WORDS] = {status, flags, 0, 0}, cleared by the call, copied to h_status_pinned when
+ * given: GAPRO_ERR_BAD_ARG with GAPRO_SPP_FLAG_INDEX (an index outside [0, S)) or GAPRO_SPP_FLAG_MAP (a map value
+ * outside [0, R)).  A flagged point is left out of every segment and row and receives no gradient; nothing is read or
+ * written out of range.  Refused before anything is launched (GAPRO_ERR_BAD_ARG): a null argument, N outside
+ * [1, 2^31 - 1], S outside [1, GAPRO_SPP_MAX_SEGMENTS], R beyond it, n_batches beyond GAPRO_SPP_MAX_BATCHES;
+ * GAPRO_ERR_WORKSPACE: fewer than gapro_spp_plan_workspace_bytes(N, n_batches) bytes (0 for sizes the build refuses).
+ * gapro_spp_pool_forward: a thread per (segment, channel), consecutive lanes on consecutive channels; reduce is
+ * GAPRO_SPP_MEAN or GAPRO_SPP_MAX (d_arg needed); through_map != 0 reads src [n_rows, C] through the plan's map,
+ * through_map == 0 reads src [N, C] by point (a plan with a map serves both).  gapro_spp_pool_backward writes
+ * d_grad_src [n_rows or N, C] whole.  Both only enqueue; C is any positive int.
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_SPP_SORT_TILE 4096
+#define GAPRO_SPP_MAX_SEGMENTS (1 << 24)
+#define GAPRO_SPP_MAX_BATCHES 65536
+#define GAPRO_SPP_STATUS_WORDS 4
+#define GAPRO_SPP_FLAG_INDEX 1
+#define GAPRO_SPP_FLAG_MAP 2
+#define GAPRO_SPP_MEAN 0
+#define GAPRO_SPP_MAX 1
+typedef struct gapro_spp_plan {
+  int64_t n_points;          /* N */
+  int64_t n_spps;            /* S */
+  int64_t n_rows;            /* R; 0: no point_map */
+  const void* d_index;       /* [N] */
+  const void* d_point_map;   /* [N] or NULL */
+  int32_t index_i64;         /* 1: d_index is int64 */
+  int32_t map_i64;
+  int32_t* d_seg_off;        /* [S + 1] */
+  int32_t* d_seg_pts;        /* [N] */
+  int32_t* d_counts;         /* [S] */
+  int32_t* d_row_off;        /* [R + 1] or NULL */
+  int32_t* d_row_pts;        /* [N] or NULL */
+  int32_t* d_seg_rows;       /* [N] or NULL */
+} gapro_spp_plan;
+size_t gapro_spp_plan_workspace_bytes(int64_t n_points, int64_t n_batches);
+int gapro_spp_plan_build(gapro_ctx* ctx, void* stream, const gapro_spp_plan* plan, int64_t n_batches,
+                         const void* d_batch_offsets /* or NULL */, int32_t offsets_i64,
+                         int64_t* d_spp_batch_offsets /* [n_batches + 1] or NULL */, void* d_workspace,
+                         size_t workspace_bytes, int32_t* d_status, int32_t* h_status_pinned /* NULL: no copy */);
+int gapro_spp_pool_forward(gapro_ctx* ctx, void* stream, const gapro_spp_plan* plan, const float* d_src,
+                           int64_t src_rows, int64_t src_ld, int32_t n_channels, int32_t reduce, int32_t through_map,
+                           float* d_out /* [S, C] */, int64_t* d_arg /* [S, C]; NULL for the mean */);
+int gapro_spp_pool_backward(gapro_ctx* ctx, void* stream, const gapro_spp_plan* plan,
+                            const float* d_grad_out /* [S, C] */, int32_t n_channels, int32_t reduce,
+                            int32_t through_map, const int64_t* d_arg /* max */,
+                            float* d_grad_src /* [n_rows or N, C] */);
+
+/* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
  * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
  * to superpoint means (:64-69) or by keeping the npoint_nearest points of each side nearest to the centroid of the
