@@ -25,7 +25,7 @@ _EXPORTS = {
                      "voxelization_idx", "voxelization", "spformer_match", "spformer_layer_losses",
                      "spformer_criterion", "spformer_instances", "spformer_predict", "superpoint_plan",
                      "superpoint_pool", "scatter_mean", "scatter_max", "custom_scatter_mean", "isbnet_spp_pool",
-                     "spformer_pool"),
+                     "spformer_pool", "dynamic_mask_head", "mask_heads_forward", "dyco_param_count"),
 }
 __all__ = [n for names in _EXPORTS.values() for n in names]
 

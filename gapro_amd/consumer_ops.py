@@ -91,6 +91,25 @@ def _index_arg(t, name, who, n=None):
     return _as_index(t)
 
 
+def _host_offsets_arg(who, batch_offsets, B, N):
+    """``batch_offsets`` as ``B + 1`` host ints that do not decrease and stay inside ``[0, N]``."""
+    if isinstance(batch_offsets, torch.Tensor):
+        if batch_offsets.device.type != "cpu":
+            raise ValueError("%s: batch_offsets must be on the host (a sequence, a NumPy array or a CPU tensor)" % who)
+        batch_offsets = batch_offsets.tolist()
+    try:
+        off = [int(v) for v in batch_offsets]
+        if any(o != v for o, v in zip(off, batch_offsets)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("%s: batch_offsets must be a host sequence of integers" % who) from None
+    if len(off) != B + 1:
+        raise ValueError("%s: %d batch offsets for batch_size %d; batch_size + 1 are expected" % (who, len(off), B))
+    if off[0] < 0 or off[-1] > N or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError("%s: batch_offsets must not decrease and must stay inside [0, %d]" % (who, N))
+    return off
+
+
 def _n_spps_arg(who, n_spps, spps):
     """The bound of the superpoint ids: the caller's positive int, or ``max(spps) + 1`` of the device tensor."""
     if n_spps is not None:
@@ -776,20 +795,7 @@ def _check_loss_args(who, cls_logits, mask_logits, conf_logits, box_preds, prob_
     if empty_weight is not None:
         _tensor_arg(who, "empty_weight", empty_weight, (n_classes,))
     _finite_arg(who, "voxel_scale", voxel_scale)
-    if isinstance(batch_offsets, torch.Tensor):
-        if batch_offsets.device.type != "cpu":
-            raise ValueError("%s: batch_offsets must be on the host (a sequence, a NumPy array or a CPU tensor)" % who)
-        batch_offsets = batch_offsets.tolist()
-    try:
-        off = [int(v) for v in batch_offsets]
-        if any(o != v for o, v in zip(off, batch_offsets)):
-            raise ValueError
-    except (TypeError, ValueError):
-        raise ValueError("%s: batch_offsets must be a host sequence of integers" % who) from None
-    if len(off) != B + 1:
-        raise ValueError("%s: %d batch offsets for batch_size %d; batch_size + 1 are expected" % (who, len(off), B))
-    if off[0] < 0 or off[-1] > N or any(b < a for a, b in zip(off, off[1:])):
-        raise ValueError("%s: batch_offsets must not decrease and must stay inside [0, %d]" % (who, N))
+    off = _host_offsets_arg(who, batch_offsets, B, N)
     tensors = [conf_logits, box_preds, prob_labels, levelset_feats, levelset_coords]
     if empty_weight is not None:
         tensors.append(empty_weight)
@@ -2146,6 +2152,154 @@ def spformer_pool(x, coords_float, rgb_feats, superpoints, v2p_map, prob_labels=
     if prob_labels is not None:
         outs += [superpoint_pool(t.detach(), plan, pool, through_map=False) for t in labels]
     return tuple(outs)
+
+
+# ---- ISBNet's dynamic-convolution mask head (gapro_amd/csrc/dyco_head.hip) ------------------------------
+def dyco_param_count(mask_dim_out):
+    """The length P of a controller row for ``mask_dim_out`` channels: ``(C + 6) C + C C/2 + C/2 + C + C/2 + 1`` (1793
+    at C = 32, 513 at C = 16).  Any other C is a ``ValueError``: it is not built."""
+    ok = _is_int(mask_dim_out) and 0 < mask_dim_out < 2 ** 31
+    P = int(_lib.load().gapro_dyco_param_count(mask_dim_out)) if ok else 0
+    if P == 0:
+        raise ValueError("dyco_param_count: mask_dim_out must be 16 or 32; %r is not built" % (mask_dim_out,))
+    return P
+
+
+def _float_arg(who, name, t, shape):
+    """A float32, half or bfloat16 tensor of ``shape`` (a str names a dimension of any size)."""
+    ok = isinstance(t, torch.Tensor) and t.dtype in _SPP_FLOATS and t.dim() == len(shape)
+    if ok:
+        ok = all(h == want or want.__class__ is str for h, want in zip(t.shape, shape))
+    if not ok:
+        raise ValueError("%s: %s must be a float32, half or bfloat16 tensor of shape [%s]"
+                         % (who, name, ", ".join(str(v) for v in shape)))
+
+
+class _DynamicMaskHead(torch.autograd.Function):
+    """The one autograd node of ``dynamic_mask_head``, which checks the arguments first: the packed logits forward, at
+    most two kernels backward."""
+
+    @staticmethod
+    def forward(fctx, off, controllers, mask_features, locs_float, box_preds, queries_locs, queries_box_preds):
+        B, Q, _ = (int(v) for v in controllers.shape)
+        N, Cn = (int(v) for v in mask_features.shape)
+        dev = controllers.device
+        tensors = [t.detach().contiguous() for t in (controllers, locs_float, box_preds, queries_locs,
+                                                     queries_box_preds)]
+        feats = _row_contiguous(mask_features.detach())
+        h_off = (C.c_int64 * (B + 1))(*off)
+        out = torch.empty(Q * (off[-1] - off[0]), dtype=torch.float32, device=dev)
+        fctx.dims = (B, Q, Cn, h_off, N, int(feats.stride(0)))
+        if out.numel() > 0:
+            ctx, stream = _ctx_stream(controllers)
+            with torch.cuda.device(dev):
+                ctx.check(ctx.lib.gapro_dyco_forward(ctx.handle, stream, B, Q, Cn, h_off, N, tensors[0].data_ptr(),
+                                                     feats.data_ptr(), int(feats.stride(0)), tensors[1].data_ptr(),
+                                                     tensors[2].data_ptr(), tensors[3].data_ptr(),
+                                                     tensors[4].data_ptr(), None, 0, out.data_ptr()))
+        fctx.save_for_backward(feats, *tensors)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad_out):
+        feats, controllers, locs_float, box_preds, queries_locs, queries_box_preds = fctx.saved_tensors
+        B, Q, Cn, h_off, N, ld = fctx.dims
+        need = fctx.needs_input_grad
+        dev = controllers.device
+        grad_out = grad_out.to(dtype=torch.float32).contiguous()
+        ctx, stream = _ctx_stream(controllers)
+        with torch.cuda.device(dev):
+            g_ctrl = torch.empty_like(controllers) if need[1] else None
+            g_feat = torch.empty((N, Cn), dtype=torch.float32, device=dev) if need[2] else None
+            g_box = torch.empty_like(box_preds) if need[4] else None
+            g_qbox = torch.empty_like(queries_box_preds) if need[6] else None
+            ctx.check(ctx.lib.gapro_dyco_backward(ctx.handle, stream, B, Q, Cn, h_off, N, controllers.data_ptr(),
+                                                  _ptr(feats), ld, _ptr(locs_float), _ptr(box_preds),
+                                                  queries_locs.data_ptr(), queries_box_preds.data_ptr(),
+                                                  _ptr(grad_out), None, 0, _ptr(g_ctrl), _ptr(g_qbox), _ptr(g_feat),
+                                                  _ptr(g_box)))
+        return None, g_ctrl, g_feat, None, g_box, None, g_qbox
+
+
+def dynamic_mask_head(controllers, mask_features, locs_float, box_preds, queries_locs, queries_box_preds,
+                      batch_offsets, *, check=True):
+    """The dynamic-convolution loop of ``ISBNet.forward_head`` (isbnet/model/isbnet.py:783-828, with
+    ``parse_dynamic_params`` :834-853 and ``mask_heads_forward`` :855-885) for a whole batch: ``mask_logits``, a list of B
+    entries, ``None`` for a sample without points and otherwise ``f32[Q, N_b]``, a view into ONE packed output -- what
+    ``hungarian_match``, ``matched_losses`` and ``get_instance`` take.  One launch forward; nothing of the reference's
+    ``[Q, C + 6, N_b]`` input exists, forward or backward.
+
+    ``controllers`` ``[B, Q, P]`` is the controller head's output as it stands (``P = dyco_param_count(C)``: W1, W2, W3,
+    b1, b2, b3 in ``parse_dynamic_params``'s order; b3 is not read), ``mask_features`` ``[N, C]`` or ``[N, C, 1]`` with C
+    16 or 32, ``locs_float`` ``[N, 3]``, ``box_preds`` ``[N, 6]``, ``queries_locs`` ``[B, Q, 3]``, ``queries_box_preds``
+    ``[B, Q, 6]``, ``batch_offsets`` ``B + 1`` host integers.  Float32, half or bfloat16 tensors, computed from their
+    float32 values; the logits are float32.
+
+    Float64 from the float32 inputs on the FP64 matrix cores, rounded once; no floating-point atomics,
+    so two calls give equal bytes.  Differentiable in ``controllers`` (the b3 column gets exact zeros), ``mask_features``,
+    ``box_preds`` and ``queries_box_preds`` by hand-derived kernels that recompute the hidden layers; ``locs_float`` and
+    ``queries_locs`` get ``None``, as they carry no gradient in the reference's step.  relu' at 0 and the derivative of
+    ``|d|`` at 0 are 0, as torch's.  Bad shapes, dtypes, devices or offsets, a C that is not built, a P that does not
+    match C and more than 64 samples are ``ValueError``s before a device is touched.  The call only enqueues; ``check``
+    is accepted for the family's signature and has nothing to read back."""
+    who = "dynamic_mask_head"
+    if not isinstance(check, bool):
+        raise ValueError("%s: check must be a bool" % who)
+    _float_arg(who, "controllers", controllers, ("B", "Q", "P"))
+    B, Q, P = (int(v) for v in controllers.shape)
+    if B < 1 or Q < 1:
+        raise ValueError("%s: controllers needs a sample and a query" % who)
+    if B > _lib.DYCO_MAX_BATCH:
+        raise ValueError("%s: %d samples; at most %d are built" % (who, B, _lib.DYCO_MAX_BATCH))
+    if isinstance(mask_features, torch.Tensor) and mask_features.dim() == 3 and mask_features.shape[2] == 1:
+        mask_features = mask_features[:, :, 0]
+    _float_arg(who, "mask_features", mask_features, ("N", "C"))
+    N, Cn = (int(v) for v in mask_features.shape)
+    if Cn not in (16, 32):
+        raise ValueError("%s: mask_features has %d channels; 16 and 32 are built" % (who, Cn))
+    if P != dyco_param_count(Cn):
+        raise ValueError("%s: controllers rows hold %d parameters; %d channels need %d"
+                         % (who, P, Cn, dyco_param_count(Cn)))
+    _float_arg(who, "locs_float", locs_float, (N, 3))
+    _float_arg(who, "box_preds", box_preds, (N, 6))
+    _float_arg(who, "queries_locs", queries_locs, (B, Q, 3))
+    _float_arg(who, "queries_box_preds", queries_box_preds, (B, Q, 6))
+    off = _host_offsets_arg(who, batch_offsets, B, N)
+    tensors = (controllers, mask_features, locs_float, box_preds, queries_locs, queries_box_preds)
+    _one_device(who, controllers.device, tensors)
+    _need_device(*tensors)
+    tensors = [t if t.dtype == torch.float32 else t.to(torch.float32) for t in tensors]
+    out = _DynamicMaskHead.apply(off, *tensors)
+    if off[-1] - off[0] == off[1] - off[0] > 0:
+        return [out.view(Q, off[1] - off[0])] + [None] * (B - 1)  # one sample holds every point: no slice node
+    return [out[Q * (a - off[0]):Q * (b - off[0])].view(Q, b - a) if b > a else None for a, b in zip(off, off[1:])]
+
+
+def mask_heads_forward(mask_features, weights, biases, num_insts, coords_, boxes_, queries_coords, queries_boxes):
+    """``ISBNet.mask_heads_forward`` (isbnet/model/isbnet.py:855-885) for one sample, for the inference path and for
+    callers that hold the parameters as ``parse_dynamic_params`` split them: ``mask_features`` ``[N, C, 1]`` (or
+    ``[N, C]``), ``weights`` ``[n, C + 6, C]``, ``[n, C, C/2]``, ``[n, C/2, 1]``, ``biases`` ``[n, C]``, ``[n, C/2]``,
+    ``[n, 1]``, ``coords_`` ``[N, 3]``, ``boxes_`` ``[N, 6]``, ``queries_coords`` ``[n, 3]``, ``queries_boxes``
+    ``[n, 6]``; returns ``f32[n, N]``.  The parameters are packed back into controller rows with torch ops, so autograd
+    reaches them, and ``dynamic_mask_head`` does the rest; the reference's sixteen S3DIS chunks are not needed, since
+    nothing of size ``n x C x N`` is materialised."""
+    who = "mask_heads_forward"
+    if not isinstance(weights, (list, tuple)) or not isinstance(biases, (list, tuple)) or len(weights) != 3 or \
+            len(biases) != 3 or not all(isinstance(t, torch.Tensor) and t.dim() >= 1 for t in (*weights, *biases)):
+        raise ValueError("%s: weights and biases must be the three tensors each of parse_dynamic_params" % who)
+    if not _is_int(num_insts) or any(int(t.shape[0]) != num_insts for t in (*weights, *biases)):
+        raise ValueError("%s: every weight and bias must have num_insts rows" % who)
+    if num_insts < 1:
+        raise ValueError("%s: num_insts must be positive" % who)
+    controllers = torch.cat([t.reshape(num_insts, -1) for t in (*weights, *biases)], dim=1)[None]
+    for name, t in (("queries_coords", queries_coords), ("queries_boxes", queries_boxes)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError("%s: %s must be a 2-D tensor" % (who, name))
+    n_points = int(mask_features.shape[0]) if isinstance(mask_features, torch.Tensor) and mask_features.dim() else 0
+    out = dynamic_mask_head(controllers, mask_features, coords_, boxes_, queries_coords[None], queries_boxes[None],
+                            [0, n_points])[0]
+    return out if out is not None else controllers.new_zeros((num_insts, 0), dtype=torch.float32)
 
 
 # ---- SPFormer's criterion (gapro_amd/csrc/spf_loss.hip, match_cost.hip, lsap.cc; DESIGN.md 4.11) ------------------------

@@ -1682,6 +1682,52 @@ int gapro_spp_pool_backward(gapro_ctx* ctx, void* stream, const gapro_spp_plan* 
                             float* d_grad_src /* [n_rows or N, C] */);
 
 /* ------------------------------------------------------------------------------------------
+ * Dynamic-convolution mask head (csrc/dyco_head.hip).  Replaces the per-sample loop of
+ * ISBNet.forward_head (isbnet/model/isbnet.py:783-828) with parse_dynamic_params (:834-853) and mask_heads_forward
+ * (:855-885), and its autograd, without the [Q, C + 6, N_b] input the reference materialises.
+ * The definition.  For sample b, point n in [off[b], off[b + 1]) and query q, with C = mask_dim_out:
+ *     x[0:3]   = queries_locs[b, q, :] - locs_float[n, :]
+ *     x[3:6]   = | (qbox[b, q, 3:6] - qbox[b, q, 0:3]) - (box_preds[n, 3:6] - box_preds[n, 0:3]) |
+ *     x[6:6+C] = mask_features[n, :]
+ *     theta    = controllers[b, q, :]
+ * theta holds P floats: W1[(C + 6) x C] (row-major, input channel major), W2[C x C/2], W3[C/2], b1[C], b2[C/2], b3[1];
+ *     h1[j]   = max(0, b1[j] + sum_a W1[a, j] x[a])
+ *     h2[k]   = max(0, b2[k] + sum_j W2[j, k] h1[j])
+ *     y[q, n] = sum_k W3[k] h2[k]
+ * b3 is not read.  P = (C + 6) C + C C/2 + C/2 + C + C/2 + 1: 1793 at C = 32, 513 at C = 16; any other C is refused.
+ * The logits are packed by sample: sample b's f32[Q, N_b] starts Q (off[b] - off[0]) floats into d_mask_logits, and
+ * d_grad_logits has the same layout.
+ * Arithmetic: float64 from the float32 inputs (FP64 MFMA), rounded once to float32 on the store; no floating-point
+ * atomics, every sum in a fixed order, so two calls give equal bytes.
+ * Gradients: controllers (the b3 column exact zeros), queries_box_preds, mask_features and box_preds; relu' at a
+ * pre-activation of exactly 0 is 0 and the derivative of |d| at d = 0 is 0.  h1 and h2 are recomputed; nothing of size
+ * Q x N x C is stored.  One kernel is organised by query (controllers, queries_box_preds: the points in ascending
+ * tiles of 16, the four waves of a workgroup added in wave order) and one by point (mask_features, box_preds: the
+ * queries in ascending order); a kernel whose two outputs are both NULL is not launched.  Every gradient array that is
+ * given is written whole by plain stores, the rows of points outside [off[0], off[B]) and of samples without points
+ * included.  mask_features has rows of stride ld_features >= C; its gradient is dense [N, C].
+ * h_batch_offsets: B + 1 host integers, not decreasing, inside [0, n_points]; B <= GAPRO_DYCO_MAX_BATCH.  Both calls
+ * only enqueue.  The workspace is not used (gapro_dyco_workspace_bytes is 0; NULL is accepted).
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_DYCO_MAX_BATCH 64
+int64_t gapro_dyco_param_count(int32_t mask_dim_out);   /* P; 0 for a C that is not built */
+size_t gapro_dyco_workspace_bytes(int32_t n_batches, int32_t n_queries, int64_t n_points, int32_t mask_dim_out);
+int gapro_dyco_forward(gapro_ctx* ctx, void* stream, int32_t n_batches, int32_t n_queries, int32_t mask_dim_out,
+                       const int64_t* h_batch_offsets, int64_t n_points, const float* d_controllers /* [B, Q, P] */,
+                       const float* d_mask_features /* [N, C], row stride ld_features */, int64_t ld_features,
+                       const float* d_locs_float /* [N, 3] */, const float* d_box_preds /* [N, 6] */,
+                       const float* d_queries_locs /* [B, Q, 3] */, const float* d_queries_box_preds /* [B, Q, 6] */,
+                       void* d_workspace, size_t workspace_bytes, float* d_mask_logits /* packed */);
+int gapro_dyco_backward(gapro_ctx* ctx, void* stream, int32_t n_batches, int32_t n_queries, int32_t mask_dim_out,
+                        const int64_t* h_batch_offsets, int64_t n_points, const float* d_controllers,
+                        const float* d_mask_features, int64_t ld_features, const float* d_locs_float,
+                        const float* d_box_preds, const float* d_queries_locs, const float* d_queries_box_preds,
+                        const float* d_grad_logits /* packed */, void* d_workspace, size_t workspace_bytes,
+                        float* d_grad_controllers /* [B, Q, P] or NULL */,
+                        float* d_grad_queries_box_preds /* [B, Q, 6] or NULL */,
+                        float* d_grad_mask_features /* [N, C] or NULL */, float* d_grad_box_preds /* [N, 6] or NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
  * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
  * to superpoint means (:64-69) or by keeping the npoint_nearest points of each side nearest to the centroid of the
