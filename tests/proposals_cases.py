@@ -1,8 +1,37 @@
 """Inputs for the predicted-instance chain (get_instance, mask_nms, rle_encode_gpu_batch): random scenes and the edge
 cases, shared by tests/test_proposals_cpu.py, tests/test_proposals_gpu.py, the golden generator and the benchmark.  NumPy
-only.  A case is ``(name, kwargs of proposals_ref.get_instance_ref)``; every case is tiny (Q <= 40, V, N <= 1100).
+only.  A case is ``(name, kwargs of proposals_ref.get_instance_ref)``; every case of ``cases()`` is tiny (Q <= 40,
+V, N <= 1100).
+
+``scale_cases()`` holds the cases at the sizes where the loops of csrc/proposals.hip take their second trip (DESIGN.md
+4.8 lists loop -> case).  Each has one deliberate large dimension and keeps the others small; none is random where a
+size or a score matters.  Every one passes ``_guard``: on the restatement's numbers any two scores, and for matrix NMS
+any two updated scores, are bit-identical or more than 4 float32 ulp apart, and with ``topk = -1`` no updated score lies
+within 4 ulp of ``final_score_thresh``: a last-place difference of an ``exp`` cannot change an order or a cut.
 """
+import functools
+
 import numpy as np
+
+# The constants of csrc/proposals.hip that no header exposes, mirrored: a change there is a change here.
+PACK_WORDS = 32                     # kPackWords: the words (of 64 voxels) of a wave's run of `pack`
+PACK_PASS_WAVES = 2048 * 4          # GAPRO_PROPOSALS_GRID_CAP * (kThreads / 64) waves: tasks of one pass of `pack`
+INTER_PASS_WORDS = 64               # `inter`: a word a lane, 64 words a trip
+GRID_PASS_ITEMS = 2048 * 256        # GAPRO_PROPOSALS_GRID_CAP * kThreads: one pass of `score` (queries), `points`
+TALLY_PASS_POINTS = 256 * 256       # kTallyGridX * kThreads: points of a row in one pass of `tally`
+SCAN_CHUNKS = 64                    # `chunks`: a chunk a lane, 64 chunks a step of the scan
+MIN_CHUNK, MAX_CHUNKS = 1024, 1024  # kMinChunk, kMaxChunks
+NMS_PASS = 256                      # kThreads: the places behind a pivot in one trip of the standard NMS loop
+MAX_TOPK, MAX_SEM = 1024, 8         # GAPRO_PROPOSALS_MAX_PRE_TOPK (kMaxTopk), GAPRO_PROPOSALS_MAX_SEM2INS (kMaxSem)
+FINISH_PASS_ROWS = 256 * 4          # kThreads * (kRowsPer - 1): `finish` needs its fifth row a thread beyond this
+MAX_SCORES = 1 << 20                # kMaxScores: Q * C at most
+
+
+def chunking(N):
+    """(nchunks, chunk_len) of N points: make_dims of csrc/proposals.hip."""
+    nchunks = min((N + 1 + MIN_CHUNK - 1) // MIN_CHUNK, MAX_CHUNKS)
+    return nchunks, (N + 1 + nchunks - 1) // nchunks
+
 
 KEYS = ("cls_logits", "mask_logits", "conf_logits", "box_preds", "v2p_map", "semantic_preds", "spps")
 
@@ -107,9 +136,9 @@ def iou_quarter_case():
     return explicit(_rows(16, (0, 5), (3, 8)), _falling(2), nms_threshold=0.25)
 
 
-def many_rows_case(Q):
+def many_rows_case(Q, seed=None):
     """Q * 4 candidates that all survive into stage 5 (a threshold of 1 suppresses nothing)."""
-    rng = np.random.default_rng(Q)
+    rng = np.random.default_rng(Q if seed is None else seed)
     bits = np.repeat(rng.random((Q, 30)) < 0.4, 10, axis=1) ^ (rng.random((Q, 300)) < 0.1)
     v2p = np.sort(rng.integers(0, 300, 400))
     return explicit(bits, _falling(Q, 4, 0.9, 0.1), pre_topk=Q * 4, npoint_thresh=20, v2p=v2p, spps=v2p // 10)
@@ -238,3 +267,223 @@ def mask_refusal():
     fine["mask_logits"] = c["mask_logits"].copy()
     fine["mask_logits"][unread[0], 5] = np.inf
     return bad, fine
+
+
+# ---- the cases at workload size --------------------------------------------------------------------------------------
+def explicit_cols(colbits, scores, voxel_spps, **params):
+    """``explicit`` in the ``voxel_spps`` form: chosen bits of the mask columns bool[Q, S_v]; voxel v reads column
+    ``voxel_spps[v]``.  Every voxel has one point and every point is its own superpoint unless given."""
+    voxel_spps = np.asarray(voxel_spps, np.int64)
+    params.setdefault("v2p", np.arange(len(voxel_spps)))
+    c = explicit(colbits, scores, **params)
+    c.update(voxel_spps=voxel_spps, semantic_preds=np.zeros(len(voxel_spps), np.int64))
+    return c
+
+
+def _two_columns(Q):
+    """Column bits of Q queries over two mask columns: the second, the first, both, in turn."""
+    q = np.arange(Q)
+    return np.stack([q % 3 != 0, q % 3 != 1], axis=1)
+
+
+def pack_run_case(V):
+    """Six rows of V voxels; voxel V - 1 is set in four of them.  At V = 2049 it is the only voxel of the second run of
+    `pack`, at V = 4097 the only bit of the 65th word.  Row 5 has exactly ``npoint_thresh`` voxels with it."""
+    rng = np.random.default_rng(V)
+    bits = rng.random((6, V)) < np.array([0.45, 0.45, 0.4, 0.4, 0.4, 0.3])[:, None]
+    bits[:, V - 1] = [1, 1, 0, 1, 0, 1]
+    v2p = np.r_[np.arange(V), rng.integers(0, V, 7)]
+    return explicit(bits, _falling(6), v2p=v2p, spps=v2p // 4, npoint_thresh=int(bits[5].sum()), type_nms="matrix",
+                    topk=-1)
+
+
+def pack_grid_case(Q):
+    """Q rows of 70 voxels, one (row, run) task each; the 16 best scores are the last rows: at Q = 8200 eight of them
+    are tasks of the second pass of `pack`."""
+    return explicit_cols(_two_columns(Q), _falling(Q)[::-1], np.arange(70) >= 33, pre_topk=16)
+
+
+def tie_block_case(n, lo, hi, n_higher, pre_topk):
+    """n scores, C = 1: the scores [lo, hi) are bit-identical (identical class rows); the last ``n_higher`` are above
+    them and every other one below, before and behind the block.  ``pre_topk`` cuts inside the block: the candidates are
+    the ``n_higher`` and the lowest indices of the block."""
+    s = np.linspace(0.2, 0.4, n)
+    s[lo:hi] = 0.5
+    s[n - n_higher:] = np.linspace(0.6, 0.55, n_higher)
+    assert hi <= n - n_higher and n_higher < pre_topk < n_higher + hi - lo
+    return explicit_cols(_two_columns(n), s.reshape(n, 1), np.arange(70) >= 33, pre_topk=pre_topk)
+
+
+def score_count_case(Q, C):
+    """Q * C distinct scores in no order, pre_topk = 1024."""
+    rng = np.random.default_rng(Q * C)
+    s = _falling(Q, C).reshape(-1)[rng.permutation(Q * C)].reshape(Q, C)
+    return explicit(rng.random((Q, 70)) < 0.5, s, pre_topk=MAX_TOPK)
+
+
+def score_cap_case():
+    """Q = 2^20, the most the select takes, C = 1.  Seven low levels in turn (ties by the hundred thousand), a block of
+    600 bit-identical scores around index 0xC0000 and the 200 best at the very end; pre_topk = 512 cuts 312 into the
+    block, 12 beyond the index whose third byte changes.  Half the queries are beyond one pass of `score`."""
+    n = MAX_SCORES
+    s = np.linspace(0.2, 0.3, 7)[np.arange(n) % 7]
+    s[0xC0000 - 300:0xC0000 + 300] = 0.5
+    s[n - 200:] = np.linspace(0.55, 0.6, 200)
+    return explicit_cols(_two_columns(n), s.reshape(n, 1), np.arange(8) % 2, pre_topk=512)
+
+
+def full_sorts_case(kind, seed=None):
+    """P = 1024 candidates (256 queries, 4 classes) that all pass ``npoint_thresh``: every thread of `filter` and `nms`
+    owns four, the LDS sorts have no padding.  With the eight sem2ins classes R = 1032: the fifth row of a thread of
+    `finish`."""
+    c = many_rows_case(256, seed)
+    if kind == "matrix_none":
+        c.update(type_nms="matrix", topk=-1)
+    elif kind == "matrix_topk":
+        c.update(type_nms="matrix", topk=MAX_TOPK)
+    if kind != "matrix_none":
+        c.update(sem2ins_classes=tuple(range(MAX_SEM)), semantic_preds=np.arange(300) // 10 % MAX_SEM)
+    return c
+
+
+def nms_far_case(distance):
+    """1024 candidates of one class, standard NMS at 0.5.  A mask is three of thirty runs of ten voxels (the superpoints
+    of 400 points), a different three for every candidate: two masks share at most two runs, an IoU of 0.5 at most, and
+    nothing is suppressed -- but candidate q + distance has the mask of candidate q for q < 200.  At distance 256 the
+    victim is the last place of the pivot's first trip, at 257 the first of its second."""
+    import itertools
+
+    rng = np.random.default_rng(257)
+    triples = np.array(list(itertools.combinations(range(30), 3)))[rng.permutation(4060)[:MAX_TOPK]]
+    on = np.zeros((MAX_TOPK, 30), bool)
+    on[np.arange(MAX_TOPK)[:, None], triples] = True
+    on[distance:distance + 200] = on[:200]
+    v2p = np.sort(rng.integers(0, 300, 400))
+    return explicit(np.repeat(on, 10, axis=1), _falling(MAX_TOPK), pre_topk=MAX_TOPK, npoint_thresh=20, v2p=v2p,
+                    spps=v2p // 10, nms_threshold=0.5)
+
+
+def boundary_case(N):
+    """N points, four rows, 68 voxels.  The points come in segments that start and end at b - 1, b and b + 1 for every
+    chunk boundary b of ``chunking(N)`` (so for every 64-chunk group) and for 64 .. 512; a segment's even and odd points
+    are two superpoints.  A point's voxel is 4 * superpoint + its kind: p % 3 == 0 (E) or not (F) among the first
+    TALLY_PASS_POINTS points, then 300 000 points L1, then L2.  Row 0 has every voxel: all ones.  Row 1 has the voxels of
+    the even points: it alternates every point.  Row 3 has whole segments.  Row 2 has E, L1 and L2 of some segments (a
+    third of the early points, so the majority comes from the points of the later passes of `tally`), only L1 of others
+    (fewer than half their points, and more than half of those among the first GRID_PASS_ITEMS: n(s) needs the later
+    pass of `points`), and everything of others.  Beyond TALLY_PASS_POINTS points a superpoint of three points has its
+    second set point there."""
+    S0, T = 8, TALLY_PASS_POINTS
+    nchunks, chunk = chunking(N)
+    cuts = {1, N - 1}
+    for b in [64, 128, 256, 512] + [chunk * i for i in range(1, nchunks + 1)]:
+        cuts.update((b - 1, b, b + 1))
+    cuts = np.array(sorted(p for p in cuts if 0 < p < N))
+    p = np.arange(N)
+    seg = np.searchsorted(cuts, p, side="right")
+    own = (5 * seg + 3) % S0
+    spps = 2 * own + (p & 1)
+    kind = np.where(p < T, np.where(p % 3 == 0, 0, 1), np.where(p < T + 300000, 2, 3))
+    v2p = 4 * spps + kind
+    if N > T:
+        three = np.array([10, 20, T + 40 if N > T + 40 else T])
+        spps[three], v2p[three] = 2 * S0, [64, 65, 66]
+    voxel_own, voxel_kind, voxel_odd = np.arange(68) // 8, np.arange(68) % 4, np.arange(68) // 4 % 2
+    extra = np.arange(68) >= 64
+    bits = np.stack([
+        np.ones(68, bool),
+        np.where(extra, True, voxel_odd == 0),
+        np.where(extra, voxel_kind != 1, (np.isin(voxel_own, (1, 4)) & (voxel_kind != 1))
+                 | ((voxel_own == 2) & (voxel_kind == 2)) | (voxel_own == 6)),
+        np.where(extra, False, voxel_own % 2 == 1)])  # every second segment: a transition at every cut
+    return explicit(bits, _falling(4), v2p=v2p, spps=spps, n_spps=2 * S0 + 1)
+
+
+def nms_1024_inputs(seed=4100):
+    """For mask_nms: 1024 masks of 4097 voxels (65 words), 64 prototypes with a few per cent of their bits flipped; a
+    prototype's sixteen masks have one class, so a pivot's victims sit up to 960 rows behind it before the sort by the
+    shuffled, distinct scores.  Returns (bits, classes, scores, boxes)."""
+    rng = np.random.default_rng(seed)
+    proto = rng.random((64, 4097)) < 0.3
+    i = np.arange(MAX_TOPK)
+    bits = proto[i % 64] ^ (rng.random((MAX_TOPK, 4097)) < 0.03)
+    bits[:, 4096] = i % 3 != 0
+    score = np.linspace(0.9, 0.15, MAX_TOPK)[rng.permutation(MAX_TOPK)].astype(np.float32)
+    return bits, (i % 4).astype(np.int64), score, rng.uniform(-4, 4, (MAX_TOPK, 6)).astype(np.float32)
+
+
+def _ulps(a, b):
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))  # the scores are >= +0.0
+
+
+def guard_values(name, values, thresh=None):
+    """Any two of the values are bit-identical or more than 4 float32 ulp apart; none is within 4 ulp of ``thresh``."""
+    v = np.sort(np.asarray(values, np.float32))
+    gap = _ulps(v[1:], v[:-1])
+    assert ((gap == 0) | (gap > 4)).all(), (name, "values within 4 ulp of each other")
+    if thresh is not None:
+        gap = _ulps(v, np.full(len(v), thresh, np.float32))
+        assert ((gap == 0) | (gap > 4)).all(), (name, "a value within 4 ulp of the threshold")
+
+
+def _guard(name, c):
+    """The condition of the module's docstring, on the restatement's numbers."""
+    import proposals_ref as ref
+
+    score = ref.scores_ref(c["cls_logits"], c["conf_logits"]).reshape(-1)
+    guard_values(name, score)
+    if c["type_nms"] == "matrix":
+        C = c["instance_classes"]
+        cand = ref.order_ref(score, min(c.get("pre_topk", 300), len(score)))
+        bits = ref.bits_ref(c["mask_logits"], c["logit_thresh"], c.get("voxel_spps"))[cand // C]
+        keep = bits.sum(axis=1) >= c["npoint_thresh"]
+        _, new = ref.nms_ref(bits[keep], (cand % C)[keep], score[cand][keep], "matrix", int(keep.sum()))
+        guard_values(name, new, 0.1 if c["topk"] == -1 else None)
+    return c
+
+
+_SCALE = {
+    "pack_v2048": lambda: pack_run_case(2048),  # control: one run of words
+    "pack_v2049": lambda: pack_run_case(2049),
+    "pack_v4097": lambda: pack_run_case(4097),
+    "pack_grid_q8192": lambda: pack_grid_case(8192),  # control: one pass of tasks
+    "pack_grid_q8200": lambda: pack_grid_case(8200),
+    "tie_across_65536": lambda: tie_block_case(66000, 65300, 65800, 100, 400),
+    "tie_across_256": lambda: tie_block_case(2000, 100, 1300, 100, MAX_TOPK),
+    "scores_1024": lambda: score_count_case(256, 4),
+    "scores_1025": lambda: score_count_case(205, 5),
+    "scores_at_the_cap": score_cap_case,
+    "p1024_standard_all": lambda: full_sorts_case("standard_all"),
+    "p1024_matrix_none": lambda: full_sorts_case("matrix_none"),
+    "p1024_matrix_topk": lambda: full_sorts_case("matrix_topk"),
+    "nms_victims_256_behind": lambda: nms_far_case(256),  # control: the last place of the first trip
+    "nms_victims_257_behind": lambda: nms_far_case(257),
+    "points_65535": lambda: boundary_case(65535),  # control: 64 chunks, one pass of `tally`
+    "points_65536": lambda: boundary_case(65536),  # 65 chunks; control: one pass of `tally`
+    "points_65537": lambda: boundary_case(65537),
+    "points_1048575": lambda: boundary_case(1048575),  # 1024 chunks of 1024
+    "points_1048576": lambda: boundary_case(1048576),  # chunks of 1025
+    "points_1300001": lambda: boundary_case(1300001),  # chunks of 1270
+}
+SCALE_NAMES = tuple(_SCALE)
+RLE_POINTS = (65535, 65536, 1048575, 1048576, 1300001)
+
+
+@functools.lru_cache(maxsize=None)
+def scale_case(name):
+    """The case of that name, built once and guarded."""
+    return _guard(name, _SCALE[name]())
+
+
+@functools.lru_cache(maxsize=None)
+def scale_reference(name):
+    """``get_instance_ref`` of the case, computed once; shared and not to be changed."""
+    import proposals_ref as ref
+
+    return ref.get_instance_ref(**scale_case(name))
+
+
+def scale_cases():
+    for name in SCALE_NAMES:
+        yield name, scale_case(name)

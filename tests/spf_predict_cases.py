@@ -92,6 +92,25 @@ def _boundary_scene(seed, N, Q=6, C=3, S=8):
     return dict(c, topk_insts=100, score_thr=0.0, npoint_thr=0)
 
 
+TIE_BLOCK = (66000, 65300, 65800, 100, 400)  # scores, the block [lo, hi), the scores above it, topk_insts
+
+
+def _tie_block_scene():
+    """66 000 queries of one class whose score is softmax(labels)[0]: the scores [65300, 65800) are bit-identical
+    (identical rows), the last 100 are above them and every other one below, before and behind the block.  ``topk_insts``
+    = 400 cuts 300 into the block, beyond flat index 65 536: the select decides among equal scores by the third byte of
+    the index.  Even and odd queries have different masks of one mask score, so equal scores give equal conf."""
+    n, lo, hi, higher, topk = TIE_BLOCK
+    c = make_scene(293, Q=2, C=1, S=8, N=300, n_inst=2)
+    p = np.linspace(0.2, 0.4, n)
+    p[lo:hi] = 0.5
+    p[n - higher:] = np.linspace(0.6, 0.55, higher)
+    labels = np.log(np.stack([p, 1.0 - p], axis=1)).astype(np.float32)
+    masks = np.where((np.arange(8)[None, :] // 3) == (np.arange(n)[:, None] % 2), 2.0, -2.0).astype(np.float32)
+    return dict(c, labels=labels, pred_scores=np.ones(n, np.float32), masks=masks, topk_insts=topk, score_thr=0.0,
+                npoint_thr=0)
+
+
 def cases():
     """(name, case) pairs."""
     out = []
@@ -106,6 +125,9 @@ def cases():
     c = make_scene(290, Q=4, C=2, S=321, N=900, n_inst=3)
     out.append(_checked("spp_321", dict(c, topk_insts=100, score_thr=0.0, npoint_thr=0)))
     out.append(_checked("points_70000", _boundary_scene(291, 70000, Q=2, C=1)))
+    # 1024 chunks of 1025 points, sixteen steps of the scan; the points beyond one pass of `points` (2048 * 256)
+    out.append(_checked("points_1048576", _boundary_scene(292, 1048576, Q=2, C=1)))
+    out.append(_checked("tie_across_65536", _tie_block_scene()))
     base = make_scene(300, Q=5, C=3, S=20, N=400, n_inst=3)
     for name, topk in (("scores_below_topk", 20), ("scores_equal_topk", 15), ("scores_above_topk", 10), ("topk_one", 1)):
         out.append(_checked(name, dict(base, topk_insts=topk, score_thr=0.0, npoint_thr=5)))

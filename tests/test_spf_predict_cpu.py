@@ -208,6 +208,31 @@ def test_ties_go_to_the_lower_flat_index_and_keep_the_candidate_order():
     assert all((out["query"][i], out["query"][j]) == (1, 4) for i, j in pairs)
 
 
+def test_a_tie_across_index_65536_is_cut_at_the_lowest_indices_of_its_block():
+    c = CASES["tie_across_65536"]
+    n, lo, hi, higher, topk = cases.TIE_BLOCK
+    s = ref.class_scores64(c["labels"], c["pred_scores"]).reshape(-1).astype(np.float32)
+    assert len(s) == n and len(np.unique(s[lo:hi].view(np.uint32))) == 1 and lo < 65536 < lo + topk - higher < hi
+    assert s[:lo].max() < s[lo] and s[hi:n - higher].max() < s[lo] < s[n - higher:].min()
+    out = ref.predict_ref(**c)
+    want = np.r_[np.arange(n - higher, n), np.arange(lo, lo + topk - higher)]
+    assert np.array_equal(out["query"], want)
+    assert out["conf"][higher].tobytes() == out["conf"][-1].tobytes()
+    assert not np.array_equal(out["masks"][-1], out["masks"][-2])
+    # a select that compared the low 16 bits of the index would take the block from 65536 on
+    low16 = np.lexsort((np.arange(n) & 0xffff, -s.astype(np.float64)))[:topk]
+    assert set(low16.tolist()) != set(want.tolist()) and 65536 in low16[higher:higher + 1]
+
+
+def test_the_large_scene_has_more_chunks_than_a_row_may_have():
+    c = CASES["points_1048576"]
+    n = len(c["superpoints"])
+    assert n == 1048576 > 2048 * 256 and (n + 1 + 1023) // 1024 > 1024  # chunks of 1025; two passes of `points`
+    out = ref.predict_ref(**c)
+    assert list(out["counts"][0]) == [1, n] or list(out["counts"][1]) == [1, n]
+    assert max(len(x) for x in out["counts"]) > 2 * 1024  # a run at most of the chunk boundaries
+
+
 def test_a_one_point_instance_has_a_flat_box_and_an_empty_superpoint_gives_nothing():
     c = CASES["one_point_instance"]
     out = ref.predict_ref(**c)
