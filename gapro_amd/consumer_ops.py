@@ -46,6 +46,13 @@ def _tensor_arg(who, name, t, shape, dtypes=_F32, nonempty=False, text=None):
                             text or "[%s]" % ", ".join(str(v) for v in shape)))
 
 
+def _f32_arg(t, name, who, shape):
+    """The predicted-instance families refuse a host tensor argument by argument, not behind all their ValueErrors."""
+    _tensor_arg(who, name, t, shape, text=tuple(shape))
+    _need_device(t)
+    return t.contiguous()
+
+
 def _one_device(who, dev, tensors):
     for t in tensors:
         if t.device != dev:
@@ -165,6 +172,47 @@ def _refuse(who, status, flags, causes):
     """A non-zero status as the ``GaproError`` of the first cause whose bit is set."""
     if status != 0:
         raise GaproError(status, "%s: %s" % (who, next(text for bit, text in causes if flags & bit)))
+
+
+def _predict_run(who, chain, anchor, inputs, params, keep, n_points, want_rows=True, want_masks=False, has_runs=True):
+    """The protocol of the two predicted-instance chains: ``count``, the call's one host read of its header, ``fill``
+    into tensors of the sizes read.  ``chain`` is (the prefix of the entry points, the header struct, the cause table,
+    the result namedtuple); ``keep`` holds the tensors the structs point to.  Returns the namedtuple of device tensors,
+    ``None`` where they were not asked for or the mode has no runs; ``n_runs``, the rows' run counts, came with the
+    header."""
+    prefix, header, causes, result = chain
+    ctx, stream = _ctx_stream(anchor)
+    lib, dev = ctx.lib, anchor.device
+    pin, ppar = C.byref(inputs), C.byref(params)
+    with torch.cuda.device(dev):
+        ws_bytes, hdr_bytes = int(getattr(lib, prefix + "workspace_bytes")(pin, ppar)), int(
+            getattr(lib, prefix + "header_bytes")(pin, ppar))
+        ws = _workspace(who, ws_bytes, dev, "the sizes or parameters are")
+        d_hdr, h_hdr = _status_pair(dev, hdr_bytes)
+        ctx.check(getattr(lib, prefix + "count")(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes,
+                                                 d_hdr.data_ptr(), h_hdr.data_ptr()))
+        hdr, raw = _host_read(dev, h_hdr, header)
+        _refuse(who, hdr.status, hdr.flags, causes)
+        rows, runs = int(hdr.n_rows), int(hdr.total_runs)
+        conf = torch.empty(rows, dtype=torch.float32, device=dev) if want_rows else None
+        label = torch.empty(rows, dtype=torch.int32, device=dev) if want_rows else None
+        box = torch.empty((rows, 6), dtype=torch.float32, device=dev) if want_rows else None
+        query = torch.empty(rows, dtype=torch.int32, device=dev) if want_rows else None
+        run_off = torch.zeros(rows + 1, dtype=torch.int64, device=dev) if has_runs else None
+        d_runs = torch.empty(2 * runs, dtype=torch.int64, device=dev) if has_runs else None
+        masks = torch.empty((rows, n_points), dtype=torch.uint8, device=dev) if want_masks else None
+        if rows > 0:
+            ctx.check(getattr(lib, prefix + "fill")(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, _ptr(conf),
+                                                    _ptr(label), _ptr(box), _ptr(query), rows, _ptr(run_off),
+                                                    _ptr(d_runs), runs, _ptr(masks), None))
+    del keep
+    n_runs = np.frombuffer(raw, dtype=np.int32, count=rows, offset=C.sizeof(header))
+    return result(conf, label, box, query, run_off, d_runs, masks, hdr, n_runs)
+
+
+def _counts_of(run_off, runs):
+    """The rows' ``counts`` arrays (views of one host copy) from two host arrays."""
+    return [runs[2 * int(run_off[r]):2 * int(run_off[r + 1])] for r in range(len(run_off) - 1)]
 
 
 _constants = {}  # (device, the values) -> the float32 tensor on the device
@@ -1212,49 +1260,7 @@ _PROPOSAL_CAUSES = ((1, "a non-finite cls_logits, conf_logits or score entry"),
 ProposalArrays = namedtuple("ProposalArrays", "conf label_id box query run_offsets runs masks header n_runs")
 
 
-def _f32_arg(t, name, who, shape):
-    """This family refuses a host tensor argument by argument, not behind all its ValueErrors."""
-    _tensor_arg(who, name, t, shape, text=tuple(shape))
-    _need_device(t)
-    return t.contiguous()
-
-
-def _proposals_run(who, anchor, inputs, params, keep, n_points, want_masks=False, want_rows=True):
-    """gapro_proposals_count, the call's one host read of its header, gapro_proposals_fill.  ``keep`` holds the tensors
-    the structs point to.  Returns ProposalArrays of device tensors (``None`` where the mode has none)."""
-    ctx, stream = _ctx_stream(anchor)
-    lib, dev = ctx.lib, anchor.device
-    pin, ppar = C.byref(inputs), C.byref(params)
-    with torch.cuda.device(dev):
-        ws_bytes, hdr_bytes = int(lib.gapro_proposals_workspace_bytes(pin, ppar)), int(
-            lib.gapro_proposals_header_bytes(pin, ppar))
-        ws = _workspace(who, ws_bytes, dev, "the sizes or parameters are")
-        d_hdr, h_hdr = _status_pair(dev, hdr_bytes)
-        ctx.check(lib.gapro_proposals_count(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, d_hdr.data_ptr(),
-                                            h_hdr.data_ptr()))
-        hdr, raw = _host_read(dev, h_hdr, _lib.ProposalsHeader)
-        _refuse(who, hdr.status, hdr.flags, _PROPOSAL_CAUSES)
-        rows, runs = int(hdr.n_rows), int(hdr.total_runs)
-        nms_only = params.mode == _lib.PROPOSALS_NMS
-        conf = torch.empty(rows, dtype=torch.float32, device=dev) if want_rows else None
-        label = torch.empty(rows, dtype=torch.int32, device=dev) if want_rows else None
-        box = torch.empty((rows, 6), dtype=torch.float32, device=dev) if want_rows else None
-        query = torch.empty(rows, dtype=torch.int32, device=dev) if want_rows else None
-        run_off = None if nms_only else torch.zeros(rows + 1, dtype=torch.int64, device=dev)
-        d_runs = None if nms_only else torch.empty(2 * runs, dtype=torch.int64, device=dev)
-        masks = torch.empty((rows, n_points), dtype=torch.uint8, device=dev) if want_masks else None
-        if rows > 0:
-            ctx.check(lib.gapro_proposals_fill(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, _ptr(conf),
-                                               _ptr(label), _ptr(box), _ptr(query), rows, _ptr(run_off), _ptr(d_runs),
-                                               runs, _ptr(masks), None))
-    del keep
-    n_runs = np.frombuffer(raw, dtype=np.int32, count=rows, offset=C.sizeof(_lib.ProposalsHeader))
-    return ProposalArrays(conf, label, box, query, run_off, d_runs, masks, hdr, n_runs)
-
-
-def _counts_of(run_off, runs):
-    """The rows' ``counts`` arrays (views of one host copy) from two host arrays."""
-    return [runs[2 * int(run_off[r]):2 * int(run_off[r + 1])] for r in range(len(run_off) - 1)]
+_PROPOSALS_CHAIN = ("gapro_proposals_", _lib.ProposalsHeader, _PROPOSAL_CAUSES, ProposalArrays)
 
 
 def get_instance(scan_id, cls_logits, mask_logits, conf_logits, box_preds, v2p_map, semantic_scores_preds, spps,
@@ -1333,8 +1339,8 @@ def get_instance(scan_id, cls_logits, mask_logits, conf_logits, box_preds, v2p_m
         logit_thresh=float(logit_thresh), final_score_thresh=0.1, nms_threshold=float(nms_threshold))
     for i, c in enumerate(sem):
         params.sem2ins_classes[i] = c
-    out = _proposals_run(who, cls_logits, inputs, params, (cls_logits, conf_logits, box_preds, mask_logits, vs, v2p, sp,
-                                                           sm), N, want_masks=return_masks)
+    out = _predict_run(who, _PROPOSALS_CHAIN, cls_logits, inputs, params,
+                       (cls_logits, conf_logits, box_preds, mask_logits, vs, v2p, sp, sm), N, want_masks=return_masks)
     if return_arrays:
         return out
     rows = int(out.header.n_rows)
@@ -1381,7 +1387,7 @@ def mask_nms(proposals_pred, categories, scores, boxes, test_cfg):
     params = _lib.ProposalsParams(mode=_lib.PROPOSALS_NMS, type_nms=_NMS_TYPES[type_nms],
                                   topk=int(getattr(test_cfg, "topk", -1)), npoint_thresh=1, final_score_thresh=0.1,
                                   nms_threshold=float(getattr(test_cfg, "nms_threshold", 0.2)))
-    out = _proposals_run(who, sc, inputs, params, (masks, sc, cat), 0)
+    out = _predict_run(who, _PROPOSALS_CHAIN, sc, inputs, params, (masks, sc, cat), 0, has_runs=False)
     idx = out.query.to(torch.int64)
     return proposals_pred[idx], categories[idx], out.conf, boxes[idx]
 
@@ -1403,7 +1409,7 @@ def rle_encode_gpu_batch(masks):
         inputs = _lib.ProposalsInputs(n_queries=int(part.shape[0]), n_voxels=0, n_points=N, mask_logits=part.data_ptr(),
                                       mask_type=_lib.PROPOSALS_MASK_U8)
         params = _lib.ProposalsParams(mode=_lib.PROPOSALS_RLE)
-        out = _proposals_run(who, part, inputs, params, (part,), N, want_rows=False)
+        out = _predict_run(who, _PROPOSALS_CHAIN, part, inputs, params, (part,), N, want_rows=False)
         offs = np.concatenate([[0], np.cumsum(out.n_runs, dtype=np.int64)])  # the counts came with the header
         runs = out.runs.cpu().numpy()
         rles += [{"length": N, "counts": c} for c in _counts_of(offs, runs)]
@@ -2732,6 +2738,7 @@ _SPF_PREDICT_CAUSES = ((1, "a non-finite labels or scores entry"),
                        (4, "a non-finite coords_float entry"),
                        (8, "a superpoint id outside the columns of masks"))
 SpfInstanceArrays = namedtuple("SpfInstanceArrays", "conf label_id box query run_offsets runs masks header n_runs")
+_SPF_PREDICT_CHAIN = ("gapro_spf_predict_", _lib.SpfPredictHeader, _SPF_PREDICT_CAUSES, SpfInstanceArrays)
 
 
 def spformer_instances(scan_id, pred_labels, pred_scores, pred_masks, superpoints, coords_float, *, num_class,
@@ -2780,42 +2787,18 @@ def spformer_instances(scan_id, pred_labels, pred_scores, pred_masks, superpoint
                                    coords_float=coords.data_ptr(), superpoints_i64=sp_i64)
     params = _lib.SpfPredictParams(num_class=num_class, topk_insts=topk_insts, npoint_thr=npoint_thr,
                                    score_thr=float(score_thr))
-    ctx, stream = _ctx_stream(labels)
-    lib, dev = ctx.lib, labels.device
-    pin, ppar = C.byref(inputs), C.byref(params)
-    with torch.cuda.device(dev):
-        ws_bytes, hdr_bytes = int(lib.gapro_spf_predict_workspace_bytes(pin, ppar)), int(
-            lib.gapro_spf_predict_header_bytes(pin, ppar))
-        ws = _workspace(who, ws_bytes, dev, "the sizes or parameters are")
-        d_hdr, h_hdr = _status_pair(dev, hdr_bytes)
-        ctx.check(lib.gapro_spf_predict_count(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, d_hdr.data_ptr(),
-                                              h_hdr.data_ptr()))
-        hdr, raw = _host_read(dev, h_hdr, _lib.SpfPredictHeader)
-        _refuse(who, hdr.status, hdr.flags, _SPF_PREDICT_CAUSES)
-        rows, runs = int(hdr.n_rows), int(hdr.total_runs)
-        conf = torch.empty(rows, dtype=torch.float32, device=dev)
-        label = torch.empty(rows, dtype=torch.int32, device=dev)
-        box = torch.empty((rows, 6), dtype=torch.float32, device=dev)
-        query = torch.empty(rows, dtype=torch.int32, device=dev)
-        run_off = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
-        d_runs = torch.empty(2 * runs, dtype=torch.int64, device=dev)
-        out_masks = torch.empty((rows, N), dtype=torch.uint8, device=dev) if return_masks else None
-        if rows > 0:
-            ctx.check(lib.gapro_spf_predict_fill(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws_bytes, _ptr(conf),
-                                                 _ptr(label), _ptr(box), _ptr(query), rows, _ptr(run_off),
-                                                 _ptr(d_runs), runs, _ptr(out_masks), None))
-    del keep
-    n_runs = np.frombuffer(raw, dtype=np.int32, count=rows, offset=C.sizeof(_lib.SpfPredictHeader))
-    out = SpfInstanceArrays(conf, label, box, query, run_off, d_runs, out_masks, hdr, n_runs)
+    out = _predict_run(who, _SPF_PREDICT_CHAIN, labels, inputs, params, keep, N, want_masks=return_masks)
     if return_arrays:
         return out
+    rows = int(out.header.n_rows)
     if rows == 0:
         return []
-    small = torch.cat([conf.view(torch.int32), label, box.view(torch.int32).reshape(-1)]).cpu().numpy()  # one copy
-    host_runs = d_runs.cpu().numpy()  # the runs: the other
+    small = torch.cat([out.conf.view(torch.int32), out.label_id, out.box.view(torch.int32).reshape(-1)])
+    small = small.cpu().numpy()  # the small arrays: one copy
+    host_runs = out.runs.cpu().numpy()  # the runs: the other
     conf_h, label_h = small[:rows].view(np.float32), small[rows:2 * rows].astype(np.int64)
     box_h = small[2 * rows:].view(np.float32).reshape(rows, 6)
-    counts = _counts_of(np.concatenate([[0], np.cumsum(n_runs, dtype=np.int64)]), host_runs)  # came with the header
+    counts = _counts_of(np.concatenate([[0], np.cumsum(out.n_runs, dtype=np.int64)]), host_runs)  # came with the header
     return [{"scan_id": scan_id, "label_id": label_h[r], "conf": conf_h[r],
              "pred_mask": {"length": N, "counts": counts[r]}, "box": box_h[r].copy()} for r in range(rows)]
 

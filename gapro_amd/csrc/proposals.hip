@@ -21,9 +21,13 @@
 //   runs     the positions of the transitions in order (and the masks); then `lengths` turns every second into a length
 // Integer atomics only, so every result is the same bits for every grid and every run.  The kernel boundaries on the
 // stream are the only ordering.  A refusal is a status word written by `filter`: every later kernel returns at once.
+// The softmax, the select / sort and the chunked run lengths (stages 1 and 7) are select_runs.h's, shared with
+// spf_predict.hip; this file supplies its point bit (`mask_at`) and its row indexing: the chunk cells of a row belong
+// to the row k before the last filter, which `final_row` gives for output row r.
 #include "common.h"
 #include "label_types.h"
 #include "launch_util.h"
+#include "select_runs.h"
 #include "wave_reduce.h"
 
 #include <cmath>
@@ -31,18 +35,10 @@
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kGridCap = GAPRO_PROPOSALS_GRID_CAP;
-constexpr int kMaxTopk = GAPRO_PROPOSALS_MAX_PRE_TOPK;  // also the length of the sorts in LDS: a power of two
 constexpr int kMaxSem = GAPRO_PROPOSALS_MAX_SEM2INS;
 constexpr int kMaxRows = kMaxTopk + kMaxSem;
-constexpr int kMaxChunks = 1024;   // chunks of points of a row (`trans`, `runs`)
-constexpr int kMinChunk = 1024;    // points of a chunk, at least
 constexpr int kPackWords = 32, kPackUnroll = 4;  // words of a wave's run of `pack`, and of them in flight
 constexpr int kTallyGridX = 256;   // workgroups along the points of one row of `tally`
-constexpr long long kMaxIndex = 0x7fffffffLL;
-constexpr long long kMaxScores = 1LL << 20;
-static_assert((kMaxTopk & (kMaxTopk - 1)) == 0 && kMaxTopk % kThreads == 0, "the LDS sorts need a power of two");
 
 enum { kFlagScore = 1, kFlagMask = 2, kFlagV2p = 4, kFlagVoxelSpp = 8, kFlagSpp = 16 };
 
@@ -148,37 +144,6 @@ struct PrPar {  // gapro_proposals_params as the kernels read it
   int sem[kMaxSem];
 };
 
-// float32 as an unsigned integer of the same order (-0.0 below +0.0; the scores here are never -0.0)
-__device__ inline unsigned order_bits(float f) {
-  const unsigned b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-// larger value first, then the lower index: the larger key
-__device__ inline unsigned long long sort_key(float value, unsigned index) {
-  return ((unsigned long long)order_bits(value) << 32) | (unsigned long long)(0xffffffffu - index);
-}
-__device__ inline unsigned key_index(unsigned long long key) { return 0xffffffffu - (unsigned)(key & 0xffffffffull); }
-
-// Bitonic sort of s[0, kMaxTopk) in LDS, descending; the whole workgroup calls.
-__device__ inline void sort_desc(unsigned long long* s) {
-  for (int k = 2; k <= kMaxTopk; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      __syncthreads();
-      for (int i = threadIdx.x; i < kMaxTopk; i += kThreads) {
-        const int l = i ^ j;
-        if (l > i) {
-          const unsigned long long a = s[i], b = s[l];
-          const bool desc = (i & k) == 0;
-          if (desc ? a < b : a > b) {
-            s[i] = b;
-            s[l] = a;
-          }
-        }
-      }
-    }
-  __syncthreads();
-}
-
 // ---- stage 1 -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_pr_score(void* base, PrDims d, const float* __restrict__ cls,
                                                        const float* __restrict__ conf) {
@@ -189,36 +154,24 @@ __global__ __launch_bounds__(kThreads) void k_pr_score(void* base, PrDims d, con
   const long long stride = (long long)gridDim.x * kThreads;
   for (long long q = (long long)blockIdx.x * kThreads + threadIdx.x; q < d.Q; q += stride) {
     const float* row = cls + q * (C + 1);
-    double mx = -INFINITY;
-    bool ok = isfinite(conf[q]);
-    for (int c = 0; c <= C; ++c) {
-      ok = ok && isfinite(row[c]);
-      mx = fmax(mx, (double)row[c]);
-    }
-    if (!ok) {
+    const RowSoftmax sm = row_softmax(row, C);
+    if (!(sm.ok && isfinite(conf[q]))) {
       bad = kFlagScore;
       for (int c = 0; c < C; ++c) w.score[q * C + c] = 0.f;
       continue;
     }
-    double den = 0.0;
-    for (int c = 0; c <= C; ++c) den += exp((double)row[c] - mx);
     const double cf = conf[q] < 0.f ? 0.0 : (conf[q] > 1.f ? 1.0 : (double)conf[q]);
-    for (int c = 0; c < C; ++c)
-      w.score[q * C + c] = (float)sqrt(exp((double)row[c] - mx) / den * cf) + 0.f;  // + 0: never -0.0
+    for (int c = 0; c < C; ++c) w.score[q * C + c] = (float)sqrt(sm.times(row[c], cf)) + 0.f;  // + 0: never -0.0
   }
   if (bad) atomicOr(&w.s->flags, bad);
 }
 
-// One workgroup.  The key of entry i is (score, lowest index first); the keys are distinct, so the P-th largest is found
-// by eight passes of an 8-bit radix select, the P keys at or above it are gathered and sorted.
+// One workgroup: the d.P largest (score, lowest index first), sorted, as candidates.
 __global__ __launch_bounds__(kThreads) void k_pr_select(void* base, PrDims d, const float* __restrict__ nms_scores,
                                                         const int* __restrict__ nms_classes) {
   PrWs w;
   pr_ws(base, d, &w);
   __shared__ unsigned long long s_key[kMaxTopk];
-  __shared__ unsigned s_hist[256], s_group[16];
-  __shared__ unsigned long long s_prefix;
-  __shared__ unsigned s_need, s_n;
   const int t = threadIdx.x;
   const bool full = d.mode == GAPRO_PROPOSALS_FULL;
   const float* __restrict__ score = full ? w.score : nms_scores;
@@ -229,48 +182,7 @@ __global__ __launch_bounds__(kThreads) void k_pr_select(void* base, PrDims d, co
       if (!isfinite(score[i])) bad = kFlagScore;
     if (bad) atomicOr(&w.s->flags, bad);
   }
-  if (t == 0) {
-    s_prefix = 0ull;
-    s_need = (unsigned)d.P;
-    s_n = 0u;
-  }
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    s_hist[t] = 0u;
-    __syncthreads();
-    const unsigned long long prefix = s_prefix, high = shift == 56 ? 0ull : ~0ull << (shift + 8);
-    for (unsigned i = t; i < n; i += kThreads) {
-      const unsigned long long key = sort_key(score[i], i);
-      if (((key ^ prefix) & high) == 0ull) atomicAdd(&s_hist[(unsigned)(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (t < 16) {  // the buckets in sixteen groups, so that the walk below reads 32 counters, not 256
-      unsigned g = 0u;
-      for (int b = 0; b < 16; ++b) g += s_hist[16 * t + b];
-      s_group[t] = g;
-    }
-    __syncthreads();
-    if (t == 0) {
-      unsigned need = s_need, above = 0u;
-      int g = 15;
-      for (; g > 0 && above + s_group[g] < need; --g) above += s_group[g];
-      int b = 16 * g + 15;
-      for (; b > 16 * g && above + s_hist[b] < need; --b) above += s_hist[b];
-      s_need = need - above;
-      s_prefix = prefix | ((unsigned long long)b << shift);
-    }
-    __syncthreads();
-  }
-  const unsigned long long kth = s_prefix;
-  for (int i = t; i < kMaxTopk; i += kThreads) s_key[i] = 0ull;
-  __syncthreads();
-  for (unsigned i = t; i < n; i += kThreads) {
-    const unsigned long long key = sort_key(score[i], i);
-    if (key >= kth) {
-      const unsigned at = atomicAdd(&s_n, 1u);
-      if (at < (unsigned)kMaxTopk) s_key[at] = key;
-    }
-  }
-  sort_desc(s_key);
+  select_topk(score, n, d.P, s_key);
   for (int j = t; j < d.P; j += kThreads) {
     const unsigned i = key_index(s_key[j]);
     w.cand_q[j] = full ? (int)(i / (unsigned)d.C) : (int)i;
@@ -398,13 +310,7 @@ __global__ __launch_bounds__(kThreads) void k_pr_filter(void* base, PrDims d, Pr
     keep[k] = j < d.P && (!full || w.npoints[w.cand_q[j]] >= (unsigned)par.npoint_thresh);
     c += keep[k];
   }
-  s_cnt[t] = c;
-  __syncthreads();
-  int at = 0, total = 0;
-  for (int j = 0; j < kThreads; ++j) {
-    at += j < t ? s_cnt[j] : 0;
-    total += s_cnt[j];
-  }
+  int total, at = block_sum_before(s_cnt, c, &total);
   for (int k = 0; k < kPer; ++k)
     if (keep[k]) {
       w.surv_q[at] = w.cand_q[j0 + k];
@@ -571,77 +477,43 @@ struct PrPointIn {
   const unsigned char* masks;  // RLE: u8[Q][N]
 };
 
-// m(k, p) for p in [0, N); 0 outside
-__device__ inline int mask_at(const PrWs& w, const PrDims& d, const PrPointIn& in, int k, long long p) {
-  if (p < 0 || p >= d.N) return 0;
-  if (d.mode == GAPRO_PROPOSALS_RLE) return in.masks[(long long)k * d.N + p] != 0;
-  const long long s = idx_at(in.spps, in.spps_i64, p);
-  return 2ull * w.ctab[(size_t)k * d.S + s] >= (unsigned long long)w.ntab[s];
+// m(k, .) of row k as select_runs.h's `bit`: m(k, p) for p in [0, N); 0 outside
+__device__ inline auto mask_at(const PrWs& w, const PrDims& d, const PrPointIn& in, int k) {
+  return [=](long long p) -> int {
+    if (p < 0 || p >= d.N) return 0;
+    if (d.mode == GAPRO_PROPOSALS_RLE) return in.masks[(long long)k * d.N + p] != 0;
+    const long long s = idx_at(in.spps, in.spps_i64, p);
+    return 2ull * w.ctab[(size_t)k * d.S + s] >= (unsigned long long)w.ntab[s];
+  };
 }
 
 // blockIdx = (chunk, row): the transitions at the positions [chunk * chunk_len, ...) of [0, N] and the row's points.
-// The loop is uniform over the workgroup.
 __global__ __launch_bounds__(kThreads) void k_pr_trans(void* base, PrDims d, PrPointIn in) {
   PrWs w;
   pr_ws(base, d, &w);
-  const int k = blockIdx.y, lane = threadIdx.x & 63;
+  const int k = blockIdx.y;
   if (k >= rows_in(w, d)) return;
-  const long long p0 = (long long)blockIdx.x * d.chunk_len, p1 = min(p0 + d.chunk_len, d.N + 1);
-  unsigned trans = 0u, ones = 0u;
-  for (long long b0 = p0; b0 < p1; b0 += kThreads) {
-    const long long p = b0 + threadIdx.x;
-    const int cur = p < p1 ? mask_at(w, d, in, k, p) : 0;
-    int prev = __shfl_up(cur, 1, 64);
-    if (lane == 0) prev = mask_at(w, d, in, k, p - 1);
-    if (p < p1) {
-      trans += cur != prev;
-      ones += cur;
-    }
-  }
-  __shared__ unsigned s_part[2 * (kThreads / 64)];
-  trans = wave_sum(trans);
-  ones = wave_sum(ones);
-  if (lane == 0) {
-    s_part[2 * (threadIdx.x >> 6)] = trans;
-    s_part[2 * (threadIdx.x >> 6) + 1] = ones;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {  // the cell is this workgroup's alone
-    for (int j = 1; j < kThreads / 64; ++j) {
-      trans += s_part[2 * j];
-      ones += s_part[2 * j + 1];
-    }
-    w.chunk_cnt[(size_t)k * d.nchunks + blockIdx.x] = trans;
-    w.chunk_ones[(size_t)k * d.nchunks + blockIdx.x] = ones;
+  const ChunkTally c = chunk_tally(d.chunk_len, d.N, mask_at(w, d, in, k));
+  if (threadIdx.x == 0) {  // the cells are this workgroup's alone
+    w.chunk_cnt[(size_t)k * d.nchunks + blockIdx.x] = c.trans;
+    w.chunk_ones[(size_t)k * d.nchunks + blockIdx.x] = c.ones;
   }
 }
 
-// A wave per row: the chunk counts become the counts before the chunk (a shuffle scan over 64 chunks at a time); the row's
-// transitions and points.
+// A wave per row: the chunk counts become the counts before the chunk; the row's transitions and points.
 __global__ __launch_bounds__(kThreads) void k_pr_chunks(void* base, PrDims d) {
   PrWs w;
   pr_ws(base, d, &w);
   const int n_pre = rows_in(w, d), lane = threadIdx.x & 63;
   const int n_waves = gridDim.x * (kThreads / 64);
   for (int k = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); k < n_pre; k += n_waves) {
-    unsigned* c = w.chunk_cnt + (size_t)k * d.nchunks;
     const unsigned* o = w.chunk_ones + (size_t)k * d.nchunks;
-    unsigned before = 0u, ones = 0u;
-    for (int j0 = 0; j0 < d.nchunks; j0 += 64) {  // uniform over the wave
-      const int j = j0 + lane;
-      const unsigned x = j < d.nchunks ? c[j] : 0u;
-      ones += j < d.nchunks ? o[j] : 0u;
-      unsigned inc = x;
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned y = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += y;
-      }
-      if (j < d.nchunks) c[j] = before + inc - x;
-      before += __shfl(inc, 63, 64);
-    }
+    const unsigned trans = scan_chunks(w.chunk_cnt + (size_t)k * d.nchunks, d.nchunks);
+    unsigned ones = 0u;
+    for (int j = lane; j < d.nchunks; j += 64) ones += o[j];
     ones = wave_sum(ones);
     if (lane == 0) {
-      w.row_trans[k] = before;
+      w.row_trans[k] = trans;
       w.row_ones[k] = ones;
     }
   }
@@ -669,17 +541,8 @@ __global__ __launch_bounds__(kThreads) void k_pr_finish(void* base, PrDims d, Pr
     rows += keep[i];
     sum += keep[i] ? trans[i] : 0u;
   }
-  s_rows[t] = rows;
-  s_sum[t] = sum;
-  __syncthreads();
-  unsigned r = 0u, n_rows = 0u;
-  unsigned long long off = 0ull, total = 0ull;
-  for (int j = 0; j < kThreads; ++j) {
-    r += j < t ? s_rows[j] : 0u;
-    off += j < t ? s_sum[j] : 0ull;
-    n_rows += s_rows[j];
-    total += s_sum[j];
-  }
+  unsigned n_rows, r = block_sum_before(s_rows, rows, &n_rows);
+  unsigned long long total, off = block_sum_before(s_sum, sum, &total);
   int* counts = (int*)(header + 1);
   for (int i = 0; i < kRowsPer; ++i)
     if (keep[i]) {
@@ -706,10 +569,6 @@ __global__ __launch_bounds__(kThreads) void k_pr_finish(void* base, PrDims d, Pr
 }
 
 // ---- fill --------------------------------------------------------------------------------------------------------
-__device__ inline bool fill_ok(const PrWs& w, long long cap_rows, long long cap_runs) {
-  return w.s->status == GAPRO_OK && w.s->n_rows <= cap_rows && w.s->total_trans <= 2 * cap_runs;
-}
-
 __global__ __launch_bounds__(kThreads) void k_pr_fill_rows(void* base, PrDims d, const unsigned* __restrict__ box_in,
                                                            long long cap_rows, long long cap_runs,
                                                            float* __restrict__ conf, int* __restrict__ label,
@@ -718,7 +577,7 @@ __global__ __launch_bounds__(kThreads) void k_pr_fill_rows(void* base, PrDims d,
                                                            gapro_proposals_header* __restrict__ header) {
   PrWs w;
   pr_ws(base, d, &w);
-  if (!fill_ok(w, cap_rows, cap_runs)) {
+  if (!fill_ok(*w.s, cap_rows, cap_runs)) {
     if (header && blockIdx.x == 0 && threadIdx.x == 0 && w.s->status == GAPRO_OK) header->status = GAPRO_ERR_WORKSPACE;
     return;
   }
@@ -736,48 +595,24 @@ __global__ __launch_bounds__(kThreads) void k_pr_fill_rows(void* base, PrDims d,
 }
 
 // blockIdx = (chunk, output row): the positions of the chunk's transitions, 1-based, in order; the mask bytes.
-// The loop is uniform over the workgroup.
 __global__ __launch_bounds__(kThreads) void k_pr_fill_runs(void* base, PrDims d, PrPointIn in, long long cap_rows,
                                                            long long cap_runs, long long* __restrict__ runs,
                                                            unsigned char* __restrict__ masks) {
   PrWs w;
   pr_ws(base, d, &w);
-  if (!fill_ok(w, cap_rows, cap_runs)) return;
-  const int r = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (!fill_ok(*w.s, cap_rows, cap_runs)) return;
+  const int r = blockIdx.y;
   if (r >= w.s->n_rows) return;
-  __shared__ unsigned s_wave[kThreads / 64];
   const int k = w.final_row[r];
-  long long at = w.run_off[r] + w.chunk_cnt[(size_t)k * d.nchunks + blockIdx.x];
-  const long long p0 = (long long)blockIdx.x * d.chunk_len, p1 = min(p0 + d.chunk_len, d.N + 1);
-  for (long long b0 = p0; b0 < p1; b0 += kThreads) {
-    const long long p = b0 + threadIdx.x;
-    const int cur = p < p1 ? mask_at(w, d, in, k, p) : 0;
-    int prev = __shfl_up(cur, 1, 64);
-    if (lane == 0) prev = mask_at(w, d, in, k, p - 1);
-    const bool tr = p < p1 && cur != prev;
-    const unsigned long long b = __ballot(tr);
-    if (lane == 0) s_wave[wave] = (unsigned)__popcll(b);
-    __syncthreads();
-    unsigned before = 0u, total = 0u;
-    for (int j = 0; j < kThreads / 64; ++j) {
-      before += j < wave ? s_wave[j] : 0u;
-      total += s_wave[j];
-    }
-    if (tr) runs[at + before + __popcll(b & ((1ull << lane) - 1ull))] = p + 1;
-    if (masks && p < p1 && p < d.N) masks[(long long)r * d.N + p] = (unsigned char)cur;
-    at += total;
-    __syncthreads();  // s_wave is written again
-  }
+  emit_runs(d.chunk_len, d.N, mask_at(w, d, in, k), w.run_off[r] + w.chunk_cnt[(size_t)k * d.nchunks + blockIdx.x], runs,
+            masks ? masks + (long long)r * d.N : nullptr);
 }
 
-// every second value of a row is the end of a run: it becomes the length.  The rows hold whole pairs.
 __global__ __launch_bounds__(kThreads) void k_pr_fill_lengths(void* base, PrDims d, long long cap_rows, long long cap_runs,
                                                               long long* __restrict__ runs) {
   PrWs w;
   pr_ws(base, d, &w);
-  if (!fill_ok(w, cap_rows, cap_runs)) return;
-  const long long n = w.s->total_trans / 2, stride = (long long)gridDim.x * kThreads;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) runs[2 * i + 1] -= runs[2 * i];
+  if (fill_ok(*w.s, cap_rows, cap_runs)) ends_to_lengths(runs, w.s->total_trans / 2);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
@@ -827,10 +662,8 @@ bool make_dims(const gapro_proposals_inputs* in, const gapro_proposals_params* p
       if ((long long)d->R * d->S > kMaxIndex) return false;
     }
   }
-  long long nc = (d->N + 1 + kMinChunk - 1) / kMinChunk;
-  if (nc > kMaxChunks) nc = kMaxChunks;
-  d->nchunks = mode == GAPRO_PROPOSALS_NMS ? 1 : (int)nc;
-  d->chunk_len = (d->N + 1 + d->nchunks - 1) / d->nchunks;
+  chunking(d->N, &d->nchunks, &d->chunk_len);
+  if (mode == GAPRO_PROPOSALS_NMS) d->nchunks = 1;  // no runs: N is 1 here
   return true;
 }
 

@@ -17,27 +17,19 @@
 //   runs     the positions of the transitions in order (and the masks); then `lengths` turns every second into a length
 // Integer atomics only, so every result is the same bits for every grid and every run.  The kernel boundaries on the
 // stream are the only ordering.  A refusal is a status word written by `filter`: every later kernel returns at once.
-// The select / sort and the chunked run lengths restate csrc/proposals.hip's (stages 1 and 7 there) with this file's
-// point-bit function; that file is left as it is.
+// The softmax, the select / sort and the chunked run lengths are select_runs.h's, shared with proposals.hip; this file
+// supplies its point bit (`mask_at`: the superpoint bit of the point) and its row indexing: the chunk cells of a row
+// belong to output row r, and `row_cand[r]` only finds the row's bits.
 #include "common.h"
 #include "label_types.h"
 #include "launch_util.h"
+#include "select_runs.h"
 #include "wave_reduce.h"
 
 #include <cmath>
 #include <cstdint>
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kGridCap = GAPRO_PROPOSALS_GRID_CAP;
-constexpr int kMaxTopk = GAPRO_PROPOSALS_MAX_PRE_TOPK;  // also the length of the sorts in LDS: a power of two
-constexpr int kMaxChunks = 1024;  // chunks of points of a row (`trans`, `runs`)
-constexpr int kMinChunk = 1024;   // points of a chunk, at least
-constexpr long long kMaxIndex = 0x7fffffffLL;
-constexpr long long kMaxScores = 1LL << 20;
-static_assert((kMaxTopk & (kMaxTopk - 1)) == 0 && kMaxTopk % kThreads == 0, "the LDS sorts need a power of two");
 
 enum { kFlagScore = 1, kFlagMask = 2, kFlagCoords = 4, kFlagSpp = 8 };
 
@@ -111,47 +103,6 @@ __host__ __device__ inline size_t sp_ws(void* base, const SpDims& d, SpWs* w) {
   return (size_t)(p - (char*)base);
 }
 
-// float32 as an unsigned integer of the same order (-0.0 below +0.0), and back
-__device__ inline unsigned order_bits(float f) {
-  const unsigned b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ inline unsigned order_bits_inv(unsigned u) { return (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u; }
-// larger value first, then the lower index: the larger key
-__device__ inline unsigned long long sort_key(float value, unsigned index) {
-  return ((unsigned long long)order_bits(value) << 32) | (unsigned long long)(0xffffffffu - index);
-}
-__device__ inline unsigned key_index(unsigned long long key) { return 0xffffffffu - (unsigned)(key & 0xffffffffull); }
-
-// Bitonic sort of s[0, kMaxTopk) in LDS, descending; the whole workgroup calls.
-__device__ inline void sort_desc(unsigned long long* s) {
-  for (int k = 2; k <= kMaxTopk; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      __syncthreads();
-      for (int i = threadIdx.x; i < kMaxTopk; i += kThreads) {
-        const int l = i ^ j;
-        if (l > i) {
-          const unsigned long long a = s[i], b = s[l];
-          const bool desc = (i & k) == 0;
-          if (desc ? a < b : a > b) {
-            s[i] = b;
-            s[l] = a;
-          }
-        }
-      }
-    }
-  __syncthreads();
-}
-
-// softmax(labels[q, :])[c] * pred_scores[q] in float64: exp(x - max) over the sum of these terms in ascending c
-__device__ inline double class_score(const float* __restrict__ row, int C, int c, float ps) {
-  double mx = -INFINITY;
-  for (int j = 0; j <= C; ++j) mx = fmax(mx, (double)row[j]);
-  double den = 0.0;
-  for (int j = 0; j <= C; ++j) den += exp((double)row[j] - mx);
-  return exp((double)row[c] - mx) / den * (double)ps;
-}
-
 // ---- step 1 ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_sp_score(void* base, SpDims d, const float* __restrict__ labels,
                                                        const float* __restrict__ pred_scores) {
@@ -162,80 +113,25 @@ __global__ __launch_bounds__(kThreads) void k_sp_score(void* base, SpDims d, con
   const long long stride = (long long)gridDim.x * kThreads;
   for (long long q = (long long)blockIdx.x * kThreads + threadIdx.x; q < d.Q; q += stride) {
     const float* row = labels + q * (C + 1);
-    double mx = -INFINITY;
-    bool ok = isfinite(pred_scores[q]);
-    for (int c = 0; c <= C; ++c) {
-      ok = ok && isfinite(row[c]);
-      mx = fmax(mx, (double)row[c]);
-    }
-    if (!ok) {
+    const RowSoftmax sm = row_softmax(row, C);
+    if (!(sm.ok && isfinite(pred_scores[q]))) {
       bad = kFlagScore;
       for (int c = 0; c < C; ++c) w.score[q * C + c] = 0.f;
       continue;
     }
-    double den = 0.0;
-    for (int c = 0; c <= C; ++c) den += exp((double)row[c] - mx);
     const double ps = (double)pred_scores[q];
-    for (int c = 0; c < C; ++c)
-      w.score[q * C + c] = (float)(exp((double)row[c] - mx) / den * ps) + 0.f;  // + 0: never -0.0
+    for (int c = 0; c < C; ++c) w.score[q * C + c] = (float)sm.times(row[c], ps) + 0.f;  // + 0: never -0.0
   }
   if (bad) atomicOr(&w.s->flags, bad);
 }
 
-// One workgroup.  The key of entry i is (score, lowest index first); the keys are distinct, so the K-th largest is found
-// by eight passes of an 8-bit radix select, the K keys at or above it are gathered and sorted.
+// One workgroup: the d.K largest (score, lowest index first), sorted, as candidates.
 __global__ __launch_bounds__(kThreads) void k_sp_select(void* base, SpDims d) {
   SpWs w;
   sp_ws(base, d, &w);
   __shared__ unsigned long long s_key[kMaxTopk];
-  __shared__ unsigned s_hist[256], s_group[16];
-  __shared__ unsigned long long s_prefix;
-  __shared__ unsigned s_need, s_n;
   const int t = threadIdx.x;
-  const float* __restrict__ score = w.score;
-  const unsigned n = (unsigned)(d.Q * d.C);
-  if (t == 0) {
-    s_prefix = 0ull;
-    s_need = (unsigned)d.K;
-    s_n = 0u;
-  }
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    s_hist[t] = 0u;
-    __syncthreads();
-    const unsigned long long prefix = s_prefix, high = shift == 56 ? 0ull : ~0ull << (shift + 8);
-    for (unsigned i = t; i < n; i += kThreads) {
-      const unsigned long long key = sort_key(score[i], i);
-      if (((key ^ prefix) & high) == 0ull) atomicAdd(&s_hist[(unsigned)(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (t < 16) {  // the buckets in sixteen groups, so that the walk below reads 32 counters, not 256
-      unsigned g = 0u;
-      for (int b = 0; b < 16; ++b) g += s_hist[16 * t + b];
-      s_group[t] = g;
-    }
-    __syncthreads();
-    if (t == 0) {
-      unsigned need = s_need, above = 0u;
-      int g = 15;
-      for (; g > 0 && above + s_group[g] < need; --g) above += s_group[g];
-      int b = 16 * g + 15;
-      for (; b > 16 * g && above + s_hist[b] < need; --b) above += s_hist[b];
-      s_need = need - above;
-      s_prefix = prefix | ((unsigned long long)b << shift);
-    }
-    __syncthreads();
-  }
-  const unsigned long long kth = s_prefix;
-  for (int i = t; i < kMaxTopk; i += kThreads) s_key[i] = 0ull;
-  __syncthreads();
-  for (unsigned i = t; i < n; i += kThreads) {
-    const unsigned long long key = sort_key(score[i], i);
-    if (key >= kth) {
-      const unsigned at = atomicAdd(&s_n, 1u);
-      if (at < (unsigned)kMaxTopk) s_key[at] = key;
-    }
-  }
-  sort_desc(s_key);
+  select_topk(w.score, (unsigned)(d.Q * d.C), d.K, s_key);
   for (int j = t; j < d.K; j += kThreads) {
     const unsigned i = key_index(s_key[j]);
     w.cand_q[j] = (int)(i / (unsigned)d.C);
@@ -346,7 +242,8 @@ __global__ __launch_bounds__(kThreads) void k_sp_rows(void* base, SpDims d, cons
       float conf = 0.f;
       if (!bad && cnt > 0ull && !(w.s->flags & kFlagScore)) {
         const int c = w.cand_cls[k];
-        const double cs = class_score(labels + (long long)q * (d.C + 1), d.C, c, pred_scores[q]);
+        const float* __restrict__ cls = labels + (long long)q * (d.C + 1);  // k_sp_score's term, before it is rounded
+        const double cs = row_softmax(cls, d.C).times(cls[c], (double)pred_scores[q]);
         conf = (float)(cs * sum / ((double)cnt + 1e-6)) + 0.f;
       }
       w.cand_conf[k] = conf;
@@ -411,63 +308,35 @@ __global__ __launch_bounds__(kThreads) void k_sp_filter(void* base, SpDims d, fl
 }
 
 // ---- step 6 ------------------------------------------------------------------------------------------------------
-// m(k, p) for p in [0, N); 0 outside.  `filter` found every superpoint id in range, or there are no rows.
-__device__ inline int mask_at(const SpWs& w, const SpDims& d, const void* spps, int spps_i64, int k, long long p) {
-  if (p < 0 || p >= d.N) return 0;
-  const long long s = idx_at(spps, spps_i64, p);
-  return (int)((w.bits[(long long)k * d.W + (s >> 6)] >> (s & 63)) & 1ull);
+// m(k, .) of candidate k as select_runs.h's `bit`: m(k, p) for p in [0, N); 0 outside.  `filter` found every superpoint
+// id in range, or there are no rows.
+__device__ inline auto mask_at(const SpWs& w, const SpDims& d, const void* spps, int spps_i64, int k) {
+  return [=](long long p) -> int {
+    if (p < 0 || p >= d.N) return 0;
+    const long long s = idx_at(spps, spps_i64, p);
+    return (int)((w.bits[(long long)k * d.W + (s >> 6)] >> (s & 63)) & 1ull);
+  };
 }
 
 // blockIdx = (chunk, output row): the transitions at the positions [chunk * chunk_len, ...) of [0, N].
-// The loop is uniform over the workgroup.
 __global__ __launch_bounds__(kThreads) void k_sp_trans(void* base, SpDims d, const void* __restrict__ spps,
                                                        int spps_i64) {
   SpWs w;
   sp_ws(base, d, &w);
-  const int r = blockIdx.y, lane = threadIdx.x & 63;
+  const int r = blockIdx.y;
   if (r >= w.s->n_rows) return;
-  const int k = w.row_cand[r];
-  const long long p0 = (long long)blockIdx.x * d.chunk_len, p1 = min(p0 + d.chunk_len, d.N + 1);
-  unsigned trans = 0u;
-  for (long long b0 = p0; b0 < p1; b0 += kThreads) {
-    const long long p = b0 + threadIdx.x;
-    const int cur = p < p1 ? mask_at(w, d, spps, spps_i64, k, p) : 0;
-    int prev = __shfl_up(cur, 1, 64);
-    if (lane == 0) prev = mask_at(w, d, spps, spps_i64, k, p - 1);
-    if (p < p1) trans += cur != prev;
-  }
-  __shared__ unsigned s_part[kWaves];
-  trans = wave_sum(trans);
-  if (lane == 0) s_part[threadIdx.x >> 6] = trans;
-  __syncthreads();
-  if (threadIdx.x == 0) {  // the cell is this workgroup's alone
-    for (int j = 1; j < kWaves; ++j) trans += s_part[j];
-    w.chunk_cnt[(size_t)r * d.nchunks + blockIdx.x] = trans;
-  }
+  const ChunkTally c = chunk_tally(d.chunk_len, d.N, mask_at(w, d, spps, spps_i64, w.row_cand[r]));
+  if (threadIdx.x == 0) w.chunk_cnt[(size_t)r * d.nchunks + blockIdx.x] = c.trans;  // the cell is this workgroup's alone
 }
 
-// A wave per row: the chunk counts become the counts before the chunk (a shuffle scan over 64 chunks at a time); the row's
-// transitions.
+// A wave per row: the chunk counts become the counts before the chunk; the row's transitions.
 __global__ __launch_bounds__(kThreads) void k_sp_chunks(void* base, SpDims d) {
   SpWs w;
   sp_ws(base, d, &w);
-  const int n_rows = w.s->n_rows, lane = threadIdx.x & 63;
-  const int n_waves = gridDim.x * kWaves;
+  const int n_rows = w.s->n_rows, n_waves = gridDim.x * kWaves;
   for (int r = blockIdx.x * kWaves + (threadIdx.x >> 6); r < n_rows; r += n_waves) {
-    unsigned* c = w.chunk_cnt + (size_t)r * d.nchunks;
-    unsigned before = 0u;
-    for (int j0 = 0; j0 < d.nchunks; j0 += 64) {  // uniform over the wave
-      const int j = j0 + lane;
-      const unsigned x = j < d.nchunks ? c[j] : 0u;
-      unsigned inc = x;
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned y = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += y;
-      }
-      if (j < d.nchunks) c[j] = before + inc - x;
-      before += __shfl(inc, 63, 64);
-    }
-    if (lane == 0) w.row_trans[r] = before;
+    const unsigned trans = scan_chunks(w.chunk_cnt + (size_t)r * d.nchunks, d.nchunks);
+    if ((threadIdx.x & 63) == 0) w.row_trans[r] = trans;
   }
 }
 
@@ -486,13 +355,7 @@ __global__ __launch_bounds__(kThreads) void k_sp_finish(void* base, SpDims d,
     trans[i] = r0 + i < n_rows ? w.row_trans[r0 + i] : 0u;
     sum += trans[i];
   }
-  s_sum[t] = sum;
-  __syncthreads();
-  unsigned long long off = 0ull, total = 0ull;
-  for (int j = 0; j < kThreads; ++j) {
-    off += j < t ? s_sum[j] : 0ull;
-    total += s_sum[j];
-  }
+  unsigned long long total, off = block_sum_before(s_sum, sum, &total);
   int* counts = (int*)(header + 1);
   for (int i = 0; i < kRowsPer; ++i)
     if (r0 + i < n_rows) {
@@ -514,10 +377,6 @@ __global__ __launch_bounds__(kThreads) void k_sp_finish(void* base, SpDims d,
 }
 
 // ---- fill --------------------------------------------------------------------------------------------------------
-__device__ inline bool fill_ok(const SpWs& w, long long cap_rows, long long cap_runs) {
-  return w.s->status == GAPRO_OK && w.s->n_rows <= cap_rows && w.s->total_trans <= 2 * cap_runs;
-}
-
 __global__ __launch_bounds__(kThreads) void k_sp_fill_rows(void* base, SpDims d, long long cap_rows, long long cap_runs,
                                                            float* __restrict__ conf, int* __restrict__ label,
                                                            unsigned* __restrict__ box, int* __restrict__ query,
@@ -525,7 +384,7 @@ __global__ __launch_bounds__(kThreads) void k_sp_fill_rows(void* base, SpDims d,
                                                            gapro_spf_predict_header* __restrict__ header) {
   SpWs w;
   sp_ws(base, d, &w);
-  if (!fill_ok(w, cap_rows, cap_runs)) {
+  if (!fill_ok(*w.s, cap_rows, cap_runs)) {
     if (header && blockIdx.x == 0 && threadIdx.x == 0 && w.s->status == GAPRO_OK) header->status = GAPRO_ERR_WORKSPACE;
     return;
   }
@@ -543,49 +402,25 @@ __global__ __launch_bounds__(kThreads) void k_sp_fill_rows(void* base, SpDims d,
 }
 
 // blockIdx = (chunk, output row): the positions of the chunk's transitions, 1-based, in order; the mask bytes.
-// The loop is uniform over the workgroup.
 __global__ __launch_bounds__(kThreads) void k_sp_fill_runs(void* base, SpDims d, const void* __restrict__ spps,
                                                            int spps_i64, long long cap_rows, long long cap_runs,
                                                            long long* __restrict__ runs,
                                                            unsigned char* __restrict__ masks) {
   SpWs w;
   sp_ws(base, d, &w);
-  if (!fill_ok(w, cap_rows, cap_runs)) return;
-  const int r = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (!fill_ok(*w.s, cap_rows, cap_runs)) return;
+  const int r = blockIdx.y;
   if (r >= w.s->n_rows) return;
-  __shared__ unsigned s_wave[kWaves];
-  const int k = w.row_cand[r];
-  long long at = w.run_off[r] + w.chunk_cnt[(size_t)r * d.nchunks + blockIdx.x];
-  const long long p0 = (long long)blockIdx.x * d.chunk_len, p1 = min(p0 + d.chunk_len, d.N + 1);
-  for (long long b0 = p0; b0 < p1; b0 += kThreads) {
-    const long long p = b0 + threadIdx.x;
-    const int cur = p < p1 ? mask_at(w, d, spps, spps_i64, k, p) : 0;
-    int prev = __shfl_up(cur, 1, 64);
-    if (lane == 0) prev = mask_at(w, d, spps, spps_i64, k, p - 1);
-    const bool tr = p < p1 && cur != prev;
-    const unsigned long long b = __ballot(tr);
-    if (lane == 0) s_wave[wave] = (unsigned)__popcll(b);
-    __syncthreads();
-    unsigned before = 0u, total = 0u;
-    for (int j = 0; j < kWaves; ++j) {
-      before += j < wave ? s_wave[j] : 0u;
-      total += s_wave[j];
-    }
-    if (tr && runs) runs[at + before + __popcll(b & ((1ull << lane) - 1ull))] = p + 1;
-    if (masks && p < p1 && p < d.N) masks[(long long)r * d.N + p] = (unsigned char)cur;
-    at += total;
-    __syncthreads();  // s_wave is written again
-  }
+  emit_runs(d.chunk_len, d.N, mask_at(w, d, spps, spps_i64, w.row_cand[r]),
+            w.run_off[r] + w.chunk_cnt[(size_t)r * d.nchunks + blockIdx.x], runs,
+            masks ? masks + (long long)r * d.N : nullptr);
 }
 
-// every second value of a row is the end of a run: it becomes the length.  The rows hold whole pairs.
 __global__ __launch_bounds__(kThreads) void k_sp_fill_lengths(void* base, SpDims d, long long cap_rows,
                                                               long long cap_runs, long long* __restrict__ runs) {
   SpWs w;
   sp_ws(base, d, &w);
-  if (!fill_ok(w, cap_rows, cap_runs)) return;
-  const long long n = w.s->total_trans / 2, stride = (long long)gridDim.x * kThreads;
-  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) runs[2 * i + 1] -= runs[2 * i];
+  if (fill_ok(*w.s, cap_rows, cap_runs)) ends_to_lengths(runs, w.s->total_trans / 2);
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------
@@ -603,10 +438,7 @@ bool make_dims(const gapro_spf_predict_inputs* in, const gapro_spf_predict_param
   d->W = (S + 63) / 64;
   d->C = (int)C;
   d->K = (int)(Q * C < p->topk_insts ? Q * C : p->topk_insts);
-  long long nc = (N + 1 + kMinChunk - 1) / kMinChunk;
-  if (nc > kMaxChunks) nc = kMaxChunks;
-  d->nchunks = (int)nc;
-  d->chunk_len = (N + 1 + d->nchunks - 1) / d->nchunks;
+  chunking(N, &d->nchunks, &d->chunk_len);
   return true;
 }
 

@@ -13,7 +13,8 @@ import functools
 
 import numpy as np
 
-# The constants of csrc/proposals.hip that no header exposes, mirrored: a change there is a change here.
+# The constants of csrc/proposals.hip and of csrc/select_runs.h (kThreads, kMinChunk, kMaxChunks, kMaxTopk, kMaxScores:
+# shared with csrc/spf_predict.hip) that no public header exposes, mirrored: a change there is a change here.
 PACK_WORDS = 32                     # kPackWords: the words (of 64 voxels) of a wave's run of `pack`
 PACK_PASS_WAVES = 2048 * 4          # GAPRO_PROPOSALS_GRID_CAP * (kThreads / 64) waves: tasks of one pass of `pack`
 INTER_PASS_WORDS = 64               # `inter`: a word a lane, 64 words a trip
@@ -28,7 +29,7 @@ MAX_SCORES = 1 << 20                # kMaxScores: Q * C at most
 
 
 def chunking(N):
-    """(nchunks, chunk_len) of N points: make_dims of csrc/proposals.hip."""
+    """(nchunks, chunk_len) of N points: ``chunking`` of csrc/select_runs.h, which both chains' make_dims call."""
     nchunks = min((N + 1 + MIN_CHUNK - 1) // MIN_CHUNK, MAX_CHUNKS)
     return nchunks, (N + 1 + nchunks - 1) // nchunks
 

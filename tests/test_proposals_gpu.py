@@ -141,9 +141,9 @@ def test_the_flags_name_every_cause():
     from gapro_amd import consumer_ops as ops
 
     seen = {}
-    run = ops._proposals_run
+    run = ops._predict_run
 
-    def spy(who, anchor, inputs, params, keep, n_points, **kw):
+    def spy(who, chain, anchor, inputs, params, keep, n_points, **kw):
         ctx, stream = ops._ctx_stream(anchor)
         lib, pin, ppar = ctx.lib, C.byref(inputs), C.byref(params)
         ws = torch.empty(int(lib.gapro_proposals_workspace_bytes(pin, ppar)), dtype=torch.uint8, device=anchor.device)
@@ -152,9 +152,9 @@ def test_the_flags_name_every_cause():
         ctx.check(lib.gapro_proposals_count(ctx.handle, stream, pin, ppar, ws.data_ptr(), ws.numel(), d_hdr.data_ptr(),
                                             None))
         seen["hdr"] = _lib.ProposalsHeader.from_buffer_copy(d_hdr.cpu().numpy().tobytes())
-        return run(who, anchor, inputs, params, keep, n_points, **kw)
+        return run(who, chain, anchor, inputs, params, keep, n_points, **kw)
 
-    ops._proposals_run = spy
+    ops._predict_run = spy
     try:
         for name, case, status, flags in cases.refusals():
             with pytest.raises(_lib.GaproError):
@@ -168,7 +168,7 @@ def test_the_flags_name_every_cause():
         _check(_host(_call(fine, return_arrays=True, return_masks=True)), ref.get_instance_ref(**fine),
                len(fine["v2p_map"]))
     finally:
-        ops._proposals_run = run
+        ops._predict_run = run
 
 
 def test_too_small_outputs_are_refused_and_nothing_is_written():
@@ -181,17 +181,17 @@ def test_too_small_outputs_are_refused_and_nothing_is_written():
 
     c = CASES["run_shapes"]
     captured = {}
-    run = ops._proposals_run
+    run = ops._predict_run
 
-    def grab(who, anchor, inputs, params, keep, n_points, **kw):
+    def grab(who, chain, anchor, inputs, params, keep, n_points, **kw):
         captured.update(inputs=inputs, params=params, keep=keep, anchor=anchor)
-        return run(who, anchor, inputs, params, keep, n_points, **kw)
+        return run(who, chain, anchor, inputs, params, keep, n_points, **kw)
 
-    ops._proposals_run = grab
+    ops._predict_run = grab
     try:
         full = _call(c, return_arrays=True)
     finally:
-        ops._proposals_run = run
+        ops._predict_run = run
     rows, runs = int(full.header.n_rows), int(full.header.total_runs)
     ctx, stream = ops._ctx_stream(captured["anchor"])
     lib, pin, ppar = ctx.lib, C.byref(captured["inputs"]), C.byref(captured["params"])
