@@ -25,7 +25,8 @@ _EXPORTS = {
                      "voxelization_idx", "voxelization", "spformer_match", "spformer_layer_losses",
                      "spformer_criterion", "spformer_instances", "spformer_predict", "superpoint_plan",
                      "superpoint_pool", "scatter_mean", "scatter_max", "custom_scatter_mean", "isbnet_spp_pool",
-                     "spformer_pool", "dynamic_mask_head", "mask_heads_forward", "dyco_param_count"),
+                     "spformer_pool", "dynamic_mask_head", "mask_heads_forward", "dyco_param_count", "subm_plan",
+                     "downsample_plan", "subm_conv3d", "sparse_conv3d", "sparse_inverse_conv3d", "SparseConvPlan"),
 }
 __all__ = [n for names in _EXPORTS.values() for n in names]
 

@@ -277,6 +277,8 @@ VOXELIZE_STATUS_WORDS = 4     # GAPRO_VOXELIZE_STATUS_WORDS: status, flags, 0, 0
 SPP_SORT_TILE, SPP_MAX_SEGMENTS, SPP_MAX_BATCHES, SPP_STATUS_WORDS = 4096, 1 << 24, 65536, 4   # GAPRO_SPP_*
 SPP_FLAG_INDEX, SPP_FLAG_MAP, SPP_MEAN, SPP_MAX = 1, 2, 0, 1
 DYCO_MAX_BATCH = 64  # GAPRO_DYCO_MAX_BATCH
+SPCONV_STATUS_WORDS = 4       # GAPRO_SPCONV_STATUS_WORDS: status, flags, n_out (the down plan's header), 0
+SPCONV_MAX_ROWS, SPCONV_MAX_CHANNELS, SPCONV_CIN_CHUNK, SPCONV_MIN_CHUNK_ROWS = 1 << 30, 512, 32, 256  # GAPRO_SPCONV_*
 
 
 class SppPlan(C.Structure):
@@ -435,6 +437,20 @@ SIGNATURES = {
                                      _P, _P, _P, C.c_size_t, _P]),
     "gapro_dyco_backward": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, C.c_int64, _P, _P,
                                       _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P]),
+    "gapro_spconv_subm_plan_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gapro_spconv_subm_plan": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_size_t, _P, _P, _P]),
+    "gapro_spconv_down_plan_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gapro_spconv_down_count": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, _P, C.c_size_t, _P, _P]),
+    "gapro_spconv_down_fill": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, _P, C.c_int32, C.c_int64, _P, C.c_size_t,
+                                         _P, _P, _P, _P, _P, _P]),
+    "gapro_spconv_chunk_rows": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "gapro_spconv_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "gapro_spconv_forward": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P,
+                                       _P, _P]),
+    "gapro_spconv_backward_input": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32,
+                                              C.c_int32, _P, _P, _P]),
+    "gapro_spconv_backward_weight": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int32, C.c_int32,
+                                               _P, _P, _P, C.c_size_t, _P, _P]),
     "gapro_schedule_build": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
     "gapro_schedule_free": (None, [_P]),
     "gapro_schedule_get_counts": (C.c_int, [_P, C.POINTER(ScheduleCounts)]),
@@ -619,7 +635,7 @@ def load() -> C.CDLL:
                                             "gapro_fit_launch_plan", "gapro_inst_", "gapro_spp_gt_", "gapro_match_",
                                             "gapro_proposals_", "gapro_fps_", "gapro_ball_query_",
                                             "gapro_lsap_", "gapro_voxelize_", "gapro_voxel_pool_", "gapro_spf_predict_",
-                                            "gapro_spp_plan_", "gapro_spp_pool_", "gapro_dyco_")):
+                                            "gapro_spp_plan_", "gapro_spp_pool_", "gapro_dyco_", "gapro_spconv_")):
                 continue  # an older build under A/B comparison: no model export, no training-set assembly (a call
                 #           raises AttributeError)
             if not variant or not name.startswith(("gapro_pth_", "gapro_scene_", "gapro_feed_")):

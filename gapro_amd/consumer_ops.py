@@ -2826,3 +2826,240 @@ def spformer_predict(scan_ids, out, superpoints, insts, coords_float, *, num_cla
                               coords_float, num_class=num_class, topk_insts=topk_insts, score_thr=score_thr,
                               npoint_thr=npoint_thr)
     return dict(scan_id=scan_ids[0], pred_instances=pred, gt_instances=insts[0].gt_instances)
+
+
+# ---- sparse convolutions: spconv's three layers of the consumers' U-Nets (csrc/spconv.hip) ---------------
+_SPCONV_CAUSES = ((1, "two rows of coords with the same coordinates"),
+                  (2, "a coordinate outside spatial_shape"),
+                  (4, "a batch index outside [0, batch_size)"),
+                  (8, "a workspace that is not the count's"))
+
+
+class SparseConvPlan:
+    """The rulebook of one ``indice_key``: built once a step by ``subm_plan`` or ``downsample_plan`` and passed to every
+    layer of its level.  ``kind`` is ``"subm"`` (``neighbours int32[27, V]``) or ``"down"`` (``children int32[8, V_c]``,
+    ``parent int32[V]``, ``child_slot int32[V]``); ``n_in`` / ``n_out`` are the rows of the strided (or submanifold)
+    layer's input and output, ``coords`` (int32 ``[n_out, 4]``) and ``spatial_shape`` those of its output -- what the
+    next level's plans take."""
+    __slots__ = ("kind", "device", "n_in", "n_out", "batch_size", "in_shape", "spatial_shape", "coords", "neighbours",
+                 "children", "parent", "child_slot")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _plan_args(who, coords, spatial_shape, batch_size, check):
+    if not isinstance(coords, torch.Tensor) or coords.dtype not in _INT or coords.dim() != 2 or coords.shape[1] != 4:
+        raise ValueError("%s: coords must be an int32 or int64 tensor of shape [V, 4]" % who)
+    try:
+        shape = tuple(spatial_shape)
+    except TypeError:
+        shape = ()
+    if len(shape) != 3 or not all(_is_int(d, (int, np.integer)) and 1 <= d <= 2 ** 31 - 3 for d in shape):
+        raise ValueError("%s: spatial_shape must be three positive ints (Dz, Dy, Dx)" % who)
+    _positive_int_arg(who, "batch_size", batch_size, (int, np.integer))
+    if not isinstance(check, bool):
+        raise ValueError("%s: check must be a bool" % who)
+    shape, batch_size = tuple(int(d) for d in shape), int(batch_size)
+    if batch_size * (shape[0] + 2) * (shape[1] + 2) * (shape[2] + 2) >= 2 ** 63:
+        raise ValueError("%s: batch_size and spatial_shape are beyond the 63-bit coordinate key" % who)
+    if int(coords.shape[0]) > _lib.SPCONV_MAX_ROWS:
+        raise ValueError("%s: %d rows are beyond the library's bounds" % (who, int(coords.shape[0])))
+    _need_device(coords)
+    return coords.detach().contiguous(), shape, batch_size
+
+
+def subm_plan(coords, spatial_shape, batch_size, *, check=True):
+    """The plan of ``SubMConv3d(k=3, padding=1)`` layers that share an ``indice_key``: ``coords`` is int ``[V, 4]``
+    with columns (batch, z, y, x) and unique rows, as ``voxelization_idx`` returns it and ``SparseConvTensor`` takes it.
+    ``neighbours[k, r]`` is the row at ``p_r + d_k`` (``k = (dz + 1) 9 + (dy + 1) 3 + (dx + 1)``) in the same sample and
+    inside the grid, or -1.  The call only enqueues; ``check=True`` adds ONE host read of the status word: a duplicate
+    row, a coordinate outside ``spatial_shape`` and a batch index outside ``[0, batch_size)`` are a ``GaproError``."""
+    who = "subm_plan"
+    coords, shape, batch_size = _plan_args(who, coords, spatial_shape, batch_size, check)
+    V, dev = int(coords.shape[0]), coords.device
+    plan = SparseConvPlan(kind="subm", device=dev, n_in=V, n_out=V, batch_size=batch_size, in_shape=shape,
+                          spatial_shape=shape, coords=coords,
+                          neighbours=torch.empty((27, V), dtype=torch.int32, device=dev))
+    if V == 0:
+        return plan
+    ctx, stream = _ctx_stream(coords)
+    lib = ctx.lib
+    h_shape = (C.c_int32 * 3)(*shape)
+    with torch.cuda.device(dev):
+        ws = _workspace(who, int(lib.gapro_spconv_subm_plan_workspace_bytes(V)), dev, "%d rows are" % V)
+        d_status, h_status = _status_pair(dev, _lib.SPCONV_STATUS_WORDS, torch.int32, read=check)
+        ctx.check(lib.gapro_spconv_subm_plan(ctx.handle, stream, V, coords.data_ptr(),
+                                             int(coords.dtype == torch.int64), h_shape, batch_size, ws.data_ptr(),
+                                             ws.numel(), plan.neighbours.data_ptr(), d_status.data_ptr(),
+                                             _ptr(h_status)))
+        if h_status is not None:  # the call's host read of its status, asked for by check=True
+            status, flags = _host_read(dev, h_status)[:2]
+            _refuse(who, status, flags, _SPCONV_CAUSES)
+    return plan
+
+
+def downsample_plan(coords, spatial_shape, batch_size, *, check=True):
+    """The plan of ``SparseConv3d(k=2, stride=2)`` and of the ``SparseInverseConv3d(k=2)`` on the same ``indice_key``.
+    The coarse voxel of a row is ``(b, z >> 1, y >> 1, x >> 1)``; a row in the last slice of an odd extent is in none
+    (``parent = -1``).  COARSE ROWS ARE NUMBERED BY THEIR FIRST CHILD IN ASCENDING INPUT ROW.  ``.coords`` (int32
+    ``[n_out, 4]``), ``.spatial_shape`` (``(D - 2) // 2 + 1`` per axis) and ``.n_out`` describe the coarse level.  One
+    host read (the header: status and ``n_out``); with ``check=True`` a duplicate row, a coordinate outside
+    ``spatial_shape`` and a batch index outside ``[0, batch_size)`` are a ``GaproError``, with ``check=False`` such rows
+    simply have no pairs."""
+    who = "downsample_plan"
+    coords, shape, batch_size = _plan_args(who, coords, spatial_shape, batch_size, check)
+    V, dev = int(coords.shape[0]), coords.device
+    out_shape = tuple((d - 2) // 2 + 1 if d >= 2 else 0 for d in shape)
+    plan = SparseConvPlan(kind="down", device=dev, n_in=V, n_out=0, batch_size=batch_size, in_shape=shape,
+                          spatial_shape=out_shape, parent=torch.empty(V, dtype=torch.int32, device=dev),
+                          child_slot=torch.empty(V, dtype=torch.int32, device=dev))
+    if V > 0:
+        ctx, stream = _ctx_stream(coords)
+        lib = ctx.lib
+        h_shape = (C.c_int32 * 3)(*shape)
+        i64 = int(coords.dtype == torch.int64)
+        with torch.cuda.device(dev):
+            ws = _workspace(who, int(lib.gapro_spconv_down_plan_workspace_bytes(V)), dev, "%d rows are" % V)
+            d_hdr, h_hdr = _status_pair(dev, _lib.SPCONV_STATUS_WORDS, torch.int32)
+            ctx.check(lib.gapro_spconv_down_count(ctx.handle, stream, V, coords.data_ptr(), i64, h_shape, batch_size,
+                                                  ws.data_ptr(), ws.numel(), d_hdr.data_ptr(), h_hdr.data_ptr()))
+            status, flags, n_out = _host_read(dev, h_hdr)[:3]  # the call's one host read
+            if check:
+                _refuse(who, status, flags, _SPCONV_CAUSES)
+            plan.n_out = int(n_out)
+            plan.coords = torch.empty((plan.n_out, 4), dtype=torch.int32, device=dev)
+            plan.children = torch.empty((8, plan.n_out), dtype=torch.int32, device=dev)
+            d_status, _ = _status_pair(dev, _lib.SPCONV_STATUS_WORDS, torch.int32, read=False)
+            ctx.check(lib.gapro_spconv_down_fill(ctx.handle, stream, V, coords.data_ptr(), i64, h_shape, batch_size,
+                                                 plan.n_out, ws.data_ptr(), ws.numel(), _ptr(plan.coords),
+                                                 _ptr(plan.children), plan.parent.data_ptr(),
+                                                 plan.child_slot.data_ptr(), d_status.data_ptr(), None))
+    else:
+        plan.coords = torch.empty((0, 4), dtype=torch.int32, device=dev)
+        plan.children = torch.empty((8, 0), dtype=torch.int32, device=dev)
+    return plan
+
+
+# layer -> (plan kind, kernel edge, then per direction the table's (attribute, one-of attribute, reverse_k))
+_SPCONV_LAYERS = {"subm": ("subm", 3, ("neighbours", None), ("neighbours", None, 1)),
+                  "down": ("down", 2, ("children", None), ("parent", "child_slot", 0)),
+                  "inverse": ("down", 2, ("parent", "child_slot"), ("children", None, 0))}
+
+
+class _SparseConv(torch.autograd.Function):
+    """The one autograd node of the three layers, which ``_sparse_conv`` calls with checked arguments: one gather-GEMM
+    launch forward; backward the same kernel on the transposed table and the two stages of the weight gradient."""
+
+    @staticmethod
+    def forward(fctx, feats, weight, bias, plan, layer):
+        _, _, fwd, _ = _SPCONV_LAYERS[layer]
+        rows_in, rows_out = (plan.n_out, plan.n_in) if layer == "inverse" else (plan.n_in, plan.n_out)
+        Co, Ci = int(weight.shape[0]), int(weight.shape[-1])
+        K = weight.numel() // (Co * Ci)
+        dev = feats.device
+        feats, weight = feats.detach().contiguous(), weight.detach().contiguous()
+        bias = None if bias is None else bias.detach().contiguous()
+        fctx.plan, fctx.layer, fctx.dims, fctx.has_bias = plan, layer, (rows_out, rows_in, K, Ci, Co), bias is not None
+        fctx.save_for_backward(feats, weight)
+        out = torch.empty((rows_out, Co), dtype=torch.float32, device=dev)
+        if rows_out == 0:
+            return out
+        if rows_in == 0:  # no coarse row: bias alone
+            return out.zero_() if bias is None else out.copy_(bias.expand(rows_out, Co))
+        ctx, stream = _ctx_stream(feats)
+        with torch.cuda.device(dev):
+            ctx.check(ctx.lib.gapro_spconv_forward(ctx.handle, stream, rows_out, rows_in, K,
+                                                   getattr(plan, fwd[0]).data_ptr(),
+                                                   _ptr(getattr(plan, fwd[1])) if fwd[1] else None, Ci, Co,
+                                                   feats.data_ptr(), weight.data_ptr(), _ptr(bias), out.data_ptr()))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad_out):
+        feats, weight = fctx.saved_tensors
+        plan, layer = fctx.plan, fctx.layer
+        rows_out, rows_in, K, Ci, Co = fctx.dims
+        _, _, fwd, bwd = _SPCONV_LAYERS[layer]
+        need = fctx.needs_input_grad
+        dev = feats.device
+        grad_out = grad_out.to(dtype=torch.float32).contiguous()
+        g_feats = torch.empty((rows_in, Ci), dtype=torch.float32, device=dev) if need[0] else None
+        g_weight = torch.empty_like(weight) if need[1] else None
+        g_bias = torch.empty(Co, dtype=torch.float32, device=dev) if fctx.has_bias and need[2] else None
+        if rows_out == 0 or rows_in == 0:
+            for g in (g_feats, g_weight):
+                if g is not None:
+                    g.zero_()
+            if g_bias is not None:
+                g_bias.copy_(grad_out.sum(0)) if rows_out else g_bias.zero_()
+            return g_feats, g_weight, g_bias, None, None
+        ctx, stream = _ctx_stream(feats)
+        lib = ctx.lib
+        with torch.cuda.device(dev):
+            if g_feats is not None:
+                ctx.check(lib.gapro_spconv_backward_input(ctx.handle, stream, rows_in, rows_out, K,
+                                                          getattr(plan, bwd[0]).data_ptr(),
+                                                          _ptr(getattr(plan, bwd[1])) if bwd[1] else None, bwd[2], Ci,
+                                                          Co, grad_out.data_ptr(), weight.data_ptr(),
+                                                          g_feats.data_ptr()))
+            if g_weight is not None or g_bias is not None:
+                ws = _workspace("sparse convolution", int(lib.gapro_spconv_workspace_bytes(rows_out, K, Ci, Co)), dev)
+                ctx.check(lib.gapro_spconv_backward_weight(ctx.handle, stream, rows_out, rows_in, K,
+                                                           getattr(plan, fwd[0]).data_ptr(),
+                                                           _ptr(getattr(plan, fwd[1])) if fwd[1] else None, Ci, Co,
+                                                           feats.data_ptr(), grad_out.data_ptr(), ws.data_ptr(),
+                                                           ws.numel(), _ptr(g_weight), _ptr(g_bias)))
+        return g_feats, g_weight, g_bias, None, None
+
+
+def _sparse_conv(who, layer, feats, weight, plan, bias):
+    kind, edge, _, _ = _SPCONV_LAYERS[layer]
+    if not isinstance(plan, SparseConvPlan) or plan.kind != kind:
+        raise ValueError("%s: plan must be the SparseConvPlan of %s" % (who, "subm_plan" if kind == "subm"
+                                                                        else "downsample_plan"))
+    rows = plan.n_out if layer == "inverse" else plan.n_in
+    _float_arg(who, "feats", feats, ("V", "C_in"))
+    if int(feats.shape[0]) != rows:
+        raise ValueError("%s: feats has %d rows, the plan was built for %d" % (who, int(feats.shape[0]), rows))
+    Ci = int(feats.shape[1])
+    _float_arg(who, "weight", weight, ("C_out", edge, edge, edge, Ci))
+    Co = int(weight.shape[0])
+    if not 1 <= Ci <= _lib.SPCONV_MAX_CHANNELS or not 1 <= Co <= _lib.SPCONV_MAX_CHANNELS:
+        raise ValueError("%s: 1 .. %d channels are built; C_in = %d, C_out = %d"
+                         % (who, _lib.SPCONV_MAX_CHANNELS, Ci, Co))
+    if bias is not None:
+        _float_arg(who, "bias", bias, (Co,))
+    tensors = tuple(t for t in (feats, weight, bias) if t is not None)
+    _one_device(who, plan.device, tensors)
+    _need_device(*tensors)
+    cast = [t if t is None or t.dtype == torch.float32 else t.to(torch.float32) for t in (feats, weight, bias)]
+    out = _SparseConv.apply(cast[0], cast[1], cast[2], plan, layer)
+    return out if feats.dtype == torch.float32 else out.to(feats.dtype)
+
+
+def subm_conv3d(feats, weight, plan, bias=None):
+    """``spconv.SubMConv3d(C_in, C_out, kernel_size=3, padding=1)`` as a function: ``feats`` ``[V, C_in]`` in the row
+    order of the plan's ``coords``, ``weight`` ``[C_out, 3, 3, 3, C_in]`` (spconv 2.x's layout), ``bias`` ``[C_out]`` or
+    ``None``; returns ``[V, C_out]`` on the same rows.  ``y[r] = bias + sum_d W[:, d + 1, :] x[row(b_r, p_r + d)]``: the
+    dense cross-correlation ``conv3d(padding=1)`` read at the active sites.  Float64 inside, one rounding; float32, half
+    or bfloat16 tensors are computed from their float32 values and the result is cast back.  Differentiable in
+    ``feats``, ``weight`` and ``bias``.  A plan of another kind or row count is a ``ValueError``."""
+    return _sparse_conv("subm_conv3d", "subm", feats, weight, plan, bias)
+
+
+def sparse_conv3d(feats, weight, plan, bias=None):
+    """``spconv.SparseConv3d(C_in, C_out, kernel_size=2, stride=2)`` on a ``downsample_plan``: ``feats`` ``[plan.n_in,
+    C_in]``, ``weight`` ``[C_out, 2, 2, 2, C_in]``; returns ``[plan.n_out, C_out]`` on the rows of ``plan.coords``.
+    ``y[q] = bias + sum over the children of q of W[:, p_child & 1, :] x[child]``."""
+    return _sparse_conv("sparse_conv3d", "down", feats, weight, plan, bias)
+
+
+def sparse_inverse_conv3d(feats, weight, plan, bias=None):
+    """``spconv.SparseInverseConv3d(C_in, C_out, kernel_size=2)`` on the ``downsample_plan`` of the strided layer it
+    undoes: ``feats`` ``[plan.n_out, C_in]`` on the coarse rows, ``weight`` ``[C_out, 2, 2, 2, C_in]``; returns
+    ``[plan.n_in, C_out]`` on the strided layer's input rows.  ``y[i] = bias + W[:, p_i & 1, :] x[parent(i)]``; a row
+    without a parent gets ``bias`` alone."""
+    return _sparse_conv("sparse_inverse_conv3d", "inverse", feats, weight, plan, bias)

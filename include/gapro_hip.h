@@ -1728,6 +1728,95 @@ int gapro_dyco_backward(gapro_ctx* ctx, void* stream, int32_t n_batches, int32_t
                         float* d_grad_mask_features /* [N, C] or NULL */, float* d_grad_box_preds /* [N, 6] or NULL */);
 
 /* ------------------------------------------------------------------------------------------
+ * Sparse convolutions (csrc/spconv.hip).  The three spconv layers the U-Nets of both consumers are
+ * built from (ISBNet/isbnet/model/blocks.py:158-255, SPFormer/spformer/model/backbone.py:38-208), as functions of
+ * (features, weight, plan), and the plans ("rulebooks") they share.  spconv has no build for this GPU; that the kernel
+ * index and weight conventions below are spconv 2.x's rests on its documentation and on the reference's use of it, not
+ * on a run.
+ * The definitions.  coords is int32 or int64 [V, 4] with columns (batch, z, y, x), the rows unique, batch in [0, B) and
+ * (z, y, x) inside spatial_shape = (Dz, Dy, Dx).  A weight is f32[C_out, kz, ky, kx, C_in] (K = kz ky kx offsets,
+ * k = (kz, ky, kx) flattened), bias f32[C_out] or NULL.  row(b, p) is the row whose coordinates are (b, p), if any.
+ *   Submanifold, k = 3:   y[r] = bias + sum over d in {-1, 0, 1}^3 of W[:, d + 1, :] x[row(b_r, p_r + d)], over the
+ *       offsets whose voxel is active, in the same sample and inside [0, D).  The output rows are the input rows.
+ *       This is the dense cross-correlation conv3d(padding = 1) of the scattered grid, read at the active sites.
+ *   Strided, k = 2, stride 2, no padding:  the coarse voxel of a row is (b, z >> 1, y >> 1, x >> 1); a row whose coarse
+ *       coordinate reaches D_out = (D - 2) / 2 + 1 in any axis (the last slice of an odd extent; D_out = 0 for D = 1)
+ *       contributes to nothing.  y[q] = bias + sum over the children of q of W[:, p_child & 1, :] x[child].  COARSE ROWS
+ *       ARE NUMBERED BY THEIR FIRST CHILD IN ASCENDING INPUT ROW.
+ *   Inverse, k = 2, on a strided plan:  the output rows are the strided layer's INPUT rows;
+ *       y[i] = bias + W[:, p_i & 1, :] x[parent(i)]; a row without a parent gets bias alone.  This is the dense
+ *       conv_transpose3d(stride = 2) read at the fine active sites.
+ * Arithmetic: float64 from the float32 operands (FP64 MFMA), bias added last, one rounding on the store; no
+ * floating-point atomics; the order of every sum is fixed by the layout and, for the outputs and the input gradients,
+ * does not depend on the other rows of the call: two calls give equal bytes and a batch equals each of its samples
+ * alone.  Finite inputs are expected (an absent pair enters a tile's product as a zero).
+ * The plans.  gapro_spconv_subm_plan: neighbours int32[27][V], offset-major, -1 for "none"; no host read.
+ * gapro_spconv_down_count, ONE host read of the header {status, flags, n_out, 0}, gapro_spconv_down_fill with that
+ * n_out: coarse_coords int32[n_out, 4], children int32[8][n_out] (the child slot is (z & 1) 4 + (y & 1) 2 + (x & 1),
+ * -1 for "none"), parent int32[V] (-1 for a dropped row) and child_slot int32[V].  Status words {status, flags, ..}:
+ * a duplicate row, a coordinate outside spatial_shape and a batch index outside [0, B) set GAPRO_ERR_BAD_ARG and a
+ * flag; they are copied to h_*_pinned only when it is given.  A flagged row has no pairs.  A key packs (b, z + 1, y + 1,
+ * x + 1) over extents D + 2, so that a probe at -1 or at D is the key of no voxel of any sample; B (Dz + 2) (Dy + 2)
+ * (Dx + 2) >= 2^63 is refused.
+ * The convolutions take ONE table form: K offsets and, per output row and offset, an input row or -1 -- either
+ * d_table int32[K][rows_out] with d_k_of NULL, or "one of K": d_table int32[rows_out] and d_k_of int32[rows_out], the
+ * only pair of row r being (d_k_of[r], d_table[r]).  An entry outside [0, rows_in) is no pair.
+ *   layer      forward                      backward_input (rows_out = the layer's input rows)      backward_weight
+ *   subm       neighbours, K = 27           neighbours, reverse_k = 1 (nbrT[k] = nbr[26 - k])       neighbours
+ *   strided    children, K = 8              parent with child_slot, one of 8                        children
+ *   inverse    parent/child_slot, one of 8  children, K = 8                                         parent/child_slot
+ * backward_input is the forward kernel on the transposed table with the weights read transposed; c_in and c_out are
+ * the LAYER's in every call.  backward_weight: dW[k] = sum over rows of g[r] (x) x[table[k][r]] by FP64 MFMA with the
+ * rows as the contraction; chunks of gapro_spconv_chunk_rows rows go to float64 partials in the workspace
+ * (gapro_spconv_workspace_bytes, at most about GAPRO_SPCONV_PARTIAL_BYTES, a chunk never below
+ * GAPRO_SPCONV_MIN_CHUNK_ROWS rows) and a second kernel adds the chunks in ascending order and rounds once; d_grad_bias
+ * is the column sum of g by the same two stages.  A backward call whose outputs are all NULL launches nothing.  Every
+ * gradient given is written whole by plain stores.  1 <= C_in, C_out <= GAPRO_SPCONV_MAX_CHANNELS, any value.
+ * ---------------------------------------------------------------------------------------- */
+#define GAPRO_SPCONV_STATUS_WORDS 4
+#define GAPRO_SPCONV_FLAG_DUPLICATE 1
+#define GAPRO_SPCONV_FLAG_RANGE 2
+#define GAPRO_SPCONV_FLAG_BATCH 4
+#define GAPRO_SPCONV_FLAG_TABLE 8          /* a workspace that is not the count's, or more rows than table slots */
+#define GAPRO_SPCONV_MAX_ROWS (1LL << 30)
+#define GAPRO_SPCONV_MAX_CHANNELS 512
+#define GAPRO_SPCONV_CIN_CHUNK 32          /* contracted channels of one weight slice in LDS */
+#define GAPRO_SPCONV_MIN_CHUNK_ROWS 256
+#define GAPRO_SPCONV_PARTIAL_BYTES (64LL << 20)
+size_t gapro_spconv_subm_plan_workspace_bytes(int64_t n_rows);   /* 0: n_rows beyond the bounds */
+int gapro_spconv_subm_plan(gapro_ctx* ctx, void* stream, int64_t n_rows, const void* d_coords /* [V, 4] */,
+                           int32_t coords_i64, const int32_t* h_spatial_shape /* 3, host */, int32_t batch_size,
+                           void* d_workspace, size_t workspace_bytes, int32_t* d_neighbours /* [27][V] */,
+                           int32_t* d_status /* GAPRO_SPCONV_STATUS_WORDS */, int32_t* h_status_pinned /* or NULL */);
+size_t gapro_spconv_down_plan_workspace_bytes(int64_t n_rows);
+int gapro_spconv_down_count(gapro_ctx* ctx, void* stream, int64_t n_rows, const void* d_coords, int32_t coords_i64,
+                            const int32_t* h_spatial_shape, int32_t batch_size, void* d_workspace,
+                            size_t workspace_bytes, int32_t* d_header /* GAPRO_SPCONV_STATUS_WORDS */,
+                            int32_t* h_header_pinned /* or NULL */);
+int gapro_spconv_down_fill(gapro_ctx* ctx, void* stream, int64_t n_rows, const void* d_coords, int32_t coords_i64,
+                           const int32_t* h_spatial_shape, int32_t batch_size, int64_t n_out,
+                           const void* d_workspace /* the count's */, size_t workspace_bytes,
+                           int32_t* d_coarse_coords /* [n_out, 4] */, int32_t* d_children /* [8][n_out] */,
+                           int32_t* d_parent /* [V] */, int32_t* d_child_slot /* [V] */, int32_t* d_status,
+                           int32_t* h_status_pinned /* or NULL */);
+int64_t gapro_spconv_chunk_rows(int64_t rows_out, int32_t K, int32_t c_in, int32_t c_out);   /* 0: beyond the bounds */
+size_t gapro_spconv_workspace_bytes(int64_t rows_out, int32_t K, int32_t c_in, int32_t c_out);
+int gapro_spconv_forward(gapro_ctx* ctx, void* stream, int64_t rows_out, int64_t rows_in, int32_t K,
+                         const int32_t* d_table, const int32_t* d_k_of /* or NULL */, int32_t c_in, int32_t c_out,
+                         const float* d_x /* [rows_in, C_in] */, const float* d_weight /* [C_out, K, C_in] */,
+                         const float* d_bias /* [C_out] or NULL */, float* d_y /* [rows_out, C_out] */);
+int gapro_spconv_backward_input(gapro_ctx* ctx, void* stream, int64_t rows_out, int64_t rows_in, int32_t K,
+                                const int32_t* d_table_t, const int32_t* d_k_of /* or NULL */, int32_t reverse_k,
+                                int32_t c_in, int32_t c_out, const float* d_grad_y /* [rows_in, C_out] */,
+                                const float* d_weight, float* d_grad_x /* [rows_out, C_in] or NULL */);
+int gapro_spconv_backward_weight(gapro_ctx* ctx, void* stream, int64_t rows_out, int64_t rows_in, int32_t K,
+                                 const int32_t* d_table, const int32_t* d_k_of /* or NULL */, int32_t c_in,
+                                 int32_t c_out, const float* d_x /* [rows_in, C_in] */,
+                                 const float* d_grad_y /* [rows_out, C_out] */, void* d_workspace,
+                                 size_t workspace_bytes, float* d_grad_weight /* [C_out, K, C_in] or NULL */,
+                                 float* d_grad_bias /* [C_out] or NULL */);
+
+/* ------------------------------------------------------------------------------------------
  * Training sets of point-level fits (csrc/trainset.hip).  Replaces gaussian_process_utils.py:36-76 (fit_gp): a problem
  * is three lists of POINT indices, and its training set is built on the device, either by pooling each side's points
  * to superpoint means (:64-69) or by keeping the npoint_nearest points of each side nearest to the centroid of the
