@@ -568,6 +568,7 @@ DEBUG_SIGNATURES = {
                                             C.POINTER(C.c_float)]),
     "gapro_debug_wgloop": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_double)]),
     "gapro_debug_exact_sum": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "gapro_debug_scan": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

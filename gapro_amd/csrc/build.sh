@@ -7,7 +7,7 @@ set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 srcs=(ctx.hip devmem.hip feeder.hip partition.hip svgp_fit.hip svgp_fit_wg.hip svgp_fit_small.hip svgp_fit_wave.hip svgp_fit_large.hip svgp_fit_cluster.hip svgp_predict.hip point_refine.hip spp_vote.hip trainset.hip labels.hip eval_batch.hip eval_ap.hip consumer.hip inst_prep.hip spp_gt.hip proposals.hip spf_predict.hip query_sample.hip voxelize.hip spp_pool.hip dyco_head.hip spconv.hip match_cost.hip match_loss.hip spf_loss.hip point_loss.hip schedule.cpp pth_io.cc lsap.cc voxelize_host.cc)
 # libgapro_hip_debug.so: measurement / self-test entry points (include/gapro_hip_debug.h), never loaded by the product
-debug_srcs=(svgp_fit_debug.hip debug_peak.hip debug_exact.hip)
+debug_srcs=(svgp_fit_debug.hip debug_peak.hip debug_exact.hip debug_scan.hip)
 flags=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-pass-failed)
 
 build_lib() {  # $1 = object directory, $2 = output library, rest = extra flags

@@ -10,6 +10,7 @@
 #include "common.h"
 #include "exact_sum.h"
 #include "launch_util.h"
+#include "scan.h"
 #include "wave_reduce.h"
 
 #include <algorithm>
@@ -19,6 +20,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxStatBlocks = 1024;
 constexpr int kScanChunk = 2048;  // elements per block in the rank scan (256 threads x 8)
+static_assert(kThreads == kScanThreads, "the rank scan's kernels call block_exclusive");
 
 struct PrepareWorkspace {  // device layout, all offsets 16-byte aligned
   gapro_scene_header header;
@@ -119,26 +121,7 @@ __global__ __launch_bounds__(kThreads) void k_flags(const gapro_scene_task* __re
 }
 
 // ---- K3: exclusive scan of the flags -> dense ranks ---------------------------------------------
-__device__ inline unsigned block_exclusive_scan(unsigned v, unsigned* total) {
-  __shared__ unsigned wsum[kThreads / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned inc = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    unsigned t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  unsigned base = 0, tot = 0;
-  for (int j = 0; j < kThreads / 64; ++j) {
-    if (j < w) base += wsum[j];
-    tot += wsum[j];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
+// block_exclusive is scan.h's; the kernels keep their own shape: 8 consecutive flags a thread, scenes on blockIdx.y
 __global__ __launch_bounds__(kThreads) void k_scan_blocksum(const gapro_scene_task* __restrict__ tasks) {
   const gapro_scene_task& t = tasks[blockIdx.y];
   const PrepareWorkspace* ws = prep_ws(t);
@@ -153,8 +136,9 @@ __global__ __launch_bounds__(kThreads) void k_scan_blocksum(const gapro_scene_ta
     const long long i = base + (long long)threadIdx.x * (kScanChunk / kThreads) + j;
     if (i < range) s += flags[i];
   }
+  __shared__ unsigned wave_tot[kScanWaves];
   unsigned tot;
-  (void)block_exclusive_scan(s, &tot);
+  (void)block_exclusive(s, wave_tot, &tot);
   if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
@@ -166,12 +150,13 @@ __global__ __launch_bounds__(kThreads) void k_scan_offsets(const gapro_scene_tas
   if (ws->header.status != GAPRO_OK) return;
   const long long range = ws->header.spp_max - ws->header.spp_min + 1;
   const int nb = (int)((range + kScanChunk - 1) / kScanChunk);
+  __shared__ unsigned wave_tot[kScanWaves];
   unsigned carry = 0;
   for (int b0 = 0; b0 < nb; b0 += kThreads) {
     const int i = b0 + threadIdx.x;
     const unsigned v = i < nb ? bsum[i] : 0u;
     unsigned tot;
-    const unsigned ex = block_exclusive_scan(v, &tot);
+    const unsigned ex = block_exclusive(v, wave_tot, &tot);
     if (i < nb) bsum[i] = carry + ex;
     carry += tot;
   }
@@ -198,8 +183,9 @@ __global__ __launch_bounds__(kThreads) void k_scan_final(const gapro_scene_task*
     v[j] = i < range ? flags_to_rank[i] : 0u;
     s += v[j];
   }
+  __shared__ unsigned wave_tot[kScanWaves];
   unsigned tot;
-  unsigned ex = block_exclusive_scan(s, &tot) + bsum[blockIdx.x];
+  unsigned ex = block_exclusive(s, wave_tot, &tot) + bsum[blockIdx.x];
   for (int j = 0; j < per; ++j) {
     const long long i = base + (long long)threadIdx.x * per + j;
     if (i < range) flags_to_rank[i] = ex;

@@ -51,9 +51,12 @@ __device__ inline float sqdist(float dx, float dy, float dz) {
 
 // status[0] the code, status[1] the flags: a bad argument wins over a non-finite coordinate whatever the order
 __device__ inline void raise(int* status, int flag) {
-  atomicOr(status + 1, flag);
-  if (flag & GAPRO_QS_FLAG_NOT_FINITE) atomicCAS(status, (int)GAPRO_OK, (int)GAPRO_ERR_NOT_FINITE);
-  else atomicExch(status, (int)GAPRO_ERR_BAD_ARG);
+  if (flag & GAPRO_QS_FLAG_NOT_FINITE) {
+    atomicOr(status + 1, flag);
+    atomicCAS(status, (int)GAPRO_OK, (int)GAPRO_ERR_NOT_FINITE);
+  } else {
+    raise_bad_arg(status, flag);  // launch_util.h
+  }
 }
 
 struct Offsets {

@@ -6,6 +6,7 @@
 // workgroup (or wave) holds barriers (or shuffles): the returns in front of such a call must be uniform over it.
 #pragma once
 #include "common.h"
+#include "scan.h"
 #include "wave_reduce.h"
 
 #include <cmath>
@@ -191,11 +192,7 @@ __device__ inline unsigned scan_chunks(unsigned* c, int nchunks) {
   for (int j0 = 0; j0 < nchunks; j0 += 64) {  // uniform over the wave
     const int j = j0 + lane;
     const unsigned x = j < nchunks ? c[j] : 0u;
-    unsigned inc = x;
-    for (int off = 1; off < 64; off <<= 1) {
-      const unsigned y = __shfl_up(inc, off, 64);
-      if (lane >= off) inc += y;
-    }
+    const unsigned inc = wave_inclusive(x);
     if (j < nchunks) c[j] = before + inc - x;
     before += __shfl(inc, 63, 64);
   }

@@ -8,8 +8,8 @@
 //   k_sp_neighbours    a thread per (offset, row), rows fastest: nbr[27][V], the row at p + d or -1.
 //   k_sp_down_insert   the coarse key (b, z >> 1, y >> 1, x >> 1) into the table; per slot the first child by an integer
 //                      atomic minimum and the mask of child slots by an atomic or (a bit set twice is a duplicate row).
-//   k_sp_flag_sums / k_sp_scan_sums / k_sp_apply   a row is "first" iff its slot's minimum is the row; the exclusive scan
-//                      of those flags numbers the coarse rows by their first child in ascending input row.
+//   scan_enqueue       a row is "first" iff its slot's minimum is the row; the exclusive scan of those flags (scan.h,
+//                      three launches) numbers the coarse rows by their first child in ascending input row.
 //   k_sp_down_fill     coarse_coords, children[8][V_c], parent[V], child_slot[V].
 // The convolutions, all three layers and their input gradients through ONE kernel:
 //   k_spconv<NB>       a workgroup of four waves takes 64 output rows, a wave 16 of them, and 16 NB output channels,
@@ -29,6 +29,7 @@
 #include "common.h"
 #include "launch_util.h"
 #include "mfma64.h"
+#include "scan.h"
 #include "voxel_hash.h"
 
 #include <cstdint>
@@ -44,7 +45,6 @@ using gapro_mfma::unrotate;
 constexpr int kThreads = 256, kWaves = 4, kTile = 16;
 constexpr int kRowsWg = kWaves * kTile;            // output rows of a k_spconv workgroup
 constexpr int kChunkC = GAPRO_SPCONV_CIN_CHUNK;    // input channels of one weight slice in LDS
-constexpr int kScanItems = 4, kScanBlock = kThreads * kScanItems;
 constexpr int kGridCap = 1 << 16;
 constexpr long long kMaxRows = GAPRO_SPCONV_MAX_ROWS;
 constexpr int kMaxC = GAPRO_SPCONV_MAX_CHANNELS;
@@ -54,11 +54,6 @@ static_assert(kChunkC == 32, "a lane fetches two float4 of a chunk");
 
 typedef unsigned long long u64;
 constexpr u64 kEmptyKey = ~0ULL;
-
-__device__ inline void raise(int* status, int flag) {
-  atomicOr(status + 1, flag);
-  atomicExch(status, (int)GAPRO_ERR_BAD_ARG);
-}
 
 // ---- plans ---------------------------------------------------------------------------------------------------------------
 struct Geo {
@@ -77,11 +72,11 @@ __device__ inline bool read_row(const Geo& g, long long i, long long (&p)[4], in
 #pragma unroll
   for (int c = 0; c < 4; ++c) p[c] = coord_at(g, i, c);
   if (p[0] < 0 || p[0] >= g.B) {
-    raise(status, GAPRO_SPCONV_FLAG_BATCH);
+    raise_bad_arg(status, GAPRO_SPCONV_FLAG_BATCH);
     return false;
   }
   if (p[1] < 0 || p[1] >= g.D[0] || p[2] < 0 || p[2] >= g.D[1] || p[3] < 0 || p[3] >= g.D[2]) {
-    raise(status, GAPRO_SPCONV_FLAG_RANGE);
+    raise_bad_arg(status, GAPRO_SPCONV_FLAG_RANGE);
     return false;
   }
   return true;
@@ -127,8 +122,8 @@ __global__ __launch_bounds__(kThreads) void k_sp_insert(Geo g, u64* keys, int* _
     if (!read_row(g, i, p, status)) continue;
     bool fresh = false;
     const long long s = claim(keys, mask, fine_key(g, p[0], p[1], p[2], p[3]), &fresh);
-    if (s < 0) raise(status, GAPRO_SPCONV_FLAG_TABLE);
-    else if (!fresh) raise(status, GAPRO_SPCONV_FLAG_DUPLICATE);
+    if (s < 0) raise_bad_arg(status, GAPRO_SPCONV_FLAG_TABLE);
+    else if (!fresh) raise_bad_arg(status, GAPRO_SPCONV_FLAG_DUPLICATE);
     else vals[s] = (int)i;  // read by the next kernel only
   }
 }
@@ -167,11 +162,11 @@ __global__ __launch_bounds__(kThreads) void k_sp_down_insert(Geo g, u64* keys, i
         bool fresh = false;
         const long long s = claim(keys, mask, coarse_key(g, p[0], z, y, x), &fresh);
         if (s < 0) {
-          raise(status, GAPRO_SPCONV_FLAG_TABLE);
+          raise_bad_arg(status, GAPRO_SPCONV_FLAG_TABLE);
         } else {
           atomicMin(first + s, (int)i);
           const int bit = 1 << child_of(p);
-          if (atomicOr(child_mask + s, bit) & bit) raise(status, GAPRO_SPCONV_FLAG_DUPLICATE);
+          if (atomicOr(child_mask + s, bit) & bit) raise_bad_arg(status, GAPRO_SPCONV_FLAG_DUPLICATE);
           mine = (int)s;
         }
       }
@@ -180,81 +175,21 @@ __global__ __launch_bounds__(kThreads) void k_sp_down_insert(Geo g, u64* keys, i
   }
 }
 
-__device__ inline bool is_first(const int* __restrict__ first, const int* __restrict__ slot, long long i) {
-  const int s = slot[i];
-  return s >= 0 && first[s] == (int)i;
-}
+// the scan's value: is row i (< n) the first child of its coarse voxel
+struct IsFirst {
+  const int* __restrict__ first;
+  const int* __restrict__ slot;
+  __device__ int operator()(long long i) const {
+    const int s = slot[i];
+    return (s >= 0 && first[s] == (int)i) ? 1 : 0;
+  }
+};
 
-__global__ __launch_bounds__(kThreads) void k_sp_flag_sums(const int* __restrict__ first, const int* __restrict__ slot,
-                                                           long long n, int* __restrict__ block_sums) {
-  __shared__ int total;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * kScanBlock;
-  int mine = 0;
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    const long long i = base + j * kThreads + threadIdx.x;
-    mine += (i < n && is_first(first, slot, i)) ? 1 : 0;
-  }
-  atomicAdd(&total, mine);  // integers: any order
-  __syncthreads();
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-
-// every thread's value -> the sum of the values of the threads before it in the workgroup; *all: the workgroup's sum
-__device__ inline int block_exclusive(int v, int* wave_tot /* [kWaves] shared */, int* all) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  __syncthreads();  // the slots are free again
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  int before = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int t = wave_tot[w];
-    before += w < wave ? t : 0;
-    sum += t;
-  }
-  *all = sum;
-  return before + incl - v;
-}
-
-__global__ __launch_bounds__(kThreads) void k_sp_scan_sums(int* __restrict__ block_sums, long long n_blocks,
-                                                           int* header) {
-  __shared__ int wave_tot[kWaves];
-  int running = 0;
-  for (long long b0 = 0; b0 < n_blocks; b0 += kThreads) {  // uniform
-    const long long b = b0 + threadIdx.x;
-    const int v = b < n_blocks ? block_sums[b] : 0;
-    int all;
-    const int before = block_exclusive(v, wave_tot, &all);
-    if (b < n_blocks) block_sums[b] = running + before;
-    running += all;
-  }
-  if (threadIdx.x == 0) header[2] = running;
-}
-
-__global__ __launch_bounds__(kThreads) void k_sp_apply(const int* __restrict__ first, const int* __restrict__ slot,
-                                                       long long n, const int* __restrict__ block_sums,
-                                                       int* __restrict__ rank) {
-  __shared__ int wave_tot[kWaves];
-  const long long base = (long long)blockIdx.x * kScanBlock;
-  int running = block_sums[blockIdx.x];
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {  // 256 consecutive rows at a time, in index order
-    const long long i = base + j * kThreads + threadIdx.x;
-    const bool f = i < n && is_first(first, slot, i);
-    int all;
-    const int r = running + block_exclusive(f ? 1 : 0, wave_tot, &all);
-    running += all;
-    if (i < n) rank[i] = r;
-  }
-}
+// the scan's result: the firsts before row i
+struct EmitRank {
+  int* __restrict__ rank;
+  __device__ void operator()(long long i, int r, int) const { rank[i] = r; }
+};
 
 __global__ __launch_bounds__(kThreads) void k_sp_down_fill(Geo g, const int* __restrict__ first,
                                                            const int* __restrict__ slot, const int* __restrict__ rank,
@@ -272,7 +207,7 @@ __global__ __launch_bounds__(kThreads) void k_sp_down_fill(Geo g, const int* __r
       const int f = first[s];
       q = (f >= 0 && f < g.n) ? rank[f] : -1;
       if (q < 0 || q >= n_out) {  // not the count's workspace, or not its n_out
-        raise(status, GAPRO_SPCONV_FLAG_TABLE);
+        raise_bad_arg(status, GAPRO_SPCONV_FLAG_TABLE);
         q = -1;
       }
     }
@@ -297,29 +232,23 @@ struct PlanWs {
   int* child_mask;  // [slots] down
   int* slot;        // [n] down: the slot of a row's coarse voxel; -1: in none
   int* rank;        // [n] down: firsts before the row
-  int* block_sums;  // [ceil(n / kScanBlock)]
+  int* block_sums;  // [scan_blocks(n)]
   size_t bytes;
 };
 
 PlanWs plan_layout(void* base, long long n, bool down) {
   PlanWs w{};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void* q = p + off;
-    off += align_up(bytes, 256);
-    return q;
-  };
+  Carver c(base);
   const size_t slots = (size_t)gapro_vox_slots(n);
-  w.keys = (u64*)take(slots * sizeof(u64));
-  w.vals = (int*)take(slots * sizeof(int));
+  w.keys = c.take<u64>(slots);
+  w.vals = c.take<int>(slots);
   if (down) {
-    w.child_mask = (int*)take(slots * sizeof(int));
-    w.slot = (int*)take((size_t)n * sizeof(int));
-    w.rank = (int*)take((size_t)n * sizeof(int));
-    w.block_sums = (int*)take((size_t)((n + kScanBlock - 1) / kScanBlock) * sizeof(int));
+    w.child_mask = c.take<int>(slots);
+    w.slot = c.take<int>((size_t)n);
+    w.rank = c.take<int>((size_t)n);
+    w.block_sums = c.take<int>((size_t)scan_blocks(n));
   }
-  w.bytes = off;
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -623,18 +552,14 @@ int gapro_spconv_down_count(gapro_ctx* ctx, void* stream_, int64_t n_rows, const
   hipStream_t stream = (hipStream_t)stream_;
   const PlanWs w = plan_layout(d_workspace, n_rows, true);
   const u64 slots = (u64)gapro_vox_slots(n_rows);
-  const long long n_blocks = (n_rows + kScanBlock - 1) / kScanBlock;
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(d_header, 0, GAPRO_SPCONV_STATUS_WORDS * sizeof(int32_t), stream));
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(w.keys, 0xff, (size_t)slots * sizeof(u64), stream));   // kEmptyKey
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(w.vals, 0x7f, (size_t)slots * sizeof(int), stream));   // above every row
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(w.child_mask, 0, (size_t)slots * sizeof(int), stream));
   hipLaunchKernelGGL(k_sp_down_insert, dim3(grid_for(n_rows, 1, kGridCap)), dim3(kThreads), 0, stream, g, w.keys,
                      w.vals, w.child_mask, slots - 1, w.slot, (int*)d_header);
-  hipLaunchKernelGGL(k_sp_flag_sums, dim3((unsigned)n_blocks), dim3(kThreads), 0, stream, w.vals, w.slot,
-                     (long long)n_rows, w.block_sums);
-  hipLaunchKernelGGL(k_sp_scan_sums, dim3(1), dim3(kThreads), 0, stream, w.block_sums, n_blocks, (int*)d_header);
-  hipLaunchKernelGGL(k_sp_apply, dim3((unsigned)n_blocks), dim3(kThreads), 0, stream, w.vals, w.slot,
-                     (long long)n_rows, w.block_sums, w.rank);
+  scan_enqueue(stream, IsFirst{w.vals, w.slot}, EmitRank{w.rank}, (long long)n_rows, w.block_sums,
+               (int*)d_header + 2);
   GAPRO_LAUNCH_CHECK(ctx);
   if (h_header_pinned)
     GAPRO_HIP_CHECK(ctx, hipMemcpyAsync(h_header_pinned, d_header, GAPRO_SPCONV_STATUS_WORDS * sizeof(int32_t),

@@ -7,7 +7,7 @@
 // a stable LSD radix sort of (key, point) by 8-bit digits, ceil(bits(n_keys) / 8) passes, a pass being
 //   k_spp_hist      a workgroup a tile of kTile points: the tile's 256 digit counts (integer LDS atomics), stored
 //                   bin-major so that ONE exclusive scan of the whole array is the place of every (bin, tile) run;
-//   k_spp_scan_sums_of / k_spp_scan_sums / k_spp_scan_apply   that scan, the three-launch pattern of voxelize.hip;
+//   scan_enqueue    that scan, in place (scan.h, three launches);
 //   k_spp_scatter   the tile again, 256 points at a time in point order: a point's rank among the equal digits of its
 //                   wave by eight ballots, the waves' bin counts in LDS, the running place of each bin.
 // k_spp_offsets   a thread a key: the lower bound of the key in the sorted keys, by bisection.
@@ -16,6 +16,8 @@
 // The pooling (gapro_spp_pool_forward / _backward): a thread per output element, see k_spp_forward.
 #include "common.h"
 #include "launch_util.h"
+#include "scan.h"
+#include "wave_reduce.h"
 
 #include <cstdint>
 
@@ -27,51 +29,18 @@ constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kBins = 256;                          // an 8-bit digit
 constexpr int kTileChunks = 16;                     // chunks of kThreads points in a tile
 constexpr int kTile = kThreads * kTileChunks;       // GAPRO_SPP_SORT_TILE
-constexpr int kScanItems = 4;
-constexpr int kScanBlock = kThreads * kScanItems;
 constexpr int kGridCap = 1 << 16;
 constexpr int kAhead = 8;                          // gathered loads in flight per thread of the pooling kernels
 constexpr long long kMaxIndex = 0x7fffffffLL;
 constexpr long long kMaxKeys = GAPRO_SPP_MAX_SEGMENTS;
 static_assert(kTile == GAPRO_SPP_SORT_TILE, "the header states the tile");
 static_assert(kBins == kThreads, "a thread a bin in the sort kernels");
+static_assert(kThreads == kScanThreads, "k_spp_batch_scan calls block_exclusive");
 
 typedef unsigned long long u64;
 
 __device__ inline long long load_index(const void* p, int is64, long long i) {
   return is64 ? ((const long long*)p)[i] : (long long)((const int*)p)[i];
-}
-
-__device__ inline int wave_or(int v) {
-  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ inline int wave_add(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// every thread's value -> the sum of the values of the threads before it in the workgroup; *all: the workgroup's sum
-__device__ inline int block_exclusive(int v, int* wave_tot /* [kWaves] shared */, int* all) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  __syncthreads();  // the slots are free again
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  int before = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int t = wave_tot[w];
-    before += w < wave ? t : 0;
-    sum += t;
-  }
-  *all = sum;
-  return before + incl - v;
 }
 
 struct KeyArgs {
@@ -101,10 +70,7 @@ __global__ __launch_bounds__(kThreads) void k_spp_keys(KeyArgs a) {
       a.vals[i] = (int)i;
     }
     flag = wave_or(flag);
-    if ((threadIdx.x & 63) == 0 && flag) {
-      atomicOr(a.status + 1, flag);
-      atomicExch(a.status, (int)GAPRO_ERR_BAD_ARG);
-    }
+    if ((threadIdx.x & 63) == 0 && flag) raise_bad_arg(a.status, flag);
   }
 }
 
@@ -121,54 +87,6 @@ __global__ __launch_bounds__(kThreads) void k_spp_hist(const unsigned* __restric
   }
   __syncthreads();
   hist[(long long)threadIdx.x * n_tiles + blockIdx.x] = bins[threadIdx.x];
-}
-
-__global__ __launch_bounds__(kThreads) void k_spp_scan_sums_of(const int* __restrict__ v, long long n,
-                                                               int* __restrict__ block_sums) {
-  __shared__ int total;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * kScanBlock;
-  int mine = 0;
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    const long long i = base + j * kThreads + threadIdx.x;
-    mine += i < n ? v[i] : 0;
-  }
-  mine = wave_add(mine);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&total, mine);
-  __syncthreads();
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-
-// one workgroup: the sums become the totals before each block
-__global__ __launch_bounds__(kThreads) void k_spp_scan_sums(int* __restrict__ block_sums, long long n_blocks) {
-  __shared__ int wave_tot[kWaves];
-  int running = 0;
-  for (long long b0 = 0; b0 < n_blocks; b0 += kThreads) {  // uniform
-    const long long b = b0 + threadIdx.x;
-    const int v = b < n_blocks ? block_sums[b] : 0;
-    int all;
-    const int before = block_exclusive(v, wave_tot, &all);
-    if (b < n_blocks) block_sums[b] = running + before;
-    running += all;
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void k_spp_scan_apply(int* __restrict__ v, long long n,
-                                                             const int* __restrict__ block_sums) {
-  __shared__ int wave_tot[kWaves];
-  const long long base = (long long)blockIdx.x * kScanBlock;
-  int running = block_sums[blockIdx.x];
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {  // 256 consecutive entries at a time, in order
-    const long long i = base + j * kThreads + threadIdx.x;
-    const int x = i < n ? v[i] : 0;
-    int all;
-    const int before = block_exclusive(x, wave_tot, &all);
-    if (i < n) v[i] = running + before;
-    running += all;
-  }
 }
 
 // The places of a tile's points: `place[bin]` starts at the scanned count of (bin, tile) and runs through the tile in
@@ -446,28 +364,22 @@ struct SortWs {
   unsigned *keys_a, *keys_b;  // [n]
   int* vals;                  // [n]
   int* hist;                  // [256 tiles]
-  int* block_sums;            // [ceil(256 tiles / kScanBlock)]
+  int* block_sums;            // [scan_blocks(256 tiles)]
   int* batch_count;           // [n_batches]
   size_t bytes;
 };
 
 SortWs ws_layout(void* base, long long n, long long n_batches) {
   SortWs w{};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t count) {
-    void* q = p + off;
-    off += align_up(count * sizeof(int), 256);
-    return q;
-  };
+  Carver c(base);
   const long long n_tiles = (n + kTile - 1) / kTile, cells = n_tiles * kBins;
-  w.keys_a = (unsigned*)take((size_t)n);
-  w.keys_b = (unsigned*)take((size_t)n);
-  w.vals = (int*)take((size_t)n);
-  w.hist = (int*)take((size_t)cells);
-  w.block_sums = (int*)take((size_t)((cells + kScanBlock - 1) / kScanBlock));
-  w.batch_count = (int*)take((size_t)(n_batches > 0 ? n_batches : 1));
-  w.bytes = off;
+  w.keys_a = c.take<unsigned>((size_t)n);
+  w.keys_b = c.take<unsigned>((size_t)n);
+  w.vals = c.take<int>((size_t)n);
+  w.hist = c.take<int>((size_t)cells);
+  w.block_sums = c.take<int>((size_t)scan_blocks(cells));
+  w.batch_count = c.take<int>((size_t)(n_batches > 0 ? n_batches : 1));
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -475,7 +387,6 @@ SortWs ws_layout(void* base, long long n, long long n_batches) {
 int csr_by_key(gapro_ctx* ctx, hipStream_t stream, const SortWs& w, KeyArgs ka, long long n_keys, int* off, int* pts,
                int* counts) {
   const long long n = ka.n, n_tiles = (n + kTile - 1) / kTile, cells = n_tiles * kBins;
-  const long long scan_blocks = (cells + kScanBlock - 1) / kScanBlock;
   const int passes = key_passes(n_keys);
   // the values alternate between the workspace and pts and end in pts
   unsigned *k_in = w.keys_a, *k_out = w.keys_b;
@@ -486,11 +397,7 @@ int csr_by_key(gapro_ctx* ctx, hipStream_t stream, const SortWs& w, KeyArgs ka, 
   for (int pass = 0; pass < passes; ++pass) {
     const int shift = 8 * pass;
     hipLaunchKernelGGL(k_spp_hist, dim3((unsigned)n_tiles), dim3(kThreads), 0, stream, k_in, n, shift, n_tiles, w.hist);
-    hipLaunchKernelGGL(k_spp_scan_sums_of, dim3((unsigned)scan_blocks), dim3(kThreads), 0, stream, w.hist, cells,
-                       w.block_sums);
-    hipLaunchKernelGGL(k_spp_scan_sums, dim3(1), dim3(kThreads), 0, stream, w.block_sums, scan_blocks);
-    hipLaunchKernelGGL(k_spp_scan_apply, dim3((unsigned)scan_blocks), dim3(kThreads), 0, stream, w.hist, cells,
-                       w.block_sums);
+    scan_enqueue(stream, ScanFrom{w.hist}, ScanInto{w.hist}, cells, w.block_sums, nullptr);
     hipLaunchKernelGGL(k_spp_scatter, dim3((unsigned)n_tiles), dim3(kThreads), 0, stream, k_in, v_in, n, shift,
                        n_tiles, w.hist, k_out, v_out);
     unsigned* tk = k_in;

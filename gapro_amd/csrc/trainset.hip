@@ -13,6 +13,7 @@
 #include "common.h"
 #include "exact_sum.h"
 #include "launch_util.h"
+#include "scan.h"
 #include "wave_reduce.h"
 
 #include <algorithm>
@@ -23,6 +24,7 @@ constexpr int kThreads = 256;
 constexpr int kSelThreads = 1024;  // one workgroup per (problem, side) in the selection kernel
 constexpr int kMaxNearest = GAPRO_TRAINSET_MAX_NEAREST;  // survivors are ordered in LDS
 static_assert(kSelThreads == kMaxNearest, "k_ts_nearest orders one survivor per thread");
+static_assert(kThreads == kScanThreads, "k_ts_rank calls block_exclusive");
 
 static_assert(sizeof(gapro_trainset_desc) == 40, "gapro_trainset_desc layout is part of the ABI (ctypes mirror)");
 
@@ -74,26 +76,14 @@ __global__ __launch_bounds__(kThreads) void k_ts_mark(const gapro_trainset_desc*
 // marks -> 1 + rank among the side's superpoints (0 = not in the side); counts[side] = their number
 __global__ __launch_bounds__(kThreads) void k_ts_rank(int n_spps, int* __restrict__ marks, int* __restrict__ counts) {
   int* __restrict__ mk = marks + (long long)blockIdx.x * n_spps;
-  __shared__ int wsum[kThreads / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __shared__ int wave_tot[kScanWaves];
   int carry = 0;
-  for (int b0 = 0; b0 < n_spps; b0 += kThreads) {
+  for (int b0 = 0; b0 < n_spps; b0 += kThreads) {  // uniform
     const int i = b0 + threadIdx.x;
     const int v = i < n_spps ? mk[i] : 0;
-    int inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int j = 0; j < kThreads / 64; ++j) {
-      if (j < w) base += wsum[j];
-      tot += wsum[j];
-    }
-    __syncthreads();
-    if (i < n_spps) mk[i] = v ? carry + base + inc : 0;
+    int tot;
+    const int before = block_exclusive(v, wave_tot, &tot);
+    if (i < n_spps) mk[i] = v ? carry + before + v : 0;
     carry += tot;
   }
   if (threadIdx.x == 0) counts[blockIdx.x] = carry;

@@ -5,9 +5,8 @@
 //                claimed by compare-and-swap from empty, an occupant compared by reading its coordinate row, an equal
 //                key lowers the slot with an atomic minimum -- so a slot ends as its voxel's first point whatever the
 //                schedule.  The probe loop is bounded by the table.
-// k_vox_flag_sums / k_vox_scan_sums / k_vox_apply   a point is "first" iff its slot holds it; the exclusive scan of
-//                those flags (a sum per 1024 points, one workgroup over the sums, the scan inside each 1024) is the voxel
-//                number.  Three launches: no workgroup waits for another.
+// scan_enqueue   a point is "first" iff its slot holds it; the exclusive scan of those flags (scan.h, three launches) is
+//                the voxel number, stored as rank[i] and, for a first, as first_of[rank]; the total is header[2].
 // k_vox_assign   input_map, and per voxel an integer atomic count whose return value is the point's place in its row
 //                (any order: the fill sorts), the last point by an atomic maximum (mode 2), max_active by one atomic
 //                maximum a wave.
@@ -18,6 +17,7 @@
 // The pooling (gapro_voxel_pool_forward / _backward): a thread per output element (v, c), see k_pool_forward.
 #include "common.h"
 #include "launch_util.h"
+#include "scan.h"
 #include "voxel_hash.h"
 #include "wave_reduce.h"
 
@@ -27,9 +27,7 @@
 
 namespace {
 
-constexpr int kThreads = 256, kWaves = kThreads / 64;
-constexpr int kScanItems = 4;                         // points of a thread in the scan kernels
-constexpr int kScanBlock = kThreads * kScanItems;     // points of a workgroup there
+constexpr int kThreads = 256;
 constexpr int kGridCap = 1 << 16;
 constexpr int kEmpty = -1;
 constexpr long long kMaxIndex = 0x7fffffffLL;
@@ -37,11 +35,6 @@ constexpr int kMaxActive = GAPRO_VOXELIZE_MAX_ACTIVE;
 static_assert(kMaxActive % kThreads == 0, "k_vox_rank_wg gives every thread the same number of entries");
 
 typedef unsigned long long u64;
-
-__device__ inline void raise(int* status, int flag) {
-  atomicOr(status + 1, flag);
-  atomicExch(status, (int)GAPRO_ERR_BAD_ARG);
-}
 
 // the workspace of n points; every part is aligned to 256 bytes
 struct VoxWs {
@@ -52,28 +45,22 @@ struct VoxWs {
   int* count;       // [n] by voxel
   int* pos;         // [n] the place the point claimed in its row
   int* last;        // [n] by voxel: its last point (mode 2)
-  int* block_sums;  // [ceil(n / kScanBlock)]
+  int* block_sums;  // [scan_blocks(n)]
   size_t bytes;
 };
 
 VoxWs ws_layout(void* base, long long n) {
   VoxWs w{};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t count) {
-    int* q = (int*)(p + off);
-    off += align_up(count * sizeof(int), 256);
-    return q;
-  };
-  w.table = take((size_t)gapro_vox_slots(n));
-  w.slot = take((size_t)n);
-  w.rank = take((size_t)n);
-  w.first_of = take((size_t)n);
-  w.count = take((size_t)n);
-  w.pos = take((size_t)n);
-  w.last = take((size_t)n);
-  w.block_sums = take((size_t)((n + kScanBlock - 1) / kScanBlock));
-  w.bytes = off;
+  Carver c(base);
+  w.table = c.take<int>((size_t)gapro_vox_slots(n));
+  w.slot = c.take<int>((size_t)n);
+  w.rank = c.take<int>((size_t)n);
+  w.first_of = c.take<int>((size_t)n);
+  w.count = c.take<int>((size_t)n);
+  w.pos = c.take<int>((size_t)n);
+  w.last = c.take<int>((size_t)n);
+  w.block_sums = c.take<int>((size_t)scan_blocks(n));
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -95,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void k_vox_insert(const long long* __rest
     for (int c = 0; c < kCols; ++c) key[c] = coords[kCols * i + c];
     int mine = -1;
     if (kCols == 4 && key[0] < 0) {
-      raise(status, GAPRO_VOXELIZE_FLAG_BATCH);
+      raise_bad_arg(status, GAPRO_VOXELIZE_FLAG_BATCH);
     } else {
       u64 s = gapro_vox_hash((const int64_t*)key, kCols) & mask;
       for (u64 probe = 0; probe <= mask; ++probe, s = (s + 1) & mask) {  // bounded by the table
@@ -111,91 +98,31 @@ __global__ __launch_bounds__(kThreads) void k_vox_insert(const long long* __rest
           break;
         }
       }
-      if (mine < 0) raise(status, GAPRO_VOXELIZE_FLAG_TABLE);  // a table with more points than slots: not built
+      if (mine < 0) raise_bad_arg(status, GAPRO_VOXELIZE_FLAG_TABLE);  // a table with more points than slots: not built
     }
     slot[i] = mine;
   }
 }
 
-// is point i (< n) the first of its voxel
-__device__ inline bool is_first(const int* __restrict__ table, const int* __restrict__ slot, long long i) {
-  const int s = slot[i];
-  return s >= 0 && table[s] == (int)i;
-}
-
-__global__ __launch_bounds__(kThreads) void k_vox_flag_sums(const int* __restrict__ table, const int* __restrict__ slot,
-                                                            long long n, int* __restrict__ block_sums) {
-  __shared__ int total;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * kScanBlock;
-  int mine = 0;
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {
-    const long long i = base + j * kThreads + threadIdx.x;
-    mine += (i < n && is_first(table, slot, i)) ? 1 : 0;
+// the scan's value: is point i (< n) the first of its voxel
+struct IsFirst {
+  const int* __restrict__ table;
+  const int* __restrict__ slot;
+  __device__ int operator()(long long i) const {
+    const int s = slot[i];
+    return (s >= 0 && table[s] == (int)i) ? 1 : 0;
   }
-  mine = wave_sum(mine);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&total, mine);
-  __syncthreads();
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
+};
 
-// every thread's value -> the sum of the values of the threads before it in the workgroup; *all: the workgroup's sum
-__device__ inline int block_exclusive(int v, int* wave_tot /* [kWaves] shared */, int* all) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  __syncthreads();  // the slots are free again
-  if (lane == 63) wave_tot[wave] = incl;
-  __syncthreads();
-  int before = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int t = wave_tot[w];
-    before += w < wave ? t : 0;
-    sum += t;
-  }
-  *all = sum;
-  return before + incl - v;
-}
-
-// one workgroup: the sums become the firsts before each 1024 points; the total is the number of voxels
-__global__ __launch_bounds__(kThreads) void k_vox_scan_sums(int* __restrict__ block_sums, long long n_blocks,
-                                                            int* header) {
-  __shared__ int wave_tot[kWaves];
-  int running = 0;
-  for (long long b0 = 0; b0 < n_blocks; b0 += kThreads) {  // uniform
-    const long long b = b0 + threadIdx.x;
-    const int v = b < n_blocks ? block_sums[b] : 0;
-    int all;
-    const int before = block_exclusive(v, wave_tot, &all);
-    if (b < n_blocks) block_sums[b] = running + before;
-    running += all;
-  }
-  if (threadIdx.x == 0) header[2] = running;
-}
-
-__global__ __launch_bounds__(kThreads) void k_vox_apply(const int* __restrict__ table, const int* __restrict__ slot,
-                                                        long long n, const int* __restrict__ block_sums,
-                                                        int* __restrict__ rank, int* __restrict__ first_of) {
-  __shared__ int wave_tot[kWaves];
-  const long long base = (long long)blockIdx.x * kScanBlock;
-  int running = block_sums[blockIdx.x];
-#pragma unroll
-  for (int j = 0; j < kScanItems; ++j) {  // 256 consecutive points at a time, in index order
-    const long long i = base + j * kThreads + threadIdx.x;
-    const bool first = i < n && is_first(table, slot, i);
-    int all;
-    const int r = running + block_exclusive(first ? 1 : 0, wave_tot, &all);
-    running += all;
-    if (i < n) rank[i] = r;
+// the scan's result: the firsts before point i are its rank, and a first's rank is its voxel
+struct EmitRank {
+  int* __restrict__ rank;
+  int* __restrict__ first_of;
+  __device__ void operator()(long long i, int r, int first) const {
+    rank[i] = r;
     if (first) first_of[r] = (int)i;  // r < the number of voxels <= n
   }
-}
+};
 
 __global__ __launch_bounds__(kThreads) void k_vox_assign(const int* __restrict__ table, const int* __restrict__ slot,
                                                          const int* __restrict__ rank, long long n, int mode,
@@ -212,7 +139,7 @@ __global__ __launch_bounds__(kThreads) void k_vox_assign(const int* __restrict__
         v = rank[table[s]];  // the slot holds the voxel's first point, whose rank is the voxel's number
         p = atomicAdd(count + v, 1);
         if (mode == 2) atomicMax(last + v, (int)i);
-        if (mode == 0 && p > 0) raise(header, GAPRO_VOXELIZE_FLAG_DUPLICATE);
+        if (mode == 0 && p > 0) raise_bad_arg(header, GAPRO_VOXELIZE_FLAG_DUPLICATE);
         held = p + 1;
       }
       input_map[i] = v;
@@ -241,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void k_vox_coords(FillArgs a) {
     const int c = (int)(e - v * a.cols);
     const long long f = a.first_of[v];
     if (f < 0 || f >= a.n) {
-      raise(a.status, GAPRO_VOXELIZE_FLAG_TABLE);
+      raise_bad_arg(a.status, GAPRO_VOXELIZE_FLAG_TABLE);
       a.out_coords[e] = 0;
     } else {
       a.out_coords[e] = a.coords[f * a.cols + c];
@@ -266,14 +193,14 @@ __global__ __launch_bounds__(kThreads) void k_vox_scatter(FillArgs a) {
     const long long v = a.input_map[i];
     const int p = a.pos[i];
     if (v < 0 || v >= a.M || p < 0 || p >= a.A) {
-      raise(a.status, GAPRO_VOXELIZE_FLAG_TABLE);
+      raise_bad_arg(a.status, GAPRO_VOXELIZE_FLAG_TABLE);
       continue;
     }
     int* __restrict__ row = a.out_map + v * width;
     row[1 + p] = (int)i;
     if (p == 0) {
       const int c = a.count[v];
-      if (c < 1 || c > a.A) raise(a.status, GAPRO_VOXELIZE_FLAG_TABLE);
+      if (c < 1 || c > a.A) raise_bad_arg(a.status, GAPRO_VOXELIZE_FLAG_TABLE);
       row[0] = c < 1 ? 1 : c > a.A ? a.A : c;
     }
   }
@@ -355,7 +282,7 @@ __global__ __launch_bounds__(kThreads) void k_pool_forward(PoolArgs a) {
     const int n = r[0];
     float acc = 0.f;
     if (n < 0 || n > a.A) {
-      if (c == 0) raise(a.status, GAPRO_VOXEL_POOL_FLAG_COUNT);
+      if (c == 0) raise_bad_arg(a.status, GAPRO_VOXEL_POOL_FLAG_COUNT);
     } else {
       const float mult = pool_mult(n, a.average);
       const float* __restrict__ x = a.in + c;
@@ -373,7 +300,7 @@ __global__ __launch_bounds__(kThreads) void k_pool_forward(PoolArgs a) {
         for (int u = 0; u < 4; ++u) {
           if (k0 + u > n) break;
           if (!ok[u]) {
-            if (c == 0) raise(a.status, GAPRO_VOXEL_POOL_FLAG_INDEX);
+            if (c == 0) raise_bad_arg(a.status, GAPRO_VOXEL_POOL_FLAG_INDEX);
             continue;
           }
           const float prod = mult * f[u];
@@ -396,7 +323,7 @@ __global__ __launch_bounds__(kThreads) void k_pool_backward(PoolArgs a) {
     const int* __restrict__ r = a.rule + v * ((long long)a.A + 1);
     const int n = r[0];
     if (n < 0 || n > a.A) {
-      if (c == 0) raise(a.status, GAPRO_VOXEL_POOL_FLAG_COUNT);
+      if (c == 0) raise_bad_arg(a.status, GAPRO_VOXEL_POOL_FLAG_COUNT);
       continue;
     }
     const float g = pool_mult(n, a.average) * a.in[e];
@@ -404,7 +331,7 @@ __global__ __launch_bounds__(kThreads) void k_pool_backward(PoolArgs a) {
     for (int k = 1; k <= n; ++k) {
       const long long p = r[k];
       if (p < 0 || p >= a.N) {
-        if (c == 0) raise(a.status, GAPRO_VOXEL_POOL_FLAG_INDEX);
+        if (c == 0) raise_bad_arg(a.status, GAPRO_VOXEL_POOL_FLAG_INDEX);
         continue;
       }
       out[p * a.C] = g;
@@ -423,13 +350,13 @@ __global__ __launch_bounds__(kThreads) void k_pool_check(PoolArgs a) {
     const int* __restrict__ r = a.rule + v * ((long long)a.A + 1);
     const int n = r[0];
     if (n < 0 || n > a.A) {
-      if (k == 0) raise(a.status, GAPRO_VOXEL_POOL_FLAG_COUNT);
+      if (k == 0) raise_bad_arg(a.status, GAPRO_VOXEL_POOL_FLAG_COUNT);
       continue;
     }
     if (k >= n) continue;
     const long long p = r[1 + k];
-    if (p < 0 || p >= a.N) raise(a.status, GAPRO_VOXEL_POOL_FLAG_INDEX);
-    else if (atomicAdd(a.marks + p, 1) > 0) raise(a.status, GAPRO_VOXEL_POOL_FLAG_TWICE);
+    if (p < 0 || p >= a.N) raise_bad_arg(a.status, GAPRO_VOXEL_POOL_FLAG_INDEX);
+    else if (atomicAdd(a.marks + p, 1) > 0) raise_bad_arg(a.status, GAPRO_VOXEL_POOL_FLAG_TWICE);
   }
 }
 
@@ -465,7 +392,7 @@ int gapro_voxelize_count(gapro_ctx* ctx, void* stream_, int64_t n_points, int32_
     return gapro_fail(ctx, GAPRO_ERR_WORKSPACE, "gapro_voxelize_count: workspace too small");
   hipStream_t stream = (hipStream_t)stream_;
   const VoxWs w = ws_layout(d_workspace, n_points);
-  const long long n = n_points, slots = gapro_vox_slots(n), n_blocks = (n + kScanBlock - 1) / kScanBlock;
+  const long long n = n_points, slots = gapro_vox_slots(n);
   int* header = (int*)d_header;
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(header, 0, sizeof(gapro_voxelize_header), stream));
   GAPRO_HIP_CHECK(ctx, hipMemsetAsync(w.table, 0xff, (size_t)slots * sizeof(int), stream));  // kEmpty
@@ -479,11 +406,7 @@ int gapro_voxelize_count(gapro_ctx* ctx, void* stream_, int64_t n_points, int32_
   else
     hipLaunchKernelGGL(k_vox_insert<3>, dim3(grid), dim3(kThreads), 0, stream, coords, n, w.table, (u64)(slots - 1),
                        w.slot, header);
-  hipLaunchKernelGGL(k_vox_flag_sums, dim3((unsigned)n_blocks), dim3(kThreads), 0, stream, w.table, w.slot, n,
-                     w.block_sums);
-  hipLaunchKernelGGL(k_vox_scan_sums, dim3(1), dim3(kThreads), 0, stream, w.block_sums, n_blocks, header);
-  hipLaunchKernelGGL(k_vox_apply, dim3((unsigned)n_blocks), dim3(kThreads), 0, stream, w.table, w.slot, n,
-                     w.block_sums, w.rank, w.first_of);
+  scan_enqueue(stream, IsFirst{w.table, w.slot}, EmitRank{w.rank, w.first_of}, n, w.block_sums, header + 2);
   hipLaunchKernelGGL(k_vox_assign, dim3(grid), dim3(kThreads), 0, stream, w.table, w.slot, w.rank, n, mode,
                      (int*)d_input_map, w.count, w.pos, w.last, header);
   GAPRO_LAUNCH_CHECK(ctx);

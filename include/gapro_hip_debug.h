@@ -70,6 +70,12 @@ int gapro_debug_exact_sum(gapro_ctx* ctx, void* stream, int32_t n_shift, const d
                           int32_t* shift_out, int32_t n_fixed, const double* x, const int32_t* xk, int64_t* fixed_out,
                           int32_t n_mean, const int64_t* sum, const int32_t* mk, const double* count, double* mean_out);
 
+/* The device-wide exclusive scan of csrc/scan.h (three launches on `stream`): d_out[i] = d_in[0] + ... + d_in[i - 1] for
+ * i < n, *d_total = the sum of all n; d_out may be d_in.  d_block_sums: ceil(n / 1024) device words of scratch.  The
+ * caller keeps the sum below 2^31 (tests/test_scan_gpu.py). */
+int gapro_debug_scan(gapro_ctx* ctx, void* stream, int64_t n, const int32_t* d_in, int32_t* d_out,
+                     int32_t* d_block_sums, int32_t* d_total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ Case = namedtuple("Case", "name coords shape batch_size c_in c_out bias scale")
 
 LAYERS = ("subm", "down", "inverse")
 WAVE_TILE, WG_TILE, CIN_CHUNK, MIN_CHUNK_ROWS = 16, 64, 32, 256   # csrc/spconv.hip, GAPRO_SPCONV_*
+SCAN_BLOCK = 1024                                                  # csrc/scan.h kScanBlock
 
 
 def _random(seed, V, shape, B=1, samples=None):
@@ -25,6 +26,16 @@ def _random(seed, V, shape, B=1, samples=None):
 def _full(shape, B=1, lo=(0, 0, 0)):
     g = np.stack(np.meshgrid(np.arange(B), *[np.arange(lo[a], lo[a] + shape[a]) for a in range(3)], indexing="ij"), -1)
     return g.reshape(-1, 4).astype(np.int64)
+
+
+def _late_first_child(seed, V, shape):
+    """V distinct shuffled rows of one sample whose LAST row is alone in its coarse voxel: the first child of that
+    coarse row is input row V - 1, so its number is the scan's value at the last row."""
+    lone = np.array([0, 4, 4, 4], dtype=np.int64)
+    cells = _full(shape)
+    others = cells[((cells[:, 1:] >> 1) != (lone[1:] >> 1)).any(1)]
+    pick = np.random.default_rng(seed).permutation(len(others))[:V - 1]
+    return np.concatenate([others[pick], lone[None]])
 
 
 def _cases():
@@ -62,6 +73,9 @@ def _cases():
     add("bias", _random(19, 80, (5, 6, 5), B=2), (5, 6, 5), B=2, bias=True)
     add("bias_odd", _random(20, 45, (5, 3, 5)), (5, 3, 5), c_in=8, c_out=24, bias=True)
     add("sorted_rows", _full((4, 4, 4), B=2), (4, 4, 4), B=2)   # row order = coordinate order, for once
+    # one row past the 1024 rows of a block of the down plan's scan (csrc/scan.h): the second block starts from a carry
+    # (last in the list: tensors() seeds a case by its place)
+    add("rows_1025", _late_first_child(21, SCAN_BLOCK + 1, (11, 10, 11)), (11, 10, 11))
     return out
 
 

@@ -185,3 +185,12 @@ def test_the_cases_cover_what_they_are_named_for():
     assert len(ref.down_tables(cases.BY_NAME["extent_1"].coords, (1, 4, 5))[0]) == 0
     shuffled = cases.BY_NAME["rows_65"].coords
     assert (np.lexsort(shuffled.T[::-1]) != np.arange(len(shuffled))).any()
+    # rows_1025: coarse rows are numbered in the first and in the second block of the down plan's scan, so the carry
+    # into the second block is not zero and a coarse row's number is read from behind it
+    late = cases.BY_NAME["rows_1025"]
+    V = len(late.coords)
+    assert V == cases.SCAN_BLOCK + 1 and late.batch_size == 1 and len(np.unique(late.coords, axis=0)) == V
+    assert (np.lexsort(late.coords.T[::-1]) != np.arange(V)).any()
+    children = ref.down_tables(late.coords, late.shape)[1]
+    first_child = np.where(children >= 0, children, V).min(0)
+    assert (first_child >= cases.SCAN_BLOCK).any() and (first_child < cases.SCAN_BLOCK).any()
