@@ -36,15 +36,7 @@ using gapro_mfma::unrotate;
 constexpr int kThreads = 256, kWaves = 4;
 constexpr int kTile = 16;   // queries and instances of a tile
 constexpr int kChunk = 16;  // columns a wave takes at a time: four per lane
-constexpr int kNoSample = 0x7fffffff;
 enum { kFlagClass = 1, kFlagMask = 2 };
-
-struct MatchScalars {  // the first 64 bytes of the workspace; uploaded with the tables, so zero before the check
-  int flags;
-  int bad_sample;
-  int reserved[14];
-};
-static_assert(sizeof(MatchScalars) == 64, "MatchScalars is the first 64 bytes of the workspace");
 
 struct DevTask {  // one per sample
   const float* x;
@@ -67,7 +59,7 @@ struct MatchDims {
 };
 
 struct MatchWs {
-  MatchScalars* s;
+  RefusalHead* s;   // bad: a sample
   DevTask* tasks;   // [B]
   Tile* tiles;      // [tile capacity]
   double* col_sum;  // [total_inst] sum_s t of every instance row
@@ -80,7 +72,7 @@ __host__ __device__ inline long long tile_capacity(int B, int Q, long long total
 // the table part [0, upload) is what the call uploads; the column sums follow it
 __host__ __device__ inline size_t match_ws(void* base, int B, int Q, long long total_inst, MatchWs* w, size_t* upload) {
   char* p = (char*)base;
-  w->s = (MatchScalars*)p; p += sizeof(MatchScalars);
+  w->s = (RefusalHead*)p; p += sizeof(RefusalHead);
   w->tasks = (DevTask*)p; p += (size_t)B * sizeof(DevTask);
   w->tiles = (Tile*)p; p += (size_t)tile_capacity(B, Q, total_inst) * sizeof(Tile);
   if (upload) *upload = (size_t)(p - (char*)base);
@@ -120,7 +112,7 @@ __global__ __launch_bounds__(kThreads) void k_match_check(void* base, MatchDims 
   flags = wave_or(flags);
   if (flags != 0 && lane == 0) {
     atomicOr(&w.s->flags, flags);
-    atomicMin(&w.s->bad_sample, b);
+    atomicMin(&w.s->bad, b);
   }
 }
 
@@ -146,12 +138,7 @@ __global__ __launch_bounds__(kThreads) void k_match_cost(void* base, MatchDims d
   MatchWs w;
   match_ws(base, d.B, d.Q, d.total_inst, &w, nullptr);
   const int flags = w.s->flags;  // written by k_match_check; uniform over the grid
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    status[0] = flags ? GAPRO_ERR_BAD_ARG : GAPRO_OK;
-    status[1] = flags ? w.s->bad_sample : -1;
-    status[2] = flags;
-    status[3] = 0;
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) write_status(status, *w.s);
   if (flags) return;
 
   __shared__ double s_acc[kWaves][2][4][64];  // the waves' partial tiles of sig . t^T and x . t^T, MFMA C layout
@@ -186,10 +173,9 @@ __global__ __launch_bounds__(kThreads) void k_match_cost(void* base, MatchDims d
       const double x = (double)xv[j];
       double sig = 0.0, sp = 0.0;
       if (q_ok && s0 + j < S) {
-        const double e = exp(-fabs(x));  // in (0, 1]: no overflow on either side
-        const double den = 1.0 + e;
-        sig = (x >= 0.0 ? 1.0 : e) / den;
-        sp = (x > 0.0 ? x : 0.0) + log1p(e);  // a NaN logit makes both NaN, and with them its whole row
+        const Sig sg = sigmoid_of(x);
+        sig = sg.sig;
+        sp = softplus_of(x, sg);  // a NaN logit makes both NaN, and with them its whole row
       }
       row_sig += sig;
       row_sp += sp;
@@ -317,7 +303,7 @@ int gapro_match_cost(gapro_ctx* ctx, void* stream_, const gapro_match_task* h_ta
   match_ws(nullptr, batch_size, n_queries, total_inst, &w, &upload);
   std::vector<char> table(upload, 0);
   match_ws(table.data(), batch_size, n_queries, total_inst, &w, nullptr);
-  w.s->bad_sample = kNoSample;
+  w.s->bad = kNoBad;
   long long row_off = 0, n_tiles = 0;
   for (int b = 0; b < batch_size; ++b) {
     const gapro_match_task& t = h_tasks[b];

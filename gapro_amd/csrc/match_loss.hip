@@ -1,17 +1,19 @@
 // The criterion's seven main losses over a matched batch (include/gapro_hip.h, "Matched losses"): the loop of ISBNet's
 // Criterion.single_layer_loss (isbnet/model/criterion.py:235-331) in two launches forward and one backward.
 //   rows      a workgroup of four waves per (sample, query), skipped samples' workgroups leave at once.  Wave 0 forms
-//             the query's class term (the log-sum-exp by shuffles).  A matched query's workgroup walks its logit row,
-//             thread t on the columns t, t + 256, ..: every row sum is a per-thread float64 partial (the counts are
-//             integers), reduced by wave_reduce.h's butterfly and then across the waves through LDS in wave order.  A
-//             second walk forms the level-set term around the mean the first one gave.  Thread 0 forms the row's box,
-//             GIoU and confidence terms and writes one record of doubles.
+//             the query's class term.  A matched query's workgroup walks its logit row against the targets of its
+//             matched row (loss_rows.h: the first walk, then for a box with a member the second one around the mean
+//             the first gave).  Thread 0 forms the row's box, GIoU and confidence terms and writes one record of
+//             doubles.
 //   finish    one workgroup: wave w takes the samples w, w + 4, .., its lanes the sample's rows and queries l, l + 64,
 //             ..; a butterfly gives the sample's seven values and normalisers; thread 0 adds the samples in their order,
 //             divides by B and writes f32[7] and the status.
 //   backward  the grid of `rows`: reads the records, the normalisers and the upstream f32[7]; per query the class
 //             gradient row, the confidence and box gradients and the n_cols mask-logit gradients (zeros for an unmatched
 //             query; for a skipped sample only the zeros of its class, confidence and box rows).
+// This file's own: the records and the workspace, the class target, its weight and its refusal, the box, GIoU and
+// confidence terms, the normalisers of `finish` and the coefficients the backward forms from them, the host's checks
+// and tables.  The walks over a row, its mask-logit gradient and the class term's arithmetic are loss_rows.h's.
 // Arithmetic: every term in float64 from the float32 inputs, every sum in float64 in the order this
 // layout fixes, one rounding to float32.  The level-set membership alone is a float32 comparison, as the reference's.
 // No floating-point atomics (the two integer ones carry the refusal), no workgroup waits for another, no scratch; a lane
@@ -29,8 +31,7 @@
 namespace {
 
 constexpr int kThreads = kLossThreads, kWaves = kLossWaves;
-constexpr int kMaxF = GAPRO_MATCH_LOSS_MAX_FEATS;
-constexpr int kNoSample = 0x7fffffff;
+constexpr int kMaxF = kLossMaxF;
 constexpr int kRowRec = 24, kQueryRec = 4, kSampleRec = 12;  // doubles
 enum { kFlagClass = 1 };
 // a row's record
@@ -38,13 +39,6 @@ enum { R_DICE, R_BCE_NUM, R_SW, R_IOU_SQ, R_L1, R_GIOU, R_LS, R_SSIG, R_ST, R_SS
 static_assert(R_END <= kRowRec, "a row's record");
 // a sample's record: the seven losses of the sample, then the normalisers
 enum { S_LOSS, S_SW = 7, S_WSUM, S_N };
-
-struct LossScalars {  // the first 64 bytes of the workspace; uploaded with the tables, so zero before the first kernel
-  int flags;
-  int bad_sample;
-  int reserved[14];
-};
-static_assert(sizeof(LossScalars) == 64, "LossScalars is the first 64 bytes of the workspace");
 
 struct DevTask {  // one per sample; n_gt == 0: skipped
   const float* x;
@@ -65,7 +59,7 @@ struct LossDims {
 };
 
 struct LossWs {
-  LossScalars* s;
+  RefusalHead* s;  // bad: a sample
   DevTask* tasks;  // [B]
   int* rows;       // [total_gt] the matched query of every row
   int* inv;        // [B Q] the row of every query, or -1
@@ -76,7 +70,7 @@ struct LossWs {
 
 __host__ __device__ inline size_t loss_ws(void* base, int B, int Q, long long total_gt, LossWs* w, size_t* upload) {
   char* p = (char*)base;
-  w->s = (LossScalars*)p; p += sizeof(LossScalars);
+  w->s = (RefusalHead*)p; p += sizeof(RefusalHead);
   w->tasks = (DevTask*)p; p += (size_t)B * sizeof(DevTask);
   w->rows = (int*)p; p += (size_t)total_gt * 4;
   w->inv = (int*)p; p += (size_t)B * Q * 4;
@@ -86,6 +80,14 @@ __host__ __device__ inline size_t loss_ws(void* base, int B, int Q, long long to
   w->rrec = (double*)p; p += (size_t)total_gt * kRowRec * 8;
   w->srec = (double*)p; p += (size_t)B * kSampleRec * 8;
   return (size_t)(p - (char*)base);
+}
+
+// query q of sample t against its matched row r: the targets are the row's
+__device__ inline RowCols row_cols(const DevTask& t, int F, int q, int r, const float* __restrict__ prob,
+                                   const float* __restrict__ feats, const float* __restrict__ coords) {
+  return RowCols{t.x + (size_t)q * (size_t)t.ld, t.t + (size_t)r * (size_t)t.n_cols, prob + t.col_off,
+                 coords + (size_t)t.col_off * 3, feats + (size_t)t.col_off * (size_t)F, t.n_cols, F,
+                 box_test(t.box + (size_t)r * 6)};
 }
 
 // ---- rows ----------------------------------------------------------------------------------------------------------
@@ -106,23 +108,18 @@ __global__ __launch_bounds__(kThreads) void k_loss_rows(void* base, LossDims d, 
 
   if (wave == 0) {  // the class term of criterion.py:299-310 for this query
     const float* __restrict__ z = cls_logits + bq * (size_t)d.C;
-    double m = -INFINITY;
-    for (int c = lane; c < d.C; c += 64) m = fmax(m, (double)z[c]);
-    m = wave_max(m);
-    double sum = 0.0;
-    for (int c = lane; c < d.C; c += 64) sum += exp((double)z[c] - m);  // a NaN logit makes the sum NaN
-    sum = wave_sum(sum);
+    const double lse = wave_lse(z, d.C);
     if (lane == 0) {
       long long c = d.C - 1;
       if (r >= 0) {
         c = cls_at(t.cls, d.cls_type, r);
         if (c < 0 || c >= d.C) {  // refused: the flag, and an address inside the row
           atomicOr(&w.s->flags, kFlagClass);
-          atomicMin(&w.s->bad_sample, b);
+          atomicMin(&w.s->bad, b);
           c = d.C - 1;
         }
       }
-      const double lse = m + log(sum), wt = (double)empty_weight[c];
+      const double wt = (double)empty_weight[c];
       double* rec = w.qrec + bq * kQueryRec;
       rec[0] = wt * (lse - (double)z[c]);
       rec[1] = wt;
@@ -132,99 +129,35 @@ __global__ __launch_bounds__(kThreads) void k_loss_rows(void* base, LossDims d, 
   }
   if (r < 0) return;  // uniform over the workgroup
 
-  __shared__ double s_d[6 + kMaxF + 2][kWaves];
-  __shared__ int s_i[2][kWaves];
-  const int S = t.n_cols, F = d.F;
-  const float* __restrict__ xrow = t.x + (size_t)q * (size_t)t.ld;
-  const float* __restrict__ trow = t.t + (size_t)r * (size_t)S;
-  const float* __restrict__ wcol = prob + t.col_off;
-  const float* __restrict__ ccol = coords + (size_t)t.col_off * 3;
-  const float* __restrict__ fcol = feats + (size_t)t.col_off * (size_t)F;
   const float* __restrict__ gbox = t.box + (size_t)r * 6;
-  const BoxTest bt = box_test(gbox);
-
-  double ssig = 0.0, st = 0.0, sst = 0.0, swb = 0.0, sw = 0.0, a = 0.0;
-  double bf[kMaxF];
-#pragma unroll
-  for (int f = 0; f < kMaxF; ++f) bf[f] = 0.0;
-  double inter = 0.0;  // sum_s [x >= 0] t
-  int cnt = 0, nr = 0;
-  for (int s = threadIdx.x; s < S; s += kThreads) {
-    const double x = (double)xrow[s], tv = (double)trow[s], wv = (double)wcol[s];
-    const Sig sg = sigmoid_of(x);
-    const double sp = (x > 0.0 ? x : 0.0) + log1p(sg.e);
-    ssig += sg.sig;
-    st += tv;
-    sst += sg.sig * tv;
-    swb += wv * (sp - x * tv);
-    sw += wv;
-    if (x >= 0.0) {
-      ++cnt;
-      inter += tv;
-    }
-    if (inside(bt, ccol + (size_t)s * 3)) {
-      ++nr;
-      a += sg.sig;
-#pragma unroll
-      for (int f = 0; f < kMaxF; ++f)
-        if (f < F) bf[f] += sg.sig * (double)fcol[(size_t)s * F + f];
-    }
-  }
-  ssig = block_sum(ssig, s_d[0]);
-  st = block_sum(st, s_d[1]);
-  sst = block_sum(sst, s_d[2]);
-  swb = block_sum(swb, s_d[3]);
-  sw = block_sum(sw, s_d[4]);
-  a = block_sum(a, s_d[5]);
-  inter = block_sum(inter, s_d[6 + kMaxF + 1]);
-  cnt = block_sum(cnt, s_i[0]);
-  nr = block_sum(nr, s_i[1]);
-  double mu[kMaxF];
-  const double a_cl = a < 1e-5 ? 1e-5 : a;  // clamp(min=1e-5); a NaN stays
-#pragma unroll
-  for (int f = 0; f < kMaxF; ++f) mu[f] = f < F ? block_sum(bf[f], s_d[6 + f]) / a_cl : 0.0;
-
-  double ls = 0.0;
-  if (nr > 0) {  // uniform: the second walk, over the members only
-    for (int s = threadIdx.x; s < S; s += kThreads) {
-      if (!inside(bt, ccol + (size_t)s * 3)) continue;
-      const Sig sg = sigmoid_of((double)xrow[s]);
-      double dev = 0.0;
-#pragma unroll
-      for (int f = 0; f < kMaxF; ++f)
-        if (f < F) {
-          const double df = (double)fcol[(size_t)s * F + f] - mu[f];
-          dev += df * df;
-        }
-      ls += sg.sig * dev;
-    }
-    ls = block_sum(ls, s_d[6 + kMaxF]) / (double)nr;
-  }
+  const RowCols rc = row_cols(t, d.F, q, r, prob, feats, coords);
+  const RowSums u = walk_row(rc, true);  // any float32 target counts as the value it is: odd_target is not read
+  const double ls = u.nr > 0 ? walk_members(rc, u.mu, u.nr) : 0.0;  // uniform
   if (threadIdx.x != 0) return;
 
-  const double uni = (double)cnt + st - inter;
-  const double iou = inter / (uni + 1e-6);
+  const double uni = (double)u.cnt + u.st - u.inter;
+  const double iou = u.inter / (uni + 1e-6);
   const double conf = (double)conf_logits[bq];
   const float* __restrict__ pbox = box_preds + bq * 6;
   double l1 = 0.0;
 #pragma unroll
   for (int k = 0; k < 6; ++k) l1 += fabs((double)pbox[k] - (double)gbox[k]);
   double* rec = w.rrec + (size_t)(t.row_off + r) * kRowRec;
-  rec[R_DICE] = 1.0 - (2.0 * sst + 1.0) / (ssig + st + 1.0);
-  rec[R_BCE_NUM] = swb;
-  rec[R_SW] = sw;
+  rec[R_DICE] = 1.0 - (2.0 * u.sst + 1.0) / (u.ssig + u.st + 1.0);
+  rec[R_BCE_NUM] = u.swb;
+  rec[R_SW] = u.sw;
   rec[R_IOU_SQ] = (conf - iou) * (conf - iou);
   rec[R_L1] = l1;
   rec[R_GIOU] = giou_loss_of(pbox, gbox, nullptr);
   rec[R_LS] = ls;
-  rec[R_SSIG] = ssig;
-  rec[R_ST] = st;
-  rec[R_SST] = sst;
+  rec[R_SSIG] = u.ssig;
+  rec[R_ST] = u.st;
+  rec[R_SST] = u.sst;
   rec[R_IOU] = iou;
-  rec[R_A] = a;
-  rec[R_NR] = (double)nr;
+  rec[R_A] = u.a;
+  rec[R_NR] = (double)u.nr;
 #pragma unroll
-  for (int f = 0; f < kMaxF; ++f) rec[R_MU + f] = mu[f];
+  for (int f = 0; f < kMaxF; ++f) rec[R_MU + f] = u.mu[f];
 }
 
 // ---- finish --------------------------------------------------------------------------------------------------------
@@ -273,10 +206,7 @@ __global__ __launch_bounds__(kThreads) void k_loss_finish(void* base, LossDims d
   __syncthreads();
   if (threadIdx.x != 0) return;
   const int flags = w.s->flags;
-  status[0] = flags ? GAPRO_ERR_BAD_ARG : GAPRO_OK;
-  status[1] = flags ? w.s->bad_sample : -1;
-  status[2] = flags;
-  status[3] = 0;
+  write_status(status, *w.s);
   double total[GAPRO_MATCH_LOSS_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int b = 0; b < d.B; ++b) {  // sample order
     if (w.tasks[b].n_gt == 0) continue;
@@ -320,10 +250,7 @@ __global__ __launch_bounds__(kThreads) void k_loss_backward(const void* base, Lo
       const long long tgt = r >= 0 ? cls_at(t.cls, d.cls_type, r) : d.C - 1;  // inside [0, C): no flag
       const double lse = w.qrec[bq * kQueryRec + 2];
       const double k = (double)upstream[2] * inv_b * (double)empty_weight[tgt] / srec[S_WSUM];
-      for (int c = threadIdx.x; c < d.C; c += kThreads) {
-        const double dz = (double)z[c] - lse;
-        out[c] = (float)(k * (c == tgt ? expm1(dz) : exp(dz)));  // softmax - onehot, without the cancellation at p -> 1
-      }
+      class_grad_row(z, d.C, lse, tgt, k, threadIdx.x, kThreads, out);
     }
   }
   if (r < 0) {  // uniform over the workgroup
@@ -356,46 +283,17 @@ __global__ __launch_bounds__(kThreads) void k_loss_backward(const void* base, Lo
   }
   if (!g_mask) return;
 
-  const int S = t.n_cols, F = d.F;
-  const float* __restrict__ xrow = t.x + (size_t)q * (size_t)t.ld;
-  const float* __restrict__ trow = t.t + (size_t)r * (size_t)S;
-  const float* __restrict__ wcol = prob + t.col_off;
-  const float* __restrict__ ccol = coords + (size_t)t.col_off * 3;
-  const float* __restrict__ fcol = feats + (size_t)t.col_off * (size_t)F;
-  float* __restrict__ out = g_mask + t.grad_off + (size_t)q * (size_t)S;
-  const BoxTest bt = box_test(gbox);
-
   const double den = rec[R_SSIG] + rec[R_ST] + 1.0, numr = 2.0 * rec[R_SST] + 1.0;
   const double k_dice = (double)upstream[0] * inv_b / (n + 1e-6) / (den * den);
   const double k_bce = (double)upstream[1] * inv_b / (srec[S_SW] * (n + 1e-6));
   const double nr = rec[R_NR], a = rec[R_A];
   const double k_ls = nr > 0.0 ? (double)upstream[6] * inv_b / (n + 1e-4) / nr : 0.0;
-  const bool clamped = a < 1e-5;  // mu = (sum v f) / 1e-5: d mu / d v = f / 1e-5, and sum v (f - mu) is not zero
-  double mu[kMaxF], rf[kMaxF];
+  const double rfk = a < 1e-5 ? 2.0 * (1e-5 - a) / 1e-5 : 0.0;  // the clamped mean's own derivative (mask_grad_row)
+  double mu[kMaxF];
 #pragma unroll
-  for (int f = 0; f < kMaxF; ++f) {
-    mu[f] = rec[R_MU + f];
-    rf[f] = clamped ? 2.0 * mu[f] * (1e-5 - a) / 1e-5 : 0.0;  // 2 (sum v f - mu A) / 1e-5 with sum v f = 1e-5 mu
-  }
-  for (int s = threadIdx.x; s < S; s += kThreads) {
-    const double x = (double)xrow[s], tv = (double)trow[s], wv = (double)wcol[s];
-    const Sig sg = sigmoid_of(x);
-    const double sm = sg.e / (1.0 + sg.e);                 // min(sig, 1 - sig)
-    const double dsig = sm / (1.0 + sg.e);                 // sig (1 - sig)
-    const double sig_t = x >= 0.0 ? (1.0 - tv) - sm : sm - tv;  // sig - t, cancellation-free (consumer.hip k_wbce_grad)
-    double dv = k_dice * (numr - 2.0 * tv * den);
-    if (k_ls != 0.0 && inside(bt, ccol + (size_t)s * 3)) {
-      double dev = 0.0;
-#pragma unroll
-      for (int f = 0; f < kMaxF; ++f)
-        if (f < F) {
-          const double fv = (double)fcol[(size_t)s * F + f], df = fv - mu[f];
-          dev += df * df - rf[f] * fv;
-        }
-      dv += k_ls * dev;
-    }
-    out[s] = (float)(dsig * dv + k_bce * wv * sig_t);
-  }
+  for (int f = 0; f < kMaxF; ++f) mu[f] = rec[R_MU + f];
+  mask_grad_row(row_cols(t, d.F, q, r, prob, feats, coords), k_dice * numr, 2.0 * k_dice * den, k_bce, true, k_ls, rfk,
+                mu, g_mask + t.grad_off + (size_t)q * (size_t)t.n_cols);
 }
 
 bool dims_ok(int32_t B, int32_t Q, int64_t total_gt) {
@@ -463,7 +361,7 @@ int gapro_match_loss_forward(gapro_ctx* ctx, void* stream_, const gapro_match_lo
   loss_ws(nullptr, batch_size, n_queries, total_gt, &w, &upload);
   std::vector<char> table(upload, 0);
   loss_ws(table.data(), batch_size, n_queries, total_gt, &w, nullptr);
-  w.s->bad_sample = kNoSample;
+  w.s->bad = kNoBad;
   for (long long k = 0; k < (long long)batch_size * n_queries; ++k) w.inv[k] = -1;
   long long grad_off = 0;
   for (int b = 0; b < batch_size; ++b) {

@@ -1,6 +1,7 @@
-// What the matcher's cost kernel (match_cost.hip), the matched losses (match_loss.hip) and the point-wise losses
-// (point_loss.hip) share: the class label read, torch's NaN-propagating min / max / clamp, which the reference's box
-// terms go through, and the GIoU loss of one pair of boxes with its derivative.
+// What the matcher's cost kernel (match_cost.hip), the two criteria (match_loss.hip, spf_loss.hip) and the point-wise
+// losses (point_loss.hip) share: the class label read, the refusal head of a workspace with the status words it ends
+// as, the overflow-free sigmoid and softplus of a logit, torch's NaN-propagating min / max / clamp, which the
+// reference's box terms go through, and the GIoU loss of one pair of boxes with its derivative.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,31 @@
 __device__ inline long long cls_at(const void* cls, int type, int i) {
   return type == GAPRO_LABEL_I32 ? (long long)((const int*)cls)[i] : ((const long long*)cls)[i];
 }
+
+struct RefusalHead {  // the first 64 bytes of a workspace; uploaded with the tables, so zero before the first kernel
+  int flags;          // what the kernels refused, one bit per reason: atomicOr
+  int bad;            // the first sample or task with a reason: atomicMin from kNoBad
+  int reserved[14];
+};
+static_assert(sizeof(RefusalHead) == 64, "RefusalHead is the first 64 bytes of the workspace");
+constexpr int kNoBad = 0x7fffffff;
+
+// the GAPRO_MATCH_STATUS_WORDS of a call, by one thread, once every kernel that refuses has run
+__device__ inline void write_status(int* __restrict__ status, const RefusalHead& s) {
+  status[0] = s.flags ? GAPRO_ERR_BAD_ARG : GAPRO_OK;
+  status[1] = s.flags ? s.bad : -1;
+  status[2] = s.flags;
+  status[3] = 0;
+}
+
+struct Sig {
+  double sig, e;  // sigmoid(x) and exp(-|x|)
+};
+__device__ inline Sig sigmoid_of(double x) {
+  const double e = exp(-fabs(x));  // in (0, 1]: no overflow on either side
+  return {(x >= 0.0 ? 1.0 : e) / (1.0 + e), e};
+}
+__device__ inline double softplus_of(double x, const Sig& sg) { return (x > 0.0 ? x : 0.0) + log1p(sg.e); }
 
 __device__ inline double nan_min(double a, double b) { return (a < b || a != a) ? a : b; }  // torch.min: a NaN wins
 __device__ inline double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }

@@ -2,16 +2,20 @@
 // the loops of Criterion.forward and get_layer_loss (SPFormer/spformer/model/loss.py:415-499, 263-349) in two launches
 // forward and one backward.  A task is one (head, sample); the kernels are match_loss.hip's in shape:
 //   rows      a workgroup of four waves per (task, query).  Wave 0 forms the query's class term (skipped samples too:
-//             the class loss runs over all B Q queries).  A matched query's workgroup walks its logit row, thread t on
-//             the columns t, t + 256, ..: float64 partials (the counts are integers), reduced by the butterfly and then
-//             across the waves in wave order.  A second walk forms the level-set term around the mean the first one
-//             gave, for a box of at least min_points members.  Thread 0 writes one record of doubles.
+//             the class loss runs over all B Q queries).  A matched query's workgroup walks its logit row against the
+//             mask of its matched GT instance (loss_rows.h: the first walk, then for a box of at least min_points
+//             members the second one around the mean the first gave) and refuses a mask value that is neither 0 nor
+//             1.  Thread 0 writes one record of doubles.
 //   finish    one workgroup: wave w takes the tasks w, w + 4, .., its lanes the task's rows and queries l, l + 64, ..;
 //             a butterfly gives the task's values and normalisers (n_kept of the score filter among them).  Then thread
 //             h takes head h: the samples in their order, the batch-wide class normaliser, the divisions by B.
 //   backward  the grid of `rows` for the score and mask-logit gradients, and behind it a workgroup per four queries
 //             for the class-logit gradients (a wave per query): every element of every head's gradients, zeros included.
 // A head's arithmetic never meets another head's, so a call of seven heads gives the bytes of seven calls of one.
+// This file's own: the records and the workspace, the heads, the class target, its weight and its refusal, the mask
+// refusal, the score filter, the BCE switch and the normalisers of `finish` with the coefficients the backward forms
+// from them, the host's checks and tables.  The walks over a row, its mask-logit gradient and the class term's
+// arithmetic are loss_rows.h's.
 // Arithmetic: every term in float64 from the float32 inputs, every sum in float64 in the order
 // this layout fixes, one rounding to float32.  The level-set membership alone is a float32 comparison, as the
 // reference's.  No floating-point atomics (the integer ones carry the refusal), no workgroup waits for another, no
@@ -29,8 +33,7 @@
 namespace {
 
 constexpr int kThreads = kLossThreads, kWaves = kLossWaves;
-constexpr int kMaxF = GAPRO_MATCH_LOSS_MAX_FEATS;
-constexpr int kNoTask = 0x7fffffff;
+constexpr int kMaxF = kLossMaxF;
 constexpr int kRowRec = 20, kQueryRec = 4, kTaskRec = 12, kHeadRec = 2;  // doubles
 enum { kFlagClass = 1, kFlagMask = 2 };
 // a row's record
@@ -39,13 +42,6 @@ static_assert(R_END <= kRowRec, "a row's record");
 // a task's record: its four per-sample values, its part of the class sums, the normalisers
 enum { T_BCE, T_DICE, T_SCORE, T_LS, T_NUM, T_DEN, T_NKEPT, T_SW, T_N };
 enum { L_CLS, L_BCE, L_DICE, L_SCORE, L_LS };  // the order of d_losses
-
-struct SpfScalars {  // the first 64 bytes of the workspace; uploaded with the tables, so zero before the first kernel
-  int flags;
-  int bad_task;
-  int reserved[14];
-};
-static_assert(sizeof(SpfScalars) == 64, "SpfScalars is the first 64 bytes of the workspace");
 
 struct DevTask {  // one per (head, sample); n_gt == 0: skipped
   const float* z;      // class logits f32[Q, C]
@@ -68,7 +64,7 @@ struct SpfDims {
 };
 
 struct SpfWs {
-  SpfScalars* s;
+  RefusalHead* s;  // bad: a task
   DevTask* tasks;  // [L B]
   int* rows;       // [total_gt] the matched query of every row
   int* cols;       // [total_gt] the matched GT instance of every row
@@ -82,7 +78,7 @@ struct SpfWs {
 __host__ __device__ inline size_t spf_ws(void* base, int T, int L, int Q, long long total_gt, SpfWs* w,
                                          size_t* upload) {
   char* p = (char*)base;
-  w->s = (SpfScalars*)p; p += sizeof(SpfScalars);
+  w->s = (RefusalHead*)p; p += sizeof(RefusalHead);
   w->tasks = (DevTask*)p; p += (size_t)T * sizeof(DevTask);
   w->rows = (int*)p; p += (size_t)total_gt * 4;
   w->cols = (int*)p; p += (size_t)total_gt * 4;
@@ -94,6 +90,14 @@ __host__ __device__ inline size_t spf_ws(void* base, int T, int L, int Q, long l
   w->trec = (double*)p; p += (size_t)T * kTaskRec * 8;
   w->hrec = (double*)p; p += (size_t)L * kHeadRec * 8;
   return (size_t)(p - (char*)base);
+}
+
+// query q of task t against its matched GT instance gi: the targets are the instance's
+__device__ inline RowCols row_cols(const DevTask& t, int F, int q, int gi, const float* __restrict__ prob,
+                                   const float* __restrict__ feats, const float* __restrict__ coords) {
+  return RowCols{t.x + (size_t)q * (size_t)t.ld, t.t + (size_t)gi * (size_t)t.n_cols, prob + t.col_off,
+                 coords + (size_t)t.col_off * 3, feats + (size_t)t.col_off * (size_t)F, t.n_cols, F,
+                 box_test(t.box + (size_t)gi * 6)};
 }
 
 // ---- rows ----------------------------------------------------------------------------------------------------------
@@ -112,23 +116,18 @@ __global__ __launch_bounds__(kThreads) void k_spf_rows(void* base, SpfDims d, co
 
   if (wave == 0) {  // the class term of loss.py:419-428 for this query
     const float* __restrict__ z = t.z + (size_t)q * (size_t)d.C;
-    double m = -INFINITY;
-    for (int c = lane; c < d.C; c += 64) m = fmax(m, (double)z[c]);
-    m = wave_max(m);
-    double sum = 0.0;
-    for (int c = lane; c < d.C; c += 64) sum += exp((double)z[c] - m);  // a NaN logit makes the sum NaN
-    sum = wave_sum(sum);
+    const double lse = wave_lse(z, d.C);
     if (lane == 0) {
       long long c = d.C - 1;
       if (r >= 0) {
         c = cls_at(t.cls, d.cls_type, gi);
         if (c < 0 || c >= d.C - 1) {  // refused: the flag, and an address inside the row
           atomicOr(&w.s->flags, kFlagClass);
-          atomicMin(&w.s->bad_task, task);
+          atomicMin(&w.s->bad, task);
           c = d.C - 1;
         }
       }
-      const double lse = m + log(sum), wt = c == d.C - 1 ? d.w_none : 1.0;
+      const double wt = c == d.C - 1 ? d.w_none : 1.0;
       double* rec = w.qrec + tq * kQueryRec;
       rec[0] = wt * (lse - (double)z[c]);
       rec[1] = wt;
@@ -138,103 +137,37 @@ __global__ __launch_bounds__(kThreads) void k_spf_rows(void* base, SpfDims d, co
   }
   if (r < 0) return;  // uniform over the workgroup
 
-  __shared__ double s_d[5 + kMaxF + 1][kWaves];
-  __shared__ int s_i[4][kWaves];
-  const int S = t.n_cols, F = d.F;
   const bool weighted = (d.flags & GAPRO_SPF_WEIGHTED_BCE) != 0;
-  const float* __restrict__ xrow = t.x + (size_t)q * (size_t)t.ld;
-  const float* __restrict__ trow = t.t + (size_t)gi * (size_t)S;
-  const float* __restrict__ wcol = prob + t.col_off;
-  const float* __restrict__ ccol = coords + (size_t)t.col_off * 3;
-  const float* __restrict__ fcol = feats + (size_t)t.col_off * (size_t)F;
-  const BoxTest bt = box_test(t.box + (size_t)gi * 6);
-
-  double ssig = 0.0, sst = 0.0, sb = 0.0, sw = 0.0, a = 0.0;
-  double bf[kMaxF];
-#pragma unroll
-  for (int f = 0; f < kMaxF; ++f) bf[f] = 0.0;
-  int cnt = 0, inter = 0, st = 0, nr = 0;  // sum [x >= 0], sum [x >= 0] t, sum t, the box's members
-  bool bad = false;
-  for (int s = threadIdx.x; s < S; s += kThreads) {
-    const double x = (double)xrow[s], wv = (double)wcol[s];
-    const float tf = trow[s];
-    bad = bad || (tf != 0.0f && tf != 1.0f);
-    const bool one = tf == 1.0f;
-    const double tv = one ? 1.0 : 0.0;
-    const Sig sg = sigmoid_of(x);
-    const double sp = (x > 0.0 ? x : 0.0) + log1p(sg.e);
-    ssig += sg.sig;
-    sst += sg.sig * tv;
-    sb += (weighted ? wv : 1.0) * (sp - x * tv);
-    sw += wv;
-    st += one;
-    if (x >= 0.0) {
-      ++cnt;
-      inter += one;
-    }
-    if (inside(bt, ccol + (size_t)s * 3)) {
-      ++nr;
-      a += sg.sig;
-#pragma unroll
-      for (int f = 0; f < kMaxF; ++f)
-        if (f < F) bf[f] += sg.sig * (double)fcol[(size_t)s * F + f];
-    }
-  }
-  if (bad) {  // refused: a mask value that is neither 0 nor 1
+  const RowCols rc = row_cols(t, d.F, q, gi, prob, feats, coords);
+  const RowSums u = walk_row(rc, weighted);
+  if (u.odd_target) {  // refused: a mask value that is neither 0 nor 1
     atomicOr(&w.s->flags, kFlagMask);
-    atomicMin(&w.s->bad_task, task);
+    atomicMin(&w.s->bad, task);
   }
-  ssig = block_sum(ssig, s_d[0]);
-  sst = block_sum(sst, s_d[1]);
-  sb = block_sum(sb, s_d[2]);
-  sw = block_sum(sw, s_d[3]);
-  a = block_sum(a, s_d[4]);
-  cnt = block_sum(cnt, s_i[0]);
-  inter = block_sum(inter, s_i[1]);
-  st = block_sum(st, s_i[2]);
-  nr = block_sum(nr, s_i[3]);
-  double mu[kMaxF];
-  const double a_cl = a < 1e-5 ? 1e-5 : a;  // clamp(min=1e-5); a NaN stays
-#pragma unroll
-  for (int f = 0; f < kMaxF; ++f) mu[f] = f < F ? block_sum(bf[f], s_d[5 + f]) / a_cl : 0.0;
-
-  double ls = 0.0;
-  if (nr >= d.min_points) {  // uniform: the second walk, over the members only (loss.py:358: min_points_conds)
-    for (int s = threadIdx.x; s < S; s += kThreads) {
-      if (!inside(bt, ccol + (size_t)s * 3)) continue;
-      const Sig sg = sigmoid_of((double)xrow[s]);
-      double dev = 0.0;
-#pragma unroll
-      for (int f = 0; f < kMaxF; ++f)
-        if (f < F) {
-          const double df = (double)fcol[(size_t)s * F + f] - mu[f];
-          dev += df * df;
-        }
-      ls += sg.sig * dev;
-    }
-    ls = block_sum(ls, s_d[5 + kMaxF]) / (double)nr;
-  }
+  // uniform: a box of at least min_points members (loss.py:358: min_points_conds, and min_points >= 1)
+  const double ls = u.nr >= d.min_points ? walk_members(rc, u.mu, u.nr) : 0.0;
   if (threadIdx.x != 0) return;
 
-  const int uni = cnt + st - inter;
-  const double iou = (double)inter / ((double)uni + 1e-6);
-  const bool keep = 2 * inter > uni;  // iou > 0.5 of loss.py:458, for every pair of integers
+  // sums of 0 and 1: integers, exact in float64
+  const double uni = (double)u.cnt + u.st - u.inter;
+  const double iou = u.inter / (uni + 1e-6);
+  const bool keep = 2.0 * u.inter > uni;  // iou > 0.5 of loss.py:458, for every pair of integers
   const double diff = (double)t.score[q] - iou;
   double* rec = w.rrec + (size_t)(t.row_off + r) * kRowRec;
-  rec[R_DICE] = 1.0 - (2.0 * sst + 1.0) / (ssig + (double)st + 1.0);
-  rec[R_BCE] = sb;
+  rec[R_DICE] = 1.0 - (2.0 * u.sst + 1.0) / (u.ssig + u.st + 1.0);
+  rec[R_BCE] = u.swb;
   rec[R_SQ] = keep ? diff * diff : 0.0;
   rec[R_KEEP] = keep ? 1.0 : 0.0;
   rec[R_LS] = ls;
-  rec[R_SSIG] = ssig;
-  rec[R_ST] = (double)st;
-  rec[R_SST] = sst;
+  rec[R_SSIG] = u.ssig;
+  rec[R_ST] = u.st;
+  rec[R_SST] = u.sst;
   rec[R_IOU] = iou;
-  rec[R_A] = a;
-  rec[R_NR] = (double)nr;
-  rec[R_SW] = sw;
+  rec[R_A] = u.a;
+  rec[R_NR] = (double)u.nr;
+  rec[R_SW] = u.sw;
 #pragma unroll
-  for (int f = 0; f < kMaxF; ++f) rec[R_MU + f] = mu[f];
+  for (int f = 0; f < kMaxF; ++f) rec[R_MU + f] = u.mu[f];
 }
 
 // the divisor of a sample's BCE sum: as released the plain mean, times sum w / sum w (1, or NaN for a weight sum that is
@@ -287,12 +220,7 @@ __global__ __launch_bounds__(kThreads) void k_spf_finish(void* base, SpfDims d, 
   }
   __syncthreads();
   const int flags = w.s->flags;
-  if (threadIdx.x == 0) {
-    status[0] = flags ? GAPRO_ERR_BAD_ARG : GAPRO_OK;
-    status[1] = flags ? w.s->bad_task : -1;
-    status[2] = flags;
-    status[3] = 0;
-  }
+  if (threadIdx.x == 0) write_status(status, *w.s);
   const double inv_b = 1.0 / (double)d.B;
   for (int h = threadIdx.x; h < d.L; h += kThreads) {
     double total[4] = {0.0, 0.0, 0.0, 0.0}, num = 0.0, den = 0.0;
@@ -321,7 +249,7 @@ __device__ inline void spf_mask_grad(const SpfDims& d, const DevTask& t, int q, 
                                      const double* __restrict__ rec, const float* __restrict__ prob,
                                      const float* __restrict__ feats, const float* __restrict__ coords,
                                      float* __restrict__ g_mask) {
-  const int S = t.n_cols, F = d.F;
+  const int S = t.n_cols;
   float* __restrict__ out = g_mask + t.grad_off + (size_t)q * (size_t)S;
   if (r < 0) {  // uniform over the workgroup
     for (int s = threadIdx.x; s < S; s += kThreads) out[s] = 0.0f;
@@ -330,13 +258,6 @@ __device__ inline void spf_mask_grad(const SpfDims& d, const DevTask& t, int q, 
   const double inv_b = 1.0 / (double)d.B;
   const bool weighted = (d.flags & GAPRO_SPF_WEIGHTED_BCE) != 0;
   const double n = trec[T_N];
-  const float* __restrict__ xrow = t.x + (size_t)q * (size_t)t.ld;
-  const float* __restrict__ trow = t.t + (size_t)gi * (size_t)S;
-  const float* __restrict__ wcol = prob + t.col_off;
-  const float* __restrict__ ccol = coords + (size_t)t.col_off * 3;
-  const float* __restrict__ fcol = feats + (size_t)t.col_off * (size_t)F;
-  const BoxTest bt = box_test(t.box + (size_t)gi * 6);
-
   const double den = rec[R_SSIG] + rec[R_ST] + 1.0, numr = 2.0 * rec[R_SST] + 1.0;
   const bool main_as_released = h == d.L - 1 && !(d.flags & GAPRO_SPF_DICE_DIV_MAIN);
   const double k_dice = (double)up[L_DICE] * (main_as_released ? 1.0 : inv_b) / n / (den * den);
@@ -344,31 +265,11 @@ __device__ inline void spf_mask_grad(const SpfDims& d, const DevTask& t, int q, 
   const double k_bce = (double)up[L_BCE] * inv_b * bce_scale(d.flags, trec[T_SW], n, (double)S);
   const double nr = rec[R_NR], a = rec[R_A];
   const double k_ls = nr >= (double)d.min_points ? (double)up[L_LS] * inv_b / (n + 1e-4) / nr : 0.0;
-  const bool clamped = a < 1e-5;  // mu = (sum v f) / 1e-5: d mu / d v = f / 1e-5, and sum v (f - mu) is not zero
-  const double rfk = clamped ? 2.0 * (1e-5 - a) / 1e-5 : 0.0;  // rfk mu_f = 2 (sum v f - mu_f A) / 1e-5, sum v f = 1e-5 mu_f
+  const double rfk = a < 1e-5 ? 2.0 * (1e-5 - a) / 1e-5 : 0.0;  // the clamped mean's own derivative (mask_grad_row)
   double mu[kMaxF];
 #pragma unroll
   for (int f = 0; f < kMaxF; ++f) mu[f] = rec[R_MU + f];
-  for (int s = threadIdx.x; s < S; s += kThreads) {
-    const double x = (double)xrow[s], tv = (double)trow[s];
-    const double wv = weighted ? (double)wcol[s] : 1.0;
-    const Sig sg = sigmoid_of(x);
-    const double sm = sg.e / (1.0 + sg.e);                      // min(sig, 1 - sig)
-    const double dsig = sm / (1.0 + sg.e);                      // sig (1 - sig)
-    const double sig_t = x >= 0.0 ? (1.0 - tv) - sm : sm - tv;  // sig - t, cancellation-free (consumer.hip k_wbce_grad)
-    double dv = kd_num - tv * kd_den;  // k_dice (numr - 2 t den)
-    if (k_ls != 0.0 && inside(bt, ccol + (size_t)s * 3)) {
-      double dev = 0.0;
-#pragma unroll
-      for (int f = 0; f < kMaxF; ++f)
-        if (f < F) {
-          const double fv = (double)fcol[(size_t)s * F + f], df = fv - mu[f];
-          dev += df * df - rfk * mu[f] * fv;
-        }
-      dv += k_ls * dev;
-    }
-    out[s] = (float)(dsig * dv + k_bce * wv * sig_t);
-  }
+  mask_grad_row(row_cols(t, d.F, q, gi, prob, feats, coords), kd_num, kd_den, k_bce, weighted, k_ls, rfk, mu, out);
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------
@@ -389,10 +290,7 @@ __device__ inline void spf_label_grad(const SpfDims& d, const SpfWs& w, size_t t
   const double lse = w.qrec[tq * kQueryRec + 2];
   const double k = (double)upstream[(size_t)h * GAPRO_SPF_LOSS_N + L_CLS] * (tgt == d.C - 1 ? d.w_none : 1.0) /
                    w.hrec[h * kHeadRec];
-  for (int c = lane; c < d.C; c += 64) {
-    const double dz = (double)z[c] - lse;
-    out[c] = (float)(k * (c == tgt ? expm1(dz) : exp(dz)));  // softmax - onehot, without the cancellation at p -> 1
-  }
+  class_grad_row(z, d.C, lse, tgt, k, lane, 64, out);
 }
 
 // workgroups [0, L B Q): the score and mask-logit gradients of one (task, query) each; the workgroups behind them: the
@@ -501,7 +399,7 @@ int gapro_spf_loss_forward(gapro_ctx* ctx, void* stream_, const gapro_spf_loss_d
   spf_ws(nullptr, T, dims->n_heads, Q, total_gt, &w, &upload);
   std::vector<char> table(upload, 0);
   spf_ws(table.data(), T, dims->n_heads, Q, total_gt, &w, nullptr);
-  w.s->bad_task = kNoTask;
+  w.s->bad = kNoBad;
   for (long long k = 0; k < (long long)T * Q; ++k) w.inv[k] = -1;
   long long grad_off = 0;
   for (int k = 0; k < T; ++k) {

@@ -144,6 +144,19 @@ def losses(cls_logits, mask_logits, conf_logits, box_preds, prob_labels, batch_o
     return (total, grads) if upstream is not None else total
 
 
+def without_clamp_term(g_row, x_row, mem_row, feats, k_ls):
+    """A matched row's mask-logit gradient as it would be with the derivative of the clamped mean left out (the wrong
+    form the clamped cases guard against): ``g_row`` of the restatement, minus the term that `rf` adds there.  ``k_ls``
+    is the row's level-set coefficient, upstream / B / (n + 1e-4) / members.  Only for a row below the clamp."""
+    x, feats = np.asarray(x_row, dtype=np.float64), np.asarray(feats, dtype=np.float64)
+    sig = 1.0 / (1.0 + np.exp(-x))
+    v = sig * mem_row
+    a = v.sum()
+    assert a < 1e-5
+    rf = 2.0 * ((v @ feats) / 1e-5) * (1e-5 - a) / 1e-5
+    return np.asarray(g_row, dtype=np.float64) + sig * (1.0 - sig) * k_ls * mem_row * (feats @ rf)
+
+
 def close(got, want):
     """Device against the restatement: 1 float32 ulp of the value plus 1e-9 times the array's largest magnitude.  The
     float64 sums of the two differ by their order alone (the argument of match_ref.close), so the rounded results

@@ -93,6 +93,44 @@ def test_analytic_gradients_equal_central_differences(clamp_row):
         assert np.abs(g).max() > 0 or (clamp_row and key != "mask"), key
 
 
+def _fails_close(got, want):
+    with pytest.raises(AssertionError, match="max error"):
+        loss_ref.close(np.asarray(got).astype(np.float32), want)
+
+
+@pytest.mark.parametrize("binarise", [lambda t: t == 1, lambda t: t != 0], ids=["eq1", "ne0"])
+def test_the_fractional_case_separates_a_walk_that_binarises(binarise):
+    """tests/test_losses_gpu.py's case at its own tolerance: with the targets made 0 / 1 either way, the losses that read
+    them and every sample's mask gradients leave `close`."""
+    from test_losses_gpu import UP, fractional_case
+
+    args, gt = fractional_case()
+    want, wgrads = loss_ref.losses(gt=gt, upstream=UP, **args)
+    wrong = {**gt, "inst_labels": [binarise(t).astype(np.float32) for t in gt["inst_labels"]]}
+    got, grads = loss_ref.losses(gt=wrong, upstream=UP, **args)
+    for k in ("dice_loss", "bce_loss", "iou_loss"):
+        i = loss_ref.NAMES.index(k)
+        print("%s: %.3g of the value" % (k, abs(got[i] - want[i]) / abs(want[i])))
+        _fails_close(got[i:i + 1], want[i:i + 1])
+    for g, w in zip(grads["mask"], wgrads["mask"]):
+        print("mask gradient: %.3g of the largest magnitude" % (np.abs(g - w).max() / np.abs(w).max()))
+        _fails_close(g, w)
+
+
+def test_the_clamped_case_separates_a_gradient_without_the_clamps_own_term():
+    from test_losses_gpu import LEVELSET_ONLY, clamped_case
+
+    args, gt, mem = clamped_case()
+    assert 3 <= mem.sum() <= 12
+    _, wgrads = loss_ref.losses(gt=gt, upstream=LEVELSET_ONLY, **args)
+    want = wgrads["mask"][0]
+    assert loss_ref.close(want.astype(np.float32), want)
+    k_ls = 1.0 / (1.0 + 1e-4) / mem.sum()
+    wrong = loss_ref.without_clamp_term(want[0], args["mask_logits"][0][0], mem, args["levelset_feats"], k_ls)
+    print("without the term: %.3g of the largest magnitude" % (np.abs(wrong - want[0]).max() / np.abs(want).max()))
+    _fails_close(wrong[None, :], want)
+
+
 def _torch_problem(Q=5, S=9, n=2, C=4, F=3, B=2):
     rng = np.random.default_rng(11)
     t = lambda a, d=torch.float32: torch.as_tensor(np.asarray(a)).to(d)  # noqa: E731

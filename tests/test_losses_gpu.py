@@ -50,6 +50,27 @@ def _problem(seed, Q, C, F, shapes):
     return args, gt
 
 
+LEVELSET_ONLY = np.array([0, 0, 0, 0, 0, 0, 1], dtype=np.float32)
+
+
+def fractional_case():
+    """Targets from {0, 0.25, 0.5, 1}: the op takes any float32 target as the value it is."""
+    args, gt = _problem(16, 5, 4, 3, [(3, 257), (1, 64)])
+    rng = np.random.default_rng(17)
+    gt["inst_labels"] = [rng.choice(np.array([0, 0.25, 0.5, 1], dtype=np.float32), a.shape) for a in gt["inst_labels"]]
+    return args, gt
+
+
+def clamped_case():
+    """One matched row alone, the members of its label box at -14: A = members * sigmoid(-14) lies below the clamp
+    of 1e-5 and within a factor of five of it, so the clamped mean's own derivative is of the level-set term's size.
+    Returns the members too."""
+    args, gt = _problem(303, 1, 3, 3, [(1, 65)])  # a seed whose box holds 6 of the 65 columns
+    mem = ref.members(args["levelset_coords"], gt["box_labels"][0])[0]
+    args["mask_logits"][0][0, mem] = -14.0
+    return args, gt, mem
+
+
 def _run(args, gt, up=UP, backward=True, requires=("cls", "mask", "conf", "box"), cls_dtype=None, logits=None, **kw):
     """One call (and its backward): the f32[7] and the gradients as NumPy, ``None`` where none was asked for."""
     import torch
@@ -172,6 +193,17 @@ def test_member_logits_at_minus_thirty_take_the_clamped_mean():
     assert mem[0].sum() / (1.0 + np.exp(30.0)) < 1e-5
     _, grads, _, wgrads = _compare(args, gt, up=np.array([0, 0, 0, 0, 0, 0, 1], dtype=np.float32))
     assert grads["mask"][0][rows[0], mem[0]].all()  # tiny, and not flushed
+    _compare(args, gt)
+    # at -14 the clamp's own term is of the gradient's size, and the gradient array is this one row
+    args, gt, mem = clamped_case()
+    assert 3 <= mem.sum() <= 12 and 2e-6 <= mem.sum() / (1.0 + np.exp(14.0)) < 1e-5
+    _, grads, _, _ = _compare(args, gt, up=LEVELSET_ONLY)
+    assert grads["mask"][0][0, mem].all()
+
+
+def test_fractional_targets_are_taken_as_they_are():
+    args, gt = fractional_case()
+    assert all(((a > 0) & (a < 1)).any() for a in gt["inst_labels"])
     _compare(args, gt)
 
 

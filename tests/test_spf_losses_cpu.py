@@ -93,6 +93,24 @@ def test_integer_score_filter_is_the_float32_expression_for_every_pair():
     assert np.array_equal(f64[ok], np.broadcast_to(want, ok.shape)[ok])
 
 
+def test_the_clamped_case_separates_a_gradient_without_the_clamps_own_term():
+    """tests/test_spf_losses_gpu.py's case at its own tolerance."""
+    from loss_ref import close, without_clamp_term
+    from test_spf_losses_gpu import LEVELSET_ONLY, clamped_case
+
+    p, mem = clamped_case()
+    assert 3 <= mem.sum() <= 12
+    _, grads = ref.layer_losses(p["labels"], p["scores"], p["masks"], p["gts"], p["indices"], p["sp_coords"],
+                                p["sp_rgb_feats"], p["sp_prob_labels"], upstream=LEVELSET_ONLY, min_points=3)
+    want = grads["masks"][0][0]
+    assert want[0, mem].all() and close(want.astype(np.float32), want)
+    k_ls = 1.0 / (1.0 + 1e-4) / mem.sum()
+    wrong = without_clamp_term(want[0], p["masks"][0][0][0], mem, p["sp_rgb_feats"], k_ls)
+    print("without the term: an error of %.3g" % np.abs(wrong - want[0]).max())
+    with pytest.raises(AssertionError, match="max error"):
+        close(wrong[None, :].astype(np.float32), want)
+
+
 @pytest.mark.parametrize("name", ref.FIXTURES)
 def test_host_solver_reproduces_every_fixture_assignment(name):
     z, args = ref.fixture(name)

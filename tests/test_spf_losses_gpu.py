@@ -61,6 +61,19 @@ def problem(seed, L1, Q, C, F, shapes):
     return p
 
 
+LEVELSET_ONLY = np.array([[0, 0, 0, 0, 1]], dtype=np.float32)
+
+
+def clamped_case():
+    """One head, one matched row alone, the members of its instance's box at -14: A = members * sigmoid(-14) lies below
+    the clamp of 1e-5 and within a factor of five of it, so the clamped mean's own derivative is of the level-set
+    term's size.  For min_points = 3.  Returns the members too."""
+    p = problem(61, 1, 1, 4, 3, [(1, 65)])
+    mem = ref.members(p["sp_coords"], p["gts"][0][2])[0]
+    p["masks"][0][0][0, mem] = -14.0
+    return p, mem
+
+
 def insts_of(p, cls_dtype=None, mask_dtype=None):
     import torch
 
@@ -186,6 +199,13 @@ def test_boxes_of_99_100_and_101_members_and_min_points():
     none, grads, _, _ = compare(p, min_points=102)
     assert (one[:, col] > default[:, col]).all() and (default[:, col] > edge[:, col]).all() and not none[:, col].any()
     assert np.array_equal(np.delete(one, col, 1), np.delete(default, col, 1))
+
+
+def test_member_logits_at_minus_fourteen_take_the_clamped_mean():
+    p, mem = clamped_case()
+    assert 3 <= mem.sum() <= 12 and 2e-6 <= mem.sum() / (1.0 + np.exp(14.0)) < 1e-5
+    got, grads, _, _ = compare(p, up=LEVELSET_ONLY, min_points=3)
+    assert got[0, ref.NAMES.index("levelset_loss")] > 0 and grads["masks"][0][0][0, mem].all()
 
 
 def score_problem(kind):
